@@ -44,9 +44,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-# before anything initialises HIP (torch.cuda does, long before libscanfuse.so is loaded): sf_fuse_run drives seven streams, the runtime's
-# default of four hardware queues puts some of them in one queue (scannet_amd/__init__.py)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 TOTAL_FRAMES = 5578
 W, H = 640, 480
@@ -552,11 +549,92 @@ def end_to_end(frames_dev, poses, n, params, local_rank, torch, colour=None, cac
 
 
 def repeats_for(K, cfg_name="4mm"):
-    """How often the K timed steps are repeated (fresh volume each time) so that the timed regions add up to ~1 s of GPU time at the rate this
-    path runs at (~30 us per frame at 4 mm, ~1 ms at 1 mm) -- a function of K and the configuration alone, so every rank of a multi-GPU run takes
+    """How often the W warm-up + K steps run untimed (fresh volume each time) before the timed ones, so that they add up to ~1 s of GPU time at the
+    rate this path runs at (~30 us per frame at 4 mm, ~1 ms at 1 mm): the timed steps find the device at its working clocks (one priming pass left a
+    20-step region at 32 k frames/s against 35 k after ~1 s).  A function of K and the configuration alone, so every rank of a multi-GPU run takes
     the same number."""
     per_frame = 30e-6 if cfg_name == "4mm" else 1e-3
     return int(min(2000, max(3, -(-1.0 // (K * per_frame)))))
+
+
+DUMP_MAX_COORDS = 1 << 20       # block coordinates written by --dump-outputs (float32: 12 MiB); a larger volume gives a keyed sample of them
+DUMP_SAMPLE_BLOCKS = 2048       # whole blocks written: 2 048 x 512 voxels x (sdf, weight, r, g, b) float32 = 20 MiB
+
+
+def _block_keys(coords):
+    """A fixed pseudo-random key per block (splitmix64 of the packed coordinates): a sample taken as the smallest keys depends on the block set
+    alone, so two volumes that differ in a few blocks still share the rest of their samples."""
+    c = coords.astype(np.int64) & 0x1FFFFF
+    z = ((c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def block_sample(coords, n):
+    """Indices of at most n of the blocks, ascending (the export's (x, y, z) order): the n smallest keys."""
+    if len(coords) <= n:
+        return np.arange(len(coords))
+    return np.sort(np.argpartition(_block_keys(coords), n - 1)[:n])
+
+
+DUMP_SLAB_BLOCKS = 1 << 16      # blocks per export while dumping: 256 MiB of voxels on the host at a time
+
+
+def _count_x(fuser, lo, hi):
+    """Live blocks with lo <= x < hi (sf_fuser_export_blocks_where with no buffers: a count, nothing copied)."""
+    from scannet_amd import _abi
+    n = C.c_uint64(0)
+    _abi.check(_abi.lib().sf_fuser_export_blocks_where(fuser._h, 0, int(lo), int(hi), 0, None, None, 0, C.byref(n), 0))
+    return n.value
+
+
+def dump_outputs(fuser, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the fused volume as sf_fuser_export_blocks returns it, blocks
+    sorted by (x, y, z) -- as float32 .npy files, 33 MiB at most:
+      block_coords   [n, 3]         every live block (the DUMP_MAX_COORDS smallest keys of a larger volume)
+      sample_coords  [m, 3]         the DUMP_SAMPLE_BLOCKS blocks with the smallest keys, and their 512 voxels each:
+      sample_sdf     [m, 512]       signed distance
+      sample_weight  [m, 512]       integration weight
+      sample_rgb     [m, 512, 3]    colour
+    The volume comes over in slabs along x of at most DUMP_SLAB_BLOCKS blocks (a single x layer may hold more); the host keeps every block's
+    coordinates (12 B each) and the voxels of the sample so far, never the whole volume (2.9 M blocks = 12 GB at 1 mm)."""
+    X0, X1 = -(1 << 31), (1 << 31) - 1
+    parts, best_k, best_c, best_v = [], np.zeros(0, np.uint64), np.zeros((0, 3), np.int32), None
+    if _count_x(fuser, X0, X1):
+        lo, hi = X0, X1                  # the smallest x that holds a block: count(X0, lo) == 0 < count(X0, hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (lo, mid) if _count_x(fuser, X0, mid) else (mid, hi)
+        x = lo
+        lo, hi = X0, X1                  # and the largest: count(lo, X1) > 0 == count(hi, X1)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if _count_x(fuser, mid, X1) else (lo, mid)
+        x_last, w = lo, 1
+        while x <= x_last:
+            w = min(w, x_last + 1 - x)
+            while w > 1 and _count_x(fuser, x, x + w) > DUMP_SLAB_BLOCKS:
+                w //= 2
+            c, v = fuser.export_blocks_where(0, x, x + w)    # sorted by (x, y, z); the slabs follow each other along x
+            parts.append(c)
+            k = np.concatenate([best_k, _block_keys(c)])
+            c = np.concatenate([best_c, c])
+            v = v if best_v is None else np.concatenate([best_v, v])
+            keep = np.argpartition(k, DUMP_SAMPLE_BLOCKS - 1)[:DUMP_SAMPLE_BLOCKS] if len(k) > DUMP_SAMPLE_BLOCKS else slice(None)
+            best_k, best_c, best_v = k[keep], c[keep], v[keep]
+            x, w = x + w, w * 2
+    coords = np.concatenate(parts) if parts else np.zeros((0, 3), np.int32)
+    order = np.lexsort((best_c[:, 2], best_c[:, 1], best_c[:, 0]))   # the sample in export order
+    sc = best_c[order]
+    sv = best_v[order] if best_v is not None else np.zeros((0, 512), [("sdf", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("w", "u1")])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"block_coords": coords[block_sample(coords, DUMP_MAX_COORDS)], "sample_coords": sc, "sample_sdf": sv["sdf"],
+              "sample_weight": sv["w"], "sample_rgb": np.stack([sv["r"], sv["g"], sv["b"]], -1)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
@@ -603,9 +681,12 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
             colour_frames[0] = out
         return colour_frames[0]
 
-    def run(n_warm, n_timed, profile, single_frame=False, colour=None, extra_tune=None, repeats=1, prm=None):
+    def run(n_warm, n_timed, profile, single_frame=False, colour=None, extra_tune=None, repeats=1, prm=None, prime=0, last=None):
         """`repeats` times on one fuser (sf_fuser_reset in between): fuse frames [0, n_warm) untimed, then frames [n_warm, n_warm + n_timed) between
-        two barrier+synchronize pairs.  Elapsed times per repeat (max over ranks), kernel events and counters summed over the repeats."""
+        two barrier+synchronize pairs.  Elapsed times per repeat (max over ranks), kernel events and counters summed over the repeats.
+        `prime`: the same two calls that many times before the first repeat, untimed, each on an emptied volume (repeats_for) -- a fuser's first
+        pass pays one-off costs (the first of 1 667 repeats of a 20-step run measured 473 frames/s against a median of 32 k) and the device's clocks
+        follow its load.  `last(fuser)` runs after the last timed step."""
         colour = rgbd if colour is None else colour
         fuser = fusion.Fuser(prm if prm is not None else params, device=local_rank, **dict(dict(TUNE, **({"batch": 1} if single_frame else {})), **(extra_tune or {})))
         rgb = colour_tensor(n_warm + n_timed) if colour else None
@@ -619,11 +700,15 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
 
         times, own_times, t_enq_sum, kernel_ms, launches, blocks, tiles = [], [], 0.0, 0.0, 0, 0, 0
         st1 = None
-        for rep in range(repeats):
-            if rep:
+        for rep in range(-prime, repeats):   # rep < 0: the priming passes
+            if rep > -prime:
                 fuser.reset()
             fuser.integrate_batch_device(frames[:n_warm].data_ptr(), stride, poses[:n_warm], rgb.data_ptr() if colour else None, cstride)
             sync_all()
+            if rep < 0:
+                fuser.integrate_batch_device(frames[n_warm:].data_ptr(), stride, poses[n_warm:n_warm + n_timed], rgb[n_warm:].data_ptr() if colour else None, cstride)
+                sync_all()
+                continue
             st0 = fuser.stats()
             if profile:
                 fuser.profile(True)
@@ -647,6 +732,8 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
                 fuser.profile(False)
             blocks += st1["total_frame_blocks"] - st0["total_frame_blocks"]
             tiles += st1["total_pass_tiles"] - st0["total_pass_tiles"]
+        if last is not None:
+            last(fuser)
         ceiling = None
         if single_frame and profile:
             # the last frame's tile traffic without the arithmetic: what this access pattern (scattered 4 KiB RMW) can reach
@@ -750,12 +837,14 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
             r["front_chain"] = fc
         return r
 
-    R = 1 if child else (args.repeats if args.repeats else repeats_for(K, cfg_name))
+    R = 1 if child else max(1, args.repeats)   # --steps K times K steps; --repeats N times them N times
+    P = 0 if child else repeats_for(K, cfg_name)   # untimed passes over the same steps first
+    dump = (lambda f: dump_outputs(f, args.dump_outputs)) if (args.dump_outputs and rank == 0) else None
     xr = "true" if TUNE.get("xrow", 1) else "false"
     kname = ("k_integrate<1,2,true,2,false,4,%s>" if rgbd else "k_integrate<1,0,true,2,false,4,%s>") % xr
     # the timed region runs WITHOUT the HIP events around every integrate launch (they cost ~2 % of the frames/s: profiles/r03_small_experiments.txt);
     # kernel durations come from the roofline sample below, fused again with the events on.  --single-frame keeps them: its line is the roofline.
-    m = run(Wm, K, args.single_frame and not args.no_profile, single_frame=args.single_frame, repeats=R)
+    m = run(Wm, K, args.single_frame and not args.no_profile, single_frame=args.single_frame, repeats=R, prime=P, last=dump)
     # the roofline window, on EVERY rank (run() holds barriers and an all-reduce when N > 1: a pass only rank 0 entered would hang the job)
     mr = m if (child or args.no_profile or m["batch"] == 1) else run(roof_W, roof_K, True)
     # every rank's own rate, gathered (N > 1): the driver computes scaling efficiency from `value`, a reader sees the spread here
@@ -803,8 +892,8 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
             "per_rank_frames_per_s": per_rank,
             "repeats": {"n": len(ts), "timed_s_total": round(sum(ts), 4), "value_median": round(world * K / m["elapsed"], 2),
                         "value_min": round(world * K / max(ts), 2), "value_max": round(world * K / min(ts), 2),
-                        "what": "the %d warm-up + %d timed steps repeated on an emptied volume (sf_fuser_reset) until the timed regions add up to ~1 s; "
-                                "`value` is the median repeat" % (Wm, K)},
+                        "what": "the %d warm-up + %d timed steps on an emptied volume (sf_fuser_reset), after %d untimed passes over the same steps (~1 s); "
+                                "--repeats N times them N times, `value` is the median repeat" % (Wm, K, P)},
             "config": {"workload": cfg["label"] + ", frames %d..%d per rank, %s resident in HBM" % (Wm, K + Wm - 1, "depth AND colour (a 640x480 RGB8 frame per depth frame, 921 600 B)" if rgbd else "depth (geometry only: --depth-only)"),
                        "rgbd": rgbd, "tune": dict(TUNE),
                        "scene": {0: "empty box room", 1: "box room furnished with 48 boxes (csrc/synth.hip clutter_boxes), sensor holes"}[args.scene],
@@ -823,7 +912,7 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
         extras = world == 1 and not args.no_profile and not args.single_frame and not child
         if extras and rgbd and not args.no_depth_only and cfg_name == "4mm":
             # the geometry-only pass over the same frames (the headline of rounds 1-3): rate with the same repeats, kernel duration and VALU counters
-            md = run(Wm, K, False, colour=False, repeats=R)
+            md = run(Wm, K, False, colour=False, repeats=R, prime=P)
             out["value_depth_only"] = round(K / md["elapsed"], 2)
             mdr = run(roof_W, roof_K, True, colour=False)
             vd = pmc_valu(args, cfg_name, roof_K, roof_W, False, True) if pmc_on else None
@@ -1116,6 +1205,8 @@ def run_partition(args, rank, local_rank, world, dist, torch):
     fuser.integrate_batch_device(frames[Wm:].data_ptr(), stride, poses[Wm:])
     sync_all()
     t_fuse = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # rank 0's stripes (all of the volume at N = 1), before the boundary exchange adds ghosts
+        dump_outputs(fuser, args.dump_outputs)
     # the exchange step + meshing (reported beside the metric, not part of the K timed steps)
     t1 = time.perf_counter()
     sent, got = partition.exchange_boundary(fuser, mode=args.exchange) if world > 1 else (fuser.count_boundary(), 0)
@@ -1296,7 +1387,7 @@ def compact_line(out, detail_path=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps: frames (scans for --config scans); exactly this many are timed unless --repeats")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", choices=["4mm", "1mm", "scans", "partition"], default="4mm")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1312,7 +1403,11 @@ def main():
     ap.add_argument("--no-prefix-check", action="store_true", help="--config partition: skip the merged-mesh check of a bounded prefix against one fuser")
     ap.add_argument("--teardown", action="store_true", help="leave through the interpreter's normal teardown (set for the runs under rocprofv3)")
     ap.add_argument("--child", action="store_true", help="a counter pass of another bench.py: the K timed steps once, nothing else")
-    ap.add_argument("--repeats", type=int, default=0, help="how often the timed steps are repeated on an emptied volume (default: until ~1 s of timed GPU time)")
+    ap.add_argument("--repeats", type=int, default=0, help="time the K steps this many times, each on an emptied volume (N x K timed steps; `value` is the "
+                                                           "median repeat; default 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step (rank 0's "
+                                                                         "fused volume: every block's coordinates, a fixed keyed sample of whole blocks) as float32 "
+                                                                         ".npy files under DIR (bench_outputs/ is git-ignored); --config 4mm / 1mm / partition")
     ap.add_argument("--scene", type=int, choices=[0, 1], default=1, help="synthetic scene: 0 = the empty box room of rounds 1-2, 1 = the furnished room (default)")
     ap.add_argument("--noise", type=int, choices=[0, 1, 2], default=2, help="depth noise: 1 = the LCG ramp of rounds 1-2, 2 = three LSBs hashed per pixel and frame (default)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end leg (.sens in /tmp -> sf_fuse_run)")
@@ -1335,6 +1430,9 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="testing aid: every rank on GPU 0 over the gloo backend (RCCL refuses two ranks on one device) -- "
                                                              "exercises the N > 1 control flow (barriers, max over ranks) on a one-GPU box; the rates mean nothing")
     args = ap.parse_args()
+    if args.dump_outputs and args.config == "scans":
+        raise SystemExit("bench.py: --dump-outputs writes the fused volume of --config 4mm / 1mm / partition; a step of --config scans is a whole "
+                         "scan through fusion, meshing and the host stage, whose outputs it does not write")
     if args.pmc_steps is None:
         args.pmc_steps = 400 if args.config == "4mm" else 64
     TUNE.update({kv.split("=")[0]: int(kv.split("=")[1]) for kv in args.tune})

@@ -367,8 +367,11 @@ SF_API int sf_mlx_load(const char* path, sf_clean_script* out) {
   size_t p = 0;
   std::string current;
   while ((p = text.find('<', p)) != std::string::npos) {
-    const size_t e = text.find('>', p);
-    if (e == std::string::npos) break;
+    // the tag ends at the first '>' outside a quoted attribute value: XML allows '>' inside one (MeshLab's tooltips hold "&lt;br>")
+    size_t e = p + 1;
+    for (bool quoted = false; e < text.size() && (quoted || text[e] != '>'); ++e)
+      if (text[e] == '"') quoted = !quoted;
+    if (e >= text.size()) break;
     const std::string tag = text.substr(p + 1, e - p - 1);
     p = e + 1;
     if (tag.compare(0, 7, "filter ") == 0) {

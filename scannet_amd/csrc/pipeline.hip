@@ -42,9 +42,8 @@ int jpeg_gpu_reconstruct(hipStream_t stream, int n, const uint8_t* const* d_payl
 // The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of streams that share a queue
 // run one after the other.  sf_fuse_run drives up to seven streams (the fuser's two, two for colour copies, three for the inflate kernels); on four
 // queues every third batch's inflate sat in the integrate pass's queue (29 k -> 20 k frames/s in the loop).  The variable belongs to the PROCESS
-// (it is read at its first HIP call): the library does not touch the environment -- the bin/ tools and bench.py export GPU_MAX_HW_QUEUES=16 in
-// their own main() before the first HIP call, and a run that finds fewer queues than it has streams says so through
-// sf_last_error() while returning SF_OK (sf_fuse_run_note).
+// (it is read at its first HIP call): neither the library nor its tools touch the environment, and a run that finds
+// fewer queues than it has streams says so through sf_fuse_run_note() while returning SF_OK.
 
 // the default of the JPEG entropy decoding (see gpu_huffman in sf_fuse_run), decided by measurement (profiles/r05_e2e_rgbd.json: 1296x968 pictures of ~200 KB,
 // device + 4 host threads 12.3 k frames/s before the five side streams, host decoding on 16 threads 10.0 k, on 4 threads 3.2 k): on the device whenever the
@@ -852,8 +851,8 @@ SF_API int sf_fuse_run(sf_fuser* f, const sf_sens* s, uint64_t first, uint64_t l
     const int streams_used = 2 + (copy_stream ? 2 : 0) + (gpu_inflate ? NZ : 0), queues = hardware_queues_of_the_process();
     t_run_note[0] = 0;
     if (streams_used > queues)   // through sf_fuse_run_note(), not sf_last_error(): a caller that reads a non-empty last error as a failure must not
-      std::snprintf(t_run_note, sizeof(t_run_note), "sf_fuse_run drove %d streams over %d hardware queues (kernels of streams that share a queue run one after the other); "
-                    "export GPU_MAX_HW_QUEUES=16 before the process's first HIP call", streams_used, queues);
+      std::snprintf(t_run_note, sizeof(t_run_note), "sf_fuse_run drove %d streams over %d hardware queues (kernels of streams that share a queue run one after the other; "
+                    "GPU_MAX_HW_QUEUES, read at the process's first HIP call, sets the number)", streams_used, queues);
   }
   if (stats) {
     stats->frames_total = total;

@@ -396,9 +396,6 @@ int run_ranks(const Args& a, int argc_in, const char** argv_in) {
 }  // namespace
 
 int main(int argc, const char** argv_in) {
-  // This PROCESS drives sf_fuse_run's seven streams: ask the HIP runtime for a hardware queue each before its first call (default 4: kernels of
-  // streams that share a queue run one after the other).  The application's decision, not the library's; a value the user exported wins.
-  (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);
   // ranks of a partitioned run hand device memory to each other (RCCL, hipIpc): the host driver of this platform supports dmabuf IPC only
   (void)setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);
   // --upstream[=voxelhashing|bundlefusion]: the upstream-conformance preset (scanfuse.h sf_params_upstream_preset; default: SURVEY App. C).  Not an

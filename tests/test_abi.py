@@ -47,7 +47,7 @@ def test_every_declaration_cites_the_reference():
         assert anchor in text, anchor
 
 
-def test_struct_layouts_match_the_header():
+def test_struct_layouts_match_the_header(tmp_path):
     # compile a tiny C program against the header and compare sizeof / offsetof with the ctypes mirror
     src = r'''
 #include <stdio.h>
@@ -58,7 +58,7 @@ int main(void) {
          offsetof(sf_stats, total_frame_blocks), sizeof(sf_sens_info), sizeof(sf_run_stats));
   return 0;
 }'''
-    exe = "/tmp/sf_layout_check"
+    exe = str(tmp_path / "sf_layout_check")
     subprocess.run(["gcc", "-x", "c", "-std=c11", "-I" + os.path.join(ROOT, "include"), "-o", exe, "-"], input=src, text=True, check=True)
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     from scannet_amd import fusion, sens

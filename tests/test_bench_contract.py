@@ -32,6 +32,56 @@ def test_bench_help_names_the_configs():
         assert word in r.stdout, word
 
 
+def test_dump_sample_is_fixed_by_the_block_set():
+    """--dump-outputs writes a sample of a large volume: the blocks with the smallest keys of a hash of their coordinates.  The same blocks give the same
+    sample in any order and number of calls; a volume with a few blocks more or less keeps the rest of its sample; indices come back in export order."""
+    b = _load_bench()
+    import numpy as np
+    rng = np.random.default_rng(0)
+    coords = np.unique(rng.integers(-600, 600, (200000, 3)).astype(np.int32), axis=0)   # sorted by (x, y, z), like export_blocks
+    s = b.block_sample(coords, 2048)
+    assert len(s) == 2048 and np.all(np.diff(s) > 0) and np.array_equal(s, b.block_sample(coords, 2048))
+    perm = rng.permutation(len(coords))
+    assert np.array_equal(np.sort(perm[b.block_sample(coords[perm], 2048)]), s)
+    fewer = np.delete(coords, rng.choice(len(coords), 50, replace=False), axis=0)
+    shared = len({tuple(c) for c in coords[s]} & {tuple(c) for c in fewer[b.block_sample(fewer, 2048)]})
+    assert shared >= 2048 - 50
+    assert np.array_equal(b.block_sample(coords[:100], 2048), np.arange(100))
+
+
+def test_dump_in_slabs_writes_what_one_export_would(tmp_path, monkeypatch):
+    """dump_outputs takes the volume over in slabs along x (host memory bounded by the slab, not the volume): its files must be those of ONE export of
+    the whole volume -- every block's coordinates in export order and the keyed sample of whole blocks.  A stand-in for the fuser, small slabs."""
+    import numpy as np
+    b = _load_bench()
+    rng = np.random.default_rng(1)
+    coords = np.unique(rng.integers(-300, 300, (30000, 3)).astype(np.int32), axis=0)
+    coords[:, 0] = coords[:, 0] // 7   # several hundred blocks per x layer
+    coords = np.unique(coords, axis=0)
+    dt = np.dtype([("sdf", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("w", "u1")])
+    vox = np.zeros((len(coords), 512), dt)
+    for f in ("sdf", "r", "g", "b", "w"):
+        vox[f] = rng.integers(0, 255, vox.shape)
+
+    class Volume:
+        def export_blocks_where(self, axis, lo, hi):
+            m = (coords[:, axis] >= lo) & (coords[:, axis] < hi)
+            return coords[m], vox[m]
+
+    monkeypatch.setattr(b, "_count_x", lambda f, lo, hi: int(((coords[:, 0] >= lo) & (coords[:, 0] < hi)).sum()))
+    monkeypatch.setattr(b, "DUMP_SLAB_BLOCKS", 1000)
+    b.dump_outputs(Volume(), str(tmp_path / "d"))
+    s = b.block_sample(coords, b.DUMP_SAMPLE_BLOCKS)
+    want = {"block_coords": coords, "sample_coords": coords[s], "sample_sdf": vox["sdf"][s], "sample_weight": vox["w"][s],
+            "sample_rgb": np.stack([vox["r"][s], vox["g"][s], vox["b"][s]], -1)}
+    for name, a in want.items():
+        got = np.load(str(tmp_path / "d" / (name + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32)), name
+    monkeypatch.setattr(b, "_count_x", lambda f, lo, hi: 0)   # an empty volume
+    b.dump_outputs(Volume(), str(tmp_path / "e"))
+    assert np.load(str(tmp_path / "e" / "sample_sdf.npy")).shape == (0, 512)
+
+
 def test_repeats_rule_is_a_function_of_the_arguments_alone():
     """Every rank of a multi-GPU run must take the same number of repeats without talking to the others: the rule only reads K and the config."""
     import importlib.util

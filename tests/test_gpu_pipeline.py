@@ -119,9 +119,21 @@ def test_fuse_run_inflates_depth_on_the_gpu_or_on_the_host(tmp_path, where, monk
             c.run(sens.SensorData(short), decode_threads=2)
 
 
-def test_drop_in_executables(tmp_path):
-    """`depthsensing p1 p2 scan.sens` -> scan_vh.ply, then `segmentator scan_vh.ply` -> scan_vh.0.010000.segs.json;
-    stderr stays empty (Server/util.py:42-44 logs stderr as an error)."""
+DROP_IN_GOLDEN = os.path.join(ROOT, "tests", "golden", "drop_in_segmentator_golden.json")
+
+
+def _mesh_sha256(path):
+    from scannet_amd import segmentator
+    import hashlib
+    h = hashlib.sha256()
+    for a in segmentator.Mesh.read(path).arrays():
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def _drop_in_clean_mesh(tmp_path):
+    """The `improve` stage by the drop-in executables: `depthsensing p1 p2 scene0000_00.sens` -> scene0000_00_vh.ply, `meshclean ... -s clean.mlx` ->
+    scene0000_00_vh_clean.ply (also what tests/golden/make_drop_in_golden.py records the reference Segmentator on).  Returns (params, ply, clean ply)."""
     W, H = 320, 240
     sens_path = str(tmp_path / "scene0000_00.sens")
     _write_sens(sens_path, 30, W, H, 1200)
@@ -146,6 +158,14 @@ def test_drop_in_executables(tmp_path):
     clean_ply = str(tmp_path / "scene0000_00_vh_clean.ply")
     cl = subprocess.run([os.path.join(ROOT, "bin", "meshclean"), "-i", ply, "-o", clean_ply, "-m", "vc", "-s", str(mlx)], capture_output=True, text=True)
     assert cl.returncode == 0 and cl.stderr == "", cl.stderr
+    return params, ply, clean_ply
+
+
+def test_drop_in_executables(tmp_path):
+    """`depthsensing p1 p2 scan.sens` -> scan_vh.ply, then `segmentator scan_vh.ply` -> scan_vh.0.010000.segs.json;
+    stderr stays empty (Server/util.py:42-44 logs stderr as an error)."""
+    import hashlib
+    params, ply, clean_ply = _drop_in_clean_mesh(tmp_path)
     from scannet_amd import segmentator
     nv0, nf0 = segmentator.Mesh.read(ply).counts()
     nv, nf = segmentator.Mesh.read(clean_ply).counts()
@@ -155,21 +175,27 @@ def test_drop_in_executables(tmp_path):
     js = json.load(open(str(tmp_path / "scene0000_00_vh_clean.0.010000.segs.json")))
     assert js["params"] == {"kThresh": 0.01, "segMinVerts": 20} and js["sceneId"] == "/scene0000_00_vh_clean"
     assert len(js["segIndices"]) == nv
-    # north_star: "bit-exact on segIndices for a fixed kThresh" -- the REFERENCE Segmentator (oracle/_ref/segmentator_ref, compiled from the reference's
-    # own sources by oracle/Makefile; it travels to the GPU box prebuilt) on the very mesh the GPU extracted and cleaned: same segIndices, same file bytes
+    # north_star: "bit-exact on segIndices for a fixed kThresh" -- the REFERENCE Segmentator on the very mesh the GPU extracted and cleaned: same
+    # segIndices, same file bytes.  Its bytes on this mesh are recorded in tests/golden/drop_in_segmentator_golden.json (make_drop_in_golden.py); where
+    # oracle/_ref/segmentator_ref is built (compiled from the reference's own sources by oracle/Makefile) it runs here as well
     # (segmentator.cpp:253-287 writes beside its input, so it gets a copy of the mesh in a directory of its own)
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "segmentator_ref")
-    assert os.path.exists(ref_bin), "oracle/_ref/segmentator_ref is missing: __graft_entry__.build() makes it where /root/reference exists and it ships with the snapshot"
-    ref_dir = tmp_path / "ref"
-    ref_dir.mkdir()
-    shutil.copy(clean_ply, str(ref_dir / "scene0000_00_vh_clean.ply"))
-    rr = subprocess.run([ref_bin, str(ref_dir / "scene0000_00_vh_clean.ply")], capture_output=True, text=True)
-    assert rr.returncode == 0, rr.stderr
     ours = open(str(tmp_path / "scene0000_00_vh_clean.0.010000.segs.json"), "rb").read()
-    theirs = open(str(ref_dir / "scene0000_00_vh_clean.0.010000.segs.json"), "rb").read()
-    assert json.loads(theirs)["segIndices"] == js["segIndices"]
-    assert len(set(js["segIndices"])) > 10          # a real over-segmentation, not one label
-    assert ours == theirs
+    gold = json.load(open(DROP_IN_GOLDEN))
+    regen = "regenerate with tests/golden/make_drop_in_golden.py (needs the reference build and a GPU)"
+    assert _mesh_sha256(clean_ply) == gold["mesh_sha256"], "fusion, meshing or cleaning changed the mesh the reference's bytes were recorded on: " + regen
+    assert hashlib.sha256(ours).hexdigest() == gold["segs_json_sha256"] and len(ours) == gold["segs_json_bytes"], \
+        "bin/segmentator's segs.json differs from the reference's on this mesh (or the golden is stale: %s)" % regen
+    assert len(set(js["segIndices"])) == gold["num_segments"] > 10          # a real over-segmentation, not one label
+    ref_bin = os.path.join(ROOT, "oracle", "_ref", "segmentator_ref")
+    if os.path.exists(ref_bin):
+        ref_dir = tmp_path / "ref"
+        ref_dir.mkdir()
+        shutil.copy(clean_ply, str(ref_dir / "scene0000_00_vh_clean.ply"))
+        rr = subprocess.run([ref_bin, str(ref_dir / "scene0000_00_vh_clean.ply")], capture_output=True, text=True)
+        assert rr.returncode == 0, rr.stderr
+        theirs = open(str(ref_dir / "scene0000_00_vh_clean.0.010000.segs.json"), "rb").read()
+        assert json.loads(theirs)["segIndices"] == js["segIndices"]
+        assert ours == theirs
     # failure protocol: non-zero exit and a message on stderr
     bad = subprocess.run([os.path.join(ROOT, "bin", "depthsensing"), str(params), str(params), str(tmp_path / "missing.sens")], capture_output=True, text=True)
     assert bad.returncode != 0 and "could not open" in bad.stderr

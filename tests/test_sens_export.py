@@ -175,7 +175,7 @@ def test_png_writer_rgb_and_grey(tmp_path):
             assert (w.value, h.value, c.value, b.value) == (5, 9, 3, 16) and np.array_equal(back, a)
         else:
             assert np.array_equal(np.asarray(Image.open(p)).astype(dt), a)
-    assert L.sf_png_write(b"/tmp/x.png", a.ctypes.data, 5, 9, 2, 8) != 0
+    assert L.sf_png_write(str(tmp_path / "x.png").encode(), a.ctypes.data, 5, 9, 2, 8) != 0
 
 
 def test_images_back_into_a_sens(tmp_path):

@@ -14,8 +14,7 @@ from scannet_amd.segmentator import Mesh
 from tests import meshes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MLX = "/root/reference/Server/tools/meshclean/simplify.mlx"
-# the same filters and values as Server/tools/meshclean/simplify.mlx:3-24 (tooltips dropped), for boxes without /root/reference
+# the same filters and values as Server/tools/meshclean/simplify.mlx:3-24 (tooltips dropped)
 SIMPLIFY_MLX = """<!DOCTYPE FilterScript>
 <FilterScript>
  <filter name="Quadric Edge Collapse Decimation">
@@ -159,10 +158,36 @@ def test_parameters_and_edge_cases():
     assert st["faces_out"] == 1
 
 
+def test_script_params_behind_markup_in_attributes(tmp_path):
+    """MeshLab writes every Param with a tooltip that may hold markup -- "&lt;br>", "&#xa;", a bare '>' -- and not always after name= (the shipped
+    simplify.mlx puts QualityThr's tooltip before it).  Every value must be read, not left at its default: each one below differs from the default."""
+    tip = 'tooltip="first line&lt;br>second line&#xa; values > 0 &lt; 1 &lt;b>bold&lt;/b>"'
+    params = [("TargetFaceNum", "5000", "RichInt"), ("TargetPerc", "0.35", "RichFloat"), ("QualityThr", "0.45", "RichFloat"),
+              ("PreserveBoundary", "true", "RichBool"), ("BoundaryWeight", "2.5", "RichFloat"), ("PreserveNormal", "true", "RichBool"),
+              ("PreserveTopology", "true", "RichBool"), ("OptimalPlacement", "false", "RichBool"), ("PlanarQuadric", "true", "RichBool"),
+              ("QualityWeight", "true", "RichBool"), ("AutoClean", "false", "RichBool")]
+    lines = ['<!DOCTYPE FilterScript>', '<FilterScript>', ' <filter name="Quadric Edge Collapse Decimation">']
+    lines += ['  <Param value="%s" %s type="%s" name="%s" description="d&lt;i>"/>' % (v, tip, t, n) for n, v, t in params]
+    lines += [' </filter>', ' <filter name="Merge Close Vertices">',
+              '  <Param min="0" max="0.1" %s description="x > y" name="Threshold" value="0.0021" type="RichAbsPerc"/>' % tip, ' </filter>',
+              ' <filter name="Remove Duplicate Faces"/>', ' <filter name="Remove Isolated pieces (wrt Face Num.)">',
+              '  <Param description="n:" name="MinComponentSize" %s value="333" type="RichInt"/>' % tip, ' </filter>',
+              ' <filter name="Remove Unreferenced Vertex"/>', '</FilterScript>']
+    path = tmp_path / "markup.mlx"
+    path.write_text("\n".join(lines) + "\n")
+    s = meshclean.load_script(str(path))
+    sp = s.simplify_params
+    assert s.simplify == 1 and sp.target_faces == 5000 and abs(sp.target_perc - 0.35) < 1e-7 and abs(sp.quality_thr - 0.45) < 1e-7
+    assert abs(sp.boundary_weight - 2.5) < 1e-7
+    assert (sp.preserve_boundary, sp.preserve_normal, sp.preserve_topology, sp.optimal_placement, sp.planar_quadric, sp.quality_weight,
+            sp.auto_clean) == (1, 1, 1, 0, 1, 1, 0)
+    assert (s.merge_close_vertices, s.remove_duplicate_faces, s.remove_small_components, s.remove_unreferenced) == (1, 1, 1, 1)
+    assert abs(s.merge_distance - 0.0021) < 1e-9 and s.min_component_faces == 333
+
+
 def test_shipped_script_and_cli(tmp_path):
-    path = REF_MLX if os.path.exists(REF_MLX) else str(tmp_path / "simplify.mlx")
-    if path != REF_MLX:
-        open(path, "w").write(SIMPLIFY_MLX)
+    path = str(tmp_path / "simplify.mlx")
+    open(path, "w").write(SIMPLIFY_MLX)
     for p in (path, str(tmp_path / "mine.mlx")):
         if p != path:
             open(p, "w").write(SIMPLIFY_MLX)

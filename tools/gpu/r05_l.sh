@@ -9,7 +9,6 @@ cd /tmp
 SF_RUN_TIMING=1 python - <<'PY' 2>&1 | cut -c1-420
 import os, sys
 sys.path.insert(0, os.environ["GRAFT_REPO_ROOT"])
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from scannet_amd import fusion, sens, synth
 W, H, cw, ch = 640, 480, 1296, 968
 fx, fy, mx, my = synth.intrinsics(W, H)
