@@ -236,6 +236,33 @@ int sf_fuse_run_prepare(const struct sf_sens* s, const sf_params* p, int device)
 struct sf_mesh;
 int sf_fuser_extract_mesh(sf_fuser* f, struct sf_mesh** out);
 
+/* Ray casting: depth, world normal and colour images of the fused volume seen from a camera (the model view DepthSensing.exe renders every frame;
+ * the ray-cast keys of Server/tools/recons/zParametersScanNet.txt:22-23,36-37,61-63).  The semantics, per pixel, are DESIGN.md section "Ray casting".
+ * A miss gives depth -inf, normal (-inf, -inf, -inf), colour 0, 0, 0.  A ray cast changes nothing in the volume, its counters or frame numbering. */
+typedef struct sf_raycast_params {
+  int32_t width, height;            /* s_rayCastWidth / Height; 0: the fuser's integration size                                  */
+  float fx, fy, mx, my;             /* all 0: the fuser's depth intrinsics scaled by width / W, height / H                       */
+  float depth_min, depth_max;       /* s_renderDepthMin / Max: 0.1, 6.0                                                          */
+  float ray_increment_factor;       /* s_SDFRayIncrementFactor: 0.8 (sample spacing = factor x s_SDFTruncation)                  */
+  float thres_sample_dist_factor;   /* s_SDFRayThresSampleDistFactor: 50.5                                                       */
+  float thres_dist_factor;          /* s_SDFRayThresDistFactor: 50.0                                                             */
+  int32_t refine_iters;             /* regula-falsi steps, 1..8: 3                                                               */
+  int32_t reserved[4];
+} sf_raycast_params;
+void sf_raycast_params_default(sf_raycast_params* r);
+/* the seven keys above from an mLib ParameterFile (s_rayCastWidth / Height -> width / height); keys that are absent leave *r as it is */
+int sf_raycast_params_load_file(const char* path, sf_raycast_params* r);
+/* The image size W x H these parameters give on this fuser (what the buffers below must hold), or SF_ERR_INVALID_ARG as the calls below. */
+int sf_fuser_raycast_size(sf_fuser* f, const sf_raycast_params* r, int32_t* width, int32_t* height);
+/* One pose (row-major camToWorld), host buffers, synchronous: depth W*H f32 (metres along camera z), normals W*H*3 f32, rgb W*H*3 u8; any
+ * output may be NULL.  SF_ERR_INVALID_ARG for a size <= 0 after defaults, a non-finite parameter, depth_min >= depth_max, refine_iters outside
+ * 1..8, a non-positive sample spacing, or a ray that would take more than 65 536 samples (DESIGN.md section "Ray casting"). */
+int sf_fuser_raycast(sf_fuser* f, const float pose[16], const sf_raycast_params* r, float* depth, float* normals_xyz, uint8_t* rgb);
+/* n poses (host, 16 floats each; a pose with a non-finite element in its first three rows -- the all -inf "tracking lost" pose among them --
+ * gives an all-miss image), outputs in HBM image after image; queued on sf_fuser_stream behind
+ * every frame queued on the handle before it, and ahead of everything queued after it. */
+int sf_fuser_raycast_device(sf_fuser* f, const float* poses, uint64_t n, const sf_raycast_params* r, void* d_depth, void* d_normals_xyz, void* d_rgb);
+
 /* Host <-> device helpers so that callers without a HIP binding can stage inputs in HBM. */
 int sf_device_malloc(int device, uint64_t bytes, void** out);
 int sf_device_free(void* p);

@@ -352,6 +352,7 @@ struct sf_fuser {
   void* mc_bounce[2] = {nullptr, nullptr};            // page-locked bounce buffers of the mesh download (mc.hip), allocated on first use
   hipEvent_t mc_bounce_ev[2] = {nullptr, nullptr};
   double mc_timing[12] = {0};   // phases of the most recent sf_fuser_extract_mesh (mc.hip; sf_fuser_mc_timing)
+  hipEvent_t ev_raycast[3] = {nullptr, nullptr, nullptr};   // raycast.hip: the two front streams' tails before a ray cast, the ray cast itself (made on first use)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
 };

@@ -7,6 +7,7 @@
 // tree (.gitmodules:1-3), the grammar is taken from the shipped files and from the in-tree X-macro
 // readers (Alignment/src/globalAppState.h:8-41).
 #include <cctype>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -84,13 +85,10 @@ bool parse_float(const std::string& tok, float* out) {
   return true;
 }
 
-}  // namespace
-
-SF_API int sf_params_load_file(const char* path, sf_params* p) {
-  if (!path || !p) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+// the statements of an mLib ParameterFile: name -> value tokens (a later statement of the same name wins)
+int read_param_file(const char* path, std::map<std::string, std::vector<std::string>>& kv) {
   std::ifstream in(path);
   if (!in) return sf::fail(SF_ERR_IO, "could not open parameter file %s", path);
-  std::map<std::string, std::vector<std::string>> kv;
   std::string line;
   int lineno = 0;
   while (std::getline(in, line)) {
@@ -123,6 +121,16 @@ SF_API int sf_params_load_file(const char* path, sf_params* p) {
     if (name.empty()) return sf::fail(SF_ERR_FORMAT, "%s:%d: empty parameter name", path, lineno);
     kv[name] = toks;
   }
+  return SF_OK;
+}
+
+}  // namespace
+
+SF_API int sf_params_load_file(const char* path, sf_params* p) {
+  if (!path || !p) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  std::map<std::string, std::vector<std::string>> kv;
+  int rc = read_param_file(path, kv);
+  if (rc != SF_OK) return rc;
   auto getf = [&](const char* k, float* dst) -> int {
     auto it = kv.find(k);
     if (it == kv.end()) return SF_OK;
@@ -141,7 +149,6 @@ SF_API int sf_params_load_file(const char* path, sf_params* p) {
     *dst = (int64_t)std::strtoll(t.c_str(), nullptr, 10);
     return SF_OK;
   };
-  int rc;
 #define GETF(key, field) if ((rc = getf(key, &p->field)) != SF_OK) return rc
   GETF("s_sensorDepthMax", depth_max);
   GETF("s_sensorDepthMin", depth_min);
@@ -171,6 +178,38 @@ SF_API int sf_params_load_file(const char* path, sf_params* p) {
   v = p->weight_wrap;  if ((rc = geti("s_scanfuseWeightWrap", &v)) != SF_OK) return rc;  p->weight_wrap = (int32_t)v;
   if (!(p->voxel_size > 0) || p->hash_num_buckets == 0 || p->num_sdf_blocks == 0)
     return sf::fail(SF_ERR_FORMAT, "%s: non-positive voxel size / hash size", path);
+  return SF_OK;
+}
+
+SF_API void sf_raycast_params_default(sf_raycast_params* r) {
+  if (!r) return;
+  std::memset(r, 0, sizeof(*r));
+  r->depth_min = 0.1f; r->depth_max = 6.0f;    // s_renderDepthMin / Max (zParametersScanNet.txt:36-37)
+  r->ray_increment_factor = 0.8f;              // s_SDFRayIncrementFactor (:61)
+  r->thres_sample_dist_factor = 50.5f;         // s_SDFRayThresSampleDistFactor (:62)
+  r->thres_dist_factor = 50.0f;                // s_SDFRayThresDistFactor (:63)
+  r->refine_iters = 3;
+}
+
+// the ray-cast keys of the same file (zParametersScanNet.txt:22-23,36-37,61-63), which sf_params_load_file leaves alone
+SF_API int sf_raycast_params_load_file(const char* path, sf_raycast_params* r) {
+  if (!path || !r) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  std::map<std::string, std::vector<std::string>> kv;
+  const int rc = read_param_file(path, kv);
+  if (rc != SF_OK) return rc;
+  const struct { const char* key; float* f; int32_t* i; } keys[] = {
+      {"s_rayCastWidth", nullptr, &r->width}, {"s_rayCastHeight", nullptr, &r->height},
+      {"s_renderDepthMin", &r->depth_min, nullptr}, {"s_renderDepthMax", &r->depth_max, nullptr},
+      {"s_SDFRayIncrementFactor", &r->ray_increment_factor, nullptr},
+      {"s_SDFRayThresSampleDistFactor", &r->thres_sample_dist_factor, nullptr}, {"s_SDFRayThresDistFactor", &r->thres_dist_factor, nullptr}};
+  for (const auto& k : keys) {
+    auto it = kv.find(k.key);
+    if (it == kv.end()) continue;
+    float v;
+    if (it->second.empty() || !parse_float(it->second[0], &v) || !std::isfinite(v)) return sf::fail(SF_ERR_FORMAT, "%s: bad value for %s", path, k.key);
+    if (k.f) *k.f = v;
+    else *k.i = (int32_t)std::strtol(it->second[0].c_str(), nullptr, 10);
+  }
   return SF_OK;
 }
 

@@ -22,6 +22,7 @@
 #include <unistd.h>
 
 #include <cerrno>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +35,15 @@
 #include "scanfuse.h"
 
 extern char** environ;
+
+// The ray cast of --render-depth is the one use of these device-half entry points here, and tests/fake_fuser links this source against a stand-in
+// of the device half that does not provide them: weak references, checked before use.
+#pragma weak sf_fuser_raycast_size
+#pragma weak sf_fuser_raycast_device
+#pragma weak sf_fuser_sync
+#pragma weak sf_device_malloc
+#pragma weak sf_device_download
+#pragma weak sf_device_free
 
 namespace {
 
@@ -66,6 +76,8 @@ struct Args {
   int ranks = 1, rank = -1;      // rank >= 0: this process is one rank of a partitioned run (started by the parent below)
   bool share_gpu = false;        // testing aid: every rank on the same device
   std::string ipc;               // the directory the ranks exchange through
+  const char* render_dir = nullptr;   // --render-depth=<dir>: ray-cast depth images of the fused volume (see render_depth below)
+  int render_every = 1;
   const char* pos[8];
   int n_pos = 0;
 };
@@ -146,6 +158,64 @@ std::string output_path(const Args& a) {
   const size_t dot = out.find_last_of('.');
   if (dot != std::string::npos) out = out.substr(0, dot);
   return out + "_vh.ply";
+}
+
+// ---- --render-depth=<dir> [--render-every=N] (not an argument of the tool this replaces): after the mesh, the volume ray-cast at the pose of every N-th
+// frame whose pose is valid -- sf_raycast_params from the parameter file (s_rayCastWidth / Height, s_renderDepthMin / Max, s_SDFRay*), the fuser's
+// intrinsics -- written as <dir>/<frame>.png: 16-bit depth in the file's depth units, round(z * depth_shift) clamped to 65535, 0 where the ray missed
+// (the layout of SensReader/python's export_depth_images).
+int render_depth(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info& info) {
+  if (!sf_fuser_raycast_size || !sf_fuser_raycast_device || !sf_fuser_sync || !sf_device_malloc || !sf_device_download || !sf_device_free)
+    return die_msg("--render-depth: this libscanfuse has no ray caster");
+  sf_raycast_params rp;
+  sf_raycast_params_default(&rp);
+  if (sf_raycast_params_load_file(a.pos[1], &rp) != SF_OK) return die("ray-cast parameters");
+  int32_t W = 0, H = 0;   // the library's own answer: the buffers below hold exactly what the kernel writes
+  if (sf_fuser_raycast_size(fuser, &rp, &W, &H) != SF_OK) return die("ray-cast parameters");
+  ::mkdir(a.render_dir, 0777);   // may exist already
+  struct stat st;
+  if (::stat(a.render_dir, &st) != 0 || !S_ISDIR(st.st_mode)) return die_msg("could not create the directory %s", a.render_dir);
+  const uint64_t BATCH = 32;
+  const size_t npx = (size_t)W * H;
+  const int device = std::getenv("SF_DEVICE") ? std::atoi(std::getenv("SF_DEVICE")) : 0;
+  void* d_depth = nullptr;
+  if (sf_device_malloc(device, BATCH * npx * 4, &d_depth) != SF_OK) return die("ray-cast buffer");
+  std::vector<float> poses, depth(BATCH * npx);
+  std::vector<uint64_t> frames;
+  std::vector<uint16_t> img(npx);
+  uint64_t written = 0;
+  int rc = 0;
+  for (uint64_t i = 0; i <= info.num_frames && !rc; i += (uint64_t)a.render_every) {
+    if (i < info.num_frames) {
+      float pose[16];
+      int valid = 0;
+      if (sf_sens_pose(sens, i, pose, &valid) != SF_OK) { rc = die("pose"); break; }
+      if (valid) {
+        poses.insert(poses.end(), pose, pose + 16);
+        frames.push_back(i);
+      }
+    }
+    if (frames.size() == BATCH || (i + (uint64_t)a.render_every > info.num_frames && !frames.empty())) {
+      if (sf_fuser_raycast_device(fuser, poses.data(), frames.size(), &rp, d_depth, nullptr, nullptr) != SF_OK || sf_fuser_sync(fuser) != SF_OK) { rc = die("ray cast"); break; }
+      if (sf_device_download(depth.data(), d_depth, frames.size() * npx * 4) != SF_OK) { rc = die("ray-cast download"); break; }
+      for (size_t j = 0; j < frames.size() && !rc; j++) {
+        const float* z = depth.data() + j * npx;
+        for (size_t k = 0; k < npx; k++) {
+          const float v = z[k] * info.depth_shift;
+          img[k] = z[k] > 0.0f ? (uint16_t)std::min(65535.0f, std::round(v)) : 0;
+        }
+        const std::string out = std::string(a.render_dir) + "/" + std::to_string(frames[j]) + ".png";
+        if (sf_png_write_gray(out.c_str(), img.data(), (uint32_t)W, (uint32_t)H, 16) != SF_OK) rc = die("png");
+        else written++;
+      }
+      poses.clear();
+      frames.clear();
+    }
+    if (i == info.num_frames) break;
+  }
+  sf_device_free(d_depth);
+  if (!rc) say("Ray-cast %llu depth images (%d x %d, every %d frames) written to %s\n", (unsigned long long)written, W, H, a.render_every, a.render_dir);
+  return rc;
 }
 
 // ---- one process, one GPU: the whole scan (ranks == 1) or this rank's stripes of it ------------------------------------------------------------------
@@ -272,6 +342,7 @@ int fuse_scan(const Args& a) {
     say("Mesh with %llu vertices, %llu faces written to %s\n", (unsigned long long)nv, (unsigned long long)nf, out.c_str());
   }
   sf_mesh_free(mesh);
+  if (a.render_dir && render_depth(a, fuser, sens, info) != 0) return 1;
   sf_fuser_destroy(fuser);
   sf_sens_close(sens);
   return 0;
@@ -412,6 +483,8 @@ int main(int argc, const char** argv_in) {
     else if (!std::strcmp(s, "--share-gpu")) a.share_gpu = true;
     else if (!std::strncmp(s, "--rank-of=", 10)) a.rank = std::atoi(s + 10);
     else if (!std::strncmp(s, "--exchange-dir=", 15)) a.ipc = s + 15;
+    else if (!std::strncmp(s, "--render-depth=", 15) && s[15]) a.render_dir = s + 15;
+    else if (!std::strncmp(s, "--render-every=", 15)) a.render_every = std::atoi(s + 15);
     else if (i > 0 && !std::strncmp(s, "--", 2)) bad = true;
     else if (a.n_pos < 8) a.pos[a.n_pos++] = s;
   }
@@ -419,6 +492,9 @@ int main(int argc, const char** argv_in) {
     std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
     return 255;
   }
+  if (a.render_dir && a.ranks > 1)
+    return die_msg("--render-depth ray-casts one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to render", a.ranks);
+  if (a.render_every < 1) return die_msg("--render-every=%d: expected a positive frame step", a.render_every);
   if (a.rank >= 0) {
     std::snprintf(g_prefix, sizeof g_prefix, "[rank %d/%d] ", a.rank, a.ranks);
     std::setvbuf(stdout, nullptr, _IOLBF, 0);   // whole lines into the stream the ranks share

@@ -38,6 +38,37 @@ def load_params(path, base=None):
     return p
 
 
+class SfRaycastParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("mx", C.c_float), ("my", C.c_float),
+                ("depth_min", C.c_float), ("depth_max", C.c_float),
+                ("ray_increment_factor", C.c_float), ("thres_sample_dist_factor", C.c_float), ("thres_dist_factor", C.c_float),
+                ("refine_iters", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def default_raycast_params(**over):
+    """sf_raycast_params_default (zParametersScanNet.txt's ray-cast values; size and intrinsics 0 = the fuser's); keyword overrides."""
+    r = SfRaycastParams()
+    L = _abi.lib()
+    L.sf_raycast_params_default.argtypes = [C.POINTER(SfRaycastParams)]
+    L.sf_raycast_params_default.restype = None
+    L.sf_raycast_params_default(C.byref(r))
+    for k, v in over.items():
+        if not hasattr(r, k) or k == "reserved":
+            raise AttributeError("sf_raycast_params has no field %r" % k)
+        setattr(r, k, v)
+    return r
+
+
+def load_raycast_params(path, base=None):
+    """The ray-cast keys (s_rayCastWidth / Height, s_renderDepthMin / Max, s_SDFRay*) of an mLib ParameterFile."""
+    r = base if base is not None else default_raycast_params()
+    L = _abi.lib()
+    L.sf_raycast_params_load_file.argtypes = [C.c_char_p, C.POINTER(SfRaycastParams)]
+    check(L.sf_raycast_params_load_file(str(path).encode(), C.byref(r)))
+    return r
+
+
 def device_count():
     n = C.c_int(0)
     rc = _abi.lib().sf_device_count(C.byref(n))
@@ -280,6 +311,39 @@ class Fuser:
         h = C.c_void_p()
         check(_abi.lib().sf_fuser_extract_mesh(self._h, C.byref(h)))
         return Mesh(h)
+
+    # -- ray casting (DESIGN.md "Ray casting") ---------------------------------------------------------
+    def raycast_size(self, params=None):
+        """(width, height) of the images raycast() / raycast_device() make with these parameters (sf_fuser_raycast_size; invalid ones raise)."""
+        r = params if params is not None else default_raycast_params()
+        L = _abi.lib()
+        L.sf_fuser_raycast_size.argtypes = [C.c_void_p, C.POINTER(SfRaycastParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        w, h = C.c_int32(0), C.c_int32(0)
+        check(L.sf_fuser_raycast_size(self._h, C.byref(r), C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def raycast(self, pose, params=None, normals=True, color=True):
+        """Ray-cast the volume from camToWorld `pose` -> (depth [H,W] f32 metres along camera z, normals [H,W,3] f32 world frame or None,
+        rgb [H,W,3] u8 or None).  Misses: depth and normal -inf, colour 0."""
+        r = params if params is not None else default_raycast_params()
+        W, H = self.raycast_size(r)
+        pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(16)
+        depth = np.empty((H, W), np.float32)
+        nrm = np.empty((H, W, 3), np.float32) if normals else None
+        rgb = np.empty((H, W, 3), np.uint8) if color else None
+        L = _abi.lib()
+        L.sf_fuser_raycast.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SfRaycastParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        check(L.sf_fuser_raycast(self._h, _ptr(pose), C.byref(r), _ptr(depth), _ptr(nrm), _ptr(rgb)))
+        return depth, nrm, rgb
+
+    def raycast_device(self, poses, d_depth=None, d_normals=None, d_rgb=None, params=None):
+        """n poses ([n,16] or [n,4,4], host) -> device buffers (torch tensors or raw pointers), image after image: depth n*H*W f32,
+        normals n*H*W*3 f32, rgb n*H*W*3 u8; any may be None.  Queued on self.stream, returns without waiting."""
+        r = params if params is not None else default_raycast_params()
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+        L = _abi.lib()
+        L.sf_fuser_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfRaycastParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        check(L.sf_fuser_raycast_device(self._h, _ptr(poses), len(poses), C.byref(r), _ptr(d_depth), _ptr(d_normals), _ptr(d_rgb)))
 
     def export_blocks(self):
         """-> (coords int32 [n,3], voxels VOXEL_DTYPE [n,512]) sorted lexicographically by (x,y,z)."""
