@@ -19,25 +19,13 @@ extern "C" {
  *   "overlap"     0/1    pre-pass / allocation / compaction of the next batch on a second stream (default 1)
  *   "xcd_walk"    0/1    each XCD walks one contiguous eighth of the block list (default 1)
  *   "pipe"        0/1    colourless one-frame passes run the software-pipelined persistent kernel (default 1)
- *   "pipe_wgs"    1..3   persistent workgroups per CU of that kernel (default 3)
  *   "pipe_overlap" -1/0/1 the next frame's pre-pass / allocation / compaction runs on the second stream beside that kernel: -1 = when the previous
  *                        pass touched more than 512 MiB of tiles (default), 0 never, 1 always
- *   "nt"          -1/0/1 that kernel's tile loads and stores non-temporal: -1 = when the previous pass touched more than 512 MiB of tiles (default)
- *   "front_cus"   0..128 the second stream owns that many CUs (spread over the chip), the main stream the rest (hipExtStreamCreateWithCUMask); 0 = shared
  *   "alloc_group" 1..32  consecutive frames one allocation workgroup walks (default 16: half of a 32-frame pass)
- *   "alloc_group_head" 0..32 the same for the FIRST pass of a multi-pass batch call, whose front chain nothing hides (default 4; 0 = like every pass)
  *   "alloc_ray"   0/1    the allocation kernel's occupancy bitmap in ray space (k_alloc_ray; default: whenever the voxel size lets the window hold a
  *                        pixel tile's rays: >= 2.5 mm voxels with the shipped camera) or as a 32^3-block cube anchored at the first ray (k_alloc)
- *   "prepass_fuse" 0/1   one colourless frame per pass: the allocation kernel converts the depth itself (default 1), no separate pre-pass launch
- *   "ramp"        0..32  frames of the FIRST pass of a sf_fuser_integrate_batch_device call (default 8; 0 = a full pass): nothing overlaps that
- *                        pass's pre-pass / allocation, so a short one starts the pipeline sooner
- *   "ramp_geo"    0/1    the passes behind the first one double (ramp, 2 ramp, 4 ramp, ... batch) instead of jumping to the batch size, and a call of more than
- *                        `ramp` but no more than `batch` frames is fused as two halves (default 1)
  *   "tail_wide"   0/1    the LAST pass of a sf_fuser_integrate_batch_device call (no front chain runs beside it) takes the variant of k_integrate that fuses
  *                        the tile in halves at 8 waves per SIMD (default 1: +0.8 % on a 20-frame call; slower for a pass as a whole when allocation runs beside it)
- *   "xrow"        0/1    passes of several frames run k_integrate in the x-row lane layout: a lane holds one x-row of the block (y = lane & 7, z = lane >> 3)
- *                        instead of two x-neighbours in four z-layers -- the same voxels, 18 fma fewer per lane and frame, and the gathers of one instruction
- *                        fall on two image rows instead of four or five (default 1)
  *   "front_prio"  -1/0/1 which front stream a pass's pre-pass / allocation / compaction goes down: -1 (default) a second one at the device's LOWEST priority beside the
  *                        persistent kernel of one frame per launch out of cache reach (at the highest priority the allocation's 72 KiB workgroups take the LDS the integrate
  *                        kernel's third workgroup per CU needs: 0.54 -> 0.62 of peak HBM shipped at 1 mm), the high-priority one for passes of several frames; 1 always high
@@ -68,7 +56,7 @@ int sf_fuser_mc_timing(const sf_fuser* f, double* out, int n);
  * for streams the device leaves to the host inflater (anything but ONE final fixed-Huffman block -- what the reference's writer and this
  * library's emit; expect_bytes not a multiple of 4), SF_ERR_FORMAT for corrupt streams and streams that inflate to another size. */
 int sf_zlib_inflate_gpu(const void* src, uint64_t src_bytes, uint64_t expect_bytes, int device, void* dst);
-/* The two kernels of that path timed apart (HIP events) on `count` <= 32 resident streams: microseconds per launch (tools/gpu/inflate_bench.py); skip (a -DSF_MEASURE_ABLATE build only, SF_ERR_UNSUPPORTED otherwise): 1 = the token kernel without its writing pass, 2 = without its scans either. */
+/* The two kernels of that path timed apart (HIP events) on `count` <= 32 resident streams: microseconds per launch (tools/gpu/inflate_bench.py); skip must be 0 (SF_ERR_UNSUPPORTED otherwise). */
 int sf_zlib_inflate_gpu_bench(const void* const* srcs, const uint64_t* src_bytes, int count, uint64_t expect_bytes, int device, int repeats, int skip, double* us_tokens, double* us_copy);
 
 /* Where the frames of the calling thread's last sf_fuse_run were decoded: out[0] zlib depth frames inflated on the device, out[1] by the host threads

@@ -12,12 +12,12 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the TSDF / Segmentator arithmetic is specified operation by operation;
 # only explicit fmaf() may fuse.  HIP's default correctly-rounded fp32 divide / sqrt is relied upon.
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden", "-Wall", "-Wno-unused-result",
-          "-I" + os.path.join(ROOT, "include")] + os.environ.get("SCANFUSE_BUILD_FLAGS", "").split()   # e.g. -DSF_MEASURE_ABLATE for tools/gpu/r03_ablate.sh
+          "-I" + os.path.join(ROOT, "include")] + os.environ.get("SCANFUSE_BUILD_FLAGS", "").split()   # extra compiler flags, e.g. -g or -save-temps
 
 
 # fuser.hip / calib.hip: the voxel pairs of the integrate kernels are two plain fp32 operations each (fuser_internal.h: packed fp32 buys no issue rate on
 # gfx950); the SLP vectoriser would pack them again
-PER_FILE = {} if "-DSF_PACKED_PAIRS" in COMMON else {"fuser.hip": ["-fno-slp-vectorize"], "calib.hip": ["-fno-slp-vectorize"]}
+PER_FILE = {"fuser.hip": ["-fno-slp-vectorize"], "calib.hip": ["-fno-slp-vectorize"]}
 
 
 def sources():

@@ -321,17 +321,6 @@ __device__ inline void raise_high_water(const HashRefs& h, int hw) {
 }
 __device__ inline void give_block(const HashRefs& h, HashEntry* e, uint64_t key, int at) { raise_high_water(h, give_block_quiet(h, e, key, at)); }
 
-// -DSF_ALLOC_TIMING (measurement build, tools/gpu/alloc_1mm_probe.py): where a workgroup of k_alloc spends its time -- thread 0 adds the 100 MHz clock between
-// the barriers that separate the phases into g_alloc_t (sf_alloc_timing_read): [0] zeroing + ray set-up, [1] anchoring, [2] walk, [3] scan, [4] drain, [5] whole
-// workgroup, [8] the longest workgroup, [9] rounds walked, [10] workgroups
-#ifdef SF_ALLOC_TIMING
-__device__ unsigned long long g_alloc_t[16];
-__device__ unsigned int g_alloc_log[1 + 256 * 12];   // workgroups that took more than 250 us: [0] how many, then 12 words each (sf_alloc_timing_log)
-#define AT_MARK(i) do { if (threadIdx.x == 0) { const unsigned long long now_ = wall_clock64(); atomicAdd(&g_alloc_t[i], now_ - at_prev_); at_ph_[i] += (unsigned)(now_ - at_prev_); at_prev_ = now_; } } while (0)
-#else
-#define AT_MARK(i) do { } while (0)
-#endif
-
 template <int WIN_LOG2, bool MULTI>
 __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_all, HashEntry* table, int32_t* heap,
                                                uint64_t* block_keys, int32_t* block_entry, uint8_t* block_flags, int32_t* counters, ParamsK P,
@@ -339,10 +328,7 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
   constexpr int WIN = 1 << WIN_LOG2;                // window edge in blocks
   // the queue of a workgroup: at 1 mm voxels (WIN 64) a pixel tile's rays visit ~1 300 blocks per frame -- with the 512 entries that serve 4 mm ALL of them
   // overflowed into the one-by-one path (sf_fuser_alloc_direct_count: 1.3 M blocks per frame, k_alloc<6> 2.2 ms: tools/gpu/alloc_1mm_probe.py)
-#ifndef SF_ALLOC6_LIST
-#define SF_ALLOC6_LIST 4096
-#endif
-  constexpr int LIST = WIN_LOG2 >= 6 ? SF_ALLOC6_LIST : ALLOC_LIST;
+  constexpr int LIST = WIN_LOG2 >= 6 ? 4096 : ALLOC_LIST;
   // (8 192 entries and a 2 048-slot set take the direct path from 1.3 M to 8 k blocks per frame and the kernel nowhere: its time is the table probes themselves,
   // profiles/r06_alloc_1mm.txt; 4 096 entries keep two workgroups per CU)
   constexpr int SET_LOG2 = 8, SET = 1 << SET_LOG2;
@@ -363,11 +349,6 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
   // trip the wave waits for: at 1 mm voxels a tile names ~1 300 blocks per frame and a wave of k_alloc<6> spent its life -- 610 scalar loads, three quarters
   // of its cycles waiting (profiles/r06_pmc_alloc_1mm.txt) -- in that chain
   __shared__ uint32_t s_fk[2][sizeof(FrameK) / 4];
-#ifdef SF_ALLOC_TIMING
-  unsigned long long at_prev_ = wall_clock64();
-  const unsigned long long at_start_ = at_prev_;
-  unsigned at_ph_[5] = {0, 0, 0, 0, 0}, at_rounds_ = 0, at_queued_ = 0;
-#endif
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) { s_count = 0; s_chooser = 256; s_anchored = 0; }
@@ -402,11 +383,7 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
   // the three words every workgroup of the launch shares were what a tile of a newly seen surface waited for: at 1 mm voxels ~1 900 new blocks, 8 iterations,
   // 25 us each; such workgroups (3 % of them) took 200 - 800 us where the mean is 59, and the longest one IS the kernel (profiles/r06_alloc_1mm.txt).
   auto drain = [&]() {
-#ifdef SF_ABLATE_ALLOC_PHASE2   // measurement only (the volume is WRONG): no table probes
-    const int n_unique = 0;
-#else
     const int n_unique = min(s_count, LIST);
-#endif
     uint32_t* const s_ent = reinterpret_cast<uint32_t*>(s_list);
     if (threadIdx.x == 0) s_claimed = 0;
     // DU keys per lane and iteration, their first probes side by side: the table is 16-byte entries scattered over hundreds of megabytes, a look-up is a chain
@@ -489,10 +466,7 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
     if (lane == 0) raise_high_water(h, hw);
   };
 
-#ifndef SF_ALLOC6_ROUNDS
-#define SF_ALLOC6_ROUNDS 8
-#endif
-  constexpr int ROUNDS = (WIN_LOG2 >= 6 && !MULTI) ? SF_ALLOC6_ROUNDS : 1;   // windows a frame's rays may be walked in before the slow path (below)
+  constexpr int ROUNDS = (WIN_LOG2 >= 6 && !MULTI) ? 8 : 1;   // windows a frame's rays may be walked in before the slow path (below)
   const bool in_image = x < P.W && y < P.H;
   const float kx = ((float)x - P.mx) / P.fx, ky = ((float)y - P.my) / P.fy;  // the pixel's ray direction is the same for every frame
   const float rvoxel = 1.0f / P.voxel;                                        // RN(1 / voxel) for world_to_block
@@ -567,7 +541,6 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
         for (int i = threadIdx.x; i < WIN_WORDS; i += 256) s_frame[i] = 0u;
       }
       __syncthreads();  // s_frame zeroed, previous frame's scan finished
-      AT_MARK(0);
       // The tile's rays stay inside a small region of block space: the first active lane of the first frame that has
       // one anchors the WIN^3 window there for the whole group.
       if (s_anchored == 0) {
@@ -608,18 +581,10 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
       }
       if (ROUNDS > 1 && s_chooser == 256) break;   // uniform: no ray (left) to walk
       const int anx = s_anchor[0], any_ = s_anchor[1], anz = s_anchor[2];
-      AT_MARK(1);
-#ifdef SF_ALLOC_TIMING
-      if (threadIdx.x == 0) { atomicAdd(&g_alloc_t[9], 1ull); at_rounds_++; }
-#endif
 
       // ---- DDA: one LDS bit per visited block
       bool left_window = false;
-#ifdef SF_ABLATE_ALLOC_WALK   // measurement only (the volume is WRONG): no DDA walk
-      if (false) {
-#else
       if (pending) {
-#endif
         int c_x = a_cx, c_y = a_cy, c_z = a_cz;   // (the ray's start stays: it may walk again)
         float tmx = a_tmx, tmy = a_tmy, tmz = a_tmz;
         uint64_t last_key = KEY_EMPTY;
@@ -665,9 +630,7 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
       }
       pending = left_window;
       __syncthreads();
-      AT_MARK(2);
       // ---- scan: blocks this frame visits that no earlier frame of the group queued -> frustum test -> queue
-#ifndef SF_ABLATE_ALLOC_SCAN   // measurement only (the volume is WRONG): no scan
       // A lane takes a WORD (32 x-consecutive blocks) as far as whole words go -- read it, take out what an earlier frame of the group queued and what the presence
       // cache knows -- and a BLOCK from there on: the wave then walks the words that have bits left two at a time, lane b of each half-wave testing block b.
       // (One thread per word all the way -- a loop over the word's bits around the frustum test -- kept a wave as long as the fullest of its 64 words: a tile that looks at
@@ -717,43 +680,19 @@ __global__ __launch_bounds__(256) void k_alloc(const float* __restrict__ depthf_
         }
         if (MULTI && queued) s_done[w] |= queued;  // word w is only ever touched by this lane
       }
-#endif
       if (ROUNDS > 1) {   // the queue is emptied between rounds
         __syncthreads();
-        AT_MARK(3);
-#ifdef SF_ALLOC_TIMING
-        if (threadIdx.x == 0) at_queued_ += (unsigned)s_count;
-#endif
         drain();
         __syncthreads();
-        AT_MARK(4);
         if (threadIdx.x == 0) s_count = 0;
       }
     }
   }
   __syncthreads();
-  AT_MARK(3);
   drain();
   for (int o = 32; o > 0; o >>= 1) { n_direct += __shfl_xor(n_direct, o); n_probed += __shfl_xor(n_probed, o); }
   if (lane == 0 && n_direct) atomicAdd(&counters[C_ALLOC_DIRECT], n_direct);
   if (lane == 0 && n_probed) atomicAdd(&counters[C_ALLOC_PROBED], n_probed);
-#ifdef SF_ALLOC_TIMING
-  __syncthreads();
-  AT_MARK(4);
-  if (threadIdx.x == 0) {
-    atomicAdd(&g_alloc_t[5], at_prev_ - at_start_);
-    atomicMax(&g_alloc_t[8], at_prev_ - at_start_);
-    atomicAdd(&g_alloc_t[10], 1ull);
-  }
-  if (threadIdx.x == 0 && at_prev_ - at_start_ > 25000ull) {
-    const unsigned slot = atomicAdd(&g_alloc_log[0], 1u);
-    if (slot < 256u) {
-      unsigned* r = &g_alloc_log[1 + 12 * slot];
-      r[0] = blockIdx.x | (blockIdx.y << 16); r[1] = at_rounds_; r[2] = at_ph_[0]; r[3] = at_ph_[1]; r[4] = at_ph_[2]; r[5] = at_ph_[3]; r[6] = at_ph_[4];
-      r[7] = (unsigned)(at_prev_ - at_start_); r[8] = (unsigned)n_direct; r[9] = (unsigned)n_probed; r[10] = at_queued_ + (unsigned)s_count; r[11] = 0;
-    }
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -788,7 +727,7 @@ struct WindowMap {
   int k0, sgn, su, ou, fu, sv, ov, fv;
 };
 template <int AXIS>
-__device__ inline bool ray_walk_bits(const RayWalk& r, const WindowMap& w, uint32_t* s_frame, bool no_atomics) {
+__device__ inline bool ray_walk_bits(const RayWalk& r, const WindowMap& w, uint32_t* s_frame) {
   // (a, u, v) = (AXIS, AXIS + 1, AXIS + 2) mod 3
   const int c_a = AXIS == 0 ? r.cx : (AXIS == 1 ? r.cy : r.cz), c_u = AXIS == 0 ? r.cy : (AXIS == 1 ? r.cz : r.cx), c_v = AXIS == 0 ? r.cz : (AXIS == 1 ? r.cx : r.cy);
   const int s_a = AXIS == 0 ? r.sx : (AXIS == 1 ? r.sy : r.sz), s_u = AXIS == 0 ? r.sy : (AXIS == 1 ? r.sz : r.sx), s_v = AXIS == 0 ? r.sz : (AXIS == 1 ? r.sx : r.sy);
@@ -808,7 +747,7 @@ __device__ inline bool ray_walk_bits(const RayWalk& r, const WindowMap& w, uint3
     const uint32_t bit = inwin ? (((uint32_t)k << (2 * RW_LAT_LOG2)) | (dv << RW_LAT_LOG2) | du) : 0xFFFFFFFFu;
     // lanes whose left neighbour (DPP row_shr:1) sets the same bit stay silent: 64 same-address ds_or serialise (see k_alloc)
     const uint32_t left = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFEu, (int)bit, 0x111, 0xF, 0xF, false);
-    if (inwin && left != bit && !no_atomics) atomicOr(&s_frame[bit >> 5], 1u << (bit & 31));
+    if (inwin && left != bit) atomicOr(&s_frame[bit >> 5], 1u << (bit & 31));
     left_window = left_window || !inwin;
     const bool go_x = tmx < tmy && tmx < tmz;
     const bool go_z = !go_x && tmz < tmy;
@@ -831,14 +770,10 @@ __device__ inline bool ray_walk_bits(const RayWalk& r, const WindowMap& w, uint3
 }
 
 template <bool MULTI>
-#ifndef SF_ALLOC_WAVES_MIN
-#define SF_ALLOC_WAVES_MIN 1   // waves per SIMD k_alloc_ray is register-budgeted for (8: <= 64 registers: a wave of it fits any slot a 64-register wave of k_integrate frees)
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SF_ALLOC_WAVES_MIN, 8))) void k_alloc_ray(const float* __restrict__ depthf_all, HashEntry* table, int32_t* heap,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_alloc_ray(const float* __restrict__ depthf_all, HashEntry* table, int32_t* heap,
                                                    uint64_t* block_keys, int32_t* block_entry, uint8_t* block_flags, int32_t* counters, ParamsK P,
-                                                   BatchFrames B, int group_frames, int ablate, const uint16_t* __restrict__ fuse_depth16,
+                                                   BatchFrames B, int group_frames, const uint16_t* __restrict__ fuse_depth16,
                                                    float* depthf_out, int compact_counter) {
-  // ablate (tune "alloc_ablate", measurements only -- the volume is wrong with any bit set): 1 no LDS atomics, 2 no scan, 4 no DDA walk, 8 no barriers
   // fuse_depth16 != nullptr (one frame per pass, no colour, no resampling: a live stream): the kernel is ALSO the depth pre-pass -- every lane
   // converts its own pixel (k_prepass's arithmetic), stores it for the integrate kernel's gathers and walks it; one launch and one
   // dependency hop less in a chain of four that is the whole frame time
@@ -856,7 +791,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SF_ALLOC_WA
   const int y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
   // No presence cache here (fuser_internal.h BrickCache: the cube window's kernels use it): the "already queued" bitmap of the ray-space window leaves this kernel
   // few look-ups to save -- 34.7 k against 34.8 k frames/s on the long stream with the cache on / off -- and its code, even switched off at run time, cost a 20-frame
-  // call into an empty volume 2 % (35.1 k -> 34.3 k, five libraries on one box: tools/gpu/r06_zr.sh).  The cache stays right: it only ever holds blocks the cube
+  // call into an empty volume 2 % (35.1 k -> 34.3 k, five libraries on one box: profiles/r06_alloc_1mm.txt).  The cache stays right: it only ever holds blocks the cube
   // kernels FOUND in the table, and whatever takes blocks out of the table clears it.
   const HashRefs h{table, heap, block_keys, block_entry, block_flags, counters, BrickCache{nullptr, 0u}, B.seq0};
   for (int i = threadIdx.x; i < ALLOC_SET; i += 256) s_keys[i] = KEY_EMPTY;
@@ -1019,7 +954,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SF_ALLOC_WA
     // coordinates relative to the window origin (ru, rv), so that a step costs an add on one of them instead of the whole map -- and the
     // three-way branch of the reference walk is evaluated as three lane masks (the same comparisons in the same order: x if strictly
     // smallest, else z if smaller than y, else y), so no lane waits for the branches the others take.
-    if (active && !(ablate & 4)) {
+    if (active) {
       // The axis the window runs along is the same for every lane of the workgroup (a scalar): the hot walk is compiled THREE times, once per
       // axis, and chosen by a scalar branch -- inside each copy "the window axis" is a compile-time name for one of x / y / z, so a step's
       // "which coordinate moves" is the very lane mask its comparison produced.  (With w_axis as a run-time select on the three masks the
@@ -1027,9 +962,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SF_ALLOC_WA
       const RayWalk rw{a_cx, a_cy, a_cz, a_sx, a_sy, a_sz, a_ex, a_ey, a_ez, a_tmx, a_tmy, a_tmz, a_tdx, a_tdy, a_tdz};
       const WindowMap wm{w_k0, w_sgn, w_su, w_ou, w_fu, w_sv, w_ov, w_fv};
       bool left_window;
-      if (w_axis == 0) left_window = ray_walk_bits<0>(rw, wm, s_frame, (ablate & 1) != 0);
-      else if (w_axis == 1) left_window = ray_walk_bits<1>(rw, wm, s_frame, (ablate & 1) != 0);
-      else left_window = ray_walk_bits<2>(rw, wm, s_frame, (ablate & 1) != 0);
+      if (w_axis == 0) left_window = ray_walk_bits<0>(rw, wm, s_frame);
+      else if (w_axis == 1) left_window = ray_walk_bits<1>(rw, wm, s_frame);
+      else left_window = ray_walk_bits<2>(rw, wm, s_frame);
       if (left_window) {   // the same walk once more (one copy, the axis a run-time value), this time for the blocks OUTSIDE the window: LDS hash set, then the global table
         const int c_a = w_axis == 0 ? a_cx : (w_axis == 1 ? a_cy : a_cz), c_u = w_axis == 0 ? a_cy : (w_axis == 1 ? a_cz : a_cx), c_v = w_axis == 0 ? a_cz : (w_axis == 1 ? a_cx : a_cy);
         const int s_a = w_axis == 0 ? a_sx : (w_axis == 1 ? a_sy : a_sz), s_u = w_axis == 0 ? a_sy : (w_axis == 1 ? a_sz : a_sx), s_v = w_axis == 0 ? a_sz : (w_axis == 1 ? a_sx : a_sy);
@@ -1085,53 +1020,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SF_ALLOC_WA
         }
       }
     }
-    if (!(ablate & 8)) __syncthreads();
+    __syncthreads();
     // ---- scan: thread t owns slab t (8 words): blocks this frame visits that no earlier frame of the group queued -> frustum test -> queue
-    if (!(ablate & 2)) {
-      const int k = (int)threadIdx.x;
-      const uint4 f0 = s_frame4[2 * k], f1 = s_frame4[2 * k + 1];
-      bool occupied = (f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w) != 0u;   // ~10 threads of the workgroup
-      if (MULTI && occupied) {
-        // the usual case inside a pass: everything this frame visits in the slab was queued by an earlier frame -- two more reads say so, and
-        // the slab is cleared for the next frame without walking its words
-        const uint4 d0 = s_done4[2 * k], d1 = s_done4[2 * k + 1];
-        if (((f0.x & ~d0.x) | (f0.y & ~d0.y) | (f0.z & ~d0.z) | (f0.w & ~d0.w) | (f1.x & ~d1.x) | (f1.y & ~d1.y) | (f1.z & ~d1.z) | (f1.w & ~d1.w)) == 0u) {
-          s_frame4[2 * k] = make_uint4(0, 0, 0, 0);
-          s_frame4[2 * k + 1] = make_uint4(0, 0, 0, 0);
-          occupied = false;
-        }
-      }
-      if (occupied) {
-        uint32_t* const s_done = reinterpret_cast<uint32_t*>(s_done4);
-        const int ca = w_sgn > 0 ? w_k0 + k : w_k0 - k;
-        const int cu0 = w_ou + ((w_su * k + w_fu) >> 12), cv0 = w_ov + ((w_sv * k + w_fv) >> 12);
-#pragma unroll 1
-        for (int w = 0; w < 8; w++) {   // the words come from LDS again: a register array indexed by w would live in scratch
-          const uint32_t fw = s_frame[8 * k + w];
-          if (fw == 0u) continue;
-          s_frame[8 * k + w] = 0u;      // ready for the next frame (nobody else touches this slab before the next barrier)
-          const uint32_t dw = MULTI ? s_done[8 * k + w] : 0u;
-          uint32_t bits = fw & ~dw, queued = 0u;
-          while (bits) {
-            const int b = __ffs((int)bits) - 1;
-            bits &= bits - 1u;
-            const int idx = w * 32 + b;
-            const int cu = cu0 + (idx & (RW_LAT - 1)), cv = cv0 + (idx >> RW_LAT_LOG2);
-            const int bx = w_axis == 0 ? ca : (w_axis == 1 ? cv : cu);
-            const int by = w_axis == 0 ? cu : (w_axis == 1 ? ca : cv);
-            const int bz = w_axis == 0 ? cv : (w_axis == 1 ? cu : ca);
-            if (!slab_owns(P, bx, by, bz)) { queued |= 1u << b; continue; }  // another GPU's block: never ours, stop looking at it
-            if (!block_in_frustum(P, F, bx, by, bz)) continue;  // a later frame may still want it
-            queued |= 1u << b;
-            const int pos = atomicAdd(&s_count, 1);
-            if (pos < ALLOC_LIST) { s_list[pos] = pack_key(bx, by, bz); s_birth[pos] = (uint8_t)j; }
-            else direct(pack_key(bx, by, bz), bx, by, bz, B.seq0 + (uint32_t)j);
-          }
-          if (MULTI && queued) s_done[8 * k + w] = dw | queued;
-        }
+    const int k = (int)threadIdx.x;
+    const uint4 f0 = s_frame4[2 * k], f1 = s_frame4[2 * k + 1];
+    bool occupied = (f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w) != 0u;   // ~10 threads of the workgroup
+    if (MULTI && occupied) {
+      // the usual case inside a pass: everything this frame visits in the slab was queued by an earlier frame -- two more reads say so, and
+      // the slab is cleared for the next frame without walking its words
+      const uint4 d0 = s_done4[2 * k], d1 = s_done4[2 * k + 1];
+      if (((f0.x & ~d0.x) | (f0.y & ~d0.y) | (f0.z & ~d0.z) | (f0.w & ~d0.w) | (f1.x & ~d1.x) | (f1.y & ~d1.y) | (f1.z & ~d1.z) | (f1.w & ~d1.w)) == 0u) {
+        s_frame4[2 * k] = make_uint4(0, 0, 0, 0);
+        s_frame4[2 * k + 1] = make_uint4(0, 0, 0, 0);
+        occupied = false;
       }
     }
-    if (!(ablate & 8)) __syncthreads();   // slabs re-zeroed before the next frame's rays set bits
+    if (occupied) {
+      uint32_t* const s_done = reinterpret_cast<uint32_t*>(s_done4);
+      const int ca = w_sgn > 0 ? w_k0 + k : w_k0 - k;
+      const int cu0 = w_ou + ((w_su * k + w_fu) >> 12), cv0 = w_ov + ((w_sv * k + w_fv) >> 12);
+#pragma unroll 1
+      for (int w = 0; w < 8; w++) {   // the words come from LDS again: a register array indexed by w would live in scratch
+        const uint32_t fw = s_frame[8 * k + w];
+        if (fw == 0u) continue;
+        s_frame[8 * k + w] = 0u;      // ready for the next frame (nobody else touches this slab before the next barrier)
+        const uint32_t dw = MULTI ? s_done[8 * k + w] : 0u;
+        uint32_t bits = fw & ~dw, queued = 0u;
+        while (bits) {
+          const int b = __ffs((int)bits) - 1;
+          bits &= bits - 1u;
+          const int idx = w * 32 + b;
+          const int cu = cu0 + (idx & (RW_LAT - 1)), cv = cv0 + (idx >> RW_LAT_LOG2);
+          const int bx = w_axis == 0 ? ca : (w_axis == 1 ? cv : cu);
+          const int by = w_axis == 0 ? cu : (w_axis == 1 ? ca : cv);
+          const int bz = w_axis == 0 ? cv : (w_axis == 1 ? cu : ca);
+          if (!slab_owns(P, bx, by, bz)) { queued |= 1u << b; continue; }  // another GPU's block: never ours, stop looking at it
+          if (!block_in_frustum(P, F, bx, by, bz)) continue;  // a later frame may still want it
+          queued |= 1u << b;
+          const int pos = atomicAdd(&s_count, 1);
+          if (pos < ALLOC_LIST) { s_list[pos] = pack_key(bx, by, bz); s_birth[pos] = (uint8_t)j; }
+          else direct(pack_key(bx, by, bz), bx, by, bz, B.seq0 + (uint32_t)j);
+        }
+        if (MULTI && queued) s_done[8 * k + w] = dw | queued;
+      }
+    }
+    __syncthreads();   // slabs re-zeroed before the next frame's rays set bits
   }
 
   // ---- phase 2: queued keys -> global hash, all lanes in parallel (k_alloc's)
@@ -1438,7 +1371,7 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_compactify_few(CompactArgs 
 //     clamped addresses, phase B applies the update under a select (a per-voxel early-out chain serialises eight
 //     L2 round trips and costs a scalar branch pair per test);
 //   * the lane's voxel pairs are written as v2f pairs (fuser_internal.h) and compiled as two plain fp32 operations each: on gfx950 a v_pk_*_f32 holds the
-//     SIMD as long as two plain ones and issues beside nothing (rounds 1-4 shipped the packed form; -DSF_PACKED_PAIRS still builds it);
+//     SIMD as long as two plain ones and issues beside nothing (rounds 1-4 shipped the packed form);
 //   * the two IEEE divisions of DESIGN.md 3.5 are expanded by hand.  1/pcz: v_rcp_f32 seed + two Newton steps --
 //     the arithmetic core of the compiler's own correctly rounded expansion without the div_scale / div_fixup
 //     range handling (pcz is a camera-space depth in metres; exhaustive check over all mantissas and seed errors up
@@ -1451,23 +1384,8 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_compactify_few(CompactArgs 
 
 constexpr int RTAB = 512;  // LDS table of correctly rounded 1/m, m = weight + weight_sample < 512
 
-// A wave-uniform value in a VECTOR register -- an experiment kept behind -DSF_VREG_CONSTANTS.  On gfx950 v_fma / v_mul / v_add_f32, v_add_u32, v_and_b32,
-// v_mov_b32 ... issue every ~2.2 cycles per SIMD when all their sources are vector registers or inline constants and every ~4.3 cycles as soon as one
-// source is a scalar register (tools/gpu/valu_peak.hip, profiles/r05_valu_issue_table.txt), and the compiler feeds the per-frame matrix and the camera
-// constants to every fma straight from the scalar registers they were loaded into.  Copying them into vector registers once per frame (18 v_mov, opaque
-// to the compiler) made the pass SLOWER (packed 830 -> 870 us, plain pairs 808 -> 837 us: profiles/r05_integrate_ab.txt).  The launch already runs at the
-// no-overlap price of its instruction mix (frac 1.03); why 88 fp32 instructions fewer in the 4.3-cycle class do not show up in it is not
-// understood -- the 18 extra moves per frame and what they do to the schedule cost more than the cheaper fma's gave back.
-__device__ inline float vreg(float x) {
-#ifdef SF_VREG_CONSTANTS
-  float r;
-  asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(x));
-  return r;
-#else
-  return x;
-#endif
-}
-// the per-frame / per-kernel constants the projection and the update multiply with, in vector registers (fuse_project, fuse_update)
+// the per-frame / per-kernel constants the projection and the update multiply with (fuse_project, fuse_update).  They stay in the scalar registers they are
+// loaded into: copying them into vector registers once per frame made the pass slower (plain pairs 808 -> 837 us: profiles/r05_integrate_ab.txt)
 struct FrameV {
   float ti[12];
   float fx, fy, mx, my, tscale, tbase;
@@ -1475,9 +1393,9 @@ struct FrameV {
 __device__ inline FrameV frame_constants(const ParamsK& P, const float* __restrict__ Ti) {
   FrameV F;
 #pragma unroll
-  for (int k = 0; k < 12; k++) F.ti[k] = vreg(Ti[k]);
-  F.fx = vreg(P.fx); F.fy = vreg(P.fy); F.mx = vreg(P.mx); F.my = vreg(P.my);
-  F.tscale = vreg(P.tscale); F.tbase = vreg(P.tbase);
+  for (int k = 0; k < 12; k++) F.ti[k] = Ti[k];
+  F.fx = P.fx; F.fy = P.fy; F.mx = P.mx; F.my = P.my;
+  F.tscale = P.tscale; F.tbase = P.tbase;
   return F;
 }
 
@@ -1743,10 +1661,6 @@ __device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti,
   const FrameV FV = frame_constants(P, Ti);
   if (XR) fuse_project_xr<J0, NJ>(P, FV, wxp, wy, wz[0], pz, pix, ok);   // wz[0]: the lane's one z
   else fuse_project<J0, NJ, false>(P, FV, wx, wy, wz, pz, pix, ok);
-#ifdef SF_ABLATE_GATHER   // measurement only (wrong voxels): every lane gathers ONE texel per row -- what do the gathers' cache look-ups cost a pass?
-#pragma unroll
-  for (int k = 0; k < 2 * NJ; k++) pix[k] = (uint32_t)(SF_ABLATE_GATHER == 1 ? 0 : (pix[k] & ~63u));
-#endif
   const uint32_t img_bytes = (uint32_t)(P.W * P.H) * 4u;
   if (COLOR) {
     // RGB-D: depth and colour of a pixel sit side by side in the pre-pass's texel plane -- one 8-byte gather per voxel (two 4-byte gathers into
@@ -1769,31 +1683,20 @@ __device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti,
 
 // 4 waves per SIMD (<= 128 VGPRs).  Tried for the one-frame-per-launch case: 5 waves / 96 VGPRs with the tile in two
 // half passes -- the spills cost more than the occupancy buys (183 us vs 112 us per launch).
-#ifndef SF_INT_WAVES
-#define SF_INT_WAVES 5   // workgroups (of 4 waves) per CU the register budget of k_integrate is set for (plain pairs: 91 registers)
-#endif
-#ifndef SF_INT_NJ
-#define SF_INT_NJ 4      // rows of the tile fused together per frame: 4 = the whole tile at once, 2 / 1 = in halves / quarters (fewer live registers)
-#endif
+constexpr int INT_WAVES = 5;   // workgroups (of 4 waves) per CU the register budget of k_integrate is set for (plain pairs: 91 registers)
+constexpr int INT_NJ = 4;      // rows of the tile fused together per frame: 4 = the whole tile at once, 2 = in halves (fewer live registers)
 // NJ = 2 (the tile in halves: 63 registers, 8 waves per SIMD) looks 15 % faster in the two-stream schedule (696 against 814 us per launch) only because its
 // waves take every register of the SIMDs and the allocation kernel on the other stream starves (372 -> 818 us): the pass as a whole is slower
 // (profiles/r05_integrate_ab.txt).  Alone the two variants are within a few per cent.  NJ = 2 runs the LAST pass of a sf_fuser_integrate_batch_device call
 // -- nothing is queued behind that pass, no front chain runs beside it: +0.8 % on a 20-frame call, measured --, every other pass NJ = 4 at 5 waves.  Same
 // voxels either way (tests/test_gpu_tsdf.py::test_batched_pass_equals_frame_by_frame runs both).
-template <int SIGN, int COLOR, bool TAB, int WM, bool ROWS, int NJ = SF_INT_NJ, bool XR = false>
-__global__ __launch_bounds__(256, NJ == 2 ? (XR ? 7 : 8) : SF_INT_WAVES) void k_integrate(uint4* __restrict__ voxels, const uint64_t* __restrict__ block_keys,
+template <int SIGN, int COLOR, bool TAB, int WM, bool ROWS, int NJ = INT_NJ, bool XR = false>
+__global__ __launch_bounds__(256, NJ == 2 ? (XR ? 7 : 8) : INT_WAVES) void k_integrate(uint4* __restrict__ voxels, const uint64_t* __restrict__ block_keys,
                                                    const int32_t* __restrict__ compact, const uint32_t* __restrict__ cmask,
                                                    const float* __restrict__ depthf_all, const uint2* __restrict__ texel_all,
                                                    int32_t* counters, int32_t* host_mirror, int compact_counter, int xcd_walk, ParamsK P,
                                                    BatchTi B) {
   __shared__ float s_rtab[RTAB];  // correctly rounded 1/m for the weighted-mean division (fuse_tile)
-#ifdef SF_INT_PAD_VGPR
-  // occupancy experiment: name a high register so that the kernel's allocation is SF_INT_PAD_VGPR + 1 registers whatever it uses (fewer waves per SIMD,
-  // slots of the size the allocation kernel's waves need)
-#define SF_STR2(x) #x
-#define SF_STR(x) SF_STR2(x)
-  asm volatile("" ::: "v" SF_STR(SF_INT_PAD_VGPR));
-#endif
   if (TAB) {
     for (int i = threadIdx.x; i < RTAB; i += 256) s_rtab[i] = 1.0f / (float)(i > 0 ? i : 1);
     __syncthreads();
@@ -1890,12 +1793,13 @@ __global__ __launch_bounds__(256, NJ == 2 ? (XR ? 7 : 8) : SF_INT_WAVES) void k_
 // ---------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int PIPE_WGS = 3;   // workgroups of k_integrate_pipe per CU (48 KiB of LDS each): its occupancy bound and its persistent grid, PIPE_WGS per CU
 
 // NT: tile loads and stores carry the non-temporal hint -- for passes whose tile set is many times the 256 MiB Infinity Cache (1 mm voxels:
 // 5-7 GB per frame), where keeping streamed tiles on-die only evicts the depth image and the list; below that size the cache hits of
 // consecutive frames are worth more (measured), so run_batch picks the variant from the previous pass's list length.
 template <bool TAB, int WM, bool NT>
-__global__ __launch_bounds__(256, 3) void k_integrate_pipe(uint4* __restrict__ voxels, const uint64_t* __restrict__ block_keys,
+__global__ __launch_bounds__(256, PIPE_WGS) void k_integrate_pipe(uint4* __restrict__ voxels, const uint64_t* __restrict__ block_keys,
                                                         const int32_t* __restrict__ compact, const float* __restrict__ depthf, int32_t* counters,
                                                         int32_t* host_mirror, int compact_counter, ParamsK P, BatchTi B) {
   __shared__ uint4 s_tile[4][2][256];   // per wave: two 4 KiB tile slots
@@ -2073,49 +1977,11 @@ __global__ __launch_bounds__(256, 3) void k_integrate_pipe(uint4* __restrict__ v
 // with the same four 1 KiB loads per wave and (mode 0) written back unchanged, same grid, same list walk.  Its duration
 // is the ceiling the access pattern itself (scattered 4 KiB read-modify-write) allows on this HBM; bench.py reports
 // the one-frame-per-launch kernel against it (sf_fuser_calib_tile_rmw).  The volume is left bit-identical.
-// ---------------------------------------------------------------------------------------------------
-template <bool NT>
-__global__ __launch_bounds__(256, 4) void k_tile_rmw(uint4* __restrict__ voxels, const int32_t* __restrict__ compact,
-                                                  const int32_t* __restrict__ counters, int compact_counter, int xcd_walk, int read_only,
-                                                  uint32_t* sink) {
-  const int n = counters[compact_counter];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wg_total = (n + 3) >> 2;
-  const int chunk = xcd_walk ? (wg_total + 7) >> 3 : wg_total;
-  const int lanes = xcd_walk ? 8 : 1;
-  const int sub = xcd_walk ? (int)(blockIdx.x & 7) : 0;
-  const int per_sub = max(1, (int)gridDim.x / lanes);
-  uint32_t acc = 0;
-  for (int loc = xcd_walk ? (int)(blockIdx.x >> 3) : (int)blockIdx.x; loc < chunk; loc += per_sub) {
-    const int i = ((sub * chunk + loc) << 2) + wave;
-    if (i >= n) continue;
-    uint4* vb = voxels + (size_t)compact[i] * 256;
-    uint4 v[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (NT) { const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(&vb[j * 64 + lane])); v[j] = make_uint4(t.x, t.y, t.z, t.w); }
-      else v[j] = vb[j * 64 + lane];
-    }
-    if (read_only) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) acc ^= v[j].x ^ v[j].y ^ v[j].z ^ v[j].w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        asm volatile("" : "+v"(v[j].x));  // opaque to the optimiser: the store below stays
-        if (NT) __builtin_nontemporal_store((u32x4){v[j].x, v[j].y, v[j].z, v[j].w}, reinterpret_cast<u32x4*>(&vb[j * 64 + lane]));
-        else vb[j * 64 + lane] = v[j];
-      }
-    }
-  }
-  if (read_only && acc == 0x9E3779B9u) *sink = acc;
-}
-
 // The same traffic taken apart (sf_fuser_calib_tile_rmw_ex): WHICH tiles -- the pass's list (scattered over the pool) or tiles 0 .. n - 1 of the pool
 // (one contiguous span of the same size) -- and HOW a wave turns from reading to writing -- tile by tile, or G tiles read and then G tiles written.
 // If the contiguous copy runs no faster than the scattered one, the 4 KiB granularity is not what holds the pattern below the read-only rate; if the
 // batched turnaround does not either, it is HBM's read / write mix itself.
+// ---------------------------------------------------------------------------------------------------
 template <bool NT, int G>
 __global__ __launch_bounds__(256, 4) void k_tile_rmw_ex(uint4* __restrict__ voxels, const int32_t* __restrict__ compact, const int32_t* __restrict__ counters,
                                                      int compact_counter, int xcd_walk, int read_only, int contiguous, uint32_t* sink) {
@@ -2381,7 +2247,16 @@ static bool pipe_batch(const sf_fuser* f, int n, bool color, int sign) {
 // MI355X (profiles/r02): at 4 mm (48-67 k tiles per frame, front kernels 36 us) running them beside k_integrate_pipe stretches it by more
 // than it hides (7.8 k frames/s serial, 7.5 k overlapped, also with the two streams on disjoint CU masks); at 1 mm (1.7 M tiles, front
 // kernels 1 ms) it hides 0.5 ms per frame (310 vs 269 frames/s).  So: overlap once the previous pass's tile set is beyond 512 MiB.
-static bool big_pass(const sf_fuser* f) { return (uint64_t)(uint32_t)*f->host_mirror * 4096ull > (512ull << 20); }
+// The same size also turns k_integrate_pipe's tile traffic non-temporal (twice the Infinity Cache: DESIGN.md 5.2).
+static bool big_tile_set(uint32_t tiles) { return (uint64_t)tiles * 4096ull > (512ull << 20); }
+static bool big_pass(const sf_fuser* f) { return big_tile_set((uint32_t)*f->host_mirror); }
+// Grid of the list-walking kernels (k_integrate, the tile read-modify-write): enough workgroups (4 list entries each) for `entries` +25 %; the kernels'
+// grid-stride loop covers any excess, surplus workgroups exit at once.  Whole sub-grids of 8 for the XCD-aware walk.
+static int list_grid(const sf_fuser* f, int entries) {
+  int grid = (entries + entries / 4 + 4096 + 3) / 4;
+  if (grid > f->num_cus * 64) grid = f->num_cus * 64;
+  return (grid + 7) & ~7;
+}
 // The decision is latched at the end of every pass (run_batch) so that a caller's staging (sf_input_stream) and the pass that follows see the
 // same answer: host_mirror is written by the device while they run.
 bool sf_single_stream_batch(const sf_fuser* f, int n, bool color, int sign) { return pipe_batch(f, n, color, sign) && !f->pipe_beside; }
@@ -2392,7 +2267,7 @@ hipStream_t sf_input_stream(const sf_fuser* f, int n, bool color, int sign) {
   // kernel, or the next pass waits for them.  Beside the PERSISTENT kernel of one frame per launch (1 mm voxels: the tile set is far beyond the cache) that
   // priority is what the integrate kernel pays for: the allocation's 72 KiB workgroups, dispatched first, take the LDS its third workgroup per CU needs until
   // they are through -- 0.54 of peak HBM shipped and 322-335 frames/s, against 0.60-0.61 / 360 with the front chain at the MAIN stream's priority and 0.62 / 369
-  // at the device's lowest (tools/gpu/r06_zk.sh, r06_zv.sh: two or three runs each, nothing else changed).  So such a frame's front chain goes down a second
+  // at the device's lowest (profiles/r06_alloc_1mm.txt: two or three runs each, nothing else changed).  So such a frame's front chain goes down a second
   // front stream, `front_lo` (front_prio -1, the default; 1 / 0: always the high-priority / always the second one), at the device's lowest priority.  One thing to
   // know about that: the first stream of a priority class makes the runtime open that class's hardware queues for the life of the PROCESS, and a later sf_fuse_run
   // in the same process -- seven to nine busy streams -- then runs 12 % slower (depth-only end to end 34.2 k -> 30.0 k frames/s; bench.py therefore runs its 1 mm
@@ -2447,31 +2322,27 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
     (void)hipStreamWaitEvent(sa, f->ev_fused[sl], 0);
   }
   // one colourless frame at the integration size through the ray-space allocation kernel: that kernel converts the depth itself
-  const bool fuse_pre = f->prepass_fuse && f->alloc_ray && n == 1 && sign > 0 && !col && f->pk.inW == 0;
+  const bool fuse_pre = f->alloc_ray && n == 1 && sign > 0 && !col && f->pk.inW == 0;
   if (!fuse_pre)
     hipLaunchKernelGGL(k_prepass, dim3((npx / 8 + 255) / 256 + 1, n), dim3(256), 0, sa, in, f->depthf2[sl], f->color2[sl], npx, f->p.depth_shift,
                        f->p.depth_min, f->p.depth_max, f->counters, cc, f->pk, f->ray_kx, f->ray_ky);
   if (sign > 0) {
-    // WIN 64 (32 KiB bitmap) has no room for the second bitmap: one frame per workgroup there
     // frames one allocation workgroup walks.  The FIRST pass of a batch call has nothing to run beside: its front chain is pure latency in front of the first
-    // integrate launch (a 20-frame call: k_alloc_ray 133 us of a 650 us region at 8 frames per workgroup), so it is cut into more, shorter workgroups
-    // (tune "alloc_group_head"); every other pass hides its allocation behind the previous integrate launch and takes the cheaper, longer ones
-    const int group = (f->head_pass && f->alloc_group_head > 0) ? std::min(f->alloc_group, f->alloc_group_head) : f->alloc_group;
-    // WIN 64 (32 KiB bitmap): a second bitmap of that size makes the workgroup 102 KiB -- one per CU; tune "alloc_group_win64" (default 1: one frame per workgroup)
-    const int gf = (f->alloc_win64 && !f->alloc_ray) ? std::min(f->alloc_group_win64, n) : std::min(group, n);
+    // integrate launch (a 20-frame call: k_alloc_ray 133 us of a 650 us region at 8 frames per workgroup), so it is cut into more, shorter workgroups of at most
+    // 4 frames (a 20-frame call: 30.8 k -> 31.8 k frames/s); every other pass hides its allocation behind the previous integrate launch and takes the cheaper,
+    // longer ones.  The cube window's WIN 64 (32 KiB bitmap) has no room for the second bitmap: one frame per workgroup there.
+    const int group = f->head_pass ? std::min(f->alloc_group, 4) : f->alloc_group;
+    const bool win64 = f->alloc_win64 && !f->alloc_ray;
+    const int gf = win64 ? 1 : std::min(group, n);
     const dim3 ag((f->p.depth_width + 15) / 16, (f->p.depth_height + 15) / 16, (n + gf - 1) / gf);
     const BrickCache bc{f->brick_on ? f->bricks : nullptr, f->brick_lines - 1u};
 #define LAUNCH_ALLOC(WL, MU) \
   hipLaunchKernelGGL((k_alloc<WL, MU>), ag, dim3(256), 0, sa, f->depthf2[sl], f->table, f->heap, f->block_keys, f->block_entry, f->block_flags, f->counters, f->pk, bf, gf, bc)
-    // alloc_wgs > 0: at most that many allocation workgroups per CU, by asking for LDS the kernel does not use (160 KiB per CU).  The kernel
-    // is latency-bound (barriers, LDS atomics: 35 % VALU utilisation) and, unthrottled, parks 4-5 waves of 72 VGPRs on every SIMD for ~200 us of
-    // each pass -- registers the integrate kernel next to it needs for ITS waves (timeline: profiles/r03_timeline_*.txt)
-    const unsigned alloc_pad = (f->alloc_wgs > 0 && n > 1) ? (unsigned)std::max(0, (160 * 1024) / (f->alloc_wgs + 1) + 1024 - 23048) : 0u;
 #define LAUNCH_ALLOC_RAY(MU) \
-  hipLaunchKernelGGL((k_alloc_ray<MU>), ag, dim3(256), alloc_pad, sa, f->depthf2[sl], f->table, f->heap, f->block_keys, f->block_entry, f->block_flags, f->counters, f->pk, bf, gf, f->alloc_ablate, \
+  hipLaunchKernelGGL((k_alloc_ray<MU>), ag, dim3(256), 0, sa, f->depthf2[sl], f->table, f->heap, f->block_keys, f->block_entry, f->block_flags, f->counters, f->pk, bf, gf, \
                      fuse_pre ? in.depth[0] : (const uint16_t*)nullptr, f->depthf2[sl], cc)
     if (f->alloc_ray) { if (gf == 1) LAUNCH_ALLOC_RAY(false); else LAUNCH_ALLOC_RAY(true); }
-    else if (f->alloc_win64) { if (gf == 1) LAUNCH_ALLOC(6, false); else LAUNCH_ALLOC(6, true); }
+    else if (win64) LAUNCH_ALLOC(6, false);
     else if (gf == 1) LAUNCH_ALLOC(5, false);
     else LAUNCH_ALLOC(5, true);
 #undef LAUNCH_ALLOC
@@ -2487,14 +2358,7 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
     (void)hipEventRecord(f->ev_compact[sl], sa);
     (void)hipStreamWaitEvent(s, f->ev_compact[sl], 0);
   }
-  // grid: enough workgroups (4 blocks each) for the last list length the device reported, +25 %; the kernel's
-  // grid-stride loop covers any excess, surplus workgroups exit at once.
-  const int last = *f->host_mirror;
-  int est = last + last / 4 + 4096;
-  int grid = (est + 3) / 4;
-  const int grid_max = f->num_cus * 64;
-  if (grid > grid_max) grid = grid_max;
-  grid = (grid + 7) & ~7;  // whole sub-grids for the XCD-aware walk
+  const int grid = list_grid(f, *f->host_mirror);   // sized for the last list length the device reported
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (f->profile) {
     if (f->events_used == f->events.size()) {
@@ -2517,11 +2381,10 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
     else LAUNCH_INT_R(1, CL, TB, W1, false);                          \
   } while (0)
   const bool tab = tab_ok;  // the LDS reciprocal table covers weight + sample < 512
-  // one frame per launch without colour: the software-pipelined kernel (SF_PIPE=0: always k_integrate)
+  // one frame per launch without colour: the software-pipelined kernel (tune "pipe" 0: always k_integrate)
   if (pipe) {
-    const dim3 pg((unsigned)((f->num_cus - f->front_cus) * f->pipe_wgs));   // persistent: exactly what the main stream's CUs hold
-    // non-temporal tile traffic once the previous pass's tile set was beyond twice the Infinity Cache (tune "nt": 0 never, 1 always)
-    const bool nt = f->nt_mode == 1 || (f->nt_mode < 0 && big_pass(f));
+    const dim3 pg((unsigned)(f->num_cus * PIPE_WGS));   // persistent: exactly what the CUs hold
+    const bool nt = big_pass(f);   // non-temporal tile traffic once the previous pass's tile set was beyond twice the Infinity Cache
 #define LAUNCH_PIPE(WMODE)                                                                                                                     \
   do {                                                                                                                                         \
     if (nt) hipLaunchKernelGGL((k_integrate_pipe<true, WMODE, true>), pg, dim3(256), 0, s, f->voxels, f->block_keys, f->compact2[sl],          \
@@ -2535,18 +2398,17 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
 #undef LAUNCH_PIPE
   } else if (sign > 0) {
     if (ws1 && f->pk.wmax == 255) {   // the shipped setting
-      const bool wide = f->tail_pass && f->tail_wide && n > 1;   // the last pass of a batch call: no front chain beside it, the 8-wave variant (k_integrate)
-#define LAUNCH_INT_WIDE(CL) hipLaunchKernelGGL((k_integrate<1, CL, true, 2, false, 2>), dim3(grid), dim3(256), 0, s, f->voxels, f->block_keys, f->compact2[sl], f->cmask2[sl], \
-                                               f->depthf2[sl], f->color2[sl], f->counters, f->host_mirror, cc, f->xcd_walk ? 1 : 0, f->pk, bt)
-      // the x-row lane layout (fuse_project_xr) for every pass of several frames: same voxels, the gathers of one instruction on two image rows instead of five
+      // a pass of several frames runs the x-row lane layout (fuse_project_xr): same voxels, the gathers of one instruction on two image rows instead of five.
+      // The last pass of a batch call has no front chain beside it: the 8-wave variant (NJ 2)
+      const int cl = col ? (f->p.colour_first ? 1 : 2) : 0;
+      const bool wide = f->tail_pass && f->tail_wide;
 #define LAUNCH_INT_XR(CL, NJV) hipLaunchKernelGGL((k_integrate<1, CL, true, 2, false, NJV, true>), dim3(grid), dim3(256), 0, s, f->voxels, f->block_keys, f->compact2[sl], f->cmask2[sl], \
                                                   f->depthf2[sl], f->color2[sl], f->counters, f->host_mirror, cc, f->xcd_walk ? 1 : 0, f->pk, bt)
-      const bool xr = f->xrow && n > 1;
-      if (col && !f->p.colour_first) { if (xr && wide) LAUNCH_INT_XR(2, 2); else if (xr) LAUNCH_INT_XR(2, SF_INT_NJ); else if (wide) LAUNCH_INT_WIDE(2); else LAUNCH_INT(1, 2, true, 2); }
-      else if (col) LAUNCH_INT(1, 1, true, 2);
-      else { if (xr && wide) LAUNCH_INT_XR(0, 2); else if (xr) LAUNCH_INT_XR(0, SF_INT_NJ); else if (wide) LAUNCH_INT_WIDE(0); else LAUNCH_INT(1, 0, true, 2); }
+      if (cl == 1) LAUNCH_INT(1, 1, true, 2);
+      else if (n == 1) { if (cl == 2) LAUNCH_INT_R(1, 2, true, 2, true); else LAUNCH_INT_R(1, 0, true, 2, true); }
+      else if (cl == 2) { if (wide) LAUNCH_INT_XR(2, 2); else LAUNCH_INT_XR(2, INT_NJ); }
+      else { if (wide) LAUNCH_INT_XR(0, 2); else LAUNCH_INT_XR(0, INT_NJ); }
 #undef LAUNCH_INT_XR
-#undef LAUNCH_INT_WIDE
     }
     else if (ws1) { if (col) LAUNCH_INT(1, 1, true, 1); else LAUNCH_INT(1, 0, true, 1); }
     else if (tab)                { if (col) LAUNCH_INT(1, 1, true, 0); else LAUNCH_INT(1, 0, true, 0); }
@@ -2560,7 +2422,7 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
   if (f->overlap && sa != s) (void)hipEventRecord(f->ev_fused[sl], s);
   if (f->overlap && sa == s) f->serial_tail = true;  // no cross-stream traffic at all while single-stream batches follow each other
   f->pipe_beside = f->pipe_overlap == 1 || (f->pipe_overlap < 0 && big_pass(f));
-  if ((f->pipe_beside || f->front_prio == 0) && f->front_lo == nullptr && f->front_cus == 0 && f->overlap) {   // the second front stream, on first need (sf_input_stream)
+  if ((f->pipe_beside || f->front_prio == 0) && f->front_lo == nullptr && f->overlap) {   // the second front stream, on first need (sf_input_stream)
     int prio_lo = 0, prio_hi = 0;
     hipError_t e_ = hipSuccess;
     if (f->front_lo_lowest) {
@@ -2889,16 +2751,18 @@ static int integrate_batch_device(sf_fuser* f, const void* d_depth, uint64_t fra
       pp[m] = poses + 16 * i;
       m++;
     }
-    // the first pass of a call has nothing to hide its pre-pass / allocation / compaction behind: a short one (f->ramp frames) gets the
-    // integrate stream busy sooner, and (ramp_geo) the passes behind it double -- ramp, 2 ramp, 4 ramp ... up to the batch size -- so that the
-    // front chain of pass k + 1 still fits under the integrate launch of pass k (same voxels under any batching)
+    // the first pass of a call has nothing to hide its pre-pass / allocation / compaction behind: a short one (`ramp` frames) gets the
+    // integrate stream busy sooner, and the passes behind it double -- ramp, 2 ramp, 4 ramp ... up to the batch size -- so that the
+    // front chain of pass k + 1 still fits under the integrate launch of pass k (same voxels under any batching; a 20-frame call: 29.3 k frames/s
+    // with no ramp, 30.0 k with 4 frames, 30.7 k with 8).
     // A call that would fit ONE pass (ramp < n <= batch) is fused as two halves: the second half's front chain hides behind the first half's integrate launch
     // (20 frames: 8 + 12 gives 31.4 k frames/s, 10 + 10 32.5 k, 6 + 12 + 2 29.6 k, 12 + 8 31.2 k).
+    constexpr int ramp = 8;
     int want = f->batch;
-    if (f->ramp > 0 && f->ramp < f->batch && n > (uint64_t)f->ramp) {
-      if (n <= (uint64_t)f->batch && f->ramp_geo) want = (int)((n + 1) / 2);
-      else if (pass == 0) want = f->ramp;
-      else if (f->ramp_geo && pass < 6) want = std::min(f->batch, f->ramp << pass);
+    if (ramp < f->batch && n > (uint64_t)ramp) {
+      if (n <= (uint64_t)f->batch) want = (int)((n + 1) / 2);
+      else if (pass == 0) want = ramp;
+      else if (pass < 6) want = std::min(f->batch, ramp << pass);
     }
     if (m == want || (i == n && m > 0)) {
       f->tail_pass = i == n;   // nothing of this call follows: its integrate launch has the chip to itself
@@ -2935,68 +2799,14 @@ SF_API int sf_fuser_tune(sf_fuser* f, const char* key, int value) {
   else if (k == "overlap" && in(0, 1)) f->overlap = value != 0;
   else if (k == "xcd_walk" && in(0, 1)) f->xcd_walk = value != 0;
   else if (k == "pipe" && in(0, 1)) f->pipe_mode = value;
-  else if (k == "pipe_wgs" && in(1, 3)) f->pipe_wgs = value;
   else if (k == "pipe_overlap" && in(-1, 1)) { f->pipe_overlap = value; f->pipe_beside = value == 1; }
-  else if (k == "nt" && in(-1, 1)) f->nt_mode = value;
-  else if (k == "front_cus" && in(0, 128)) {
-    // the two streams on disjoint sets of CUs (hipExtStreamCreateWithCUMask): `value` CUs, spread evenly over the chip, run the pre-pass /
-    // allocation / compaction of the NEXT pass while the rest runs integrate -- the short latency-bound kernels no longer queue behind (or
-    // squeeze in between) the workgroups of the bandwidth-bound one.  0: both streams on every CU.
-    const int ncu = f->num_cus;
-    if (value >= ncu) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_tune: front_cus = %d on a device with %d CUs (the main stream needs at least one)", value, ncu);
-    std::vector<uint32_t> front_mask((size_t)(ncu + 31) / 32, 0u), main_mask((size_t)(ncu + 31) / 32, 0u);
-    const int every = value > 0 ? ncu / value : 0;   // >= 1 because value < ncu
-    for (int c = 0; c < ncu; c++) {
-      const bool to_front = value > 0 && (c % every) == 0 && (c / every) < value;
-      (to_front ? front_mask : main_mask)[(size_t)c / 32] |= 1u << (c % 32);
-    }
-    // the new pair first: a failure leaves the fuser on its old streams instead of on none
-    hipStream_t ns = nullptr, nf = nullptr;
-    hipError_t e;
-    if (value == 0) {
-      int prio_lo = 0, prio_hi = 0;
-      e = hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-      if (e == hipSuccess) e = hipStreamCreateWithFlags(&ns, hipStreamNonBlocking);
-      if (e == hipSuccess) e = hipStreamCreateWithPriority(&nf, hipStreamNonBlocking, prio_hi);
-    } else {
-      e = hipExtStreamCreateWithCUMask(&ns, (uint32_t)main_mask.size(), main_mask.data());
-      if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&nf, (uint32_t)front_mask.size(), front_mask.data());
-    }
-    if (e != hipSuccess) {
-      if (ns) (void)hipStreamDestroy(ns);
-      if (nf) (void)hipStreamDestroy(nf);
-      return sf::fail(SF_ERR_DEVICE, "sf_fuser_tune: front_cus = %d: %s", value, hipGetErrorString(e));
-    }
-    (void)hipStreamDestroy(f->stream);
-    (void)hipStreamDestroy(f->front);
-    if (f->front_lo) { (void)hipStreamDestroy(f->front_lo); f->front_lo = nullptr; }
-    f->stream = ns;
-    f->front = nf;
-    f->last_front = nullptr;
-    // (a CU-masked front stream is the only front stream: the mask, not a priority, keeps it out of the integrate kernel's way; back at 0 the second
-    // one is made again on first need)
-    f->front_cus = value;
-  }
   else if (k == "alloc_group" && in(1, MAX_BATCH)) f->alloc_group = value;
-  else if (k == "alloc_group_head" && in(0, MAX_BATCH)) f->alloc_group_head = value;
-  else if (k == "alloc_group_win64" && in(1, MAX_BATCH)) f->alloc_group_win64 = value;
-  else if (k == "alloc_wgs" && in(0, 8)) f->alloc_wgs = value;
-  else if (k == "prepass_fuse" && in(0, 1)) f->prepass_fuse = value != 0;
-#ifdef SF_MEASURE_ABLATE
-  else if (k == "alloc_ablate" && in(0, 15)) f->alloc_ablate = value;   // parts of k_alloc_ray switched off: the volume is WRONG with any bit set
-#else
-  else if (k == "alloc_ablate")
-    return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_tune: alloc_ablate switches parts of the allocation off (the volume is wrong under it): only in a library built with -DSF_MEASURE_ABLATE");
-#endif
   // which of the two front streams a pass's pre-pass / allocation / compaction goes down (sf_input_stream): -1 the second one (front_lo) beside the persistent kernel of
   // one frame per launch, the high-priority one otherwise (default); 1 always the high-priority one (rounds 2-5); 0 always the second one
   else if (k == "front_prio" && in(-1, 1)) f->front_prio = value;
   else if (k == "front_lo_lowest" && in(0, 1)) f->front_lo_lowest = value != 0;   // before the stream's first need: 1 = the device's lowest priority, 0 = the main stream's
   else if (k == "alloc_ray" && in(0, 1)) f->alloc_ray = value != 0;   // 1: the ray-space window whatever the geometry (rays outside it take the slow path), 0: the cube window
-  else if (k == "ramp" && in(0, MAX_BATCH)) f->ramp = value;
-  else if (k == "ramp_geo" && in(0, 1)) f->ramp_geo = value != 0;
   else if (k == "tail_wide" && in(0, 1)) f->tail_wide = value;
-  else if (k == "xrow" && in(0, 1)) f->xrow = value != 0;
   else if (k == "brick_cache" && in(0, 1)) {   // 0: every look-up of the allocation kernels probes the table
     f->brick_on = value != 0;
     SF_HIP_CHECK(hipMemsetAsync(f->bricks, 0, (size_t)f->brick_lines * 128, f->stream));
@@ -3069,29 +2879,6 @@ SF_API int sf_fuser_alloc_probe_count(sf_fuser* f, uint64_t* out) {
   return SF_OK;
 }
 
-#ifdef SF_ALLOC_TIMING
-// measurement build only: the 16 words of g_alloc_t, cleared behind the read
-SF_API int sf_alloc_timing_read(sf_fuser* f, uint64_t* out16) {
-  if (!f || !out16) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  SF_HIP_CHECK(sf_quiesce(f));
-  SF_HIP_CHECK(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_alloc_t), 16 * 8));
-  unsigned long long z[16] = {};
-  SF_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_alloc_t), z, 16 * 8));
-  return SF_OK;
-}
-// ... and the log of its slow workgroups: 1 + 256 * 12 words, cleared behind the read
-SF_API int sf_alloc_timing_log(sf_fuser* f, uint32_t* out) {
-  if (!f || !out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  SF_HIP_CHECK(sf_quiesce(f));
-  SF_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_alloc_log), (1 + 256 * 12) * 4));
-  static unsigned z[1 + 256 * 12];
-  SF_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_alloc_log), z, sizeof(z)));
-  return SF_OK;
-}
-#endif
-
 SF_API int sf_fuser_profile_enable(sf_fuser* f, int on) {
   if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
   f->profile = on != 0;
@@ -3118,46 +2905,6 @@ SF_API int sf_fuser_profile_read(sf_fuser* f, double* integrate_ms, uint64_t* la
   return SF_OK;
 }
 
-SF_API int sf_fuser_calib_tile_rmw(sf_fuser* f, int read_only, int iters, double* avg_us, uint32_t* tiles) {
-  if (!f || iters < 1) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_calib_tile_rmw: bad argument");
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  SF_HIP_CHECK(sf_quiesce(f));
-  const int sl = f->slot ^ 1;  // the list of the most recent pass
-  const int cc = sl ? (int)C_COMPACT_B : (int)C_COMPACT;
-  int32_t n = 0;
-  SF_HIP_CHECK(hipMemcpy(&n, &f->counters[cc], 4, hipMemcpyDeviceToHost));
-  int grid = (n + n / 4 + 4096 + 3) / 4;  // the sizing rule of run_batch
-  if (grid > f->num_cus * 64) grid = f->num_cus * 64;
-  grid = (grid + 7) & ~7;
-  uint32_t* sink = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&sink, 4));
-  hipEvent_t e0, e1;
-  SF_HIP_CHECK(hipEventCreate(&e0));
-  SF_HIP_CHECK(hipEventCreate(&e1));
-  double total_ms = 0;
-  for (int it = 0; it < iters + 1; it++) {  // first launch untimed
-    SF_HIP_CHECK(hipEventRecord(e0, f->stream));
-    // the same cache policy the integrate kernel would pick for this tile set (non-temporal beyond 512 MiB)
-    if (f->nt_mode == 1 || (f->nt_mode < 0 && (uint64_t)(uint32_t)n * 4096ull > (512ull << 20)))
-      hipLaunchKernelGGL(k_tile_rmw<true>, dim3(grid), dim3(256), 0, f->stream, f->voxels, f->compact2[sl], f->counters, cc, f->xcd_walk ? 1 : 0,
-                         read_only ? 1 : 0, sink);
-    else
-      hipLaunchKernelGGL(k_tile_rmw<false>, dim3(grid), dim3(256), 0, f->stream, f->voxels, f->compact2[sl], f->counters, cc, f->xcd_walk ? 1 : 0,
-                         read_only ? 1 : 0, sink);
-    SF_HIP_CHECK(hipEventRecord(e1, f->stream));
-    SF_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    SF_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    if (it > 0) total_ms += ms;
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(sink);
-  if (avg_us) *avg_us = total_ms * 1e3 / iters;
-  if (tiles) *tiles = (uint32_t)n;
-  return SF_OK;
-}
-
 // scanfuse_internal.h: the pattern ceiling taken apart.  mode bit 0: read only; bit 1: contiguous tiles 0 .. n - 1 instead of the pass's list; bits 2-3:
 // tiles per turnaround 1 / 2 / 4 (0, 1, 2).  Every tile is written back as it was read: the volume is unchanged whatever it holds.
 SF_API int sf_fuser_calib_tile_rmw_ex(sf_fuser* f, int mode, int iters, double* avg_us, uint32_t* tiles) {
@@ -3168,18 +2915,15 @@ SF_API int sf_fuser_calib_tile_rmw_ex(sf_fuser* f, int mode, int iters, double* 
   const int cc = sl ? (int)C_COMPACT_B : (int)C_COMPACT;
   int32_t n = 0;
   SF_HIP_CHECK(hipMemcpy(&n, &f->counters[cc], 4, hipMemcpyDeviceToHost));
-  if (n < 1 || (uint32_t)n > (uint32_t)f->p.num_sdf_blocks) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_calib_tile_rmw_ex: no pass to repeat");
+  if ((uint32_t)n > (uint32_t)f->p.num_sdf_blocks) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_calib_tile_rmw_ex: list length %d out of range", n);
   const int read_only = mode & 1, contiguous = (mode >> 1) & 1, G = 1 << (mode >> 2);
-  const int units = (n + G - 1) / G;
-  int grid = (units + units / 4 + 4096 + 3) / 4;
-  if (grid > f->num_cus * 64) grid = f->num_cus * 64;
-  grid = (grid + 7) & ~7;
+  const int grid = list_grid(f, (n + G - 1) / G);
   uint32_t* sink = nullptr;
   SF_HIP_CHECK(hipMalloc((void**)&sink, 4));
   hipEvent_t e0, e1;
   SF_HIP_CHECK(hipEventCreate(&e0));
   SF_HIP_CHECK(hipEventCreate(&e1));
-  const bool nt = f->nt_mode == 1 || (f->nt_mode < 0 && (uint64_t)(uint32_t)n * 4096ull > (512ull << 20));
+  const bool nt = big_tile_set((uint32_t)n);   // the cache policy k_integrate_pipe would pick for this tile set
   double total_ms = 0;
   for (int it = 0; it < iters + 1; it++) {  // first launch untimed
     SF_HIP_CHECK(hipEventRecord(e0, f->stream));
@@ -3199,6 +2943,10 @@ SF_API int sf_fuser_calib_tile_rmw_ex(sf_fuser* f, int mode, int iters, double* 
   if (avg_us) *avg_us = total_ms * 1e3 / iters;
   if (tiles) *tiles = (uint32_t)n;
   return SF_OK;
+}
+// the pattern itself: the pass's list, tile by tile
+SF_API int sf_fuser_calib_tile_rmw(sf_fuser* f, int read_only, int iters, double* avg_us, uint32_t* tiles) {
+  return sf_fuser_calib_tile_rmw_ex(f, read_only ? 1 : 0, iters, avg_us, tiles);
 }
 
 int sf_compact_live(sf_fuser* f, int32_t* n_out, int include_ghosts) {

@@ -214,20 +214,9 @@ __device__ inline int hash_lookup(const HashEntry* __restrict__ table, const Par
 }
 
 #ifdef __HIPCC__
-// Packed fp32 helpers and the two hand-expanded, correctly rounded divisions of k_integrate.
-#ifdef SF_PACKED_PAIRS   // rounds 1-4: v_pk_fma / v_pk_mul / v_pk_add_f32 on the lane's voxel pair (build with -DSF_PACKED_PAIRS and without -fno-slp-vectorize)
-typedef float v2f __attribute__((ext_vector_type(2)));
-__device__ inline v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ inline v2f splat(float x) { return (v2f){x, x}; }
-// one v_pk_add_f32 (the compiler splits a packed add whose two results go separate ways into two v_add_f32)
-__device__ inline v2f pk_add(v2f a, v2f b) {
-  v2f r;
-  asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-#else
-// The default since round 5: the same pairs as two plain fp32 operations each.  tools/gpu/valu_peak.hip (profiles/r05_valu_issue_table.txt): on gfx950 a
-// v_pk_*_f32 holds the SIMD for ~4.2 cycles and issues beside nothing; a plain v_fma / v_mul / v_add_f32 holds it ~2.2 cycles and issues beside the
+// Voxel-pair helpers and the two hand-expanded, correctly rounded divisions of k_integrate.
+// Since round 5 the pairs are two plain fp32 operations each (rounds 1-4 used v_pk_fma / v_pk_mul / v_pk_add_f32).
+// tools/gpu/valu_peak.hip (profiles/r05_valu_issue_table.txt): on gfx950 a v_pk_*_f32 holds the SIMD for ~4.2 cycles and issues beside nothing; a plain v_fma / v_mul / v_add_f32 holds it ~2.2 cycles and issues beside the
 // conversions, compares and selects of another wave -- packing buys no throughput on this part, and the splats cost moves.  Same arithmetic, same bits;
 // the pass 830 -> 808 us, 9 registers fewer (5 waves per SIMD instead of 4).  fuser.hip is built with -fno-slp-vectorize so that the compiler does not
 // pack the pairs again.
@@ -243,7 +232,6 @@ __device__ inline v2f operator-(v2f a) { return v2f{-a.x, -a.y}; }
 __device__ inline v2f pk_fma(v2f a, v2f b, v2f c) { return v2f{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)}; }
 __device__ inline v2f splat(float x) { return v2f{x, x}; }
 __device__ inline v2f pk_add(v2f a, v2f b) { return a + b; }
-#endif
 // RN(1 / b) for normal-range b: v_rcp_f32 seed (1 ulp) + two Newton steps
 __device__ inline v2f recip_rn(v2f b) {
   v2f r = {__builtin_amdgcn_rcpf(b.x), __builtin_amdgcn_rcpf(b.y)};
@@ -293,10 +281,8 @@ struct sf_fuser {
   bool overlap = true;  // sf_fuser_tune("overlap", 0) runs everything on one stream
   float* depthf2[2] = {nullptr, nullptr};      // MAX_BATCH x W*H per batch slot
   bool head_pass = false;   // set around the first run_batch of a multi-pass sf_fuser_integrate_batch_device call
-  int alloc_group_head = 4; // tune "alloc_group_head": frames per allocation workgroup in that pass (0 = as every pass).  A 20-frame call: 30.8 k -> 31.8 k frames/s
   bool tail_pass = false;   // set around the last run_batch of a sf_fuser_integrate_batch_device call
   int tail_wide = 1;        // tune "tail_wide": that pass runs the 8-waves-per-SIMD variant of k_integrate
-  bool xrow = true;         // tune "xrow": passes of several frames run k_integrate in the x-row lane layout (a lane = one x-row of the block: fuse_project_xr)
   uint2* color2[2] = {nullptr, nullptr};       // MAX_BATCH x W*H {depth bits, rgb} texels per batch slot (RGB-D batches)
   int32_t* compact2[2] = {nullptr, nullptr};   // heap slots of the blocks some frame of the batch sees
   uint32_t* cmask2[2] = {nullptr, nullptr};    // per compact entry: bit j = frame j of the batch updates this block
@@ -331,20 +317,11 @@ struct sf_fuser {
   int32_t* host_mirror = nullptr;  // pinned, device-visible: N_blk of the most recent integrate
   int num_cus = 256;
   bool alloc_win64 = false;  // 64^3-block LDS window when a ray segment spans more than ~20 blocks
-  bool prepass_fuse = true;  // one colourless frame per pass: k_alloc_ray converts the depth itself, no k_prepass launch (tune "prepass_fuse")
-  int alloc_ablate = 0;      // measurement only (tune "alloc_ablate"): parts of k_alloc_ray switched off, the volume is WRONG with any bit set
-  int alloc_wgs = 0;         // > 0: allocation workgroups per CU capped (LDS padding) so that the integrate kernel beside them keeps its waves (tune "alloc_wgs")
   bool alloc_ray = false;    // k_alloc_ray (occupancy bitmap in ray space: 16 x 16 blocks across the pixel tile's pencil of rays, 256 slabs along it) instead of the cube window
   bool xcd_walk = true;  // k_integrate: each XCD walks one contiguous eighth of the list (tune "xcd_walk" 0: plain grid-stride)
   int pipe_mode = 1;    // 1: colourless one-frame launches run k_integrate_pipe (tune "pipe" 0: k_integrate)
-  int pipe_wgs = 3;     // persistent workgroups per CU of k_integrate_pipe (48 KiB of LDS each)
-  int front_cus = 0;    // > 0: the front stream owns that many CUs, the main stream the others (tune "front_cus")
-  int nt_mode = -1;     // k_integrate_pipe tile traffic non-temporal: -1 = when the previous pass's tiles exceed 512 MiB, 0 never, 1 always (tune "nt")
   bool pipe_beside = false;  // the latched decision for the next pass (see sf_single_stream_batch)
   int pipe_overlap = -1;  // the next frame's pre-pass / allocation / compaction on the front stream beside k_integrate_pipe: -1 = when the previous pass's tiles exceed 512 MiB, 0 never, 1 always (tune "pipe_overlap")
-  int ramp = 8;         // > 0: the first pass of an integrate_batch call takes only that many frames (tune "ramp"; a 20-frame call: 29.3 k frames/s at 0, 30.0 k at 4, 30.7 k at 8)
-  bool ramp_geo = true; // the passes behind the first double (ramp, 2 ramp, ... batch) instead of jumping to the batch size (tune "ramp_geo")
-  int alloc_group_win64 = 1;   // the same for k_alloc<6> (voxels below ~1.6 mm: the 64^3-block window), tune "alloc_group_win64"
   int alloc_group = 16; // consecutive frames of a batch one k_alloc workgroup walks (tune "alloc_group"; 4 -> 16: 35.0 -> 35.8 k frames/s, the blocks a pixel tile queues are looked up in the table once per batch)
   int compact_grid = 1024;  // 1024 directory entries per workgroup, grid-stride beyond
   uint64_t frames_integrated = 0, frames_skipped = 0;

@@ -50,22 +50,12 @@ int jpeg_gpu_reconstruct(hipStream_t stream, int n, const uint8_t* const* d_payl
 // batch has a side stream to decode on
 #define SF_JPEG_DEVICE_HUFFMAN_DEFAULT(has_side_stream) (has_side_stream)
 
-// -DSF_SIDE_PRIO=1 creates the side streams (inflate and JPEG kernels, colour copies) at the device's highest stream priority.  The idea: their kernels are
-// small grids of LARGE workgroups (1024 lanes, 100+ registers per lane) that need a whole free CU, and at the default priority they might wait behind the
-// integrate pass.  Measured (profiles/r06_e2e_rgbd_ab.txt): 16 267 against 16 182 frames/s on a 2 048-frame RGB-D scan -- nothing; the default stays 0.
-#ifndef SF_SIDE_PRIO
-#define SF_SIDE_PRIO 0
-#endif
-
 namespace {
 
-hipError_t create_side_stream(hipStream_t* out) {
-#if SF_SIDE_PRIO
-  int lo = 0, hi = 0;
-  if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo) return hipStreamCreateWithPriority(out, hipStreamNonBlocking, hi);
-#endif
-  return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-}
+// The side streams (inflate and JPEG kernels, colour copies) run at the default priority.  Their kernels are small grids of LARGE workgroups (1024 lanes,
+// 100+ registers per lane) that need a whole free CU; at the device's highest priority they ran no faster (profiles/r06_e2e_rgbd_ab.txt: 16 267 against
+// 16 182 frames/s on a 2 048-frame RGB-D scan).
+hipError_t create_side_stream(hipStream_t* out) { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }
 
 thread_local uint64_t t_run_counts[4] = {0, 0, 0, 0};   // of this thread's last sf_fuse_run: depth frames inflated on the device / by the host threads, colour
 thread_local char t_run_note[320] = "";   // sf_fuse_run_note(): a hint about the calling thread's last run that is not an error

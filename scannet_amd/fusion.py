@@ -95,8 +95,9 @@ class Fuser:
         self.tune(**tune)
 
     def tune(self, **switches):
-        """Scheduling switches (include/scanfuse_internal.h sf_fuser_tune: batch, overlap, xcd_walk, pipe, pipe_wgs, alloc_group);
-        the voxels are bit-identical under all of them -- bench.py and the tests use this, a pipeline stage never needs to."""
+        """Scheduling switches (include/scanfuse_internal.h sf_fuser_tune: batch, overlap, xcd_walk, pipe, pipe_overlap, front_prio,
+        front_lo_lowest, alloc_group, alloc_ray, brick_cache, tail_wide); the voxels are bit-identical under all of them -- bench.py and
+        the tests use this, a pipeline stage never needs to."""
         L = _abi.lib()
         L.sf_fuser_tune.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         for k, v in switches.items():
