@@ -263,6 +263,43 @@ int sf_fuser_raycast(sf_fuser* f, const float pose[16], const sf_raycast_params*
  * every frame queued on the handle before it, and ahead of everything queued after it. */
 int sf_fuser_raycast_device(sf_fuser* f, const float* poses, uint64_t n, const sf_raycast_params* r, void* d_depth, void* d_normals_xyz, void* d_rgb);
 
+/* Camera tracking: depth-only, frame-to-model projective point-to-plane ICP over an image pyramid (what DepthSensing.exe does with the keys of
+ * zParametersTrackingDefault.txt, the second argument of scan_processor.py:126).  The semantics, per pixel and per iteration, are DESIGN.md section
+ * "Camera tracking".  The key names below are VoxelHashing's as remembered (the upstream tracker is not in the reference tree).  Lists are finest
+ * level first.  A track changes nothing in the volume, its counters or frame numbering. */
+typedef struct sf_track_params {
+  int32_t levels;                   /* s_maxLevels: pyramid levels, 1..4: 3                                                      */
+  int32_t max_iters[4];             /* s_maxOuterIter: iterations per level, 1..100: 10 5 4 4                                   */
+  float dist_thres[4];              /* s_distThres: metres, > 0: 0.15 0.15 0.15 0.15                                            */
+  float normal_thres[4];            /* s_normalThres: smallest cosine between the two normals, -1..1: 0.7 0.7 0.7 0.7            */
+  float early_out;                  /* s_residualEarlyOut: a level ends when max |xi| of an update falls below this, >= 0: 1e-5  */
+  int32_t min_correspondences;      /* s_minCorrespondences: fewest level-0 correspondences, >= 6: 1000                          */
+  float max_translation;            /* s_maxTranslation: metres between the guess and the result, > 0: 0.3                       */
+  float max_rotation;               /* s_maxRotation: radians between the guess and the result, > 0: 0.5                         */
+  sf_raycast_params raycast;        /* the model render: width, height and intrinsics must be 0 (the fuser's integration camera)  */
+  int32_t reserved[8];
+} sf_track_params;
+void sf_track_params_default(sf_track_params* t);
+/* the keys above from an mLib ParameterFile (zParametersTrackingDefault.txt); keys that are absent leave *t as it is; t->raycast is not touched */
+int sf_track_params_load_file(const char* path, sf_track_params* t);
+typedef struct sf_track_result {
+  int32_t tracked;                  /* 1: pose_out is the result; 0: lost, pose_out is all -inf (the .sens "tracking lost" pose)   */
+  int32_t iterations[4];            /* iterations run per level, finest first                                                    */
+  int32_t correspondences;          /* of the last level-0 system                                                               */
+  float rms_residual;               /* sqrt(sum r^2 / correspondences) of that system                                           */
+  int32_t lost_reason;              /* 0 tracked, 1 no usable guess / reference pose, 2 too few correspondences, 3 singular system, 4 motion above the bound */
+  int32_t reserved[6];
+} sf_track_result;
+/* One depth frame (host, u16, the fuser's input size; the fuser's pre-pass rule makes metres at the integration size) tracked against the volume:
+ * the model is ray-cast once at ref (NULL: the guess), the estimate starts at guess; pose_out row-major camToWorld.  Synchronous.  Sees every frame
+ * queued on the handle before it.  SF_ERR_INVALID_ARG for a parameter that is out of range or not finite; a guess or reference with a non-finite
+ * element gives "lost", not an error. */
+int sf_fuser_track(sf_fuser* f, const uint16_t* depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
+                   sf_track_result* result);
+/* The same for a depth frame already in HBM (read on sf_fuser_stream(f)). */
+int sf_fuser_track_device(sf_fuser* f, const void* d_depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
+                          sf_track_result* result);
+
 /* Host <-> device helpers so that callers without a HIP binding can stage inputs in HBM. */
 int sf_device_malloc(int device, uint64_t bytes, void** out);
 int sf_device_free(void* p);

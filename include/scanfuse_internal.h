@@ -114,6 +114,12 @@ int sf_fuser_calib_tile_rmw(sf_fuser* f, int read_only, int iters, double* avg_u
  * Every tile is written back as read: the volume is unchanged. */
 int sf_fuser_calib_tile_rmw_ex(sf_fuser* f, int mode, int iters, double* avg_us, uint32_t* tiles);
 
+/* Test hook of the camera tracker (tests/test_track.py): one level's 29-value system for the estimate T and the reference pose T_ref (DESIGN.md
+ * "Camera tracking": the 21 entries of J^T J, row by row of its upper triangle, the 6 of J^T r, sum r^2, the count), summed as sf_fuser_track sums
+ * it.  depth: host u16 at the input size.  mask (optional): the level's W_l x H_l image, 1 where a pixel is a correspondence. */
+int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, const float T[16], const float T_ref[16], const sf_track_params* t,
+                          double sys[29], uint8_t* mask);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

@@ -330,12 +330,14 @@ struct sf_fuser {
   hipEvent_t mc_bounce_ev[2] = {nullptr, nullptr};
   double mc_timing[12] = {0};   // phases of the most recent sf_fuser_extract_mesh (mc.hip; sf_fuser_mc_timing)
   hipEvent_t ev_raycast[3] = {nullptr, nullptr, nullptr};   // raycast.hip: the two front streams' tails before a ray cast, the ray cast itself (made on first use)
+  struct TrackWork* track = nullptr;   // track.hip: the tracker's pyramids, model maps and read-back buffers (made on first use)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
 };
 
 
 hipError_t sf_quiesce(sf_fuser* f);                 // drain both streams
+void sf_track_release(sf_fuser* f);                 // track.hip: frees f->track
 void sf_run_resources_prepare(int device, size_t pinned_bytes, size_t device_bytes, size_t plan_bytes);   // pipeline.hip: the side streams and the pinned ring of sf_fuse_run, created in the background
 bool sf_single_stream_batch(const sf_fuser* f, int n, bool color, int sign);   // run_batch keeps this batch on f->stream alone
 hipStream_t sf_input_stream(const sf_fuser* f, int n, bool color, int sign);   // where the batch's frames must be staged

@@ -213,6 +213,48 @@ SF_API int sf_raycast_params_load_file(const char* path, sf_raycast_params* r) {
   return SF_OK;
 }
 
+SF_API void sf_track_params_default(sf_track_params* t) {
+  if (!t) return;
+  std::memset(t, 0, sizeof(*t));
+  t->levels = 3;
+  const int32_t iters[4] = {10, 5, 4, 4};
+  for (int l = 0; l < 4; l++) {
+    t->max_iters[l] = iters[l];
+    t->dist_thres[l] = 0.15f;
+    t->normal_thres[l] = 0.7f;
+  }
+  t->early_out = 1e-5f;
+  t->min_correspondences = 1000;
+  t->max_translation = 0.3f;
+  t->max_rotation = 0.5f;
+  sf_raycast_params_default(&t->raycast);
+}
+
+// the tracking keys of zParametersTrackingDefault.txt (names as remembered from VoxelHashing); a list sets the levels it names, finest first
+SF_API int sf_track_params_load_file(const char* path, sf_track_params* t) {
+  if (!path || !t) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  std::map<std::string, std::vector<std::string>> kv;
+  const int rc = read_param_file(path, kv);
+  if (rc != SF_OK) return rc;
+  const struct { const char* key; float* f; int32_t* i; int n; } keys[] = {
+      {"s_maxLevels", nullptr, &t->levels, 1}, {"s_maxOuterIter", nullptr, t->max_iters, 4},
+      {"s_distThres", t->dist_thres, nullptr, 4}, {"s_normalThres", t->normal_thres, nullptr, 4},
+      {"s_residualEarlyOut", &t->early_out, nullptr, 1}, {"s_minCorrespondences", nullptr, &t->min_correspondences, 1},
+      {"s_maxTranslation", &t->max_translation, nullptr, 1}, {"s_maxRotation", &t->max_rotation, nullptr, 1}};
+  for (const auto& k : keys) {
+    auto it = kv.find(k.key);
+    if (it == kv.end()) continue;
+    if (it->second.empty() || (int)it->second.size() > k.n) return sf::fail(SF_ERR_FORMAT, "%s: %s takes 1..%d values", path, k.key, k.n);
+    for (size_t j = 0; j < it->second.size(); j++) {
+      float v;
+      if (!parse_float(it->second[j], &v) || !std::isfinite(v)) return sf::fail(SF_ERR_FORMAT, "%s: bad value for %s", path, k.key);
+      if (k.f) k.f[j] = v;
+      else k.i[j] = (int32_t)std::strtol(it->second[j].c_str(), nullptr, 10);
+    }
+  }
+  return SF_OK;
+}
+
 namespace {
 // CPUs this process may actually use: the cgroup CPU quota when there is one (a container that shows 256 logical CPUs may be allowed
 // the time of 16: threads beyond that only add contention), else the hardware concurrency

@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
@@ -44,6 +45,9 @@ extern char** environ;
 #pragma weak sf_device_malloc
 #pragma weak sf_device_download
 #pragma weak sf_device_free
+// --track's frame loop: the same arrangement
+#pragma weak sf_fuser_track
+#pragma weak sf_fuser_integrate
 
 namespace {
 
@@ -78,6 +82,8 @@ struct Args {
   std::string ipc;               // the directory the ranks exchange through
   const char* render_dir = nullptr;   // --render-depth=<dir>: ray-cast depth images of the fused volume (see render_depth below)
   int render_every = 1;
+  bool track = false;                 // --track: camera poses from frame-to-model tracking (see track_scan below)
+  const char* write_sens = nullptr;   // --write-sens=<out.sens>: the input with the tracked trajectory
   const char* pos[8];
   int n_pos = 0;
 };
@@ -218,6 +224,60 @@ int render_depth(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_in
   return rc;
 }
 
+// ---- --track [--write-sens=<out.sens>] (what the reference tool does with its second parameter file: DepthSensing.exe tracks the camera when the
+// trajectory is to be rewritten, zParametersScanNet.txt s_trackingEnabled / s_overwriteOrigSensTrajectory): frame 0 at its pose in the file (identity
+// when that pose is invalid), every later frame tracked against the volume fused so far (sf_fuser_track, starting from the last tracked pose) and
+// fused at the pose found.  A lost frame is not fused and gets the -inf pose.  One frame after the other: frame k's pose needs the volume through k - 1.
+int track_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info& info, const sf_params& p) {
+  if (!sf_fuser_track || !sf_fuser_integrate) return die_msg("--track: this libscanfuse has no tracker");
+  sf_track_params tp;
+  sf_track_params_default(&tp);
+  if (sf_track_params_load_file(a.pos[2], &tp) != SF_OK) return die("tracking parameters");
+  if (sf_raycast_params_load_file(a.pos[1], &tp.raycast) != SF_OK) return die("ray-cast parameters");
+  tp.raycast.width = tp.raycast.height = 0;   // the tracker casts at the integration size with the integration camera
+  tp.raycast.fx = tp.raycast.fy = tp.raycast.mx = tp.raycast.my = 0.0f;
+  const bool color = info.color_width > 0 && info.color_height > 0 &&
+                     (p.color_width > 0 || (info.color_width == info.depth_width && info.color_height == info.depth_height));
+  std::vector<uint16_t> depth((size_t)info.depth_width * info.depth_height);
+  std::vector<uint8_t> rgb(color ? (size_t)info.color_width * info.color_height * 3 : 0);
+  float last[16], pose[16];
+  uint64_t tracked = 0, lost = 0;
+  double ms_track = 0.0;
+  for (uint64_t i = 0; i < info.num_frames; i++) {
+    if (sf_sens_decode_depth(sens, i, depth.data()) != SF_OK) return die("depth frame");
+    if (color && sf_sens_decode_color(sens, i, rgb.data()) != SF_OK) return die("colour frame");
+    bool ok = true;
+    if (i == 0) {
+      int valid = 0;
+      if (sf_sens_pose(sens, 0, pose, &valid) != SF_OK) return die("pose");
+      if (!valid)
+        for (int k = 0; k < 16; k++) pose[k] = k % 5 == 0 ? 1.0f : 0.0f;
+    } else {
+      sf_track_result res;
+      const auto t0 = std::chrono::steady_clock::now();
+      if (sf_fuser_track(fuser, depth.data(), last, nullptr, &tp, pose, &res) != SF_OK) return die("tracking");
+      ms_track += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      ok = res.tracked != 0;
+      if (ok) tracked++;
+      else lost++;
+    }
+    if (ok) {
+      const int rc = sf_fuser_integrate(fuser, depth.data(), color ? rgb.data() : nullptr, pose);
+      if (rc != SF_OK && rc != SF_ERR_SKIPPED) return die("integrate");
+      std::memcpy(last, pose, sizeof(last));
+    }
+    if (a.write_sens && sf_sens_set_pose(sens, i, pose) != SF_OK) return die("pose");
+  }
+  if (sf_fuser_sync(fuser) != SF_OK) return die("fuse");
+  const uint64_t n = info.num_frames > 1 ? info.num_frames - 1 : 0;
+  say("Tracked %llu frames, lost %llu, %.3f ms per frame\n", (unsigned long long)tracked, (unsigned long long)lost, n ? ms_track / (double)n : 0.0);
+  if (a.write_sens) {
+    if (sf_sens_save(sens, a.write_sens) != SF_OK) return die("write-sens");
+    say("Tracked trajectory written to %s\n", a.write_sens);
+  }
+  return 0;
+}
+
 // ---- one process, one GPU: the whole scan (ranks == 1) or this rank's stripes of it ------------------------------------------------------------------
 int fuse_scan(const Args& a) {
   const bool part = a.rank >= 0;
@@ -257,17 +317,21 @@ int fuse_scan(const Args& a) {
   sf_fuser* fuser = nullptr;
   if (sf_fuser_create(&p, device, &fuser) != SF_OK) return die("fuser");
   if (part && sf_fuser_set_stripes(fuser, 0, 0, STRIPE_BLOCKS, a.ranks, a.rank) != SF_OK) return die("stripes");
-  sf_run_stats rs;
-  // decode threads: the library's default (one per usable core) for one process; the ranks of a partitioned run share the host's cores
-  const int cores = (int)std::thread::hardware_concurrency();
-  const int decode_threads = part ? std::max(4, cores / std::max(1, a.ranks)) : 0;
-  if (sf_fuse_run(fuser, sens, 0, 0, decode_threads, &rs) != SF_OK) return die("fuse");
-  sf_stats st;
-  sf_fuser_stats(fuser, &st);
-  say("Integrated %llu frames (%llu skipped: invalid pose) in %.3f s = %.1f frames/s with %u decode threads; %u SDF blocks, heapFreeCount = %u\n",
-      (unsigned long long)rs.frames_integrated, (unsigned long long)rs.frames_skipped, rs.seconds_total,
-      rs.seconds_total > 0 ? (double)rs.frames_total / rs.seconds_total : 0.0, rs.decode_threads, st.blocks_allocated, st.heap_free);
-  if (st.alloc_failures) say("WARNING: %u block allocations failed (s_hashNumSDFBlocks / s_hashNumBuckets too small)\n", st.alloc_failures);
+  if (a.track) {
+    if (track_scan(a, fuser, sens, info, p) != 0) return 1;
+  } else {
+    sf_run_stats rs;
+    // decode threads: the library's default (one per usable core) for one process; the ranks of a partitioned run share the host's cores
+    const int cores = (int)std::thread::hardware_concurrency();
+    const int decode_threads = part ? std::max(4, cores / std::max(1, a.ranks)) : 0;
+    if (sf_fuse_run(fuser, sens, 0, 0, decode_threads, &rs) != SF_OK) return die("fuse");
+    sf_stats st;
+    sf_fuser_stats(fuser, &st);
+    say("Integrated %llu frames (%llu skipped: invalid pose) in %.3f s = %.1f frames/s with %u decode threads; %u SDF blocks, heapFreeCount = %u\n",
+        (unsigned long long)rs.frames_integrated, (unsigned long long)rs.frames_skipped, rs.seconds_total,
+        rs.seconds_total > 0 ? (double)rs.frames_total / rs.seconds_total : 0.0, rs.decode_threads, st.blocks_allocated, st.heap_free);
+    if (st.alloc_failures) say("WARNING: %u block allocations failed (s_hashNumSDFBlocks / s_hashNumBuckets too small)\n", st.alloc_failures);
+  }
   if (p.gc_enabled) {
     uint32_t freed = 0;
     if (sf_fuser_garbage_collect(fuser, &freed) != SF_OK) return die("garbage collection");
@@ -485,15 +549,20 @@ int main(int argc, const char** argv_in) {
     else if (!std::strncmp(s, "--exchange-dir=", 15)) a.ipc = s + 15;
     else if (!std::strncmp(s, "--render-depth=", 15) && s[15]) a.render_dir = s + 15;
     else if (!std::strncmp(s, "--render-every=", 15)) a.render_every = std::atoi(s + 15);
+    else if (!std::strcmp(s, "--track")) a.track = true;
+    else if (!std::strncmp(s, "--write-sens=", 13) && s[13]) a.write_sens = s + 13;
     else if (i > 0 && !std::strncmp(s, "--", 2)) bad = true;
     else if (a.n_pos < 8) a.pos[a.n_pos++] = s;
   }
   if (a.n_pos < 4 || bad || a.ranks < 1 || a.ranks > 64 || (a.rank >= 0 && (a.rank >= a.ranks || a.ipc.empty()))) {
-    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
+    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
     return 255;
   }
   if (a.render_dir && a.ranks > 1)
     return die_msg("--render-depth ray-casts one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to render", a.ranks);
+  if (a.track && a.ranks > 1)
+    return die_msg("--track tracks the camera against one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to track", a.ranks);
+  if (a.write_sens && !a.track) return die_msg("--write-sens writes the tracked trajectory: it needs --track");
   if (a.render_every < 1) return die_msg("--render-every=%d: expected a positive frame step", a.render_every);
   if (a.rank >= 0) {
     std::snprintf(g_prefix, sizeof g_prefix, "[rank %d/%d] ", a.rank, a.ranks);

@@ -1,0 +1,541 @@
+// track.hip -- camera tracking against the fused volume: depth-only, frame-to-model, projective point-to-plane ICP over an image pyramid
+// (DESIGN.md "Camera tracking").
+//
+// Per frame: the depth frame becomes metres at the integration size (the fuser's pre-pass rule), then a pyramid of 2x2 reductions with a vertex and
+// a normal map per level; the volume is ray-cast once at the reference pose (raycast.hip, depth and normals) and turned into a world vertex map.
+// Per iteration: k_track_assoc pairs every input pixel with the model pixel it projects to, builds its point-to-plane row and reduces the 29 values
+// of the normal equations of its 256-pixel workgroup (xor butterfly in the wave, (w0 + w1) + (w2 + w3) across waves: no atomics); k_track_final
+// sums the partials in index order in double.  The host solves the 6x6 system in double and updates the pose.  Every step is deterministic and
+// tests/track_checker.c restates it bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "common.h"
+#include "fuser_internal.h"
+#include "scanfuse_internal.h"
+
+namespace {
+
+constexpr int TK_MAX_LEVELS = 4;
+constexpr int TK_NSYS = 29;         // 21 of J^T J, 6 of J^T r, sum r^2, count
+constexpr int TK_PSTRIDE = 32;      // floats per workgroup partial
+constexpr float TK_DOWN_THRES = 0.03f;   // 2x2 reduction: depths within this many metres of the reference pixel's are averaged
+constexpr double TK_PIVOT_REL = 1e-5;     // a Cholesky pivot at or below this share of its diagonal entry counts as non-positive
+
+struct Cam {
+  int W, H;
+  float fx, fy, mx, my;
+};
+struct Rows {
+  float T[12];   // rows 0..2 of a rigid transform
+};
+struct AssocArgs {
+  Cam c;
+  int W0, shift;   // the model image (level 0) and the level's subsampling of it
+  Rows T, M;       // the estimate (world), the estimate in the reference camera (T_ref^-1 T)
+  float dist_thres, normal_thres;
+};
+
+__device__ inline float3 xf(const Rows& R, float3 v) {
+  return make_float3(fmaf(R.T[2], v.z, fmaf(R.T[1], v.y, fmaf(R.T[0], v.x, R.T[3]))), fmaf(R.T[6], v.z, fmaf(R.T[5], v.y, fmaf(R.T[4], v.x, R.T[7]))),
+                     fmaf(R.T[10], v.z, fmaf(R.T[9], v.y, fmaf(R.T[8], v.x, R.T[11]))));
+}
+__device__ inline float3 rot(const Rows& R, float3 n) {
+  return make_float3(fmaf(R.T[2], n.z, fmaf(R.T[1], n.y, R.T[0] * n.x)), fmaf(R.T[6], n.z, fmaf(R.T[5], n.y, R.T[4] * n.x)),
+                     fmaf(R.T[10], n.z, fmaf(R.T[9], n.y, R.T[8] * n.x)));
+}
+__device__ inline float dot3(float3 a, float3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ inline float3 cross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+__device__ inline float3 unproject(const Cam& c, int x, int y, float d) {
+  return make_float3(((float)x - c.mx) / c.fx * d, ((float)y - c.my) / c.fy * d, d);
+}
+
+// u16 frame at the input size -> metres at the integration size: k_prepass's rule (nearest resample, then the depth range)
+__global__ void __launch_bounds__(256) k_track_depth0(const uint16_t* __restrict__ in, const ParamsK P, float* __restrict__ d0) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P.W * P.H) return;
+  uint16_t u;
+  if (P.inW > 0) {
+    const unsigned xi = (unsigned)((float)(i % P.W) * P.rsx + 0.5f), yi = (unsigned)((float)(i / P.W) * P.rsy + 0.5f);
+    u = (xi < (unsigned)P.inW && yi < (unsigned)P.inH) ? in[(size_t)yi * P.inW + xi] : (uint16_t)0;
+  } else {
+    u = in[i];
+  }
+  float v = (float)u / P.depth_shift;
+  if (u == 0 || v < P.dmin || v > P.dmax) v = -INFINITY;
+  d0[i] = v;
+}
+
+// one 2x2 reduction: the mean of the valid depths of the 2x2 block within TK_DOWN_THRES of its top-left (reference) pixel, in the order
+// (0,0), (1,0), (0,1), (1,1); invalid where the reference pixel is
+__global__ void __launch_bounds__(256) k_track_down(const float* __restrict__ src, int Ws, float* __restrict__ dst, int Wd, int Hd) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Wd * Hd) return;
+  const int x = i % Wd, y = i / Wd;
+  const float* s = src + (size_t)(2 * y) * Ws + 2 * x;
+  const float r = s[0];
+  float out = -INFINITY;
+  if (r > 0.0f) {
+    const float v[4] = {s[0], s[1], s[Ws], s[Ws + 1]};
+    float sum = 0.0f, cnt = 0.0f;
+    for (int k = 0; k < 4; k++)
+      if (v[k] > 0.0f && fabsf(v[k] - r) <= TK_DOWN_THRES) {
+        sum = sum + v[k];
+        cnt = cnt + 1.0f;
+      }
+    out = sum / cnt;
+  }
+  dst[i] = out;
+}
+
+// camera-space vertex and normal of every pixel of a level; x = -inf where invalid.  Normal: cross(v(x, y+1) - v, v(x+1, y) - v) normalised
+__global__ void __launch_bounds__(256) k_track_vn(const float* __restrict__ d, const Cam c, float4* __restrict__ vmap, float4* __restrict__ nmap) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= c.W * c.H) return;
+  const int x = i % c.W, y = i / c.W;
+  const float dz = d[i];
+  float4 vo = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f), no = vo;
+  if (dz > 0.0f) {
+    const float3 v = unproject(c, x, y, dz);
+    vo = make_float4(v.x, v.y, v.z, 0.0f);
+    if (x + 1 < c.W && y + 1 < c.H) {
+      const float dr = d[i + 1], dd = d[i + c.W];
+      if (dr > 0.0f && dd > 0.0f) {
+        const float3 vr = unproject(c, x + 1, y, dr), vd = unproject(c, x, y + 1, dd);
+        const float3 n = cross3(make_float3(vd.x - v.x, vd.y - v.y, vd.z - v.z), make_float3(vr.x - v.x, vr.y - v.y, vr.z - v.z));
+        const float len = sqrtf(dot3(n, n));
+        if (len > 0.0f) no = make_float4(n.x / len, n.y / len, n.z / len, 0.0f);
+      }
+    }
+  }
+  vmap[i] = vo;
+  nmap[i] = no;
+}
+
+// the ray-cast image (level 0) as world vertices T_ref * unproject(depth) and world normals; x = -inf where either is missing
+__global__ void __launch_bounds__(256) k_track_model(const float* __restrict__ md, const float* __restrict__ mn, const Cam c, const Rows Tref,
+                                                     float4* __restrict__ mq, float4* __restrict__ mnorm) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= c.W * c.H) return;
+  const float dz = md[i];
+  const float nx = mn[3 * (size_t)i], ny = mn[3 * (size_t)i + 1], nz = mn[3 * (size_t)i + 2];
+  float4 q = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f), n = q;
+  if (dz > 0.0f && nx > -INFINITY) {
+    const float3 p = xf(Tref, unproject(c, i % c.W, i / c.W, dz));
+    q = make_float4(p.x, p.y, p.z, 0.0f);
+    n = make_float4(nx, ny, nz, 0.0f);
+  }
+  mq[i] = q;
+  mnorm[i] = n;
+}
+
+// one level's association and point-to-plane rows, reduced to one 29-float partial per 256-pixel workgroup
+__global__ void __launch_bounds__(256) k_track_assoc(const float4* __restrict__ vmap, const float4* __restrict__ nmap, const float4* __restrict__ mq,
+                                                     const float4* __restrict__ mnorm, const AssocArgs A, float* __restrict__ partials,
+                                                     uint8_t* __restrict__ mask) {
+  __shared__ float red[4][TK_NSYS];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int npx = A.c.W * A.c.H;
+  float acc[TK_NSYS];
+#pragma unroll
+  for (int k = 0; k < TK_NSYS; k++) acc[k] = 0.0f;
+  bool ok = false;
+  if (i < npx) {
+    const float4 v4 = vmap[i], n4 = nmap[i];
+    if (v4.z > 0.0f && n4.x > -INFINITY) {
+      const float3 v = make_float3(v4.x, v4.y, v4.z);
+      const float3 p = xf(A.T, v), n = rot(A.T, make_float3(n4.x, n4.y, n4.z));
+      const float3 pc = xf(A.M, v);
+      if (pc.z > 0.0f) {
+        const float ux = floorf(fmaf(pc.x / pc.z, A.c.fx, A.c.mx) + 0.5f), uy = floorf(fmaf(pc.y / pc.z, A.c.fy, A.c.my) + 0.5f);
+        if (ux >= 0.0f && ux < (float)A.c.W && uy >= 0.0f && uy < (float)A.c.H) {
+          const size_t j = (size_t)((int)uy << A.shift) * A.W0 + ((int)ux << A.shift);
+          const float4 q4 = mq[j];
+          if (q4.x > -INFINITY) {
+            const float4 m4 = mnorm[j];
+            const float3 nm = make_float3(m4.x, m4.y, m4.z);
+            const float3 d = make_float3(p.x - q4.x, p.y - q4.y, p.z - q4.z);
+            if (sqrtf(dot3(d, d)) <= A.dist_thres && dot3(nm, n) >= A.normal_thres) {
+              const float r = dot3(nm, d);
+              const float3 c = cross3(p, nm);
+              const float J[6] = {c.x, c.y, c.z, nm.x, nm.y, nm.z};
+              int k = 0;
+#pragma unroll
+              for (int a = 0; a < 6; a++)
+#pragma unroll
+                for (int b = a; b < 6; b++) acc[k++] = J[a] * J[b];
+#pragma unroll
+              for (int a = 0; a < 6; a++) acc[21 + a] = J[a] * r;
+              acc[27] = r * r;
+              acc[28] = 1.0f;
+              ok = true;
+            }
+          }
+        }
+      }
+    }
+    if (mask) mask[i] = ok ? 1 : 0;
+  }
+  // xor butterfly within the wave: every lane ends with the wave's sum (a + b and b + a are the same float)
+#pragma unroll
+  for (int k = 0; k < TK_NSYS; k++)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc[k] = acc[k] + __shfl_xor(acc[k], off);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < TK_NSYS; k++) red[wave][k] = acc[k];
+  __syncthreads();
+  if (threadIdx.x < TK_NSYS) {
+    const int k = threadIdx.x;
+    partials[(size_t)blockIdx.x * TK_PSTRIDE + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+  }
+}
+
+// the workgroups' partials summed in index order, in double: lane k sums value k
+__global__ void __launch_bounds__(64) k_track_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
+  const int k = threadIdx.x;
+  if (k >= TK_NSYS) return;
+  double s = 0.0;
+#pragma unroll 8
+  for (int b = 0; b < nb; b++) s += (double)partials[(size_t)b * TK_PSTRIDE + k];
+  out[k] = s;
+}
+
+}  // namespace
+
+struct TrackWork {
+  int W = 0, H = 0, levels = 0;
+  int in_px = 0;
+  uint16_t* d_in = nullptr;             // a host frame's device copy
+  float* depth[TK_MAX_LEVELS] = {};     // metres per level
+  float4* vmap[TK_MAX_LEVELS] = {};
+  float4* nmap[TK_MAX_LEVELS] = {};
+  float* model_depth = nullptr;         // the ray cast at level-0 size
+  float* model_normal = nullptr;
+  float4* mq = nullptr;                 // world vertices and normals of the model
+  float4* mn = nullptr;
+  float* partials = nullptr;
+  double* d_sys = nullptr;
+  double* h_sys = nullptr;              // page-locked read-back
+  uint8_t* d_mask = nullptr;
+};
+
+void sf_track_release(sf_fuser* f) {
+  TrackWork* w = f ? f->track : nullptr;
+  if (!w) return;
+  (void)hipFree(w->d_in);
+  for (int l = 0; l < TK_MAX_LEVELS; l++) { (void)hipFree(w->depth[l]); (void)hipFree(w->vmap[l]); (void)hipFree(w->nmap[l]); }
+  (void)hipFree(w->model_depth); (void)hipFree(w->model_normal); (void)hipFree(w->mq); (void)hipFree(w->mn);
+  (void)hipFree(w->partials); (void)hipFree(w->d_sys); (void)hipFree(w->d_mask);
+  if (w->h_sys) (void)hipHostFree(w->h_sys);
+  delete w;
+  f->track = nullptr;
+}
+
+namespace {
+
+// what can be checked without a fuser
+int check_track_params(const sf_track_params* t) {
+  if (!t) return sf::fail(SF_ERR_INVALID_ARG, "NULL tracking parameters");
+  if (t->levels < 1 || t->levels > TK_MAX_LEVELS) return sf::fail(SF_ERR_INVALID_ARG, "tracking levels %d (1..4)", t->levels);
+  for (int l = 0; l < t->levels; l++) {
+    if (t->max_iters[l] < 1 || t->max_iters[l] > 100) return sf::fail(SF_ERR_INVALID_ARG, "max_iters[%d] = %d (1..100)", l, t->max_iters[l]);
+    if (!std::isfinite(t->dist_thres[l]) || !(t->dist_thres[l] > 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "dist_thres[%d] = %g: not a positive finite number", l, t->dist_thres[l]);
+    if (!(t->normal_thres[l] >= -1.0f && t->normal_thres[l] <= 1.0f)) return sf::fail(SF_ERR_INVALID_ARG, "normal_thres[%d] = %g (-1..1)", l, t->normal_thres[l]);
+  }
+  if (!std::isfinite(t->early_out) || !(t->early_out >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "early_out %g: not a finite number >= 0", t->early_out);
+  if (t->min_correspondences < 6) return sf::fail(SF_ERR_INVALID_ARG, "min_correspondences %d (>= 6)", t->min_correspondences);
+  if (!std::isfinite(t->max_translation) || !(t->max_translation > 0.0f) || !std::isfinite(t->max_rotation) || !(t->max_rotation > 0.0f))
+    return sf::fail(SF_ERR_INVALID_ARG, "motion bound %g m, %g rad: not positive finite numbers", t->max_translation, t->max_rotation);
+  const sf_raycast_params& r = t->raycast;
+  if (r.width != 0 || r.height != 0 || r.fx != 0.0f || r.fy != 0.0f || r.mx != 0.0f || r.my != 0.0f)
+    return sf::fail(SF_ERR_INVALID_ARG, "tracking ray cast: the image size and intrinsics must be 0 (the integration camera)");
+  return SF_OK;
+}
+
+// the level cameras: level 0 the integration camera, level l (W >> l) x (H >> l) with the ray caster's scaled intrinsics
+int level_cams(const sf_fuser* f, int levels, Cam* cams) {
+  const int W = f->pk.W, H = f->pk.H;
+  for (int l = 0; l < levels; l++) {
+    Cam& c = cams[l];
+    c.W = W >> l;
+    c.H = H >> l;
+    if (c.W < 8 || c.H < 8) return sf::fail(SF_ERR_INVALID_ARG, "tracking level %d would be %d x %d (at least 8 x 8)", l, c.W, c.H);
+    const float sx = (float)c.W / (float)W, sy = (float)c.H / (float)H;
+    c.fx = f->pk.fx * sx; c.mx = f->pk.mx * sx;
+    c.fy = f->pk.fy * sy; c.my = f->pk.my * sy;
+  }
+  return SF_OK;
+}
+
+int ensure_work(sf_fuser* f, const Cam* cams, int levels) {
+  TrackWork* w = f->track;
+  if (w && w->levels >= levels) return SF_OK;
+  sf_track_release(f);
+  w = new TrackWork();
+  f->track = w;
+  w->W = cams[0].W; w->H = cams[0].H; w->levels = levels;
+  w->in_px = (int)f->in_px;
+  const size_t n0 = (size_t)w->W * w->H;
+#define TK_ALLOC(ptr, bytes)                                                                                                  \
+  do {                                                                                                                        \
+    const hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                                                                 \
+    if (e_ != hipSuccess) { sf_track_release(f); return sf::fail(SF_ERR_DEVICE, "tracking buffers: %s", hipGetErrorString(e_)); } \
+  } while (0)
+  TK_ALLOC(w->d_in, f->in_px * sizeof(uint16_t));
+  for (int l = 0; l < levels; l++) {
+    const size_t n = (size_t)cams[l].W * cams[l].H;
+    TK_ALLOC(w->depth[l], n * sizeof(float));
+    TK_ALLOC(w->vmap[l], n * sizeof(float4));
+    TK_ALLOC(w->nmap[l], n * sizeof(float4));
+  }
+  TK_ALLOC(w->model_depth, n0 * sizeof(float));
+  TK_ALLOC(w->model_normal, n0 * 3 * sizeof(float));
+  TK_ALLOC(w->mq, n0 * sizeof(float4));
+  TK_ALLOC(w->mn, n0 * sizeof(float4));
+  TK_ALLOC(w->partials, ((n0 + 255) / 256) * TK_PSTRIDE * sizeof(float));
+  TK_ALLOC(w->d_sys, TK_PSTRIDE * sizeof(double));
+  TK_ALLOC(w->d_mask, n0);
+#undef TK_ALLOC
+  const hipError_t e = hipHostMalloc((void**)&w->h_sys, TK_PSTRIDE * sizeof(double), hipHostMallocDefault);
+  if (e != hipSuccess) { w->h_sys = nullptr; sf_track_release(f); return sf::fail(SF_ERR_DEVICE, "tracking read-back buffer: %s", hipGetErrorString(e)); }
+  return SF_OK;
+}
+
+bool finite12(const float* T) {
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(T[i])) return false;
+  return true;
+}
+
+Rows rows_of(const float* T) {
+  Rows r;
+  std::memcpy(r.T, T, sizeof(r.T));
+  return r;
+}
+
+// the input pyramid of a frame in HBM and the model of the volume at T_ref, queued on f->stream
+int prepare(sf_fuser* f, const void* d_depth, const float* Tref, const sf_track_params* t, const Cam* cams) {
+  TrackWork* w = f->track;
+  const int n0 = cams[0].W * cams[0].H;
+  hipLaunchKernelGGL(k_track_depth0, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, (const uint16_t*)d_depth, f->pk, w->depth[0]);
+  SF_HIP_CHECK(hipGetLastError());
+  for (int l = 1; l < t->levels; l++) {
+    const int n = cams[l].W * cams[l].H;
+    hipLaunchKernelGGL(k_track_down, dim3((n + 255) / 256), dim3(256), 0, f->stream, w->depth[l - 1], cams[l - 1].W, w->depth[l], cams[l].W, cams[l].H);
+    SF_HIP_CHECK(hipGetLastError());
+  }
+  for (int l = 0; l < t->levels; l++) {
+    const int n = cams[l].W * cams[l].H;
+    hipLaunchKernelGGL(k_track_vn, dim3((n + 255) / 256), dim3(256), 0, f->stream, w->depth[l], cams[l], w->vmap[l], w->nmap[l]);
+    SF_HIP_CHECK(hipGetLastError());
+  }
+  // the ray cast orders itself behind both front streams and blocks later front-chain work (raycast.hip)
+  const int rc = sf_fuser_raycast_device(f, Tref, 1, &t->raycast, w->model_depth, w->model_normal, nullptr);
+  if (rc != SF_OK) return rc;
+  hipLaunchKernelGGL(k_track_model, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, w->model_depth, w->model_normal, cams[0], rows_of(Tref), w->mq, w->mn);
+  SF_HIP_CHECK(hipGetLastError());
+  return SF_OK;
+}
+
+// T_ref^-1 (cofactors over the determinant, as the oracle's frame set-up) composed with T, in double: rounded to float once
+void compose_ref(const double* Tref, const double* T, float* M) {
+  const double a00 = Tref[0], a01 = Tref[1], a02 = Tref[2], a10 = Tref[4], a11 = Tref[5], a12 = Tref[6], a20 = Tref[8], a21 = Tref[9], a22 = Tref[10];
+  const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+  const double det = a00 * c00 + a01 * c01 + a02 * c02;
+  double inv[9];
+  inv[0] = c00 / det; inv[1] = (a02 * a21 - a01 * a22) / det; inv[2] = (a01 * a12 - a02 * a11) / det;
+  inv[3] = c01 / det; inv[4] = (a00 * a22 - a02 * a20) / det; inv[5] = (a02 * a10 - a00 * a12) / det;
+  inv[6] = c02 / det; inv[7] = (a01 * a20 - a00 * a21) / det; inv[8] = (a00 * a11 - a01 * a10) / det;
+  const double dt[3] = {T[3] - Tref[3], T[7] - Tref[7], T[11] - Tref[11]};
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) M[4 * r + c] = (float)((inv[3 * r] * T[c] + inv[3 * r + 1] * T[4 + c]) + inv[3 * r + 2] * T[8 + c]);
+    M[4 * r + 3] = (float)((inv[3 * r] * dt[0] + inv[3 * r + 1] * dt[1]) + inv[3 * r + 2] * dt[2]);
+  }
+}
+
+// one level's system at the estimate T (double, rows 0..2 used), summed into w->h_sys; the mask optionally into w->d_mask
+int system_at(sf_fuser* f, int l, const Cam* cams, const double* T, const double* Tref, const sf_track_params* t, bool want_mask) {
+  TrackWork* w = f->track;
+  AssocArgs A;
+  A.c = cams[l];
+  A.W0 = cams[0].W;
+  A.shift = l;
+  for (int i = 0; i < 12; i++) A.T.T[i] = (float)T[i];
+  compose_ref(Tref, T, A.M.T);
+  A.dist_thres = t->dist_thres[l];
+  A.normal_thres = t->normal_thres[l];
+  const int n = cams[l].W * cams[l].H, nb = (n + 255) / 256;
+  hipLaunchKernelGGL(k_track_assoc, dim3(nb), dim3(256), 0, f->stream, w->vmap[l], w->nmap[l], w->mq, w->mn, A, w->partials, want_mask ? w->d_mask : nullptr);
+  SF_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_track_final, dim3(1), dim3(64), 0, f->stream, w->partials, nb, w->d_sys);
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys, w->d_sys, TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(f->stream));
+  return SF_OK;
+}
+
+// A xi = -b by Cholesky, in double; false at a pivot <= TK_PIVOT_REL x its diagonal entry
+bool solve6(const double* sys, double* xi) {
+  double A[6][6], L[6][6] = {};
+  int k = 0;
+  for (int a = 0; a < 6; a++)
+    for (int b = a; b < 6; b++) A[a][b] = A[b][a] = sys[k++];
+  for (int j = 0; j < 6; j++) {
+    double s = A[j][j];
+    for (int m = 0; m < j; m++) s -= L[j][m] * L[j][m];
+    if (!(s > TK_PIVOT_REL * A[j][j])) return false;
+    L[j][j] = std::sqrt(s);
+    for (int i = j + 1; i < 6; i++) {
+      double e = A[i][j];
+      for (int m = 0; m < j; m++) e -= L[i][m] * L[j][m];
+      L[i][j] = e / L[j][j];
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; i++) {
+    double e = -sys[21 + i];
+    for (int m = 0; m < i; m++) e -= L[i][m] * y[m];
+    y[i] = e / L[i][i];
+  }
+  for (int i = 5; i >= 0; i--) {
+    double e = y[i];
+    for (int m = i + 1; m < 6; m++) e -= L[m][i] * xi[m];
+    xi[i] = e / L[i][i];
+  }
+  return true;
+}
+
+// T <- [Rodrigues(omega) | t] T, xi = (omega, t)
+void apply_update(const double* xi, double* T) {
+  const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
+  const double th = std::sqrt((w0 * w0 + w1 * w1) + w2 * w2);
+  double a = 1.0, b = 0.5;
+  if (th >= 1e-8) {
+    a = std::sin(th) / th;
+    b = (1.0 - std::cos(th)) / (th * th);
+  }
+  const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
+  double R[3][3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
+      R[i][j] = ((i == j ? 1.0 : 0.0) + a * K[i][j]) + b * k2;
+    }
+  double out[12];
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 4; j++) out[4 * i + j] = (R[i][0] * T[j] + R[i][1] * T[4 + j]) + R[i][2] * T[8 + j];
+    out[4 * i + 3] += xi[3 + i];
+  }
+  std::memcpy(T, out, sizeof(out));
+}
+
+void lost_pose(float* pose_out) {
+  for (int i = 0; i < 16; i++) pose_out[i] = -INFINITY;
+}
+
+int track_device(sf_fuser* f, const void* d_depth, const float* guess, const float* ref, const sf_track_params* t, float* pose_out, sf_track_result* res) {
+  int rc = check_track_params(t);
+  if (rc != SF_OK) return rc;
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
+  if (!d_depth || !guess || !pose_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  sf_track_result r;
+  std::memset(&r, 0, sizeof(r));
+  lost_pose(pose_out);
+  if (!ref) ref = guess;
+  Cam cams[TK_MAX_LEVELS];
+  if ((rc = level_cams(f, t->levels, cams)) != SF_OK) return rc;
+  if (!finite12(guess) || !finite12(ref)) {
+    r.lost_reason = 1;
+    if (res) *res = r;
+    return SF_OK;
+  }
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
+  if ((rc = prepare(f, d_depth, ref, t, cams)) != SF_OK) return rc;
+  double T[12], Tref[12], G[12];
+  for (int i = 0; i < 12; i++) { T[i] = guess[i]; G[i] = guess[i]; Tref[i] = ref[i]; }
+  const double* sys = f->track->h_sys;
+  for (int l = t->levels - 1; l >= 0 && r.lost_reason == 0; l--) {
+    for (int it = 0; it < t->max_iters[l]; it++) {
+      if ((rc = system_at(f, l, cams, T, Tref, t, false)) != SF_OK) return rc;
+      if (l == 0) {
+        r.correspondences = (int32_t)sys[28];
+        r.rms_residual = sys[28] > 0.0 ? (float)std::sqrt(sys[27] / sys[28]) : 0.0f;
+        if (sys[28] < (double)t->min_correspondences) { r.lost_reason = 2; break; }
+      }
+      double xi[6];
+      if (!solve6(sys, xi)) { r.lost_reason = 3; break; }
+      apply_update(xi, T);
+      r.iterations[l]++;
+      double mx = 0.0;
+      for (int k = 0; k < 6; k++) mx = std::fmax(mx, std::fabs(xi[k]));
+      if (mx < (double)t->early_out) break;
+    }
+  }
+  if (r.lost_reason == 0) {
+    const double dt[3] = {T[3] - G[3], T[7] - G[7], T[11] - G[11]};
+    const double dist = std::sqrt((dt[0] * dt[0] + dt[1] * dt[1]) + dt[2] * dt[2]);
+    double tr = 0.0;   // trace(R_guess^T R)
+    for (int i = 0; i < 3; i++) tr += (G[i] * T[i] + G[4 + i] * T[4 + i]) + G[8 + i] * T[8 + i];
+    const double ang = std::acos(std::fmin(1.0, std::fmax(-1.0, (tr - 1.0) * 0.5)));
+    bool fin = true;
+    for (int i = 0; i < 12; i++) fin = fin && std::isfinite(T[i]);
+    if (!fin || !(dist <= (double)t->max_translation) || !(ang <= (double)t->max_rotation)) r.lost_reason = 4;
+  }
+  if (r.lost_reason == 0) {
+    r.tracked = 1;
+    for (int i = 0; i < 12; i++) pose_out[i] = (float)T[i];
+    pose_out[12] = pose_out[13] = pose_out[14] = 0.0f;
+    pose_out[15] = 1.0f;
+  }
+  if (res) *res = r;
+  return SF_OK;
+}
+
+}  // namespace
+
+SF_API int sf_fuser_track_device(sf_fuser* f, const void* d_depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
+                                 sf_track_result* result) {
+  return track_device(f, d_depth, guess, ref, t, pose_out, result);
+}
+
+SF_API int sf_fuser_track(sf_fuser* f, const uint16_t* depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
+                          sf_track_result* result) {
+  int rc = check_track_params(t);
+  if (rc != SF_OK) return rc;
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
+  if (!depth || !guess || !pose_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  Cam cams[TK_MAX_LEVELS];
+  if ((rc = level_cams(f, t->levels, cams)) != SF_OK) return rc;
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
+  SF_HIP_CHECK(hipMemcpyAsync(f->track->d_in, depth, f->in_px * sizeof(uint16_t), hipMemcpyHostToDevice, f->stream));
+  return track_device(f, f->track->d_in, guess, ref, t, pose_out, result);
+}
+
+SF_API int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, const float T[16], const float T_ref[16], const sf_track_params* t,
+                                 double sys[29], uint8_t* mask) {
+  int rc = check_track_params(t);
+  if (rc != SF_OK) return rc;
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
+  if (!depth || !T || !T_ref || !sys) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (level < 0 || level >= t->levels) return sf::fail(SF_ERR_INVALID_ARG, "level %d of %d", level, t->levels);
+  if (!finite12(T) || !finite12(T_ref)) return sf::fail(SF_ERR_INVALID_ARG, "non-finite pose");
+  Cam cams[TK_MAX_LEVELS];
+  if ((rc = level_cams(f, t->levels, cams)) != SF_OK) return rc;
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
+  TrackWork* w = f->track;
+  SF_HIP_CHECK(hipMemcpyAsync(w->d_in, depth, f->in_px * sizeof(uint16_t), hipMemcpyHostToDevice, f->stream));
+  if ((rc = prepare(f, w->d_in, T_ref, t, cams)) != SF_OK) return rc;
+  double Td[12], Rd[12];
+  for (int i = 0; i < 12; i++) { Td[i] = T[i]; Rd[i] = T_ref[i]; }
+  if ((rc = system_at(f, level, cams, Td, Rd, t, mask != nullptr)) != SF_OK) return rc;
+  for (int k = 0; k < TK_NSYS; k++) sys[k] = w->h_sys[k];
+  if (mask) SF_HIP_CHECK(hipMemcpy(mask, w->d_mask, (size_t)cams[level].W * cams[level].H, hipMemcpyDeviceToHost));
+  return SF_OK;
+}

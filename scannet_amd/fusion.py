@@ -69,6 +69,73 @@ def load_raycast_params(path, base=None):
     return r
 
 
+class SfTrackParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("max_iters", C.c_int32 * 4), ("dist_thres", C.c_float * 4), ("normal_thres", C.c_float * 4),
+                ("early_out", C.c_float), ("min_correspondences", C.c_int32), ("max_translation", C.c_float), ("max_rotation", C.c_float),
+                ("raycast", SfRaycastParams), ("reserved", C.c_int32 * 8)]
+
+
+class SfTrackResult(C.Structure):
+    _fields_ = [("tracked", C.c_int32), ("iterations", C.c_int32 * 4), ("correspondences", C.c_int32), ("rms_residual", C.c_float),
+                ("lost_reason", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+    def as_dict(self):
+        return dict(tracked=bool(self.tracked), iterations=list(self.iterations), correspondences=int(self.correspondences),
+                    rms_residual=float(self.rms_residual), lost_reason=int(self.lost_reason))
+
+
+def default_track_params(**over):
+    """sf_track_params_default (DESIGN.md "Camera tracking"); keyword overrides (lists for the per-level fields)."""
+    t = SfTrackParams()
+    L = _abi.lib()
+    L.sf_track_params_default.argtypes = [C.POINTER(SfTrackParams)]
+    L.sf_track_params_default.restype = None
+    L.sf_track_params_default(C.byref(t))
+    for k, v in over.items():
+        if not hasattr(t, k) or k == "reserved":
+            raise AttributeError("sf_track_params has no field %r" % k)
+        if k in ("max_iters", "dist_thres", "normal_thres"):
+            arr = getattr(t, k)
+            for i, x in enumerate(v):
+                arr[i] = x
+        else:
+            setattr(t, k, v)
+    return t
+
+
+def load_track_params(path, base=None):
+    """The tracking keys (s_maxLevels, s_maxOuterIter, s_distThres, s_normalThres, ...) of an mLib ParameterFile such as
+    zParametersTrackingDefault.txt."""
+    t = base if base is not None else default_track_params()
+    L = _abi.lib()
+    L.sf_track_params_load_file.argtypes = [C.c_char_p, C.POINTER(SfTrackParams)]
+    check(L.sf_track_params_load_file(str(path).encode(), C.byref(t)))
+    return t
+
+
+def track_and_fuse(fuser, frames, first_pose, params=None):
+    """Frame-to-model tracking loop: frame 0 is fused at first_pose, every later frame is tracked against the volume so far, starting from the last
+    tracked pose, and fused at the pose found; a lost frame is not fused.  frames: iterable of u16 depth [H,W] (or (depth, rgb) pairs).
+    -> list of poses (float32 [4,4]; all -inf where lost) and the list of result dicts (None for frame 0)."""
+    poses, results = [], []
+    last = np.ascontiguousarray(first_pose, dtype=np.float32).reshape(4, 4)
+    for k, fr in enumerate(frames):
+        depth, rgb = fr if isinstance(fr, tuple) else (fr, None)
+        if k == 0:
+            pose, res = last, None
+        else:
+            pose, res = fuser.track(depth, last, params=params)
+            res = res.as_dict()
+        if pose is None:
+            poses.append(np.full((4, 4), -np.inf, np.float32))
+        else:
+            fuser.integrate(depth, pose, rgb=rgb)
+            poses.append(pose)
+            last = pose
+        results.append(res)
+    return poses, results
+
+
 def device_count():
     n = C.c_int(0)
     rc = _abi.lib().sf_device_count(C.byref(n))
@@ -345,6 +412,47 @@ class Fuser:
         L = _abi.lib()
         L.sf_fuser_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfRaycastParams), C.c_void_p, C.c_void_p, C.c_void_p]
         check(L.sf_fuser_raycast_device(self._h, _ptr(poses), len(poses), C.byref(r), _ptr(d_depth), _ptr(d_normals), _ptr(d_rgb)))
+
+    # -- camera tracking (DESIGN.md "Camera tracking") --------------------------------------------------
+    def track(self, depth, guess, ref=None, params=None):
+        """Track one u16 depth frame (host, the fuser's input size) against the volume, starting at camToWorld `guess`; the model is ray-cast at
+        `ref` (None: the guess).  -> (pose float32 [4,4] or None when lost, SfTrackResult)."""
+        t = params if params is not None else default_track_params()
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if depth.size != self.params.depth_width * self.params.depth_height:
+            raise ValueError("depth frame has %d pixels, fuser expects %dx%d" % (depth.size, self.params.depth_width, self.params.depth_height))
+        return self._track(_abi.lib().sf_fuser_track, _ptr(depth), guess, ref, t)
+
+    def track_device(self, d_depth, guess, ref=None, params=None):
+        """track() for a u16 depth frame already in HBM (torch tensor or raw pointer), read on self.stream."""
+        t = params if params is not None else default_track_params()
+        return self._track(_abi.lib().sf_fuser_track_device, _ptr(d_depth), guess, ref, t)
+
+    def _track(self, fn, depth_ptr, guess, ref, t):
+        guess = np.ascontiguousarray(guess, dtype=np.float32).reshape(16)
+        ref = None if ref is None else np.ascontiguousarray(ref, dtype=np.float32).reshape(16)
+        out = np.empty(16, np.float32)
+        res = SfTrackResult()
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SfTrackParams), C.c_void_p, C.POINTER(SfTrackResult)]
+        check(fn(self._h, depth_ptr, _ptr(guess), _ptr(ref), C.byref(t), _ptr(out), C.byref(res)))
+        return (out.reshape(4, 4) if res.tracked else None), res
+
+    def track_system(self, depth, level, T, T_ref, params=None, mask=False):
+        """Test hook (scanfuse_internal.h sf_fuser_track_system): one level's 29-value system (float64) at estimate T with the model cast at
+        T_ref, and the level's correspondence mask (u8 [H_l, W_l]) when mask=True."""
+        t = params if params is not None else default_track_params()
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        T = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
+        T_ref = np.ascontiguousarray(T_ref, dtype=np.float32).reshape(16)
+        sys = np.zeros(29, np.float64)
+        m = None
+        if mask:
+            W, H = self.raycast_size()
+            m = np.zeros((H >> level, W >> level), np.uint8)
+        L = _abi.lib()
+        L.sf_fuser_track_system.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SfTrackParams), C.c_void_p, C.c_void_p]
+        check(L.sf_fuser_track_system(self._h, _ptr(depth), int(level), _ptr(T), _ptr(T_ref), C.byref(t), _ptr(sys), _ptr(m)))
+        return (sys, m) if mask else sys
 
     def export_blocks(self):
         """-> (coords int32 [n,3], voxels VOXEL_DTYPE [n,512]) sorted lexicographically by (x,y,z)."""
