@@ -15,9 +15,10 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidde
           "-I" + os.path.join(ROOT, "include")] + os.environ.get("SCANFUSE_BUILD_FLAGS", "").split()   # extra compiler flags, e.g. -g or -save-temps
 
 
-# fuser.hip / calib.hip: the voxel pairs of the integrate kernels are two plain fp32 operations each (fuser_internal.h: packed fp32 buys no issue rate on
-# gfx950); the SLP vectoriser would pack them again
-PER_FILE = {"fuser.hip": ["-fno-slp-vectorize"], "calib.hip": ["-fno-slp-vectorize"]}
+# fuser*.hip / calib.hip: the voxel pairs of the integrate kernels are two plain fp32 operations each (fuser_internal.h: packed fp32 buys no issue rate on
+# gfx950); the SLP vectoriser would pack them again.  Every translation unit of the fusion core gets the flag, whichever stage it holds.
+def per_file_flags(name):
+    return ["-fno-slp-vectorize"] if name.startswith("fuser") or name == "calib.hip" else []
 
 
 def sources():
@@ -43,7 +44,7 @@ def build(force=False, verbose=False):
         o = os.path.join(objdir, os.path.basename(s) + ".o")
         objs.append(o)
         if force or _stale(o, [s] + hdr):
-            cmd = [HIPCC, "--offload-arch=gfx950", "-c", s, "-o", o] + COMMON + PER_FILE.get(os.path.basename(s), [])
+            cmd = [HIPCC, "--offload-arch=gfx950", "-c", s, "-o", o] + COMMON + per_file_flags(os.path.basename(s))
             if s.endswith(".cpp"):
                 cmd = [HIPCC, "-x", "hip", "--offload-arch=gfx950", "-c", s, "-o", o] + COMMON
             if verbose:

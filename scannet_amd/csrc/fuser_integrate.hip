@@ -1,0 +1,818 @@
+// fuser_integrate.hip -- stage 4 of a fusion pass: integrate / deintegrate the pass's frames into the tiles of its list.  k_integrate (every case,
+// 25 variants), the software-pipelined k_integrate_pipe (one colourless frame per launch) and the tile read-modify-write of the calibration;
+// sf_launch_integrate picks the variant.
+#include <hip/hip_runtime.h>
+
+#include "fuser_device.h"
+#include "fuser_internal.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------
+// K4: integrate / deintegrate.  One wave per 8^3 block: the 4 KiB tile is read with four 16 B-per-lane
+// loads (two x-adjacent voxels per load; in the x-row layout of multi-frame passes the lane's own 64 contiguous bytes), updated in
+// registers by EVERY frame of the batch that sees the block (temporal blocking: HBM traffic per frame
+// falls by the batch size, the kernel turns from HBM-bound at B = 1 to VALU/L2-gather-bound) and written
+// back with the same pattern.  There is no reuse inside a tile, so it is not
+// staged through LDS; the depth image (1.2 MB f32) is gathered through L1/L2.
+// pair layout: lane l, load j: uint4 q = 64 j + l -> voxels 2q, 2q+1 -> x = (2l)&7 (+1), y = (l>>2)&7, z = 2j + (l>>5);
+// x-row layout (XR): lane l, load j: uint4 q = 4 l + j -> x = 2j (+1), y = l & 7, z = l >> 3.
+// ---------------------------------------------------------------------------------------------------
+// One frame into one tile held in registers (8 voxels per lane).  Once a batch amortises the HBM traffic the kernel sits on its instruction mix
+// (SQ_INSTS_VALU x 2 clk / SIMD clk = 0.57 of the guide's issue peak, the texture addresser busy 0.56 of the time, HBM at 9 %: bench.py `roofline`,
+// profiles/r06_integrate_xrow_ab.txt), so the update is written for instruction count:
+//   * two straight-line phases: phase A projects all eight voxels and issues the eight depth gathers together at
+//     clamped addresses, phase B applies the update under a select (a per-voxel early-out chain serialises eight
+//     L2 round trips and costs a scalar branch pair per test);
+//   * the lane's voxel pairs are written as v2f pairs (fuser_internal.h) and compiled as two plain fp32 operations each: on gfx950 a v_pk_*_f32 holds the
+//     SIMD as long as two plain ones and issues beside nothing (rounds 1-4 shipped the packed form);
+//   * the two IEEE divisions of DESIGN.md 3.5 are expanded by hand.  1/pcz: v_rcp_f32 seed + two Newton steps --
+//     the arithmetic core of the compiler's own correctly rounded expansion without the div_scale / div_fixup
+//     range handling (pcz is a camera-space depth in metres; exhaustive check over all mantissas and seed errors up
+//     to 2 ulp: tools/check_division.c).  (old*w + sdf*wn) / (w + wn): the divisor is a small integer, its
+//     correctly rounded reciprocal comes from an LDS table and ONE Markstein correction q1 = fma(fma(-m, q0, n), r, q0)
+//     yields the correctly rounded quotient (same tool: 1.4e9 cases incl. near-halfway); numerators below 2^-100
+//     take the plain division so that underflow cannot bite.
+// Every value stored is bit-identical to oracle/tsdf_oracle.c fuse_block.
+// (v2f, pk_fma, splat, recip_rn, quot_rn live in fuser_internal.h: the device self-test in calib.hip runs the same code)
+
+constexpr int RTAB = 512;  // LDS table of correctly rounded 1/m, m = weight + weight_sample < 512
+
+// the per-frame / per-kernel constants the projection and the update multiply with (fuse_project, fuse_update).  They stay in the scalar registers they are
+// loaded into: copying them into vector registers once per frame made the pass slower (plain pairs 808 -> 837 us: profiles/r05_integrate_ab.txt)
+struct FrameV {
+  float ti[12];
+  float fx, fy, mx, my, tscale, tbase;
+};
+__device__ inline FrameV frame_constants(const ParamsK& P, const float* __restrict__ Ti) {
+  FrameV F;
+#pragma unroll
+  for (int k = 0; k < 12; k++) F.ti[k] = Ti[k];
+  F.fx = P.fx; F.fy = P.fy; F.mx = P.mx; F.my = P.my;
+  F.tscale = P.tscale; F.tbase = P.tbase;
+  return F;
+}
+
+__device__ inline int cvt_i32(float x) {  // v_cvt_i32_f32: truncates, saturates, NaN -> 0 (a C cast of NaN / inf would be undefined)
+  int r;
+  asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+
+// a + b saturating at 2^32 - 1: v_add_u32 with the VOP3 clamp bit (b in a scalar register: VOP3 takes no literal on gfx9)
+__device__ inline uint32_t add_sat_u32(uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("v_add_u32_e64 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "s"(b));
+  return r;
+}
+
+// weight_mode 1 (VoxelHashing): the weight of an observation falls with its depth; (uchar) of the float, at most 255
+__device__ inline int depth_weight(const ParamsK& P, float d) {
+  const float z01 = (d - P.dmin) / (P.dmax - P.dmin);
+  const float wf = fmaxf(((float)P.wsample * 1.5f) * (1.0f - z01), 1.0f);
+  return min(cvt_i32(wf), 255);   // saturating conversion: a masked lane's garbage depth cannot trap
+}
+
+// TAB: the weighted-mean division goes through the LDS reciprocal table (integrate with 1 <= weight_sample <= 256).
+// Rows [J0, J0 + NJ) of the tile (a row = the 64 x 2 voxels one 16 B load per lane covers).  NJ = 4 gives the most
+// independent work per issue slot, NJ = 2 called twice halves the live registers (single-frame, occupancy-bound variant).
+// Phase A of one frame on rows [J0, J0 + NJ): camera-space z of the lane's voxel pairs, the pixel each voxel projects to
+// (0 when it projects outside) and whether it projects inside.
+// CLAMP: pixels that project outside read pixel 0 (callers that gather with plain global loads); without it the index of an outside
+// voxel is whatever the saturating conversion gave (callers that gather through a bounds-checked buffer resource and mask by `ok`).
+template <int J0, int NJ, bool CLAMP>
+__device__ inline void fuse_project(const ParamsK& P, const FrameV& FV, v2f wx, float wy, const float (&wz)[4], v2f (&pz)[NJ],
+                                    uint32_t (&pix)[2 * NJ], bool (&ok)[2 * NJ]) {
+  const float* Ti = FV.ti;
+  const uint32_t uw = (uint32_t)P.W, uh = (uint32_t)P.H;
+  // Row constants first, two rows or two components per packed instruction:
+  //      a{x,y}_j = fma(Ti[1|5], wy, fma(Ti[2|6], wz_j, Ti[3|7])),  az_j = fma(Ti[9], wy, fma(Ti[10], wz_j, Ti[11]))
+  v2f axy[NJ], azz[NJ / 2];
+#pragma unroll
+  for (int j = 0; j < NJ; j++)
+    axy[j] = pk_fma((v2f){Ti[1], Ti[5]}, splat(wy), pk_fma((v2f){Ti[2], Ti[6]}, splat(wz[J0 + j]), (v2f){Ti[3], Ti[7]}));
+#pragma unroll
+  for (int jj = 0; jj < NJ / 2; jj++)
+    azz[jj] = pk_fma(splat(Ti[9]), splat(wy), pk_fma(splat(Ti[10]), (v2f){wz[J0 + 2 * jj], wz[J0 + 2 * jj + 1]}, splat(Ti[11])));
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const v2f pcx = pk_fma(splat(Ti[0]), wx, splat(axy[j].x));
+    const v2f pcy = pk_fma(splat(Ti[4]), wx, splat(axy[j].y));
+    const v2f pcz = pk_fma(splat(Ti[8]), wx, splat(azz[j >> 1][j & 1]));
+    const v2f rz = recip_rn(pcz);
+    const v2f uf = pk_add(pk_fma(pcx * splat(FV.fx), rz, splat(FV.mx)), splat(0.5f));
+    const v2f vf = pk_add(pk_fma(pcy * splat(FV.fy), rz, splat(FV.my)), splat(0.5f));
+    pz[j] = pcz;
+#pragma unroll
+    for (int hx = 0; hx < 2; hx++) {
+      // pixel = (int)(u + 0.5f), THEN "skip if outside the image".  v_cvt_i32_f32 truncates towards zero like the C cast
+      // ((-1, 0) -> pixel 0) and saturates, so "0 <= pixel < W" is ONE unsigned compare of the converted value
+      const uint32_t px = (uint32_t)cvt_i32(uf[hx]), py = (uint32_t)cvt_i32(vf[hx]);
+      const bool in = (pcz[hx] > 0.0f) && (px < uw) && (py < uh);
+      const uint32_t p = __umul24(py, uw) + px;   // v_mad_u32_u24: exact for every inside pixel (py < H, W < 2^24), garbage outside
+      ok[2 * j + hx] = in;
+      pix[2 * j + hx] = CLAMP ? (in ? p : 0u) : p;
+    }
+  }
+}
+
+// The same projection for the X-ROW layout (XR): a lane holds the eight voxels of ONE x-row of the block -- y = lane & 7, z = lane >> 3, register pair j =
+// voxels x = 2j, 2j + 1 -- instead of two x-neighbours in each of four z-layers.  Two things follow:
+//   * the inner two fma of every camera-space coordinate, fma(Ti[1], wy, fma(Ti[2], wz, Ti[3])), depend on (y, z) only: ONE set per lane and frame instead of one
+//     per z-row (6 fma instead of 24; the nesting -- hence every bit -- is the specification's);
+//   * one gather instruction now reads the voxels of one x-plane of the block, 8 y x 8 z: 16 consecutive lanes (the unit the L1 coalesces) are 8 y x 2 z at one
+//     x -- two image rows' worth of pixels for a level camera -- where the pair layout spread 4 x by 4 y over four or five rows.  The L1 tag pipeline was the
+//     busiest unit of the pass (0.79-0.86 look-ups per CU and clock, 33.6 per gather instruction: profiles/r06_*).
+template <int J0, int NJ>
+__device__ inline void fuse_project_xr(const ParamsK& P, const FrameV& FV, const v2f (&wxp)[4], float wy, float wz, v2f (&pz)[NJ],
+                                       uint32_t (&pix)[2 * NJ], bool (&ok)[2 * NJ]) {
+  const float* Ti = FV.ti;
+  const uint32_t uw = (uint32_t)P.W, uh = (uint32_t)P.H;
+  const float ax = fmaf(Ti[1], wy, fmaf(Ti[2], wz, Ti[3]));
+  const float ay = fmaf(Ti[5], wy, fmaf(Ti[6], wz, Ti[7]));
+  const float az = fmaf(Ti[9], wy, fmaf(Ti[10], wz, Ti[11]));
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const v2f pcx = pk_fma(splat(Ti[0]), wxp[J0 + j], splat(ax));
+    const v2f pcy = pk_fma(splat(Ti[4]), wxp[J0 + j], splat(ay));
+    const v2f pcz = pk_fma(splat(Ti[8]), wxp[J0 + j], splat(az));
+    const v2f rz = recip_rn(pcz);
+    const v2f uf = pk_add(pk_fma(pcx * splat(FV.fx), rz, splat(FV.mx)), splat(0.5f));
+    const v2f vf = pk_add(pk_fma(pcy * splat(FV.fy), rz, splat(FV.my)), splat(0.5f));
+    pz[j] = pcz;
+#pragma unroll
+    for (int hx = 0; hx < 2; hx++) {
+      const uint32_t px = (uint32_t)cvt_i32(uf[hx]), py = (uint32_t)cvt_i32(vf[hx]);
+      const bool in = (pcz[hx] > 0.0f) && (px < uw) && (py < uh);
+      ok[2 * j + hx] = in;
+      pix[2 * j + hx] = __umul24(py, uw) + px;
+    }
+  }
+}
+
+// Phase B: the update of DESIGN.md 3.5 from the gathered depths (colours) into the tile registers.
+// WM (weight mode): 0 = any weight_sample / weight_max, 1 = weight_sample == 1, 2 = weight_sample == 1 and weight_max == 255 (the shipped
+// parameters after the uchar clamp): the weight byte then increments with saturation as ONE add-with-carry on the {rgb, weight} word;
+// 3 = the observation's weight depends on its depth (sf_params::weight_mode 1), otherwise as 0.
+// dirty[j]: lane mask (a scalar register pair) of the lanes whose row j changed -- kept on the scalar unit across the frames of a batch.
+// COLOR: 0 = geometry only, 1 = colour (every switch a wave-uniform mask), 2 = colour with colour_first == 0 compiled in.
+// ROWS: dirty[] holds one lane mask per row (one frame per launch: the HBM-bound schedule writes back only the rows some lane changed); without
+// it dirty[0] is a wave-uniform "some frame touched this tile" flag and the caller writes the whole tile back -- a ballot of an i1 that is not
+// itself a compare costs a v_cndmask + v_cmp per row (8 of the 241 VALU instructions of a lane's frame), and a pass of 32 frames is VALU-bound
+// with HBM at 8 % of its peak.
+template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS = true>
+__device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f (&rcp_m)[NJ], const float (&d)[2 * NJ], const uint32_t (&c)[2 * NJ], const v2f (&pz)[NJ],
+                                   const bool (&ok)[2 * NJ], uint4 (&v)[4], uint64_t (&dirty)[4]) {
+  constexpr bool WS1 = WM == 1 || WM == 2;
+  // ---- phase B1: which voxels does this frame update?  Then a wave-uniform early-out: 10-25 % of the (block, frame) pairs the frustum
+  // test lets through update nothing (blocks behind the surface, beyond the integration distance, over invalid depth, in the sliver
+  // between the image border and the conservative sphere test) -- everything below (weighted mean, weights, selects: ~40 % of the
+  // instructions of a frame) is skipped for them.  Measured on the configs[1] stream with the CPU checker: tools/waste.py.
+  const float wn = (float)P.wsample;
+  const uint32_t round_mask = P.colour_round ? 0x010101u : 0u;             // scalar registers
+  const uint32_t first_mask = P.colour_first ? 0x00FFFFFFu : 0xFF000000u;
+  constexpr bool wdep = WM == 3;   // depth-dependent observation weight (sf_params::weight_mode 1): its own instantiation, the generic path pays nothing for it
+  const uint32_t maxd_bits = __float_as_uint(P.maxd);
+  v2f q[NJ], sdfc[NJ];
+  v2f wnv[NJ];          // weight of this observation per voxel (a splat unless wdep)
+  int wni[2 * NJ];
+  uint32_t ncw[2 * NJ];
+  bool upd[2 * NJ];
+  bool sat[2 * NJ];
+  bool any_upd = false;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const v2f dk = {d[2 * j], d[2 * j + 1]};
+    v2f sdf = dk - pz[j];
+    const v2f t = pk_fma(splat(FV.tscale), dk, splat(FV.tbase));
+#pragma unroll
+    for (int hx = 0; hx < 2; hx++) {
+      // valid depth (-inf has the sign bit set, valid depths are positive) below the integration distance, not behind the band
+      upd[2 * j + hx] = ok[2 * j + hx] && (__float_as_uint(dk[hx]) < maxd_bits) && (sdf[hx] > -t[hx]);
+      sdf[hx] = min_f32(sdf[hx], t[hx]);
+      sat[2 * j + hx] = false;
+      any_upd = any_upd || upd[2 * j + hx];
+      wni[2 * j + hx] = wdep ? depth_weight(P, dk[hx]) : P.wsample;
+    }
+    wnv[j] = wdep ? (v2f){(float)wni[2 * j], (float)wni[2 * j + 1]} : splat(wn);
+    sdfc[j] = sdf;
+  }
+  if (!__any((int)any_upd)) return;
+  // ---- phase B2: new values into temporaries (the tile itself stays untouched until the end)
+  bool slow = false;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const v2f sdf = sdfc[j];
+    const uint32_t cwj[2] = {v[J0 + j].y, v[J0 + j].w};
+    const v2f wo = {(float)(cwj[0] >> 24), (float)(cwj[1] >> 24)};
+    const v2f old = {__uint_as_float(v[J0 + j].x), __uint_as_float(v[J0 + j].z)};
+    if (SIGN > 0) {
+      const v2f n = pk_fma(old, wo, WS1 ? sdf : sdf * wnv[j]);  // x * 1.0f == x bit for bit
+      const v2f m = wo + wnv[j];
+      if (TAB) {
+        q[j] = quot_rn(n, m, rcp_m[j]);
+        slow = slow || (fabsf(n.x) < 0x1p-100f) || (fabsf(n.y) < 0x1p-100f);
+      } else {
+        q[j] = (v2f){n.x / m.x, n.y / m.y};
+      }
+#pragma unroll
+      for (int hx = 0; hx < 2; hx++) {
+        const uint32_t cw = cwj[hx];
+        const uint32_t w = cw >> 24;
+        uint32_t rgb = cw;   // bytes 0..2 = the accumulated colour (byte 3, the weight, is masked out where the word is assembled)
+        if (COLOR) {
+          // (a + b) / 2 per channel (integer division) is ONE instruction on this ISA: v_lerp_u8 D = per byte (S0 + S1 + S2[bit 0 of the
+          // byte]) >> 1 -- the sum is formed in 9 bits, nothing crosses a byte.  colour_round 1 (combineVoxel upstream, DESIGN 6b:
+          // (uchar)(0.5f a + 0.5f b + 0.5f) = (a + b + 1) >> 1) is the same instruction with bit 0 of every colour byte of S2 set.  The weight byte
+          // of the result is garbage and never used.  colour_first 1: "first observation" is a black accumulated colour instead of a zero weight --
+          // a wave-uniform mask on the word, not a branch.  (Round 3 spent 12 VALU instructions per voxel on this blend: xor / and / shift / add3.)
+          const uint32_t ck = c[2 * j + hx];
+          const uint32_t avg = __builtin_amdgcn_lerp(cw, ck, round_mask);
+          // COLOR 2 (colour_first == 0, the shipped semantics): "no observation yet" = the weight byte is zero = the word is below 2^24 -- one compare
+          // against a literal instead of a mask and a compare
+          const bool first = COLOR == 2 ? cw < 0x01000000u : (cw & first_mask) == 0u;
+          rgb = first ? ck : avg;
+        }
+        if (WM == 2) {
+          if (COLOR) {
+            // weight byte + 1 saturating at 255: an unsigned add with the clamp bit on the whole word saturates to 0xFFFFFFFF exactly when the
+            // weight was 255; only byte 3 of the sum is kept
+            ncw[2 * j + hx] = (rgb & 0x00FFFFFFu) | (add_sat_u32(cw, 0x01000000u) & 0xFF000000u);
+          } else {
+            // without colour "keep the word at 255" is "do not touch the word": the carry of the add folds into the final select
+            uint32_t inc;
+            const bool full = __builtin_add_overflow(cw, 0x01000000u, &inc);
+            ncw[2 * j + hx] = inc;
+            sat[2 * j + hx] = full;
+          }
+        } else {
+          uint32_t nw = w + (uint32_t)wni[2 * j + hx];
+          if (nw > (uint32_t)P.wmax) nw = (uint32_t)P.wmax;
+          ncw[2 * j + hx] = (rgb & 0x00FFFFFFu) | (nw << 24);
+        }
+      }
+    } else {
+      const v2f n = pk_fma(old, wo, -(sdf * wnv[j]));
+      const v2f m = wo - wnv[j];
+      q[j] = (v2f){n.x / m.x, n.y / m.y};  // discarded when the weight drops to <= 0 (then m <= 0)
+#pragma unroll
+      for (int hx = 0; hx < 2; hx++) {
+        const int nw = (int)(cwj[hx] >> 24) - wni[2 * j + hx];
+        if (nw <= 0) { q[j][hx] = __uint_as_float(0u); ncw[2 * j + hx] = 0u; }
+        else ncw[2 * j + hx] = (cwj[hx] & 0xFFFFFFu) | ((uint32_t)nw << 24);
+      }
+    }
+  }
+  if (SIGN > 0 && TAB && __builtin_expect(__any((int)slow), 0)) {
+    // some numerator of the wave is in the underflow range (practically: never): plain IEEE division for this tile
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+      const v2f wo = {(float)(v[J0 + j].y >> 24), (float)(v[J0 + j].w >> 24)};
+      const v2f old = {__uint_as_float(v[J0 + j].x), __uint_as_float(v[J0 + j].z)};
+      const v2f n = pk_fma(old, wo, sdfc[j] * wnv[j]);
+      const v2f m = wo + wnv[j];
+      q[j] = (v2f){n.x / m.x, n.y / m.y};
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    v[J0 + j].x = upd[2 * j] ? __float_as_uint(q[j].x) : v[J0 + j].x;
+    v[J0 + j].y = (upd[2 * j] && !sat[2 * j]) ? ncw[2 * j] : v[J0 + j].y;
+    v[J0 + j].z = upd[2 * j + 1] ? __float_as_uint(q[j].y) : v[J0 + j].z;
+    v[J0 + j].w = (upd[2 * j + 1] && !sat[2 * j + 1]) ? ncw[2 * j + 1] : v[J0 + j].w;
+    if (ROWS) dirty[J0 + j] |= __ballot(upd[2 * j] || upd[2 * j + 1]);
+  }
+  if (!ROWS) dirty[0] = ~0ull;   // reached only when some lane of the wave updates a voxel (the early-out above)
+}
+
+
+// The depth (colour) image of one frame as a buffer resource: gathers address it as SGPR descriptor + 32-bit VGPR byte offset (one
+// v_mul_u32_u24 + one v_lshl_add_u32 per voxel instead of a 64-bit multiply-add, a select and a 64-bit shift-add), and an offset past
+// the image -- a voxel that projects outside, whose index is garbage -- reads 0 instead of faulting; such voxels are masked by `ok`.
+__device__ inline __amdgpu_buffer_rsrc_t image_rsrc(const void* base, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);   // raw buffer, dword data format (gfx9)
+}
+
+template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS, bool XR = false>
+__device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti, const float* __restrict__ depthf,
+                                 const uint2* __restrict__ texel, const float* rtab, v2f wx, float wy, const float (&wz)[4], const v2f (&wxp)[4],
+                                 uint4 (&v)[4], uint64_t (&dirty)[4]) {
+  v2f pz[NJ], rcp_m[NJ];
+  float d[2 * NJ];
+  uint32_t c[2 * NJ];
+  bool ok[2 * NJ];
+  uint32_t pix[2 * NJ];
+  // the weights are known before anything else: start the eight table reads now, they are consumed in phase B
+  if (TAB) {
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+      // weight_sample == 1 in the shipped parameters (WM >= 1): a constant index offset folds into the LDS instruction's immediate
+      const uint32_t ws = (WM == 1 || WM == 2) ? 1u : (uint32_t)P.wsample;
+      rcp_m[j] = (v2f){rtab[(v[J0 + j].y >> 24) + ws], rtab[(v[J0 + j].w >> 24) + ws]};
+    }
+  }
+  // ---- phase A: project; then the gathers, all issued together
+  const FrameV FV = frame_constants(P, Ti);
+  if (XR) fuse_project_xr<J0, NJ>(P, FV, wxp, wy, wz[0], pz, pix, ok);   // wz[0]: the lane's one z
+  else fuse_project<J0, NJ, false>(P, FV, wx, wy, wz, pz, pix, ok);
+  const uint32_t img_bytes = (uint32_t)(P.W * P.H) * 4u;
+  if (COLOR) {
+    // RGB-D: depth and colour of a pixel sit side by side in the pre-pass's texel plane -- one 8-byte gather per voxel (two 4-byte gathers into
+    // two planes were 16 requests per lane and frame; the texture-address unit, not the vector ALU, was the busier one)
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const __amdgpu_buffer_rsrc_t rt = image_rsrc(texel, 2u * img_bytes);
+#pragma unroll
+    for (int k = 0; k < 2 * NJ; k++) {
+      const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rt, pix[k] << 3, 0, 0);
+      d[k] = __uint_as_float(t.x);
+      c[k] = t.y;
+    }
+  } else {
+    const __amdgpu_buffer_rsrc_t rd = image_rsrc(depthf, img_bytes);
+#pragma unroll
+    for (int k = 0; k < 2 * NJ; k++) d[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, pix[k] << 2, 0, 0));
+  }
+  fuse_update<SIGN, COLOR, TAB, WM, J0, NJ, ROWS>(P, FV, rcp_m, d, c, pz, ok, v, dirty);
+}
+
+// 4 waves per SIMD (<= 128 VGPRs).  Tried for the one-frame-per-launch case: 5 waves / 96 VGPRs with the tile in two
+// half passes -- the spills cost more than the occupancy buys (183 us vs 112 us per launch).
+constexpr int INT_WAVES = 5;   // workgroups (of 4 waves) per CU the register budget of k_integrate is set for (plain pairs: 91 registers)
+constexpr int INT_NJ = 4;      // rows of the tile fused together per frame: 4 = the whole tile at once, 2 = in halves (fewer live registers)
+// NJ = 2 (the tile in halves: 63 registers, 8 waves per SIMD) looks 15 % faster in the two-stream schedule (696 against 814 us per launch) only because its
+// waves take every register of the SIMDs and the allocation kernel on the other stream starves (372 -> 818 us): the pass as a whole is slower
+// (profiles/r05_integrate_ab.txt).  Alone the two variants are within a few per cent.  NJ = 2 runs the LAST pass of a sf_fuser_integrate_batch_device call
+// -- nothing is queued behind that pass, no front chain runs beside it: +0.8 % on a 20-frame call, measured --, every other pass NJ = 4 at 5 waves.  Same
+// voxels either way (tests/test_gpu_tsdf.py::test_batched_pass_equals_frame_by_frame runs both).
+template <int SIGN, int COLOR, bool TAB, int WM, bool ROWS, int NJ = INT_NJ, bool XR = false>
+__global__ __launch_bounds__(256, NJ == 2 ? (XR ? 7 : 8) : INT_WAVES) void k_integrate(uint4* __restrict__ voxels, const uint64_t* __restrict__ block_keys,
+                                                   const int32_t* __restrict__ compact, const uint32_t* __restrict__ cmask,
+                                                   const float* __restrict__ depthf_all, const uint2* __restrict__ texel_all,
+                                                   int32_t* counters, int32_t* host_mirror, int compact_counter, int xcd_walk, ParamsK P,
+                                                   BatchTi B) {
+  __shared__ float s_rtab[RTAB];  // correctly rounded 1/m for the weighted-mean division (fuse_tile)
+  if (TAB) {
+    for (int i = threadIdx.x; i < RTAB; i += 256) s_rtab[i] = 1.0f / (float)(i > 0 ? i : 1);
+    __syncthreads();
+  }
+  const int n = counters[compact_counter];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    atomicExch(&counters[C_LAST_BLOCKS], counters[compact_counter + 1]);  // counters share cache lines with words the front stream updates atomically
+    if (host_mirror) *host_mirror = n;
+  }
+  // pair layout: lane l, load j = uint4 64 j + l = voxels x = (2l) & 7 (+1), y = (l >> 2) & 7, z = 2j + (l >> 5);
+  // x-row layout (XR): lane l, load j = uint4 4 l + j = voxels x = 2j (+1), y = l & 7, z = l >> 3 (the lane's 64 contiguous bytes of the tile)
+  const int lx = XR ? 0 : (2 * lane) & 7;
+  const int ly = XR ? lane & 7 : (lane >> 2) & 7;
+  const int lzb = XR ? lane >> 3 : lane >> 5;
+  const size_t npx = (size_t)P.W * P.H;
+  // XCD-aware walk of the list: workgroup b runs on XCD b % 8 (observed placement; a speed hint only, any placement is
+  // correct).  Each XCD takes ONE contiguous eighth of the list -- neighbouring list entries are neighbouring blocks
+  // that gather neighbouring depth pixels, so an XCD's 4 MiB L2 holds its own part of the batch's depth images instead
+  // of all eight L2s each cycling through all 16 x 1.2 MB.  xcd_walk == 0: plain grid-stride order.
+  const int wg_total = (n + 3) >> 2;                         // workgroups' worth of list entries
+  const int chunk = xcd_walk ? (wg_total + 7) >> 3 : wg_total;
+  const int lanes = xcd_walk ? 8 : 1;                        // interleaved sub-grids
+  const int sub = xcd_walk ? (int)(blockIdx.x & 7) : 0;
+  const int per_sub = max(1, (int)gridDim.x / lanes);
+  for (int loc = xcd_walk ? (int)(blockIdx.x >> 3) : (int)blockIdx.x; loc < chunk; loc += per_sub) {
+    const int i = ((sub * chunk + loc) << 2) + wave;
+    if (i >= n) continue;
+    const int slot = compact[i];
+    uint32_t frames = (uint32_t)__builtin_amdgcn_readfirstlane((int)cmask[i]);  // wave-uniform: the frame loop runs on the scalar unit
+    int bx, by, bz;
+    unpack_key(block_keys[slot], bx, by, bz);
+    uint4* vb = voxels + (size_t)slot * 256;
+    uint4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = vb[XR ? lane * 4 + j : j * 64 + lane];
+    const v2f wx = {(float)(8 * bx + lx) * P.voxel, (float)(8 * bx + lx + 1) * P.voxel};
+    const float wy = (float)(8 * by + ly) * P.voxel;
+    float wz[4];
+    v2f wxp[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      wz[j] = (float)(8 * bz + (XR ? 0 : 2 * j) + lzb) * P.voxel;
+      wxp[j] = v2f{(float)(8 * bx + 2 * j) * P.voxel, (float)(8 * bx + 2 * j + 1) * P.voxel};
+    }
+    uint64_t dirty[4] = {0ull, 0ull, 0ull, 0ull};
+    // temporal blocking: the tile stays in registers while every frame of the batch that sees the block is fused
+    // into it, in frame order (the same sequence of updates per voxel as frame-by-frame integration)
+    while (frames != 0u) {
+      const int q = __builtin_ctz(frames);
+      frames &= frames - 1u;
+      const float* Ti = B.Ti[q];
+      const float* __restrict__ depthf = depthf_all + (size_t)q * npx;
+      const uint2* __restrict__ texel = texel_all + (size_t)q * npx;
+#pragma unroll
+      for (int j0 = 0; j0 < 4; j0 += NJ) {
+        if (j0 == 0) fuse_rows<SIGN, COLOR, TAB, WM, 0, NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+        if (j0 == 1) fuse_rows<SIGN, COLOR, TAB, WM, 1 % (5 - NJ), NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+        if (j0 == 2) fuse_rows<SIGN, COLOR, TAB, WM, 2 % (5 - NJ), NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+        if (j0 == 3) fuse_rows<SIGN, COLOR, TAB, WM, 3 % (5 - NJ), NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+      }
+    }
+    if (ROWS) {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if ((dirty[j] >> lane) & 1ull) vb[XR ? lane * 4 + j : j * 64 + lane] = v[j];
+    } else if (dirty[0] != 0ull) {   // wave-uniform: some frame of the pass changed a voxel of this tile -- the whole tile goes back, four 1 KiB stores
+#pragma unroll
+      for (int j = 0; j < 4; j++) vb[XR ? lane * 4 + j : j * 64 + lane] = v[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// K4p: the same update for the HBM-bound regime (ONE frame per launch: a live stream, SF_BATCH=1), software-pipelined.
+// In k_integrate every wave is a serial chain  tile load -> project -> 8 depth gathers -> update -> store  and a SIMD holds
+// four chains; measured the chains, not HBM, bound it.  Here a persistent wave walks its share of the list
+// and keeps three things in flight for LATER tiles while it updates tile k in registers:
+//   * tile k+2 and k+3 travel HBM -> LDS by LDS-DMA (global_load_lds_dwordx4, four 1 KiB requests per tile, no VGPRs) into
+//     a two-slot ring per wave;
+//   * the eight depth gathers of tile k+1 (projected one turn early) land in LDS as well (global_load_lds_dword: per-lane
+//     source address, lane-linear destination), two 2 KiB slots per wave;
+// so nothing asynchronous ever targets a VGPR and every wait is a hand-counted s_waitcnt vmcnt(N) (vector-memory operations
+// return in order: "at most N outstanding" = everything but the N youngest has landed).  Per turn k the issue order is
+//   [tile k+1's stores of the previous turn: S(k-1)]  G(k+1) x8  D(k+3) x4   and the two waits are
+//   top : tile k+1 (requested two turns ago) has landed      -- younger: S(k-2)? G(k) 8, D(k+2) 4, S(k-1)  => vmcnt(12)
+//   mid : the gathers of tile k (issued last turn) have landed -- younger: D(k+2) 4, S(k-1), G(k+1) 8, D(k+3) 4 => vmcnt(16)
+// (stores only make the true count larger, i.e. the waits conservative).  hipcc never sees these loads (it would wait
+// vmcnt(0) at every use while an LDS-DMA is in flight); it only sees ordinary ds_reads after the waits.
+// LDS per wave: 2 x 4 KiB tiles + 2 x 2 KiB gathers = 12 KiB => 3 workgroups (12 waves, 144 KiB) per CU, and 16 KiB left for a workgroup of
+// the next frame's allocation (10.6 KiB for one frame per launch) to run beside it.  Geometry only, no colour:
+// the colour variant stays on k_integrate.  Arithmetic = fuse_project / fuse_update, bit-identical to k_integrate.
+// ---------------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int PIPE_WGS = 3;   // workgroups of k_integrate_pipe per CU (48 KiB of LDS each): its occupancy bound and its persistent grid, PIPE_WGS per CU
+
+// NT: tile loads and stores carry the non-temporal hint -- for passes whose tile set is many times the 256 MiB Infinity Cache (1 mm voxels:
+// 5-7 GB per frame), where keeping streamed tiles on-die only evicts the depth image and the list; below that size the cache hits of
+// consecutive frames are worth more (measured), so run_batch picks the variant from the previous pass's list length.
+template <bool TAB, int WM, bool NT>
+__global__ __launch_bounds__(256, PIPE_WGS) void k_integrate_pipe(uint4* __restrict__ voxels, const uint64_t* __restrict__ block_keys,
+                                                        const int32_t* __restrict__ compact, const float* __restrict__ depthf, int32_t* counters,
+                                                        int32_t* host_mirror, int compact_counter, ParamsK P, BatchTi B) {
+  __shared__ uint4 s_tile[4][2][256];   // per wave: two 4 KiB tile slots
+  __shared__ float s_gath[4][2][512];   // per wave: two slots of 8 gathers x 64 lanes
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int stride = (int)gridDim.x * 4;
+  const int i0 = (int)blockIdx.x * 4 + wave;
+  const int n = counters[compact_counter];
+  uint4* const ring = &s_tile[wave][0][0];
+  float* const gath = &s_gath[wave][0][0];
+  const uint32_t ring_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(lds_ptr_t)ring);
+  const uint32_t gath_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(lds_ptr_t)gath);
+  auto slot_of = [&](int i) { return i < n ? __builtin_amdgcn_readfirstlane(compact[i]) : 0; };
+  // LDS-DMA of one tile (4 x 1 KiB) into ring slot `ts`; the immediate offset applies to the global AND the LDS address
+  auto dma_tile = [&](int slot, int ts) {
+    const uint4* src = voxels + (size_t)slot * 256 + lane;
+    uint32_t keep;
+    if (NT)
+      asm volatile(
+          "s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[lds]\n\ts_nop 0\n\t"
+          "global_load_lds_dwordx4 %[src], off nt\n\tglobal_load_lds_dwordx4 %[src], off offset:1024 nt\n\t"
+          "global_load_lds_dwordx4 %[src], off offset:2048 nt\n\tglobal_load_lds_dwordx4 %[src], off offset:3072 nt\n\t"
+          "s_mov_b32 m0, %[keep]"
+          : [keep] "=&s"(keep)
+          : [src] "v"(src), [lds] "s"(ring_lds + (uint32_t)ts * 4096u)
+          : "memory");
+    else
+      asm volatile(
+          "s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[lds]\n\ts_nop 0\n\t"
+          "global_load_lds_dwordx4 %[src], off\n\tglobal_load_lds_dwordx4 %[src], off offset:1024\n\t"
+          "global_load_lds_dwordx4 %[src], off offset:2048\n\tglobal_load_lds_dwordx4 %[src], off offset:3072\n\t"
+          "s_mov_b32 m0, %[keep]"
+          : [keep] "=&s"(keep)
+          : [src] "v"(src), [lds] "s"(ring_lds + (uint32_t)ts * 4096u)
+          : "memory");
+  };
+  // the 8 gathers of one tile into gather slot `gs` (request j -> bytes [256 j, 256 j + 256) of the slot)
+  auto gather8 = [&](const uint32_t (&pix)[8], int gs) {
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[k] = pix[k] << 2;
+    uint32_t keep;
+    const uint32_t base = gath_lds + (uint32_t)gs * 2048u;
+    asm volatile(
+        "s_mov_b32 %[keep], m0\n\t"
+        "s_mov_b32 m0, %[b]\n\ts_nop 0\n\tglobal_load_lds_dword %[o0], %[d]\n\t"
+        "s_add_u32 m0, %[b], 0x100\n\ts_nop 0\n\tglobal_load_lds_dword %[o1], %[d]\n\t"
+        "s_add_u32 m0, %[b], 0x200\n\ts_nop 0\n\tglobal_load_lds_dword %[o2], %[d]\n\t"
+        "s_add_u32 m0, %[b], 0x300\n\ts_nop 0\n\tglobal_load_lds_dword %[o3], %[d]\n\t"
+        "s_add_u32 m0, %[b], 0x400\n\ts_nop 0\n\tglobal_load_lds_dword %[o4], %[d]\n\t"
+        "s_add_u32 m0, %[b], 0x500\n\ts_nop 0\n\tglobal_load_lds_dword %[o5], %[d]\n\t"
+        "s_add_u32 m0, %[b], 0x600\n\ts_nop 0\n\tglobal_load_lds_dword %[o6], %[d]\n\t"
+        "s_add_u32 m0, %[b], 0x700\n\ts_nop 0\n\tglobal_load_lds_dword %[o7], %[d]\n\t"
+        "s_mov_b32 m0, %[keep]"
+        : [keep] "=&s"(keep)
+        : [o0] "v"(o[0]), [o1] "v"(o[1]), [o2] "v"(o[2]), [o3] "v"(o[3]), [o4] "v"(o[4]), [o5] "v"(o[5]), [o6] "v"(o[6]), [o7] "v"(o[7]),
+          [d] "s"(depthf), [b] "s"(base)
+        : "memory", "scc");
+  };
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    atomicExch(&counters[C_LAST_BLOCKS], counters[compact_counter + 1]);
+    if (host_mirror) *host_mirror = n;
+  }
+  if (i0 >= n) return;
+  const int lx = (2 * lane) & 7;
+  const int ly = (lane >> 2) & 7;
+  const int lzb = lane >> 5;
+  const float* Ti = B.Ti[0];
+  const FrameV FV = frame_constants(P, Ti);   // one frame per launch: the constants are the kernel's
+  auto project = [&](uint64_t key, v2f (&pz)[4], uint32_t (&pix)[8], uint32_t& okmask) {
+    int bx, by, bz;
+    unpack_key(key, bx, by, bz);
+    const v2f wx = {(float)(8 * bx + lx) * P.voxel, (float)(8 * bx + lx + 1) * P.voxel};
+    const float wy = (float)(8 * by + ly) * P.voxel;
+    float wz[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) wz[j] = (float)(8 * bz + 2 * j + lzb) * P.voxel;
+    bool ok[8];
+    fuse_project<0, 4, true>(P, FV, wx, wy, wz, pz, pix, ok);
+    okmask = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; k++) okmask |= ok[k] ? (1u << k) : 0u;
+  };
+  // ---- prologue: tiles 0 and 1 requested, tile 0 read and projected, its gathers and tile 2 requested.
+  // List entries and block keys are wave-uniform scalar loads fetched ahead of their use (slot of tile k+4 and key of tile
+  // k+2 during turn k), so that no dependent scalar round trip ever opens a turn.
+  int i = i0;
+  int slot = slot_of(i), slot1 = slot_of(i + stride), slot2 = slot_of(i + 2 * stride), slot3 = slot_of(i + 3 * stride);
+  dma_tile(slot, 0);
+  if (i + stride < n) dma_tile(slot1, 1);
+  const uint64_t key0 = block_keys[slot];
+  uint64_t key1 = i + stride < n ? block_keys[slot1] : 0ull;
+  if (i + stride < n) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  uint4 v[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) v[j] = ring[0 * 256 + j * 64 + lane];
+  v2f pz[4];
+  uint32_t okmask;
+  {
+    uint32_t pix[8];
+    project(key0, pz, pix, okmask);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // tile 0 is in registers: its ring slot may be overwritten
+    gather8(pix, 0);
+    if (i + 2 * stride < n) dma_tile(slot2, 0);
+  }
+  int par = 0;  // parity of the current turn: tile k sits in gather slot par, tile k+1 in ring slot par ^ 1
+  for (;;) {
+    const int i1 = i + stride, i4 = i + 4 * stride;
+    const bool has1 = i1 < n, has2 = i + 2 * stride < n, has3 = i + 3 * stride < n;  // wave-uniform
+    uint4 vn[4];
+    v2f pzn[4];
+    uint32_t okn = 0u;
+    int slot4 = 0;
+    uint64_t key2 = 0ull;
+    if (has1) {
+      // top: tile k+1 has landed (younger than it: at least G(k) 8 + D(k+2) 4 when tile k+2 exists, else only G(k) 8)
+      if (has2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+#pragma unroll
+      for (int j = 0; j < 4; j++) vn[j] = ring[(par ^ 1) * 256 + j * 64 + lane];
+      uint32_t pixn[8];
+      project(key1, pzn, pixn, okn);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // tile k+1 is in registers before its slot is handed to tile k+3
+      gather8(pixn, par ^ 1);
+      if (has3) dma_tile(slot3, par ^ 1);
+      // scalar prefetch for later turns (after the lgkmcnt wait above, so that it is not waited for here)
+      if (i4 < n) slot4 = __builtin_amdgcn_readfirstlane(compact[i4]);
+      if (has2) key2 = block_keys[slot2];
+      // mid: the gathers of tile k have landed (younger: D(k+2) 4 if any, G(k+1) 8, D(k+3) 4 if any)
+      if (has3) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      else if (has2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    float d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = gath[par * 512 + k * 64 + lane];
+    // RN(1 / (weight + sample)) by v_rcp_f32 + two Newton steps (recip_rn: correctly rounded for every normal divisor, the same bits
+    // as k_integrate's LDS table) -- this kernel has VALU slots to spare and its LDS decides who may run beside it: 48 KiB per
+    // workgroup x 3 leaves 16 KiB per CU, room for one workgroup of the NEXT frame's allocation / compaction on the front stream
+    v2f rcp_m[4];
+    if (TAB) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) rcp_m[j] = recip_rn((v2f){(float)((v[j].y >> 24) + (uint32_t)P.wsample), (float)((v[j].w >> 24) + (uint32_t)P.wsample)});
+    }
+    bool ok[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) ok[k] = (okmask >> k) & 1u;
+    uint32_t cdummy[8];
+    uint64_t dirty[4] = {0ull, 0ull, 0ull, 0ull};
+    fuse_update<1, 0, TAB, WM, 0, 4>(P, FV, rcp_m, d, cdummy, pz, ok, v, dirty);  // consumes d: the gather slot is free again
+    uint4* vb = voxels + (size_t)slot * 256;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if ((dirty[j] >> lane) & 1ull) {
+        if (NT) __builtin_nontemporal_store((u32x4){v[j].x, v[j].y, v[j].z, v[j].w}, reinterpret_cast<u32x4*>(&vb[j * 64 + lane]));
+        else vb[j * 64 + lane] = v[j];
+      }
+    if (!has1) break;
+    i = i1;
+    slot = slot1; slot1 = slot2; slot2 = slot3; slot3 = slot4;
+    key1 = key2;
+#pragma unroll
+    for (int j = 0; j < 4; j++) { v[j] = vn[j]; pz[j] = pzn[j]; }
+    okmask = okn;
+    par ^= 1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Measurement aid: the memory traffic of k_integrate WITHOUT its arithmetic -- every tile of the compact list is read
+// with the same four 1 KiB loads per wave and (mode 0) written back unchanged, same grid, same list walk.  Its duration
+// is the ceiling the access pattern itself (scattered 4 KiB read-modify-write) allows on this HBM; bench.py reports
+// the one-frame-per-launch kernel against it (sf_fuser_calib_tile_rmw).  The volume is left bit-identical.
+// The same traffic taken apart (sf_fuser_calib_tile_rmw_ex): WHICH tiles -- the pass's list (scattered over the pool) or tiles 0 .. n - 1 of the pool
+// (one contiguous span of the same size) -- and HOW a wave turns from reading to writing -- tile by tile, or G tiles read and then G tiles written.
+// If the contiguous copy runs no faster than the scattered one, the 4 KiB granularity is not what holds the pattern below the read-only rate; if the
+// batched turnaround does not either, it is HBM's read / write mix itself.
+// ---------------------------------------------------------------------------------------------------
+template <bool NT, int G>
+__global__ __launch_bounds__(256, 4) void k_tile_rmw_ex(uint4* __restrict__ voxels, const int32_t* __restrict__ compact, const int32_t* __restrict__ counters,
+                                                     int compact_counter, int xcd_walk, int read_only, int contiguous, uint32_t* sink) {
+  const int n = counters[compact_counter];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int groups = (n + G - 1) / G;                 // wave-sized units of work: G tiles each
+  const int wg_total = (groups + 3) >> 2;
+  const int chunk = xcd_walk ? (wg_total + 7) >> 3 : wg_total;
+  const int lanes = xcd_walk ? 8 : 1;
+  const int sub = xcd_walk ? (int)(blockIdx.x & 7) : 0;
+  const int per_sub = max(1, (int)gridDim.x / lanes);
+  uint32_t acc = 0;
+  for (int loc = xcd_walk ? (int)(blockIdx.x >> 3) : (int)blockIdx.x; loc < chunk; loc += per_sub) {
+    const int u = ((sub * chunk + loc) << 2) + wave;
+    if (u >= groups) continue;
+    uint4 v[G][4];
+    uint4* vb[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      const int i = min(u * G + g, n - 1);            // the last group repeats its last tile: written back unchanged twice
+      vb[g] = voxels + (size_t)(contiguous ? i : compact[i]) * 256;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        if (NT) { const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(&vb[g][j * 64 + lane])); v[g][j] = make_uint4(t.x, t.y, t.z, t.w); }
+        else v[g][j] = vb[g][j * 64 + lane];
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        if (read_only) { acc ^= v[g][j].x ^ v[g][j].y ^ v[g][j].z ^ v[g][j].w; continue; }
+        asm volatile("" : "+v"(v[g][j].x));  // opaque to the optimiser: the store below stays
+        if (NT) __builtin_nontemporal_store((u32x4){v[g][j].x, v[g][j].y, v[g][j].z, v[g][j].w}, reinterpret_cast<u32x4*>(&vb[g][j * 64 + lane]));
+        else vb[g][j * 64 + lane] = v[g][j];
+      }
+    }
+  }
+  if (read_only && acc == 0x9E3779B9u) *sink = acc;
+}
+
+// the LDS reciprocal table of the integrate kernels is indexed by weight + sample: it covers weight_sample up to RTAB - 256
+bool recip_table_ok(const sf_fuser* f) { return f->p.weight_sample >= 1 && f->p.weight_sample <= RTAB - 256 && f->p.weight_mode == 0; }
+
+// Grid of the list-walking kernels (k_integrate, the tile read-modify-write): enough workgroups (4 list entries each) for `entries` +25 %; the kernels'
+// grid-stride loop covers any excess, surplus workgroups exit at once.  Whole sub-grids of 8 for the XCD-aware walk.
+int list_grid(const sf_fuser* f, int entries) {
+  int grid = (entries + entries / 4 + 4096 + 3) / 4;
+  if (grid > f->num_cus * 64) grid = f->num_cus * 64;
+  return (grid + 7) & ~7;
+}
+
+// One integrate launch of a pass of n frames out of batch slot sl: a member per kernel family, the variant as template arguments.
+struct IntegrateLaunch {
+  const sf_fuser* f;
+  int sl, n;
+  const BatchTi& bt;
+  hipStream_t s;
+
+  template <int SIGN, int COLOR, bool TAB, int WM, bool ROWS, int NJ = INT_NJ, bool XR = false>
+  void integrate() const {
+    const int grid = list_grid(f, *f->host_mirror);   // sized for the last list length the device reported
+    hipLaunchKernelGGL((k_integrate<SIGN, COLOR, TAB, WM, ROWS, NJ, XR>), dim3(grid), dim3(256), 0, s, f->voxels, f->block_keys, f->compact2[sl],
+                       f->cmask2[sl], f->depthf2[sl], f->color2[sl], f->counters, f->host_mirror, sf_compact_counter(sl), f->xcd_walk ? 1 : 0, f->pk, bt);
+  }
+  // per-row write-back masks for one frame per launch (HBM-bound) and for deintegration; a pass of several frames (VALU-bound) writes touched tiles whole
+  template <int SIGN, int COLOR, bool TAB, int WM>
+  void rows() const {
+    if (SIGN < 0 || n == 1) integrate<SIGN, COLOR, TAB, WM, true>();
+    else integrate<1, COLOR, TAB, WM, false>();
+  }
+  template <int SIGN, bool TAB, int WM>
+  void colour(bool col) const {
+    if (col) rows<SIGN, 1, TAB, WM>();
+    else rows<SIGN, 0, TAB, WM>();
+  }
+  // the x-row lane layout of a pass of several frames; `wide`: the 8-wave variant (NJ 2)
+  template <int COLOR>
+  void xrow(bool wide) const {
+    if (wide) integrate<1, COLOR, true, 2, false, 2, true>();
+    else integrate<1, COLOR, true, 2, false, INT_NJ, true>();
+  }
+  template <int WM>
+  void pipe(bool nt) const {
+    const dim3 pg((unsigned)(f->num_cus * PIPE_WGS));   // persistent: exactly what the CUs hold
+    if (nt) hipLaunchKernelGGL((k_integrate_pipe<true, WM, true>), pg, dim3(256), 0, s, f->voxels, f->block_keys, f->compact2[sl], f->depthf2[sl],
+                               f->counters, f->host_mirror, sf_compact_counter(sl), f->pk, bt);
+    else hipLaunchKernelGGL((k_integrate_pipe<true, WM, false>), pg, dim3(256), 0, s, f->voxels, f->block_keys, f->compact2[sl], f->depthf2[sl],
+                            f->counters, f->host_mirror, sf_compact_counter(sl), f->pk, bt);
+  }
+};
+
+template <bool NT, int G>
+void launch_tile_rmw(const sf_fuser* f, int sl, int grid, int read_only, int contiguous, uint32_t* sink) {
+  hipLaunchKernelGGL((k_tile_rmw_ex<NT, G>), dim3(grid), dim3(256), 0, f->stream, f->voxels, f->compact2[sl], f->counters, sf_compact_counter(sl),
+                     f->xcd_walk ? 1 : 0, read_only, contiguous, sink);
+}
+template <bool NT>
+void launch_tile_rmw_g(const sf_fuser* f, int sl, int G, int grid, int read_only, int contiguous, uint32_t* sink) {
+  if (G == 1) launch_tile_rmw<NT, 1>(f, sl, grid, read_only, contiguous, sink);
+  else if (G == 2) launch_tile_rmw<NT, 2>(f, sl, grid, read_only, contiguous, sink);
+  else launch_tile_rmw<NT, 4>(f, sl, grid, read_only, contiguous, sink);
+}
+
+}  // namespace
+
+// One frame per launch without colour runs the persistent k_integrate_pipe (tune "pipe" 0: always k_integrate)
+bool sf_pipe_batch(const sf_fuser* f, int n, bool color, int sign) { return sign > 0 && n == 1 && !color && recip_table_ok(f) && f->pipe_mode != 0; }
+
+void sf_launch_integrate(const sf_fuser* f, int sl, int n, int sign, bool col, const BatchTi& bt, hipStream_t s) {
+  const IntegrateLaunch L{f, sl, n, bt, s};
+  const bool ws1 = f->p.weight_sample == 1 && f->p.weight_mode == 0;   // every observation weighs exactly 1
+  const bool shipped = ws1 && f->pk.wmax == 255;                        // the shipped setting
+  if (sf_pipe_batch(f, n, col, sign)) {
+    const bool nt = sf_big_pass(f);   // non-temporal tile traffic once the previous pass's tile set was beyond twice the Infinity Cache
+    if (shipped) L.pipe<2>(nt);
+    else if (ws1) L.pipe<1>(nt);
+    else L.pipe<0>(nt);
+  } else if (sign > 0) {
+    if (shipped) {
+      // a pass of several frames runs the x-row lane layout (fuse_project_xr): same voxels, the gathers of one instruction on two image rows instead of five.
+      // The last pass of a batch call has no front chain beside it: the 8-wave variant (NJ 2)
+      const int cl = col ? (f->p.colour_first ? 1 : 2) : 0;
+      const bool wide = f->tail_pass && f->tail_wide;
+      if (cl == 1) L.rows<1, 1, true, 2>();
+      else if (n == 1) { if (cl == 2) L.integrate<1, 2, true, 2, true>(); else L.integrate<1, 0, true, 2, true>(); }
+      else if (cl == 2) L.xrow<2>(wide);
+      else L.xrow<0>(wide);
+    }
+    else if (ws1) L.colour<1, true, 1>(col);
+    else if (recip_table_ok(f)) L.colour<1, true, 0>(col);
+    else if (f->p.weight_mode == 1) L.colour<1, false, 3>(col);
+    else L.colour<1, false, 0>(col);
+  }
+  // deintegration
+  else if (f->p.weight_mode == 1) L.colour<-1, false, 3>(col);
+  else L.colour<-1, false, 0>(col);
+}
+
+// scanfuse_internal.h: the pattern ceiling taken apart.  mode bit 0: read only; bit 1: contiguous tiles 0 .. n - 1 instead of the pass's list; bits 2-3:
+// tiles per turnaround 1 / 2 / 4 (0, 1, 2).  Every tile is written back as it was read: the volume is unchanged whatever it holds.
+SF_API int sf_fuser_calib_tile_rmw_ex(sf_fuser* f, int mode, int iters, double* avg_us, uint32_t* tiles) {
+  if (!f || iters < 1 || mode < 0 || (mode >> 2) > 2) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_calib_tile_rmw_ex: bad argument");
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  SF_HIP_CHECK(sf_quiesce(f));
+  const int sl = f->slot ^ 1;  // the list of the most recent pass
+  int32_t n = 0;
+  SF_HIP_CHECK(hipMemcpy(&n, &f->counters[sf_compact_counter(sl)], 4, hipMemcpyDeviceToHost));
+  if ((uint32_t)n > (uint32_t)f->p.num_sdf_blocks) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_calib_tile_rmw_ex: list length %d out of range", n);
+  const int read_only = mode & 1, contiguous = (mode >> 1) & 1, G = 1 << (mode >> 2);
+  const int grid = list_grid(f, (n + G - 1) / G);
+  uint32_t* sink = nullptr;
+  SF_HIP_CHECK(hipMalloc((void**)&sink, 4));
+  hipEvent_t e0, e1;
+  SF_HIP_CHECK(hipEventCreate(&e0));
+  SF_HIP_CHECK(hipEventCreate(&e1));
+  const bool nt = sf_big_tile_set((uint32_t)n);   // the cache policy k_integrate_pipe would pick for this tile set
+  double total_ms = 0;
+  for (int it = 0; it < iters + 1; it++) {  // first launch untimed
+    SF_HIP_CHECK(hipEventRecord(e0, f->stream));
+    if (nt) launch_tile_rmw_g<true>(f, sl, G, grid, read_only, contiguous, sink);
+    else launch_tile_rmw_g<false>(f, sl, G, grid, read_only, contiguous, sink);
+    SF_HIP_CHECK(hipEventRecord(e1, f->stream));
+    SF_HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    SF_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    if (it > 0) total_ms += ms;
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipFree(sink);
+  if (avg_us) *avg_us = total_ms * 1e3 / iters;
+  if (tiles) *tiles = (uint32_t)n;
+  return SF_OK;
+}
+// the pattern itself: the pass's list, tile by tile
+SF_API int sf_fuser_calib_tile_rmw(sf_fuser* f, int read_only, int iters, double* avg_us, uint32_t* tiles) {
+  return sf_fuser_calib_tile_rmw_ex(f, read_only ? 1 : 0, iters, avg_us, tiles);
+}

@@ -1,4 +1,5 @@
-// fuser_internal.h -- device-side layout and the sf_fuser handle, shared by fuser.hip and mc.hip
+// fuser_internal.h -- device-side layout and the sf_fuser handle, shared by the fusion core (fuser.hip: the host side; fuser_prepass / _alloc / _compact /
+// _integrate / _blocks.hip: one stage each, kernels and their launchers) and by mc.hip, raycast.hip, track.hip, pipeline.hip and calib.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -218,8 +219,8 @@ __device__ inline int hash_lookup(const HashEntry* __restrict__ table, const Par
 // Since round 5 the pairs are two plain fp32 operations each (rounds 1-4 used v_pk_fma / v_pk_mul / v_pk_add_f32).
 // tools/gpu/valu_peak.hip (profiles/r05_valu_issue_table.txt): on gfx950 a v_pk_*_f32 holds the SIMD for ~4.2 cycles and issues beside nothing; a plain v_fma / v_mul / v_add_f32 holds it ~2.2 cycles and issues beside the
 // conversions, compares and selects of another wave -- packing buys no throughput on this part, and the splats cost moves.  Same arithmetic, same bits;
-// the pass 830 -> 808 us, 9 registers fewer (5 waves per SIMD instead of 4).  fuser.hip is built with -fno-slp-vectorize so that the compiler does not
-// pack the pairs again.
+// the pass 830 -> 808 us, 9 registers fewer (5 waves per SIMD instead of 4).  the fuser*.hip files are built with -fno-slp-vectorize so that the
+// compiler does not pack the pairs again.
 struct v2f {
   float x, y;
   __device__ float& operator[](int i) { return i ? y : x; }
@@ -342,3 +343,17 @@ void sf_run_resources_prepare(int device, size_t pinned_bytes, size_t device_byt
 bool sf_single_stream_batch(const sf_fuser* f, int n, bool color, int sign);   // run_batch keeps this batch on f->stream alone
 hipStream_t sf_input_stream(const sf_fuser* f, int n, bool color, int sign);   // where the batch's frames must be staged
 int sf_compact_live(sf_fuser* f, int32_t* n_out, int include_ghosts = 1);   // live heap slots -> f->compact, synchronous
+
+// The stages of a pass, launched by run_batch (fuser.hip) on the slot and streams it chose; each launcher picks its kernel variant itself.
+inline int sf_compact_counter(int sl) { return sl ? (int)C_COMPACT_B : (int)C_COMPACT; }   // the list-length counter of batch slot sl
+void sf_launch_prepass(const sf_fuser* f, int sl, int n, const BatchIn& in, hipStream_t s);   // fuser_prepass.hip
+void sf_launch_alloc(const sf_fuser* f, int sl, int n, const BatchFrames& bf, const BatchIn& in, hipStream_t s, bool fuse_pre);   // fuser_alloc.hip
+void sf_launch_compact(const sf_fuser* f, int sl, const BatchFrames& bf, hipStream_t s);   // fuser_compact.hip
+void sf_launch_integrate(const sf_fuser* f, int sl, int n, int sign, bool col, const BatchTi& bt, hipStream_t s);   // fuser_integrate.hip
+bool sf_pipe_batch(const sf_fuser* f, int n, bool color, int sign);   // fuser_integrate.hip: the pass runs the persistent k_integrate_pipe
+bool sf_big_tile_set(uint32_t tiles);   // fuser.hip: a tile set beyond 512 MiB (the front chain beside k_integrate_pipe, non-temporal tile traffic)
+bool sf_big_pass(const sf_fuser* f);    // ... the previous pass's
+// set-up and maintenance, on f->stream
+void sf_alloc_choose_window(sf_fuser* f, const sf_params* p);   // fuser_alloc.hip: cube window (WIN 32 / 64) or ray-space window, from the geometry
+void sf_launch_ray_tables(const sf_fuser* f);                   // fuser_prepass.hip
+void sf_launch_init_heap(const sf_fuser* f);                    // fuser_blocks.hip

@@ -2,7 +2,7 @@
 `improve` stage (external DepthSensing.exe, call site Server/scan_processor.py:137-138).
 
 Thin ctypes layer over the C ABI (include/scanfuse.h); all arithmetic runs in the HIP kernels of
-scannet_amd/csrc/fuser.hip.  There is no CPU fallback: creating a Fuser without an MI355X raises.
+scannet_amd/csrc/fuser*.hip.  There is no CPU fallback: creating a Fuser without an MI355X raises.
 """
 import ctypes as C
 

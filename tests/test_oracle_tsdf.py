@@ -505,7 +505,7 @@ def test_reference_unprojection_form_against_the_ray_slope_form(oracle):
     assert inv[2].tolist() == [0, 0, 1, 0] and inv[3].tolist() == [0, 0, 0, 1] and inv[0, 1] == 0 and inv[1, 0] == 0
     assert abs(float(inv[0, 0]) * float(fx) - 1) < 1e-6 and abs(float(inv[0, 2]) + float(mx) / float(fx)) < 1e-6
     xs, ys = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32))
-    kx, ky = (xs - mx) / fx, (ys - my) / fy          # csrc/fuser.hip k_ray_tables / k_alloc: true float32 divisions
+    kx, ky = (xs - mx) / fx, (ys - my) / fy          # csrc/fuser_prepass.hip k_ray_tables / fuser_alloc.hip k_alloc: true float32 divisions
     worst, worst_rel = 0.0, 0.0
     rng = np.random.default_rng(4)
     depths = [0.1, 0.25, 0.5, 1.0, 1.5, 2.0, 3.0, 3.999, 4.0, 5.0, 6.0] + list(rng.uniform(0.1, 6.0, 9))

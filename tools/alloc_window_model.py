@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""How often does a ray leave k_alloc_ray's ray-space window?  (numpy model of the map in csrc/fuser.hip `anchor` / `win_bit`.)
+"""How often does a ray leave k_alloc_ray's ray-space window?  (numpy model of the map in csrc/fuser_alloc.hip `anchor` / `win_bit`.)
 
 For passes of 16 consecutive frames of the bench walk (furnished scene, hashed noise) the tool lays the window of every 16x16 pixel tile along the
 mean of the tile's centre rays in the first and the last frame -- exactly the integers the kernel computes: dominant axis, k0, 12-bit fixed-point

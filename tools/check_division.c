@@ -1,4 +1,4 @@
-/* tools/check_division.c -- CPU brute-force check of the hand-expanded divisions of k_integrate and k_alloc (fuser.hip, fuser_internal.h).
+/* tools/check_division.c -- CPU brute-force check of the hand-expanded divisions of k_integrate and k_alloc (fuser_integrate.hip, fuser_alloc.hip, fuser_internal.h).
  *
  *   gcc -O2 -mfma -ffp-contract=off -o /tmp/check_division tools/check_division.c -lm && /tmp/check_division
  *
