@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- RGB-D frames/s integrated on MI355X + the roofline of the integrate kernel.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4mm|1mm|scans|partition]      (N > 1 without a launcher: bench.py re-executes itself
-                                                                                               under torch.distributed.run with N ranks, or refuses)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4mm|1mm|scans|partition] [--full]      (N > 1 without a launcher: bench.py re-executes
+                                                                                                        itself under torch.distributed.run with N ranks, or refuses)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what its headline figure needs and no more: it renders the frames of its W warm-up + K timed steps, primes the device, times the K
+steps, writes --dump-outputs and prints the result line (`roofline` is null in it).  --full adds everything measured or checked BESIDE the metric, each
+in runs of its own after the timed steps: the roofline sample with HIP events and the rocprofv3 --pmc counter passes, the geometry-only and
+one-frame-per-launch passes, the bounded 1 mm leg, the end-to-end legs, the CPU baseline and the parity of the GPU path with the oracle; for
+--config partition the boundary exchange, marching cubes and the merged-mesh check of a prefix.  The --no-* switches below trim a --full run.
 
 --config (BASELINE.json `configs`; the default is the one the metric is quoted on):
   4mm        configs[1]  scene0000_00-scale synthetic stream (5 578 frames, 640x480, 4 mm voxels, 2^19 hash buckets).  One step = one RGB-D
                          frame -- a 640x480 u16 depth image AND a 640x480 RGB image -- through the whole per-frame hot path (pre-pass, block
                          allocation, frustum compaction, TSDF + colour integrate); both streams are resident in HBM before the timed region;
                          with N > 1 every rank fuses its own scan (weak scaling).  --depth-only times the geometry-only path (rounds 1-3's
-                         headline; reported beside the metric as value_depth_only in every default line).
+                         headline; reported beside the metric as value_depth_only in every --full line).
   1mm        configs[2]  the same stream at 1 mm voxels / 2^22 buckets / 2^25 SDF blocks (137 GB of tiles): ~1.4 M tiles = 5.9 GB touched
                          per frame, far beyond the 256 MiB Infinity Cache -- the out-of-cache HBM roofline of the one-frame kernel.
   scans      configs[3]  independent scans (room size +-20 %, 300..6000 frames) popped longest-first from one queue by all ranks, no
@@ -18,7 +24,7 @@
   partition  configs[4]  ONE long scan (default 50 000 frames through a 10-room corridor world) with the block space dealt in stripes
                          to the ranks, boundary layers all-gathered over RCCL before marching cubes; one step = one frame (strong scaling).
 
-`roofline` describes the dominant kernel of the timed region and every `frac` is a fraction of a hardware peak (<= 1):
+`roofline` (--full) describes the dominant kernel of the timed region and every `frac` is a fraction of a hardware peak (<= 1):
   * 32 frames per launch (the default schedule) is VALU-issue bound: bound = "valu", frac = SQ_INSTS_VALU of the launch (separate
     rocprofv3 --pmc pass) x the mean issue cost of the kernel's frame loop at the per-class costs MEASURED on the MI355X
     (tools/gpu/valu_peak.hip, tools/valu_cost_model.py: roofline.valu_peak_calibration) over the SIMD cycles of the launch;
@@ -643,6 +649,7 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
     K = args.steps if args.steps is not None else cfg["steps"]
     Wm = args.warmup if args.warmup is not None else cfg["warmup"]
     child = args.child
+    full = args.full and not child   # everything beside the metric: runs of their own, behind the timed steps
     # the roofline sample: the timed region itself when it is long enough to hold full 16-frame passes, else a fixed window of the same stream
     # (frames 64..463) -- a 20-step run times two short launches, which says nothing about the kernel
     if K >= 400 or child or cfg_name != "4mm":
@@ -650,10 +657,10 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
     else:
         roof_W, roof_K = 64, 400
     rgbd = not args.depth_only   # the metric's own configuration: a colour frame per depth frame
-    e2e_n = 0 if (child or world > 1 or args.no_e2e or cfg_name != "4mm") else args.e2e_frames
-    cpu_n = 0 if (child or world > 1 or args.no_cpu_baseline) else args.cpu_frames
-    ooc_n = 0 if (child or world > 1 or args.no_out_of_cache or cfg_name != "4mm" or args.no_profile) else 16 + 64
-    n_frames = max(K + Wm, roof_W + roof_K if not child else 0, e2e_n, cpu_n, ooc_n)
+    e2e_n = 0 if (not full or world > 1 or args.no_e2e or cfg_name != "4mm") else args.e2e_frames
+    cpu_n = 0 if (not full or world > 1 or args.no_cpu_baseline) else args.cpu_frames
+    ooc_n = 0 if (not full or world > 1 or args.no_out_of_cache or cfg_name != "4mm" or args.no_profile) else 16 + 64
+    n_frames = max(K + Wm, roof_W + roof_K if full else 0, e2e_n, cpu_n, ooc_n)   # a plain run renders the frames of its own steps alone
     first = (rank * 697) % TOTAL_FRAMES   # every rank walks the same room from a different starting frame (an independent scan per GPU)
     stride = W * H * 2
     frames = torch.empty((n_frames, H, W), dtype=torch.int16, device="cuda")
@@ -735,7 +742,7 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
         if last is not None:
             last(fuser)
         ceiling = None
-        if single_frame and profile:
+        if single_frame and profile and full:
             # the last frame's tile traffic without the arithmetic: what this access pattern (scattered 4 KiB RMW) can reach
             rmw_us, ntiles = fuser.calib_tile_rmw(read_only=False, iters=20)
             ro_us, _ = fuser.calib_tile_rmw(read_only=True, iters=20)
@@ -846,7 +853,7 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
     # kernel durations come from the roofline sample below, fused again with the events on.  --single-frame keeps them: its line is the roofline.
     m = run(Wm, K, args.single_frame and not args.no_profile, single_frame=args.single_frame, repeats=R, prime=P, last=dump)
     # the roofline window, on EVERY rank (run() holds barriers and an all-reduce when N > 1: a pass only rank 0 entered would hang the job)
-    mr = m if (child or args.no_profile or m["batch"] == 1) else run(roof_W, roof_K, True)
+    mr = m if (not full or args.no_profile or m["batch"] == 1) else run(roof_W, roof_K, True)
     # every rank's own rate, gathered (N > 1): the driver computes scaling efficiency from `value`, a reader sees the spread here
     per_rank = None
     if world > 1:
@@ -856,7 +863,7 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
         per_rank = [round(float(t.item()), 1) for t in allr]
     out = None
     if rank == 0:
-        pmc_on = world == 1 and not args.no_pmc and not args.no_profile and not child
+        pmc_on = full and world == 1 and not args.no_pmc and not args.no_profile
         if m["batch"] == 1:
             roof = roofline_hbm(m, K, "k_integrate_pipe<true,2,*>" if not rgbd else "k_integrate<1,2,true,2,true> (one frame per launch)")
             if roof is not None and m["ceiling"]:
@@ -909,7 +916,7 @@ def run_stream(args, cfg_name, rank, local_rank, world, dist, torch):
             out["value_rgbd"] = out["value"]
         else:
             out["value_depth_only"] = out["value"]
-        extras = world == 1 and not args.no_profile and not args.single_frame and not child
+        extras = full and world == 1 and not args.no_profile and not args.single_frame
         if extras and rgbd and not args.no_depth_only and cfg_name == "4mm":
             # the geometry-only pass over the same frames (the headline of rounds 1-3): rate with the same repeats, kernel duration and VALU counters
             md = run(Wm, K, False, colour=False, repeats=R, prime=P)
@@ -1207,17 +1214,19 @@ def run_partition(args, rank, local_rank, world, dist, torch):
     t_fuse = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:   # rank 0's stripes (all of the volume at N = 1), before the boundary exchange adds ghosts
         dump_outputs(fuser, args.dump_outputs)
-    # the exchange step + meshing (reported beside the metric, not part of the K timed steps)
-    t1 = time.perf_counter()
-    sent, got = partition.exchange_boundary(fuser, mode=args.exchange) if world > 1 else (fuser.count_boundary(), 0)
-    bytes_in = partition.exchange_boundary.last_bytes if world > 1 else 0
-    sync_all()
-    t_exch = time.perf_counter() - t1
-    t2 = time.perf_counter()
-    mesh = fuser.extract_mesh()
-    nv, nf = mesh.counts()
-    sync_all()
-    t_mc = time.perf_counter() - t2
+    # the exchange step + meshing (--full: reported beside the metric, not part of the K timed steps)
+    t_exch, t_mc, sent, got, bytes_in, nf = 0.0, 0.0, 0, 0, 0, 0
+    if args.full:
+        t1 = time.perf_counter()
+        sent, got = partition.exchange_boundary(fuser, mode=args.exchange) if world > 1 else (fuser.count_boundary(), 0)
+        bytes_in = partition.exchange_boundary.last_bytes if world > 1 else 0
+        sync_all()
+        t_exch = time.perf_counter() - t1
+        t2 = time.perf_counter()
+        mesh = fuser.extract_mesh()
+        nv, nf = mesh.counts()
+        sync_all()
+        t_mc = time.perf_counter() - t2
     st = fuser.stats()
     vals = torch.tensor([t_fuse, t_exch, t_mc, float(st["blocks_allocated"]), float(sent), float(got), float(nf), float(st["alloc_failures"]), float(bytes_in)],
                         dtype=torch.float64, device="cuda")
@@ -1229,12 +1238,12 @@ def run_partition(args, rank, local_rank, world, dist, torch):
         mx = sm = mn = vals
     fuser.close()
     prefix = None
-    if world > 1 and not args.no_prefix_check:
+    if args.full and world > 1 and not args.no_prefix_check:
         prefix = partition_prefix_check(args, frames, stride, poses, params, rank, local_rank, world, dist)
     if rank != 0:
         return None
     t_fuse = float(mx[0])
-    if world > 1 and args.exchange == "neighbour" and int(sm[4]) != int(sm[5]):
+    if args.full and world > 1 and args.exchange == "neighbour" and int(sm[4]) != int(sm[5]):
         raise SystemExit("bench.py: %d boundary blocks sent but %d ghost blocks received: the ring shift lost or duplicated layers" % (int(sm[4]), int(sm[5])))
     return {
         "metric": "RGB-D frames/sec integrated (640x480, 4 mm voxel), one scan partitioned over the GPUs",
@@ -1250,8 +1259,8 @@ def run_partition(args, rank, local_rank, world, dist, torch):
                    "blocks_per_rank_max": int(mx[3]), "blocks_per_rank_min": int(mn[3]), "blocks_total": int(sm[3]), "alloc_failures": int(sm[7])},
         "exchange": {"seconds": round(float(mx[1]), 4), "boundary_blocks_sent_total": int(sm[4]), "ghost_blocks_received_total": int(sm[5]),
                      "mode": args.exchange, "payload_bytes_received_per_rank_max": int(mx[8]), "payload_bytes_received_total": int(sm[8]),
-                     "all_gather_would_receive_per_rank": int(sm[4]) * 4108},
-        "marching_cubes": {"seconds": round(float(mx[2]), 4), "faces_total": int(sm[6])},
+                     "all_gather_would_receive_per_rank": int(sm[4]) * 4108} if args.full else None,
+        "marching_cubes": {"seconds": round(float(mx[2]), 4), "faces_total": int(sm[6])} if args.full else None,
         "rccl_ranks": world if (world > 1 and dist.get_backend() == "nccl") else (0 if world > 1 else 1),
         "process_group": (dist.get_backend() if world > 1 else "none (one process)"),
         "per_rank_blocks": None if world == 1 else {"max": int(mx[3]), "min": int(mn[3])},
@@ -1390,6 +1399,10 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps: frames (scans for --config scans); exactly this many are timed unless --repeats")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", choices=["4mm", "1mm", "scans", "partition"], default="4mm")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the metric, in runs of their own behind the timed steps: roofline "
+                                                        "sample and rocprofv3 --pmc passes, geometry-only and one-frame-per-launch passes, the 1 mm leg, the end-to-end "
+                                                        "legs, the CPU baseline and the parity with the oracle; --config partition: boundary exchange, marching cubes and "
+                                                        "the prefix check.  Off by default: a plain run sets up, warms up, times the steps and prints its line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket the integrate kernel with HIP events")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes (VALU utilisation, HBM traffic)")
@@ -1504,11 +1517,12 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     # the line is out and every handle is closed: leave without the interpreter's teardown (HIP, RCCL and the OpenMP runtime of the CPU
-    # port each register exit handlers, and their order is nobody's contract)
+    # port each register exit handlers, and their order is nobody's contract).  A plain one-GPU run has loaded neither RCCL nor the CPU port:
+    # it is what the counter passes (--child --teardown) are, and leaves through the normal teardown as they do
     sys.stdout.flush()
     sys.stderr.flush()
     under_profiler = args.teardown or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if not under_profiler:   # a profiler writes its results from exactly those exit handlers
+    if not under_profiler and (args.full or world > 1):   # a profiler writes its results from exactly those exit handlers
         os._exit(0)
 
 

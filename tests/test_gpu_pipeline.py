@@ -932,11 +932,12 @@ def test_bench_with_two_ranks_sharing_one_gpu():
     """A BARE `python bench.py --gpus 2 ...` (no launcher in the command: bench.py re-executes itself under torch.distributed.run) runs two ranks:
     one process per rank, barriers, max over ranks, the roofline window on every rank, the partition's ring shift and the merged-mesh check --
     on a one-GPU box `--share-gpu` puts both ranks on GPU 0 over gloo.  A pass that only rank 0 enters hangs the job; a --gpus that is parsed and
-    never read measures one GPU (round 3).  The rates mean nothing here."""
+    never read measures one GPU (round 3).  The rates mean nothing here.  --full: the roofline window, the exchange and the prefix check are
+    measured beside the metric, which a plain run leaves out."""
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     import tempfile
-    for extra in (["--steps", "64", "--warmup", "5", "--repeats", "3", "--no-pmc"], ["--config", "partition", "--scan-frames", "600"]):
+    for extra in (["--full", "--steps", "64", "--warmup", "5", "--repeats", "3", "--no-pmc"], ["--full", "--config", "partition", "--scan-frames", "600"]):
         detail = os.path.join(tempfile.mkdtemp(prefix="sf_bench_"), "detail.json")
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu"] + extra,
                            capture_output=True, text=True, cwd=ROOT, timeout=600, env=dict(env, SF_BENCH_DETAIL=detail))
@@ -956,6 +957,38 @@ def test_bench_with_two_ranks_sharing_one_gpu():
             assert j["repeats"]["n"] == 3 and j["roofline"]["launches"] > 0
             assert len(j["per_rank_frames_per_s"]) == 2 and min(j["per_rank_frames_per_s"]) > 0
             assert j["config"]["rgbd"] is True and j["value_rgbd"] == j["value"]
+
+
+def test_a_plain_bench_run_is_lean(tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` does what its headline figure needs and nothing else: the contract's keys, the dumped
+    volume, no leg beside the metric (those sit behind --full) -- and at most 30 s of the whole run, from start to exit, lie outside its
+    N + W steps."""
+    import sys
+    import time
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    detail, dump = str(tmp_path / "detail.json"), str(tmp_path / "dump")
+    n, w = 20, 5
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(n), "--warmup", str(w), "--dump-outputs", dump],
+                       capture_output=True, text=True, cwd=ROOT, timeout=600, env=dict(env, SF_BENCH_DETAIL=detail))
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 4096 and r.stdout.rstrip().splitlines()[-1] == lines[0]
+    line = json.loads(lines[0])
+    assert line["metric"].startswith("RGB-D frames/sec integrated") and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == n and line["warmup"] == w and line["value"] > 0 and line["ms_per_step"] > 0 and line["roofline"] is None
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1.0      # one GPU: frames/s x ms per frame
+    j = json.load(open(detail))
+    assert j["value"] == line["value"] and j["repeats"]["n"] == 1 and j["config"]["rgbd"] is True and j["config"]["alloc_failures"] == 0
+    for leg in ("cpu_baseline", "parity", "parity_depth_only", "end_to_end", "end_to_end_rgbd", "roofline_single_frame", "roofline_depth_only",
+                "roofline_out_of_cache", "value_depth_only"):
+        assert leg not in j, leg
+    coords = np.load(os.path.join(dump, "block_coords.npy"))
+    assert len(coords) == j["config"]["blocks_live_end"] > 0 and np.load(os.path.join(dump, "sample_weight.npy")).max() > 0
+    outside = wall - (n + w) * line["ms_per_step"] * 1e-3
+    print("plain bench run: %.1f s from start to exit, %.1f s outside its %d steps" % (wall, outside, n + w))
+    assert outside <= 30.0, outside
 
 
 def test_bench_refuses_more_ranks_than_gpus_and_a_mismatched_launcher():

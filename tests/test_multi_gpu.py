@@ -41,17 +41,17 @@ def _bench(extra, timeout=900):
 
 @needs_two
 def test_bench_partition_on_two_gpus_over_rccl():
-    """configs[4] at N = 2: `python bench.py --gpus 2 --config partition` (bare: it re-executes itself under torch.distributed.run, one rank per GPU,
+    """configs[4] at N = 2: `python bench.py --gpus 2 --config partition --full` (bare: it re-executes itself under torch.distributed.run, one rank per GPU,
     nccl) -- stripes dealt to two fusers on two devices, the boundary layers ring-shifted device to device by RCCL send / recv, and the merged mesh of
     a prefix equal to ONE fuser's."""
-    j = _bench(["--config", "partition", "--scan-frames", "256"])
+    j = _bench(["--full", "--config", "partition", "--scan-frames", "256"])
     assert j["n_gpus"] == 2 and j["rccl_ranks"] == 2 and j["process_group"] == "nccl" and j["scaling"] == "strong"
     ex = j["exchange"]
     assert ex["mode"] == "neighbour" and ex["boundary_blocks_sent_total"] == ex["ghost_blocks_received_total"] > 0
     assert ex["payload_bytes_received_total"] == 4108 * ex["ghost_blocks_received_total"]
     pc = j["prefix_check"]
     assert pc["sha256_equal"] and pc["faces"] > 10000 and pc["boundary_blocks_sent"] == pc["ghost_blocks_received"] > 0
-    j = _bench(["--config", "partition", "--scan-frames", "256", "--exchange", "all_gather"])
+    j = _bench(["--full", "--config", "partition", "--scan-frames", "256", "--exchange", "all_gather"])
     assert j["rccl_ranks"] == 2 and j["exchange"]["mode"] == "all_gather" and j["prefix_check"]["sha256_equal"]
 
 

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-prof}
 mkdir -p $O
-Q="--no-cpu-baseline --no-pmc --no-e2e --no-out-of-cache --repeats 1 --teardown"
+Q="--full --no-cpu-baseline --no-pmc --no-e2e --no-out-of-cache --repeats 1 --teardown"
 cd /tmp
 rm -rf /tmp/kt; timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python $R/bench.py $Q > $O/kt.log 2>&1
 python $R/tools/rocpd_summary.py $(find /tmp/kt -name "*.db" | head -1) > $O/kt.txt 2>&1
