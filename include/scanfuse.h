@@ -300,6 +300,49 @@ int sf_fuser_track(sf_fuser* f, const uint16_t* depth, const float guess[16], co
 int sf_fuser_track_device(sf_fuser* f, const void* d_depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
                           sf_track_result* result);
 
+/* Re-integration: the volume-side half of a trajectory correction.  sf_fuser_deintegrate* exists "when a frame's pose is revised" (SURVEY App. C;
+ * BundleFusion's main loop takes up to s_maxFrameFixes frames per step out at their old pose and puts them back at the new one); these calls
+ * do that for many frames in ONE pass over the tiles they touch instead of two passes per frame.  The volume afterwards is bit for bit what this
+ * sequence leaves, for j = 0 .. n - 1 in order: sf_fuser_deintegrate_device(depth_j, rgb_j, old_j), then sf_fuser_integrate_device(depth_j, rgb_j, new_j).
+ * An all -inf old pose: the frame was never integrated, it is only put in; an all -inf new pose: tracking is lost now, it is only taken out; both: nothing
+ * happens.  sf_stats moves as that sequence moves it -- every all -inf pose is one skipped call of it, hence one count in frames_skipped, every other
+ * pose one in frames_integrated -- except total_pass_tiles, which counts what the passes really read.  d_rgb may be NULL (geometry only).  Up to
+ * sf_fuser_batch_frames() operations share a pass, the two of a frame always do.  Who produces the revised poses (a pose-graph or bundle solver,
+ * sf_sens_apply_transform on part of a scan, a second tracking sweep) is the caller's business: global bundle adjustment is not in this library. */
+int sf_fuser_reintegrate_batch_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes,
+                                      const float* old_poses, const float* new_poses, uint64_t n);
+/* one frame from host buffers (as sf_fuser_integrate takes them); SF_ERR_SKIPPED when both poses are all -inf */
+int sf_fuser_reintegrate(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, const float old_pose[16], const float new_pose[16]);
+
+/* The trajectory manager's three keys (Server/tools/recons/zParametersScanNet.txt:25-28).  The manager itself is BundleFusion's and is not in the
+ * reference tree: what the keys mean below is this library's statement, built from the file's own comments. */
+typedef struct sf_reint_params {
+  int32_t max_frame_fixes;          /* s_maxFrameFixes: most frames re-integrated per step, >= 0: 30                              */
+  int32_t top_n_active;             /* s_topNActive: the candidates kept (largest pose change first) before that limit, >= 0: 30 */
+  float min_pose_dist_sqrt;         /* s_minPoseDistSqrt: a frame is a candidate when its squared pose distance exceeds this: 0  */
+  int32_t reserved[5];
+} sf_reint_params;
+void sf_reint_params_default(sf_reint_params* r);
+/* the three keys from an mLib ParameterFile; keys that are absent leave *r as it is */
+int sf_reint_params_load_file(const char* path, sf_reint_params* r);
+/* One step of the manager, on the host in double precision, no GPU: which frames to re-integrate now.  Poses are n x 16 floats, row-major camToWorld:
+ * what the volume holds and what it should hold.  Distance of a frame: d2 = |t_target - t_integrated|^2 (m^2) + theta^2 (rad^2), theta the angle of
+ * M = R_integrated^T R_target, atan2(|(M21 - M12, M02 - M20, M10 - M01)| / 2, (trace M - 1) / 2), exactly 0 for identical poses; +inf when exactly one of the two is all -inf (the frame must go in or out); a frame with both all -inf is no candidate.
+ * Candidates: d2 > min_pose_dist_sqrt.  Order: d2 descending, ties by ascending frame index; the first top_n_active are kept and of those the first
+ * max_frame_fixes returned.  *n_out = how many; SF_ERR_BOUNDS (with *n_out set) when capacity is smaller. */
+int sf_reint_plan(const float* integrated_poses, const float* target_poses, uint64_t n, const sf_reint_params* r, uint64_t* frames_out, uint64_t capacity,
+                  uint64_t* n_out);
+typedef struct sf_reint_stats {
+  uint64_t steps, frames_moved, frames_removed, frames_added, passes;
+  double seconds_total;
+} sf_reint_stats;
+/* Steps of the manager over an opened .sens file until a plan is empty (max_steps = 0) or max_steps are done: plan, decode the planned frames on a pool
+ * of decode_threads (0: one per usable core, at most 32; sf_sens_decode_depth / sf_sens_decode_color), upload, re-integrate in plan order, write the new
+ * poses into integrated_poses (in: what the volume holds, out: what it holds now).  with_colour: the file's colour frames (RAW or JPEG, at the size the
+ * fuser fuses colour at) go with the depth.  The volume is never reset.  Synchronous. */
+int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float* integrated_poses, const float* target_poses, const sf_reint_params* r,
+                              uint64_t max_steps, int with_colour, int decode_threads, sf_reint_stats* stats);
+
 /* Host <-> device helpers so that callers without a HIP binding can stage inputs in HBM. */
 int sf_device_malloc(int device, uint64_t bytes, void** out);
 int sf_device_free(void* p);

@@ -134,6 +134,10 @@ def _declare_optional(L):
         "sf_segment_mesh": ([vp, u64, vp, u64, C.c_float, C.c_int, vp], C.c_int),
         "sf_segment_file": ([C.c_char_p, C.c_float, C.c_int, C.c_char_p, C.POINTER(u64)], C.c_int),
         "sf_ply_read": ([C.c_char_p, C.POINTER(vp)], C.c_int),
+        "sf_fuser_reintegrate": ([vp, vp, vp, vp, vp], C.c_int),
+        "sf_fuser_reintegrate_batch_device": ([vp, vp, u64, vp, u64, vp, vp, u64], C.c_int),
+        "sf_reint_plan": ([vp, vp, u64, vp, vp, u64, C.POINTER(u64)], C.c_int),
+        "sf_fuse_update_trajectory": ([vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp], C.c_int),
     }
     for name, (args, res) in table.items():
         if hasattr(L, name):

@@ -114,7 +114,12 @@ namespace {
 // still fusing the previous batch out of the other slot.  Allocation only touches new hash entries / heap slots,
 // integrate only the tiles of its own compact list, so the two never write the same data; slot reuse is ordered
 // by ev_fused[sl].
-int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb, const float* const* poses, int n, int sign, const void* const* d_lay = nullptr) {
+// A MIXED-SIGN pass (rs != nullptr; sf_fuser_reintegrate_batch_device): the n poses are the pass's slots, slot q deintegrates (bit q of
+// rs->neg) or integrates the pre-pass plane rs->img[q]; d_depth / d_rgb name the n_planes >= n frames the pre-pass converts, plane by plane -- a - slot's own
+// plane is the fuser's frame of zeros, so that the allocation, which walks plane q for slot q, finds nothing to allocate there --, sign = +1 when some slot
+// integrates (the allocation runs), -1 when none does, colour as rs_col says.  Everything else -- slots, streams, events, sequence numbers -- is the same pass.
+int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb, const float* const* poses, int n, int sign, const void* const* d_lay = nullptr,
+              const ReintSlots* rs = nullptr, int n_planes = 0, bool rs_col = false) {
   BatchIn in;
   BatchFrames bf;
   BatchTi bt;
@@ -123,13 +128,17 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
   std::memset(&bt, 0, sizeof(bt));
   bf.n = n;
   bf.seq0 = f->frame_seq;
-  const bool col = d_rgb != nullptr && d_rgb[0] != nullptr;
+  const bool col = rs ? rs_col : (d_rgb != nullptr && d_rgb[0] != nullptr);
   for (int j = 0; j < n; j++) {
     if (!frame_setup(f->p, poses[j], bf.f[j])) return sf::fail(SF_ERR_INVALID_ARG, "run_batch: invalid pose in batch");
     std::memcpy(bt.Ti[j], bf.f[j].Ti, sizeof(bt.Ti[j]));
     in.depth[j] = (const uint16_t*)d_depth[j];
     in.rgb[j] = col ? (const uint8_t*)d_rgb[j] : nullptr;
     in.lay[j] = (col && d_lay) ? (const uint8_t*)d_lay[j] : nullptr;
+  }
+  for (int j = n; j < n_planes; j++) {   // images only - slots read
+    in.depth[j] = (const uint16_t*)d_depth[j];
+    in.rgb[j] = col ? (const uint8_t*)d_rgb[j] : nullptr;
   }
   f->frame_seq += (uint32_t)n;
   const int sl = f->slot;
@@ -150,8 +159,8 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
     (void)hipStreamWaitEvent(sa, f->ev_fused[sl], 0);
   }
   // one colourless frame at the integration size through the ray-space allocation kernel: that kernel converts the depth itself
-  const bool fuse_pre = f->alloc_ray && n == 1 && sign > 0 && !col && f->pk.inW == 0;
-  if (!fuse_pre) sf_launch_prepass(f, sl, n, in, sa);
+  const bool fuse_pre = f->alloc_ray && n == 1 && sign > 0 && !col && f->pk.inW == 0 && !rs;
+  if (!fuse_pre) sf_launch_prepass(f, sl, rs ? n_planes : n, in, sa);
   if (sign > 0) sf_launch_alloc(f, sl, n, bf, in, sa, fuse_pre);
   sf_launch_compact(f, sl, bf, sa);
   if (f->overlap && sa != s) {
@@ -170,7 +179,8 @@ int run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb,
     f->events_used++;
     (void)hipEventRecord(e0, s);
   }
-  sf_launch_integrate(f, sl, n, sign, col, bt, s);
+  if (rs) sf_launch_reintegrate(f, sl, col, bt, *rs, s);
+  else sf_launch_integrate(f, sl, n, sign, col, bt, s);
   if (f->profile) (void)hipEventRecord(e1, s);
   if (f->overlap && sa != s) (void)hipEventRecord(f->ev_fused[sl], s);
   if (f->overlap && sa == s) f->serial_tail = true;  // no cross-stream traffic at all while single-stream batches follow each other
@@ -380,7 +390,7 @@ SF_API void sf_fuser_destroy(sf_fuser* f) {
   for (auto& e : f->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   (void)hipFree(f->table); (void)hipFree(f->bricks); (void)hipFree(f->heap); (void)hipFree(f->block_keys); (void)hipFree(f->block_entry); (void)hipFree(f->block_flags); (void)hipFree(f->voxels);
   for (int q = 0; q < 2; q++) { (void)hipFree(f->depthf2[q]); (void)hipFree(f->color2[q]); (void)hipFree(f->compact2[q]); (void)hipFree(f->cmask2[q]); }
-  (void)hipFree(f->counters); (void)hipFree(f->ray_kx); (void)hipFree(f->ray_ky);
+  (void)hipFree(f->counters); (void)hipFree(f->ray_kx); (void)hipFree(f->ray_ky); (void)hipFree(f->void_depth);
   for (int q = 0; q < 2; q++) { if (f->ev_compact[q]) (void)hipEventDestroy(f->ev_compact[q]); if (f->ev_fused[q]) (void)hipEventDestroy(f->ev_fused[q]); }
   if (f->ev_input) (void)hipEventDestroy(f->ev_input);
   if (f->front) { (void)hipStreamSynchronize(f->front); (void)hipStreamDestroy(f->front); }
@@ -531,6 +541,142 @@ SF_API int sf_fuser_integrate_batch_device_rgb(sf_fuser* f, const void* d_depth,
 }
 
 SF_API int sf_fuser_batch_frames(const sf_fuser* f) { return f ? f->batch : 0; }
+
+// ------------------------------------------------------------------------------------------------------
+// Re-integration: for frame j = 0 .. n - 1 in order, deintegrate (depth_j, old_j), then integrate (depth_j, new_j) -- as mixed-sign passes.
+// The operations of the call, in that order, are dealt into passes of up to f->batch slots; the two slots of a moved frame stay in one pass (they share the
+// frame's converted image).  A pass of + slots only is an ordinary integrate pass, a single - slot an ordinary deintegrate launch; everything else runs
+// k_reintegrate.  A frame that only leaves the volume (new pose lost) has no + slot whose plane could hold its image: the image goes to a plane behind the
+// slots' (MAX_BATCH planes per batch slot in all).
+// ------------------------------------------------------------------------------------------------------
+namespace {
+
+struct ReintPass {
+  sf_fuser* f;
+  bool col;
+  int m = 0, x = 0;   // slots, images behind the slots' planes
+  const void* dd[MAX_BATCH];
+  const void* dr[MAX_BATCH];
+  const void* xd[MAX_BATCH];   // the images of frames that only leave
+  const float* pp[MAX_BATCH];
+  int ximg[MAX_BATCH];         // slot -> index into xd, or -1
+  ReintSlots rs;
+
+  explicit ReintPass(sf_fuser* f_, bool col_) : f(f_), col(col_) { std::memset(&rs, 0, sizeof(rs)); }
+  bool fits(int slots, int extra) const { return m + slots <= std::max(f->batch, 2) && m + slots + x + extra <= MAX_BATCH; }
+  void add(const void* depth, const void* rgb, const float* pose_old, const float* pose_new) {
+    if (pose_old) {
+      rs.neg |= 1u << m;
+      ximg[m] = -1;
+      if (pose_new) rs.img[m] = (uint32_t)(m + 1);
+      else { ximg[m] = x; xd[x++] = depth; }
+      dd[m] = depth;   // (a single - slot runs the ordinary deintegrate launch on its own plane; a mixed pass puts the frame of zeros here)
+      dr[m] = rgb;
+      pp[m++] = pose_old;
+    }
+    if (pose_new) {
+      rs.img[m] = (uint32_t)m;
+      ximg[m] = -1;
+      dd[m] = depth;
+      dr[m] = rgb;
+      pp[m++] = pose_new;
+    }
+  }
+  int flush() {
+    if (m == 0) return SF_OK;
+    int rc;
+    if (rs.neg == 0u) rc = run_batch(f, dd, col ? dr : nullptr, pp, m, +1);
+    else if (m == 1) rc = run_batch(f, dd, col ? dr : nullptr, pp, 1, -1);
+    else {
+      if (!f->void_depth) {
+        SF_HIP_CHECK(hipMalloc(&f->void_depth, f->in_px * 2));
+        SF_HIP_CHECK(hipMemset(f->void_depth, 0, f->in_px * 2));
+        SF_HIP_CHECK(hipDeviceSynchronize());
+      }
+      for (int q = 0; q < m; q++) {
+        if (!((rs.neg >> q) & 1u)) continue;
+        if (ximg[q] >= 0) rs.img[q] = (uint32_t)(m + ximg[q]);
+        dd[q] = f->void_depth;
+        dr[q] = nullptr;
+      }
+      for (int k = 0; k < x; k++) { dd[m + k] = xd[k]; dr[m + k] = nullptr; }
+      const bool plus = rs.neg != (m == 32 ? 0xFFFFFFFFu : ((1u << m) - 1u));
+      rc = run_batch(f, dd, dr, pp, m, plus ? +1 : -1, nullptr, &rs, m + x, col);
+    }
+    f->reint_passes++;
+    m = x = 0;
+    std::memset(&rs, 0, sizeof(rs));
+    return rc;
+  }
+};
+
+}  // namespace
+
+SF_API int sf_fuser_reintegrate_batch_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes,
+                                             const float* old_poses, const float* new_poses, uint64_t n) {
+  if (!f || (n > 0 && (!d_depth || !old_poses || !new_poses))) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  f->reint_passes = 0;
+  ReintPass pass(f, d_rgb != nullptr);
+  for (uint64_t i = 0; i < n; i++) {
+    const float* po = old_poses + 16 * i;
+    const float* pn = new_poses + 16 * i;
+    const bool has_old = po[0] != -INFINITY, has_new = pn[0] != -INFINITY;
+    f->frames_skipped += (uint64_t)(!has_old) + (uint64_t)(!has_new);   // what the two calls of the sequence would have counted
+    if (!has_old && !has_new) continue;
+    const void* depth = (const uint8_t*)d_depth + i * frame_stride_bytes;
+    const void* rgb = d_rgb ? (const uint8_t*)d_rgb + i * rgb_stride_bytes : nullptr;
+    if (f->batch < 2) {   // one slot per pass (tune "batch" 1): the sequence itself
+      int rc = SF_OK;
+      if (has_old) { rc = run_frame(f, depth, rgb, po, -1); f->reint_passes++; }
+      if (rc == SF_OK && has_new) { rc = run_frame(f, depth, rgb, pn, +1); f->reint_passes++; }
+      if (rc != SF_OK) return rc;
+      continue;
+    }
+    const int slots = (int)has_old + (int)has_new, extra = has_old && !has_new ? 1 : 0;
+    if (!pass.fits(slots, extra)) {
+      const int rc = pass.flush();
+      if (rc != SF_OK) return rc;
+    }
+    pass.add(depth, rgb, has_old ? po : nullptr, has_new ? pn : nullptr);
+  }
+  return pass.flush();
+}
+
+// One frame from host buffers: the frame goes through the page-locked ring of fuse_host once and serves both slots.
+SF_API int sf_fuser_reintegrate(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, const float old_pose[16], const float new_pose[16]) {
+  if (!f || !depth || !old_pose || !new_pose) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  const bool has_old = old_pose[0] != -INFINITY, has_new = new_pose[0] != -INFINITY;
+  if (!has_old || !has_new || f->batch < 2) {   // at most one operation per launch: the calls of the sequence themselves
+    const int r0 = fuse_host(f, depth, rgb, old_pose, -1);
+    if (r0 != SF_OK && r0 != SF_ERR_SKIPPED) return r0;
+    const int r1 = fuse_host(f, depth, rgb, new_pose, +1);
+    if (r1 != SF_OK && r1 != SF_ERR_SKIPPED) return r1;
+    if (r0 == SF_ERR_SKIPPED && r1 == SF_ERR_SKIPPED) return SF_ERR_SKIPPED;
+    sf::last_error_ref().clear();
+    return SF_OK;
+  }
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  const size_t npx = (size_t)f->pk.W * f->pk.H;
+  const size_t rgb_bytes = (f->pk.cW ? (size_t)f->pk.cW * f->pk.cH : npx) * 3;
+  const int q = f->host_slot;
+  f->host_slot = (q + 1) % sf_fuser::HOST_RING;
+  if (f->host_frames >= (uint64_t)sf_fuser::HOST_RING) SF_HIP_CHECK(hipEventSynchronize(f->ev_h2d[q]));
+  std::memcpy(f->pinned_depth[q], depth, f->in_px * 2);
+  if (rgb) std::memcpy(f->pinned_rgb[q], rgb, rgb_bytes);
+  hipStream_t in_stream = sf_input_stream(f, 2, rgb != nullptr, +1);   // where the pass's pre-pass reads the frame
+  if (f->host_frames >= (uint64_t)sf_fuser::HOST_RING) SF_HIP_CHECK(hipStreamWaitEvent(in_stream, f->ev_consumed[q], 0));
+  SF_HIP_CHECK(hipMemcpyAsync(f->staging_depth[q], f->pinned_depth[q], f->in_px * 2, hipMemcpyHostToDevice, in_stream));
+  if (rgb) SF_HIP_CHECK(hipMemcpyAsync(f->staging_rgb[q], f->pinned_rgb[q], rgb_bytes, hipMemcpyHostToDevice, in_stream));
+  SF_HIP_CHECK(hipEventRecord(f->ev_h2d[q], in_stream));
+  f->reint_passes = 0;
+  ReintPass pass(f, rgb != nullptr);
+  pass.add(f->staging_depth[q], rgb ? f->staging_rgb[q] : nullptr, old_pose, new_pose);
+  const int rc = pass.flush();
+  SF_HIP_CHECK(hipEventRecord(f->ev_consumed[q], f->stream));
+  f->host_frames++;
+  return rc;
+}
 
 // scanfuse_internal.h: scheduling switches (bench.py, tests); every setting leaves the voxels bit-identical
 SF_API int sf_fuser_tune(sf_fuser* f, const char* key, int value) {

@@ -91,6 +91,10 @@ struct BatchFrames {  // k_alloc, k_compactify
 struct BatchTi {  // k_integrate: world -> camera rows 0..2 of every frame of the batch
   float Ti[MAX_BATCH][12];
 };
+struct ReintSlots {  // k_reintegrate: the slots of a mixed-sign pass (fuser_reintegrate.hip)
+  uint32_t neg;             // bit q: slot q takes its image OUT of the volume (deintegrate); clear: puts it in
+  uint32_t img[MAX_BATCH];  // the plane of the pass's pre-pass output slot q reads: the two slots of a moved frame name the same one
+};
 // Kernel-argument segments: HIP's portability note names 4 KB (CUDA's limit); the AMD runtime sizes the kernarg segment from the kernel's own
 // metadata, and k_alloc_ray / k_compactify take BatchFrames (4 872 B) + ParamsK + pointers = ~5.2 KB by value on gfx950 under ROCm 7.2 (every
 // -m gpu test launches them).  The bound below is what this code relies on having been tested; a toolchain with a smaller limit fails the launch
@@ -326,6 +330,8 @@ struct sf_fuser {
   int alloc_group = 16; // consecutive frames of a batch one k_alloc workgroup walks (tune "alloc_group"; 4 -> 16: 35.0 -> 35.8 k frames/s, the blocks a pixel tile queues are looked up in the table once per batch)
   int compact_grid = 1024;  // 1024 directory entries per workgroup, grid-stride beyond
   uint64_t frames_integrated = 0, frames_skipped = 0;
+  void* void_depth = nullptr;   // an input-size depth frame of zeros ("no measurement"), made by the first mixed-sign pass: what the allocation sees in a - slot
+  int reint_passes = 0;         // passes of the most recent sf_fuser_reintegrate_batch_device call
   bool profile = false;
   void* mc_bounce[2] = {nullptr, nullptr};            // page-locked bounce buffers of the mesh download (mc.hip), allocated on first use
   hipEvent_t mc_bounce_ev[2] = {nullptr, nullptr};
@@ -350,6 +356,9 @@ void sf_launch_prepass(const sf_fuser* f, int sl, int n, const BatchIn& in, hipS
 void sf_launch_alloc(const sf_fuser* f, int sl, int n, const BatchFrames& bf, const BatchIn& in, hipStream_t s, bool fuse_pre);   // fuser_alloc.hip
 void sf_launch_compact(const sf_fuser* f, int sl, const BatchFrames& bf, hipStream_t s);   // fuser_compact.hip
 void sf_launch_integrate(const sf_fuser* f, int sl, int n, int sign, bool col, const BatchTi& bt, hipStream_t s);   // fuser_integrate.hip
+void sf_launch_reintegrate(const sf_fuser* f, int sl, bool col, const BatchTi& bt, const ReintSlots& rs, hipStream_t s);   // fuser_reintegrate.hip: a mixed-sign pass
+int sf_list_grid(const sf_fuser* f, int entries);   // fuser_integrate.hip: the grid of a kernel that walks a pass's list
+inline int sf_fuser_reintegrate_passes(const sf_fuser* f) { return f->reint_passes; }
 bool sf_pipe_batch(const sf_fuser* f, int n, bool color, int sign);   // fuser_integrate.hip: the pass runs the persistent k_integrate_pipe
 bool sf_big_tile_set(uint32_t tiles);   // fuser.hip: a tile set beyond 512 MiB (the front chain beside k_integrate_pipe, non-temporal tile traffic)
 bool sf_big_pass(const sf_fuser* f);    // ... the previous pass's

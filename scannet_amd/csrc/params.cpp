@@ -255,6 +255,33 @@ SF_API int sf_track_params_load_file(const char* path, sf_track_params* t) {
   return SF_OK;
 }
 
+SF_API void sf_reint_params_default(sf_reint_params* r) {
+  if (!r) return;
+  std::memset(r, 0, sizeof(*r));
+  r->max_frame_fixes = 30;        // s_maxFrameFixes (zParametersScanNet.txt:26)
+  r->top_n_active = 30;           // s_topNActive (:27)
+  r->min_pose_dist_sqrt = 0.0f;   // s_minPoseDistSqrt (:28)
+}
+
+// the trajectory-manager keys of the same file (zParametersScanNet.txt:25-28), which no other loader reads
+SF_API int sf_reint_params_load_file(const char* path, sf_reint_params* r) {
+  if (!path || !r) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  std::map<std::string, std::vector<std::string>> kv;
+  const int rc = read_param_file(path, kv);
+  if (rc != SF_OK) return rc;
+  const struct { const char* key; float* f; int32_t* i; } keys[] = {
+      {"s_maxFrameFixes", nullptr, &r->max_frame_fixes}, {"s_topNActive", nullptr, &r->top_n_active}, {"s_minPoseDistSqrt", &r->min_pose_dist_sqrt, nullptr}};
+  for (const auto& k : keys) {
+    auto it = kv.find(k.key);
+    if (it == kv.end()) continue;
+    float v;
+    if (it->second.empty() || !parse_float(it->second[0], &v) || !std::isfinite(v) || v < 0.0f) return sf::fail(SF_ERR_FORMAT, "%s: bad value for %s", path, k.key);
+    if (k.f) *k.f = v;
+    else *k.i = (int32_t)std::strtol(it->second[0].c_str(), nullptr, 10);
+  }
+  return SF_OK;
+}
+
 namespace {
 // CPUs this process may actually use: the cgroup CPU quota when there is one (a container that shows 256 logical CPUs may be allowed
 // the time of 16: threads beyond that only add contention), else the hardware concurrency

@@ -113,6 +113,55 @@ def load_track_params(path, base=None):
     return t
 
 
+class SfReintParams(C.Structure):
+    _fields_ = [("max_frame_fixes", C.c_int32), ("top_n_active", C.c_int32), ("min_pose_dist_sqrt", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+class SfReintStats(C.Structure):
+    _fields_ = [("steps", C.c_uint64), ("frames_moved", C.c_uint64), ("frames_removed", C.c_uint64), ("frames_added", C.c_uint64),
+                ("passes", C.c_uint64), ("seconds_total", C.c_double)]
+
+
+def default_reint_params(**over):
+    """sf_reint_params_default (the trajectory-manager keys of zParametersScanNet.txt:25-28: 30 / 30 / 0.0); keyword overrides."""
+    r = SfReintParams()
+    L = _abi.lib()
+    L.sf_reint_params_default.argtypes = [C.POINTER(SfReintParams)]
+    L.sf_reint_params_default.restype = None
+    L.sf_reint_params_default(C.byref(r))
+    for k, v in over.items():
+        if not hasattr(r, k) or k == "reserved":
+            raise AttributeError("sf_reint_params has no field %r" % k)
+        setattr(r, k, v)
+    return r
+
+
+def load_reint_params(path, base=None):
+    """s_maxFrameFixes, s_topNActive and s_minPoseDistSqrt of an mLib ParameterFile; absent keys leave the base as it is."""
+    r = base if base is not None else default_reint_params()
+    L = _abi.lib()
+    L.sf_reint_params_load_file.argtypes = [C.c_char_p, C.POINTER(SfReintParams)]
+    check(L.sf_reint_params_load_file(str(path).encode(), C.byref(r)))
+    return r
+
+
+def plan_reintegration(integrated, target, params=None, capacity=None):
+    """sf_reint_plan: one step of the trajectory manager (host only).  integrated / target: [n,16] or [n,4,4] camToWorld, what the volume holds and
+    what it should hold (all -inf: not in the volume / lost) -> the frames to re-integrate now (uint64 array, largest pose change first)."""
+    r = params if params is not None else default_reint_params()
+    a = np.ascontiguousarray(integrated, dtype=np.float32).reshape(-1, 16)
+    b = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 16)
+    if a.shape != b.shape:
+        raise ValueError("integrated and target trajectories differ in length")
+    cap = int(capacity) if capacity is not None else max(0, min(int(r.max_frame_fixes), int(r.top_n_active)))
+    out = np.zeros(max(cap, 1), np.uint64)
+    n = C.c_uint64(0)
+    L = _abi.lib()
+    L.sf_reint_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfReintParams), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    check(L.sf_reint_plan(_ptr(a), _ptr(b), len(a), C.byref(r), _ptr(out), cap, C.byref(n)))
+    return out[:n.value].copy()
+
+
 def track_and_fuse(fuser, frames, first_pose, params=None):
     """Frame-to-model tracking loop: frame 0 is fused at first_pose, every later frame is tracked against the volume so far, starting from the last
     tracked pose, and fused at the pose found; a lost frame is not fused.  frames: iterable of u16 depth [H,W] (or (depth, rgb) pairs).
@@ -228,6 +277,54 @@ class Fuser:
             L = _abi.lib()
             L.sf_fuser_integrate_batch_device_rgb.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
             check(L.sf_fuser_integrate_batch_device_rgb(self._h, _ptr(d_depth), int(frame_stride_bytes), _ptr(d_rgb), int(rgb_stride_bytes), _ptr(poses), len(poses)))
+
+    # -- re-integration of frames whose poses were revised ---------------------------------
+    def reintegrate(self, depth, old_pose, new_pose, rgb=None):
+        """Take one frame (host buffers) out of the volume at old_pose and put it back at new_pose in one pass (sf_fuser_reintegrate); an all -inf
+        old / new pose: only put in / only taken out.  False when both are all -inf (nothing done)."""
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if depth.size != self.params.depth_width * self.params.depth_height:
+            raise ValueError("depth frame has %d pixels, fuser expects %dx%d" % (depth.size, self.params.depth_width, self.params.depth_height))
+        old_pose = np.ascontiguousarray(old_pose, dtype=np.float32).reshape(16)
+        new_pose = np.ascontiguousarray(new_pose, dtype=np.float32).reshape(16)
+        if rgb is not None:
+            rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+            want = (self.params.color_width * self.params.color_height if self.params.color_width > 0 else depth.size) * 3
+            if rgb.size != want:
+                raise ValueError("rgb must be HxWx3 at depth resolution (or at the colour resolution given in sf_params)")
+        L = _abi.lib()
+        L.sf_fuser_reintegrate.argtypes = [C.c_void_p] * 5
+        return check(L.sf_fuser_reintegrate(self._h, _ptr(depth), _ptr(rgb), _ptr(old_pose), _ptr(new_pose)), allow=(_abi.SF_ERR_SKIPPED,)) == 0
+
+    def reintegrate_batch_device(self, d_depth, frame_stride_bytes, old_poses, new_poses, d_rgb=None, rgb_stride_bytes=0):
+        """n device-resident frames: for each in order, deintegrate at old_poses[j], integrate at new_poses[j] -- bit for bit that sequence, as
+        mixed-sign passes of up to batch_frames operations (sf_fuser_reintegrate_batch_device)."""
+        old_poses = np.ascontiguousarray(old_poses, dtype=np.float32).reshape(-1, 16)
+        new_poses = np.ascontiguousarray(new_poses, dtype=np.float32).reshape(-1, 16)
+        if old_poses.shape != new_poses.shape:
+            raise ValueError("old and new poses differ in number")
+        L = _abi.lib()
+        L.sf_fuser_reintegrate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+        check(L.sf_fuser_reintegrate_batch_device(self._h, _ptr(d_depth), int(frame_stride_bytes), _ptr(d_rgb), int(rgb_stride_bytes), _ptr(old_poses),
+                                                  _ptr(new_poses), len(old_poses)))
+
+    def update_trajectory(self, sensor_data, integrated, target, params=None, max_steps=0, colour=False, decode_threads=0):
+        """sf_fuse_update_trajectory: steps of the trajectory manager over a scannet_amd.sens.SensorData until nothing is left to move (max_steps 0)
+        or max_steps are done.  integrated ([n,16] / [n,4,4] float32, what the volume holds) is updated IN PLACE when it is a C-contiguous float32
+        array; the updated trajectory [n,16] and the run's statistics are returned either way."""
+        r = params if params is not None else default_reint_params()
+        cur = integrated if (isinstance(integrated, np.ndarray) and integrated.dtype == np.float32 and integrated.flags.c_contiguous) \
+            else np.array(integrated, dtype=np.float32)
+        tgt = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 16)
+        if cur.size != tgt.size:
+            raise ValueError("integrated and target trajectories differ in length")
+        st = SfReintStats()
+        L = _abi.lib()
+        L.sf_fuse_update_trajectory.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SfReintParams), C.c_uint64, C.c_int, C.c_int,
+                                                C.POINTER(SfReintStats)]
+        check(L.sf_fuse_update_trajectory(self._h, sensor_data._h, _ptr(cur), _ptr(tgt), C.byref(r), int(max_steps), int(bool(colour)), int(decode_threads),
+                                          C.byref(st)))
+        return cur.reshape(-1, 16), {k: getattr(st, k) for k, _ in SfReintStats._fields_}
 
     @property
     def batch_frames(self):
