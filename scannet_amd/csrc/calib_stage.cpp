@@ -23,12 +23,11 @@
 #include <thread>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "common.h"
 #include "jpeg_idct.h"
 #include "sens.h"
 
-int jpeg_encode_rgb(const uint8_t* rgb, uint32_t width, uint32_t height, int quality, int subsample, std::vector<uint8_t>& out);  // jpeg_enc.cpp
-int jpeg_decode_coef(const uint8_t* data, uint64_t n, uint32_t expect_w, uint32_t expect_h, uint8_t* payload, uint64_t payload_capacity);  // jpeg.cpp
 size_t calibrator_payload_capacity(const sf_calibrator* c);                                                                            // calibrate.hip
 int calibrator_run_payload(sf_calibrator* c, int n, const uint8_t* const* rgb_in, const uint8_t* const* payload, const uint32_t* payload_bytes,
                            uint8_t* const* rgb_out, const uint16_t* const* depth_in, uint16_t* const* depth_out);                      // calibrate.hip

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "common.h"
 #include "jpeg_idct.h"
 
@@ -517,9 +518,6 @@ SF_API int sf_calibrator_run(sf_calibrator* c, int n, const uint8_t* const* rgb_
   SF_HIP_CHECK(hipStreamSynchronize(c->stream));
   return SF_OK;
 }
-
-int jpeg_gpu_reconstruct(hipStream_t stream, int n, const uint8_t* const* d_payload, uint8_t* const* d_rgb, uint8_t* const* d_planes, uint32_t max_blocks,
-                         uint32_t max_width, uint32_t max_height);  // jpeg_gpu.hip
 
 // bytes a frame's coefficient payload may take in sf_calibrator_run_payload (header + block table + as many entries as the pixels have bytes)
 size_t calibrator_payload_capacity(const sf_calibrator* c) {

@@ -444,32 +444,47 @@ SF_API int sf_fuser_reset(sf_fuser* f) {
   return SF_OK;
 }
 
+// The caller's buffers are ordinary (pageable) memory and are its own again the moment the call returns -- a live stream decodes the next
+// frame into the same buffer, a binding may free it.  So the frame is copied into a page-locked slot of the ring HERE, on the caller's
+// thread (614 KB: ~50 us), and everything behind that -- H2D, pre-pass, allocation, compaction, integrate -- is queued and left running.
+// Round 2 drained both streams and waited for the H2D in every call: the GPU idled while the host copied and the host idled while the GPU
+// fused (one frame per launch: 7.8 k frames/s with resident frames, less through this entry point).
+// in_stream: the stream the pre-pass will read the frame on.  *slot: f->staging_depth / f->staging_rgb [*slot] hold the frame in stream order.
+static int stage_host_frame(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, hipStream_t in_stream, int* slot) {
+  const size_t npx = (size_t)f->pk.W * f->pk.H;
+  const size_t rgb_bytes = (f->pk.cW ? (size_t)f->pk.cW * f->pk.cH : npx) * 3;
+  const int q = f->host_slot;
+  f->host_slot = (q + 1) % sf_fuser::HOST_RING;
+  const bool reused = f->host_frames >= (uint64_t)sf_fuser::HOST_RING;
+  if (reused) SF_HIP_CHECK(hipEventSynchronize(f->ev_h2d[q]));   // the copy of HOST_RING frames ago has read the slot
+  std::memcpy(f->pinned_depth[q], depth, f->in_px * 2);
+  if (rgb) std::memcpy(f->pinned_rgb[q], rgb, rgb_bytes);
+  if (reused) SF_HIP_CHECK(hipStreamWaitEvent(in_stream, f->ev_consumed[q], 0));   // the kernels that read the device copy
+  SF_HIP_CHECK(hipMemcpyAsync(f->staging_depth[q], f->pinned_depth[q], f->in_px * 2, hipMemcpyHostToDevice, in_stream));
+  if (rgb) SF_HIP_CHECK(hipMemcpyAsync(f->staging_rgb[q], f->pinned_rgb[q], rgb_bytes, hipMemcpyHostToDevice, in_stream));
+  SF_HIP_CHECK(hipEventRecord(f->ev_h2d[q], in_stream));
+  *slot = q;
+  return SF_OK;
+}
+
+// ... and the slot handed back once its frame's launches are queued: the pre-pass (the only reader of the device copy) precedes the integrate launch in
+// stream order, so an event behind that launch covers it
+static int retire_host_frame(sf_fuser* f, int slot) {
+  SF_HIP_CHECK(hipEventRecord(f->ev_consumed[slot], f->stream));
+  f->host_frames++;
+  return SF_OK;
+}
+
 static int fuse_host(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, const float* pose, int sign) {
   if (!f || !depth || !pose) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   if (pose[0] == -INFINITY) { f->frames_skipped++; return sf::fail(SF_ERR_SKIPPED, "frame skipped: camToWorld is -inf (tracking lost)"); }
   SF_HIP_CHECK(hipSetDevice(f->device));
-  const size_t npx = (size_t)f->pk.W * f->pk.H;
-  const size_t rgb_bytes = (f->pk.cW ? (size_t)f->pk.cW * f->pk.cH : npx) * 3;
-  // The caller's buffers are ordinary (pageable) memory and are its own again the moment this call returns -- a live stream decodes the next
-  // frame into the same buffer, a binding may free it.  So the frame is copied into a page-locked slot of the ring HERE, on the caller's
-  // thread (614 KB: ~50 us), and everything behind that -- H2D, pre-pass, allocation, compaction, integrate -- is queued and left running.
-  // Round 2 drained both streams and waited for the H2D in every call: the GPU idled while the host copied and the host idled while the GPU
-  // fused (one frame per launch: 7.8 k frames/s with resident frames, less through this entry point).
-  const int q = f->host_slot;
-  f->host_slot = (q + 1) % sf_fuser::HOST_RING;
-  if (f->host_frames >= (uint64_t)sf_fuser::HOST_RING) SF_HIP_CHECK(hipEventSynchronize(f->ev_h2d[q]));   // the copy of HOST_RING frames ago has read the slot
-  std::memcpy(f->pinned_depth[q], depth, f->in_px * 2);
-  if (rgb) std::memcpy(f->pinned_rgb[q], rgb, rgb_bytes);
-  hipStream_t in_stream = sf_input_stream(f, 1, rgb != nullptr, sign);  // the stream the pre-pass reads the frame on
-  if (f->host_frames >= (uint64_t)sf_fuser::HOST_RING) SF_HIP_CHECK(hipStreamWaitEvent(in_stream, f->ev_consumed[q], 0));   // the kernels that read the device copy
-  SF_HIP_CHECK(hipMemcpyAsync(f->staging_depth[q], f->pinned_depth[q], f->in_px * 2, hipMemcpyHostToDevice, in_stream));
-  if (rgb) SF_HIP_CHECK(hipMemcpyAsync(f->staging_rgb[q], f->pinned_rgb[q], rgb_bytes, hipMemcpyHostToDevice, in_stream));
-  SF_HIP_CHECK(hipEventRecord(f->ev_h2d[q], in_stream));
+  int q = 0;
+  const int rs = stage_host_frame(f, depth, rgb, sf_input_stream(f, 1, rgb != nullptr, sign), &q);
+  if (rs != SF_OK) return rs;
   const int rc = run_frame(f, f->staging_depth[q], rgb ? f->staging_rgb[q] : nullptr, pose, sign);
-  // the frame's pre-pass (the only reader of the device copy) precedes its integrate launch in stream order: an event behind that launch covers it
-  SF_HIP_CHECK(hipEventRecord(f->ev_consumed[q], f->stream));
-  f->host_frames++;
-  return rc;
+  const int rr = retire_host_frame(f, q);
+  return rr != SF_OK ? rr : rc;
 }
 
 SF_API int sf_fuser_integrate(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, const float pose[16]) {
@@ -657,25 +672,15 @@ SF_API int sf_fuser_reintegrate(sf_fuser* f, const uint16_t* depth, const uint8_
     return SF_OK;
   }
   SF_HIP_CHECK(hipSetDevice(f->device));
-  const size_t npx = (size_t)f->pk.W * f->pk.H;
-  const size_t rgb_bytes = (f->pk.cW ? (size_t)f->pk.cW * f->pk.cH : npx) * 3;
-  const int q = f->host_slot;
-  f->host_slot = (q + 1) % sf_fuser::HOST_RING;
-  if (f->host_frames >= (uint64_t)sf_fuser::HOST_RING) SF_HIP_CHECK(hipEventSynchronize(f->ev_h2d[q]));
-  std::memcpy(f->pinned_depth[q], depth, f->in_px * 2);
-  if (rgb) std::memcpy(f->pinned_rgb[q], rgb, rgb_bytes);
-  hipStream_t in_stream = sf_input_stream(f, 2, rgb != nullptr, +1);   // where the pass's pre-pass reads the frame
-  if (f->host_frames >= (uint64_t)sf_fuser::HOST_RING) SF_HIP_CHECK(hipStreamWaitEvent(in_stream, f->ev_consumed[q], 0));
-  SF_HIP_CHECK(hipMemcpyAsync(f->staging_depth[q], f->pinned_depth[q], f->in_px * 2, hipMemcpyHostToDevice, in_stream));
-  if (rgb) SF_HIP_CHECK(hipMemcpyAsync(f->staging_rgb[q], f->pinned_rgb[q], rgb_bytes, hipMemcpyHostToDevice, in_stream));
-  SF_HIP_CHECK(hipEventRecord(f->ev_h2d[q], in_stream));
+  int q = 0;
+  const int rs = stage_host_frame(f, depth, rgb, sf_input_stream(f, 2, rgb != nullptr, +1), &q);   // where the pass's pre-pass reads the frame
+  if (rs != SF_OK) return rs;
   f->reint_passes = 0;
   ReintPass pass(f, rgb != nullptr);
   pass.add(f->staging_depth[q], rgb ? f->staging_rgb[q] : nullptr, old_pose, new_pose);
   const int rc = pass.flush();
-  SF_HIP_CHECK(hipEventRecord(f->ev_consumed[q], f->stream));
-  f->host_frames++;
-  return rc;
+  const int rr = retire_host_frame(f, q);
+  return rr != SF_OK ? rr : rc;
 }
 
 // scanfuse_internal.h: scheduling switches (bench.py, tests); every setting leaves the voxels bit-identical
@@ -706,13 +711,12 @@ SF_API int sf_fuser_tune(sf_fuser* f, const char* key, int value) {
   return SF_OK;
 }
 
-// Internal (pipeline.hip): fuse n <= MAX_BATCH device-resident frames with valid poses in one pass.
+// fuser_internal.h, for pipeline.hip
 int sf_fuser_run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb, const float* const* poses, int n) {
   if (n < 1 || n > f->batch) return sf::fail(SF_ERR_INVALID_ARG, "batch of %d frames (limit %d)", n, f->batch);
   return run_batch(f, d_depth, d_rgb, poses, n, +1);
 }
 
-// ... the colour frames as JPEG component planes (d_planes[j]: what jpeg_gpu_planes left; d_layout[j]: the picture's SfJpegLayout on the device)
 int sf_fuser_run_batch_ycc(sf_fuser* f, const void* const* d_depth, const void* const* d_planes, const void* const* d_layout, const float* const* poses, int n) {
   if (n < 1 || n > f->batch) return sf::fail(SF_ERR_INVALID_ARG, "batch of %d frames (limit %d)", n, f->batch);
   return run_batch(f, d_depth, d_planes, poses, n, +1, d_layout);

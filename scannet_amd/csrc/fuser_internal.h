@@ -345,7 +345,6 @@ struct sf_fuser {
 
 hipError_t sf_quiesce(sf_fuser* f);                 // drain both streams
 void sf_track_release(sf_fuser* f);                 // track.hip: frees f->track
-void sf_run_resources_prepare(int device, size_t pinned_bytes, size_t device_bytes, size_t plan_bytes);   // pipeline.hip: the side streams and the pinned ring of sf_fuse_run, created in the background
 bool sf_single_stream_batch(const sf_fuser* f, int n, bool color, int sign);   // run_batch keeps this batch on f->stream alone
 hipStream_t sf_input_stream(const sf_fuser* f, int n, bool color, int sign);   // where the batch's frames must be staged
 int sf_compact_live(sf_fuser* f, int32_t* n_out, int include_ghosts = 1);   // live heap slots -> f->compact, synchronous
@@ -357,6 +356,10 @@ void sf_launch_alloc(const sf_fuser* f, int sl, int n, const BatchFrames& bf, co
 void sf_launch_compact(const sf_fuser* f, int sl, const BatchFrames& bf, hipStream_t s);   // fuser_compact.hip
 void sf_launch_integrate(const sf_fuser* f, int sl, int n, int sign, bool col, const BatchTi& bt, hipStream_t s);   // fuser_integrate.hip
 void sf_launch_reintegrate(const sf_fuser* f, int sl, bool col, const BatchTi& bt, const ReintSlots& rs, hipStream_t s);   // fuser_reintegrate.hip: a mixed-sign pass
+// fuser.hip, for sf_fuse_run (pipeline.hip): fuse n <= f->batch device-resident frames with valid poses in one pass; _ycc: the colour frames as JPEG component
+// planes (d_planes[j]: what jpeg_gpu_planes left; d_layout[j]: the picture's SfJpegLayout on the device)
+int sf_fuser_run_batch(sf_fuser* f, const void* const* d_depth, const void* const* d_rgb, const float* const* poses, int n);
+int sf_fuser_run_batch_ycc(sf_fuser* f, const void* const* d_depth, const void* const* d_planes, const void* const* d_layout, const float* const* poses, int n);
 int sf_list_grid(const sf_fuser* f, int entries);   // fuser_integrate.hip: the grid of a kernel that walks a pass's list
 inline int sf_fuser_reintegrate_passes(const sf_fuser* f) { return f->reint_passes; }
 bool sf_pipe_batch(const sf_fuser* f, int n, bool color, int sign);   // fuser_integrate.hip: the pass runs the persistent k_integrate_pipe

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "common.h"
 #include "inflate_lanes.h"
 
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(IG_COPY_LANES) void k_inflate_copy(InflateBatch B) 
 constexpr uint64_t IG_MAX_STREAM_BYTES = 1ull << 24;
 static_assert(IG_MAX_STREAM_BYTES * 8 / 13 * 258 < (1ull << 32), "32-bit output counts of the inflate kernels");
 // The code object of this file is loaded by the runtime when one of its kernels is first used (milliseconds, inside a scan's first sf_fuse_run unless somebody asks
-// earlier): the preparation thread of the frame pipeline asks (pipeline.hip, sf_run_resources_prepare_ex).
+// earlier): the preparation thread of the frame pipeline asks (pipeline.hip, sf_run_resources_prepare).
 void inflate_gpu_warm() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_inflate_tokens));

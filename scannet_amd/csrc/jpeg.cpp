@@ -13,6 +13,7 @@
 #include <cstring>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "common.h"
 #include "jpeg_huff.h"
 #include "jpeg_idct.h"

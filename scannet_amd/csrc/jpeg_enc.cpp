@@ -14,6 +14,7 @@
 #include <cstring>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "common.h"
 
 namespace {

@@ -13,6 +13,7 @@
 #include <atomic>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "common.h"
 #include "jpeg_idct.h"
 
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(256) void k_jpeg_rgb(JpegBatch B) {
 // RGB image out (nullptr: skip the slot), d_planes[i]: scratch of at least the summed plane sizes.  max_blocks / max_width x max_height bound the
 // grid (the layouts live on the device).
 // The code object of this file is loaded by the runtime when one of its kernels is first used (milliseconds, inside a scan's first sf_fuse_run unless somebody asks
-// earlier): the preparation thread of the frame pipeline asks (pipeline.hip, sf_run_resources_prepare_ex).
+// earlier): the preparation thread of the frame pipeline asks (pipeline.hip, sf_run_resources_prepare).
 void jpeg_gpu_warm() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_jpeg_idct));
@@ -176,9 +177,6 @@ int jpeg_gpu_planes(hipStream_t stream, int n, const uint8_t* const* d_payload, 
   SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }
-
-int jpeg_decode_rgb(const uint8_t* data, uint64_t n, uint8_t* dst, uint32_t expect_w, uint32_t expect_h);                                          // jpeg.cpp
-int jpeg_decode_coef(const uint8_t* data, uint64_t n, uint32_t expect_w, uint32_t expect_h, uint8_t* payload, uint64_t payload_capacity);  // jpeg.cpp
 
 
 // The same picture through the GPU path of the frame pipeline: entropy decoding here, reconstruction on `device`, result copied back.

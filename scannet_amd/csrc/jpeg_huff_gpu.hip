@@ -11,12 +11,9 @@
 
 #include <vector>
 
+#include "codecs_internal.h"
 #include "common.h"
 #include "jpeg_huff.h"
-
-int jpeg_prepare_huff(const uint8_t* data, uint64_t n, uint32_t expect_w, uint32_t expect_h, uint8_t* payload, uint64_t payload_capacity);   // jpeg.cpp
-int jpeg_gpu_reconstruct(hipStream_t stream, int n, const uint8_t* const* d_payload, uint8_t* const* d_rgb, uint8_t* const* d_planes, uint32_t max_blocks,
-                         uint32_t max_width, uint32_t max_height);                                                                              // jpeg_gpu.hip
 
 namespace {
 
@@ -199,7 +196,7 @@ __global__ __launch_bounds__(JH_LANES) void k_jpeg_huff(JpegHuffBatch B) {
 }  // namespace
 
 // The code object of this file is loaded by the runtime when one of its kernels is first used (milliseconds, inside a scan's first sf_fuse_run unless somebody asks
-// earlier): the preparation thread of the frame pipeline asks (pipeline.hip, sf_run_resources_prepare_ex).
+// earlier): the preparation thread of the frame pipeline asks (pipeline.hip, sf_run_resources_prepare).
 void jpeg_huff_gpu_warm() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_jpeg_huff));

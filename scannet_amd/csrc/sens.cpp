@@ -21,9 +21,9 @@
 #include <thread>
 #include <limits>
 
+#include "codecs_internal.h"
 #include "sens.h"
 
-int jpeg_decode_rgb(const uint8_t* data, uint64_t n, uint8_t* dst, uint32_t expect_w, uint32_t expect_h);  // jpeg.cpp
 int png_decode_rgb(const uint8_t* data, uint64_t n, uint8_t* dst, uint32_t expect_w, uint32_t expect_h);   // png.cpp
 
 namespace {

@@ -747,6 +747,100 @@ def test_fuse_run_with_colour_matches_frame_by_frame(tmp_path, kind, monkeypatch
         assert len(ca) > 500
 
 
+def _write_small_scan(path, n, colour, mixed_layouts, lost, nocol):
+    """Depth 160x120 (zlib) with colour 324x242 -- None, "raw" or "jpeg" (4:2:0, every second picture 4:4:4 when mixed_layouts) -- frame `lost` without a
+    pose, frame `nocol` without colour: the (depth, pose) pairs and the fuser parameters."""
+    from scannet_amd import calibrate, fusion, sens
+    W, H, CW, CH = 160, 120, 324, 242
+    K = synth.intrinsic_matrix(W, H)
+    KC = np.eye(4, dtype=np.float32)
+    KC[0, 0], KC[1, 1], KC[0, 2], KC[1, 2] = 340.3, 338.1, 160.2, 119.7
+    if colour is None:
+        sd = sens.SensorData.create(0, 0, W, H, K, K, depth_compression=1)
+    else:
+        sd = sens.SensorData.create(CW, CH, W, H, KC, K, color_compression=2 if colour == "jpeg" else 0, depth_compression=1)
+    frames = []
+    for i in range(n):
+        pose = synth.trajectory_pose(i * 7, 1200)
+        d = synth.render_room_depth(pose, W, H, noise_frame=i)
+        if i == lost:
+            pose = np.full((4, 4), -np.inf, np.float32)
+        img = _smooth_image(CW, CH, i)
+        color = None
+        if colour is not None and i != nocol:
+            color = calibrate.jpeg_encode(img, 90, not (mixed_layouts and i % 2)) if colour == "jpeg" else img
+        sd.add_frame(d, pose, color=color, timestamp_depth=i)
+        frames.append((d, pose))
+    sd.save(path)
+    sd.close()
+    fx, fy, mx, my = synth.intrinsics(W, H)
+    gp = fusion.default_params(depth_width=W, depth_height=H, fx=fx, fy=fy, mx=mx, my=my, voxel_size=0.016, num_sdf_blocks=1 << 16)
+    if colour is not None:
+        gp.color_width, gp.color_height, gp.cfx, gp.cfy, gp.cmx, gp.cmy = CW, CH, 340.3, 338.1, 160.2, 119.7
+    return frames, gp
+
+
+def _assert_run_equals_frame_by_frame(a, b, s, frames, colour):
+    """Fuser `a` ran the scan `s`; `b` integrates the host-decoded frames one by one: the same blocks, byte for byte."""
+    for i, (d, pose) in enumerate(frames):
+        if not np.isfinite(pose[0, 0]):
+            continue
+        has_colour = colour and s.frames[i].color_size_bytes > 0
+        assert b.integrate(d, pose, rgb=s.frames[i].decompress_color() if has_colour else None)
+    ca, va = a.export_blocks()
+    cb, vb = b.export_blocks()
+    oa, ob = np.lexsort(ca.T[::-1]), np.lexsort(cb.T[::-1])
+    assert np.array_equal(ca[oa], cb[ob])
+    assert np.array_equal(va[oa].view(np.uint8), vb[ob].view(np.uint8)), "voxels (sdf, weight, colour) differ"
+    assert len(ca) > 500
+
+
+@pytest.mark.parametrize("colour", [None, "raw", "jpeg"])
+def test_fuse_run_reuses_its_ring_slots(tmp_path, colour):
+    """A run whose ring slots come round: 45 frames in batches of 4 are 12 batches over 6 slots (8 with JPEG colour), so every slot is refilled while the
+    copies, the side-stream work and the pre-pass of its previous batch may still be in flight (`consumed` / `landed`).  Depth only (the device inflates),
+    raw colour, and JPEG colour as taken by default -- pictures of two sampling layouts alternate, so every batch mixes prepared segments with pictures
+    their host threads decode, and the packed copy is never taken.  One frame has no pose, one no colour."""
+    from scannet_amd import fusion, sens
+    n = 45
+    p = str(tmp_path / "ring.sens")
+    frames, gp = _write_small_scan(p, n, colour, mixed_layouts=True, lost=5, nocol=11)
+    s = sens.SensorData(p)
+    with fusion.Fuser(gp) as a, fusion.Fuser(gp) as b:
+        a.tune(batch=4)
+        rs = a.run(s, decode_threads=5)
+        assert (rs["frames_total"], rs["frames_integrated"], rs["frames_skipped"]) == (n, n - 1, 1), rs
+        assert rs["color_fused"] == (1 if colour else 0)
+        assert rs["depth_inflated_on_device"] == n - 1 and rs["depth_inflated_on_host"] == 0, rs
+        if colour == "jpeg":
+            assert rs["jpeg_entropy_on_device"] > 0 and rs["jpeg_entropy_on_host"] > 0, rs
+            assert rs["jpeg_entropy_on_device"] + rs["jpeg_entropy_on_host"] == n - 2, rs
+        _assert_run_equals_frame_by_frame(a, b, s, frames, colour)
+
+
+@pytest.mark.parametrize("entropy", ["host", "device"])
+def test_fuse_run_with_jpeg_colour_and_no_side_stream(tmp_path, entropy, monkeypatch):
+    """JPEG colour when depth is not inflated on the device (SF_INFLATE_HOST): the batch has no side stream, and the pictures of a sub-batch are reconstructed
+    on the fuser's input stream in front of its pre-pass.  By default the host threads entropy-decode; with SF_JPEG_GPU_HUFFMAN the device does that there too,
+    out of the small pinned slot -- all pictures share one layout, so the second batch (five frames, all with pose and colour) takes the packed two-copy
+    path and the first (a frame without pose, one without colour) the copy per frame."""
+    from scannet_amd import fusion, sens
+    n = 37
+    p = str(tmp_path / "noside.sens")
+    frames, gp = _write_small_scan(p, n, "jpeg", mixed_layouts=False, lost=5, nocol=11)
+    monkeypatch.setenv("SF_INFLATE_HOST", "1")
+    if entropy == "device":
+        monkeypatch.setenv("SF_JPEG_GPU_HUFFMAN", "1")
+    s = sens.SensorData(p)
+    with fusion.Fuser(gp) as a, fusion.Fuser(gp) as b:
+        rs = a.run(s, decode_threads=5)
+        assert (rs["frames_total"], rs["frames_integrated"], rs["frames_skipped"]) == (n, n - 1, 1) and rs["color_fused"] == 1, rs
+        assert rs["depth_inflated_on_device"] == 0, rs
+        assert rs["jpeg_entropy_on_device"] == (n - 2 if entropy == "device" else 0), rs
+        assert rs["jpeg_entropy_on_device"] + rs["jpeg_entropy_on_host"] == n - 2, rs
+        _assert_run_equals_frame_by_frame(a, b, s, frames, colour=True)
+
+
 @pytest.mark.parametrize("res", ["own", "same"])
 @pytest.mark.parametrize("layout", ["420", "444", "grey"])
 def test_fuse_run_converts_the_looked_up_pixels_from_the_jpeg_planes(tmp_path, res, layout, monkeypatch):

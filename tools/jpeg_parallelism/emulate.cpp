@@ -8,10 +8,9 @@
 #include <cstring>
 #include <vector>
 
+#include "../../scannet_amd/csrc/codecs_internal.h"
 #include "../../scannet_amd/csrc/jpeg_huff.h"
 
-int jpeg_prepare_huff(const uint8_t* data, uint64_t n, uint32_t expect_w, uint32_t expect_h, uint8_t* payload, uint64_t payload_capacity);
-int jpeg_decode_coef(const uint8_t* data, uint64_t n, uint32_t expect_w, uint32_t expect_h, uint8_t* payload, uint64_t payload_capacity);
 extern "C" const char* sf_last_error(void);
 
 struct Writer {

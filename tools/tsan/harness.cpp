@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "fuser_internal.h"
 #include "sens.h"
 
@@ -115,6 +116,12 @@ int main(int argc, char** argv) {
   sf_sens* s = nullptr;
   if (sf_sens_open(path.c_str(), &s) != SF_OK) { std::fprintf(stderr, "%s\n", sf_last_error()); return 5; }
   int rc_all = 0;
+  {   // the preparation thread makes the process's set beside this thread; the first run joins it
+    sf_params prm;
+    std::memset(&prm, 0, sizeof(prm));
+    prm.depth_width = W; prm.depth_height = H;
+    if (sf_fuse_run_prepare(s, &prm, 0) != SF_OK) { std::fprintf(stderr, "sf_fuse_run_prepare: %s\n", sf_last_error()); rc_all = 9; }
+  }
   for (int batch : {16, 1, 5}) {
     sf_fuser f;
     std::memset(&f.p, 0, sizeof(f.p));
