@@ -307,8 +307,9 @@ int sf_fuser_track_device(sf_fuser* f, const void* d_depth, const float guess[16
  * An all -inf old pose: the frame was never integrated, it is only put in; an all -inf new pose: tracking is lost now, it is only taken out; both: nothing
  * happens.  sf_stats moves as that sequence moves it -- every all -inf pose is one skipped call of it, hence one count in frames_skipped, every other
  * pose one in frames_integrated -- except total_pass_tiles, which counts what the passes really read.  d_rgb may be NULL (geometry only).  Up to
- * sf_fuser_batch_frames() operations share a pass, the two of a frame always do.  Who produces the revised poses (a pose-graph or bundle solver,
- * sf_sens_apply_transform on part of a scan, a second tracking sweep) is the caller's business: global bundle adjustment is not in this library. */
+ * sf_fuser_batch_frames() operations share a pass, the two of a frame always do.  Revised poses come from sf_fuser_align below (a dense-depth solver
+ * over keyframes) or from the caller (sf_sens_apply_transform on part of a scan, a second tracking sweep, a solver of its own): BundleFusion's SIFT
+ * matching, colour term, loop detection and local / global hierarchy are not in this library. */
 int sf_fuser_reintegrate_batch_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes,
                                       const float* old_poses, const float* new_poses, uint64_t n);
 /* one frame from host buffers (as sf_fuser_integrate takes them); SF_ERR_SKIPPED when both poses are all -inf */
@@ -342,6 +343,60 @@ typedef struct sf_reint_stats {
  * fuser fuses colour at) go with the depth.  The volume is never reset.  Synchronous. */
 int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float* integrated_poses, const float* target_poses, const sf_reint_params* r,
                               uint64_t max_steps, int with_colour, int decode_threads, sf_reint_stats* stats);
+
+/* Global alignment: the producer of the revised poses above.  K keyframes (u16 depth at the fuser's input size, camToWorld poses) are aligned jointly
+ * over a list of directed frame pairs by a depth-only projective point-to-plane term, BundleFusion's dense depth term between keyframes (the keys of
+ * Server/tools/recons/zParametersBundlingScanNet.txt:22-44; the code that reads them is not in the reference tree).  The semantics, per pixel, per pair
+ * and per Gauss-Newton iteration, are DESIGN.md section 4e "Global alignment".  SIFT matching, the colour term, loop detection, the bilateral depth
+ * filter and the local / global hierarchy of BundleFusion are not built.  An alignment changes nothing in the volume, its counters or frame numbering. */
+typedef struct sf_align_params {
+  int32_t level;                    /* the one image size the solver works at, (W >> level) x (H >> level), 0..3: 1                 */
+  int32_t down_width, down_height;  /* s_downsampledWidth / Height (:44-45); both 0: `level` decides, else the level of that size   */
+  int32_t max_iters;                /* s_numGlobalNonLinIterations (:41): Gauss-Newton iterations, 1..100: 8                        */
+  float dist_thres;                 /* s_denseDistThresh (:22): metres, > 0: 0.15                                                   */
+  float normal_thres;               /* s_denseNormalThresh (:23): smallest cosine between the two normals, -1..1: 0.7               */
+  float depth_min, depth_max;       /* s_denseDepthMin / Max (:26-27): metres; both 0: the fuser's own depth range                  */
+  float early_out;                  /* the loop ends after an update with max |xi| below this, >= 0: 1e-5                          */
+  int32_t min_pair_correspondences; /* a pair with fewer correspondences is dropped for that iteration, >= 1: 500                   */
+  int32_t fixed_frame;              /* the keyframe that keeps its pose (the gauge), 0..K-1: 0                                      */
+  float pair_max_dist;              /* sf_align_pairs: metres between two camera centres, >= 0: 1.0                                 */
+  float pair_max_angle;             /* sf_align_pairs: radians between two orientations, >= 0: 0.6                                  */
+  float max_translation;            /* metres between a frame's input pose and its result, > 0: 0.5                                 */
+  float max_rotation;               /* radians between them, > 0: 0.5                                                               */
+  int32_t reserved[9];
+} sf_align_params;
+void sf_align_params_default(sf_align_params* a);
+/* s_denseDistThresh, s_denseNormalThresh, s_denseDepthMin / Max, s_downsampledWidth / Height and s_numGlobalNonLinIterations of an mLib ParameterFile
+ * (zParametersBundlingScanNet.txt:22-44); keys that are absent leave *a as it is.  s_submapSize (:31) is the tool's keyframe stride, not a field. */
+int sf_align_params_load_file(const char* path, sf_align_params* a);
+typedef struct sf_align_result {
+  int32_t status;                   /* 0 solved, 1 singular system, 2 fewer than two frames connected to the fixed frame            */
+  int32_t iterations;               /* updates applied                                                                              */
+  int32_t pairs_used;               /* pairs in the last system                                                                     */
+  int32_t frames_unconnected;       /* frames with a finite pose that no kept pair connects to the fixed frame: returned as given   */
+  int32_t frames_rejected;          /* frames that moved further than the bounds: returned as given                                 */
+  int32_t reserved0;
+  int64_t correspondences;          /* of the last system                                                                           */
+  float rms_first, rms_last;        /* sqrt(sum r^2 / correspondences) of the first and of the last system                          */
+  int32_t reserved[6];
+} sf_align_result;
+/* The default pair list (host only, double): for i < j both (i, j) and (j, i) when j = i + 1, or when the camera centres are within pair_max_dist and the
+ * orientations within pair_max_angle (sf_reint_plan's angle); ascending i, then j, the forward pair first.  A frame whose pose has a non-finite element
+ * in its first three rows is in no pair.  pairs_out: 2 x capacity int32 (source, target); writing stops at the capacity, *n_out is the full count. */
+int sf_align_pairs(const float* poses, uint64_t K, const sf_align_params* a, int32_t* pairs_out, uint64_t capacity, uint64_t* n_out);
+/* The correction of the keyframes carried to every frame (host only, double): frame f, whose nearest keyframe at or before it is k, gets
+ * (T_k' T_k^-1) T_f; frames before the first keyframe use the first; a keyframe gets its new pose as it is; a keyframe whose old or new pose is not
+ * finite passes its frames to the previous usable keyframe (the first usable one when there is none before); a lost frame stays lost.
+ * keyframes: K ascending frame indices; new_key_poses: K x 16. */
+int sf_align_spread(const float* poses, uint64_t n, const uint64_t* keyframes, uint64_t K, const float* new_key_poses, float* poses_out);
+/* K keyframes in HBM, `frame_stride_bytes` apart (read on sf_fuser_stream(f)); poses_in / poses_out K x 16 floats on the host; pairs 2 x P int32.
+ * 2 <= K <= 256, 1 <= P <= 4096, source != target.  Synchronous; ordered behind every frame queued on the handle before it.  SF_ERR_INVALID_ARG for a
+ * parameter or an index out of range; a system that cannot be solved is a status of *result, with poses_out = poses_in. */
+int sf_fuser_align_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
+                          const sf_align_params* a, float* poses_out, sf_align_result* result);
+/* The same from host frames (K x input-size u16, one after the other). */
+int sf_fuser_align(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a,
+                   float* poses_out, sf_align_result* result);
 
 /* Host <-> device helpers so that callers without a HIP binding can stage inputs in HBM. */
 int sf_device_malloc(int device, uint64_t bytes, void** out);

@@ -1,0 +1,579 @@
+// align.hip -- global alignment: K keyframes aligned jointly over a list of directed frame pairs by a depth-only projective point-to-plane term
+// (DESIGN.md "Global alignment"; BundleFusion's dense depth term between keyframes, zParametersBundlingScanNet.txt:22-44).
+//
+// Once per call: k_align_prep turns every keyframe into a camera-space vertex and a normal map at the one level the solver works at (the tracker's
+// rules, track_math.h).  Per Gauss-Newton iteration: the host writes the pair table (indices, T_i, T_j, T_j^-1 T_i) and copies it over; k_align_assoc
+// pairs every source pixel of every pair with the target pixel it projects to and reduces the pair's 29 values per 256-pixel workgroup (no atomics);
+// k_align_final sums a pair's partials in index order in double; one read-back.  The host drops thin pairs, finds the frames connected to the fixed
+// frame, assembles the sparse-by-blocks normal equations densely and solves them by Cholesky in double.  Every step is deterministic and
+// tests/align_checker.c restates it bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "fuser_internal.h"
+#include "scanfuse_internal.h"
+#include "track_math.h"
+
+namespace {
+
+using namespace tk;
+
+constexpr int AL_MAX_FRAMES = 256;
+constexpr int AL_MAX_PAIRS = 4096;
+
+struct PairEntry {   // one row of the device table; read through the scalar unit (the index is blockIdx.y)
+  int32_t i, j, active, pad;
+  Rows Ti, Tj, M;    // source pose, target pose, T_j^-1 T_i
+};
+
+// depth of pixel (x, y) of level L of a frame in metres: level 0 from the u16 frame, level L the 2x2 reduction of level L - 1
+template <int L>
+__device__ inline float level_depth(const uint16_t* __restrict__ in, const ParamsK& P, int x, int y) {
+  if constexpr (L == 0) {
+    return depth0_at(in, P, y * P.W + x);
+  } else {
+    const float s00 = level_depth<L - 1>(in, P, 2 * x, 2 * y);
+    if (!(s00 > 0.0f)) return -INFINITY;   // down4 reads nothing else of an invalid reference pixel
+    return down4(s00, level_depth<L - 1>(in, P, 2 * x + 1, 2 * y), level_depth<L - 1>(in, P, 2 * x, 2 * y + 1), level_depth<L - 1>(in, P, 2 * x + 1, 2 * y + 1));
+  }
+}
+
+// the level's depth behind the solver's own gate
+template <int L>
+__device__ inline float gated_depth(const uint16_t* __restrict__ in, const ParamsK& P, int x, int y, float dmin, float dmax) {
+  const float d = level_depth<L>(in, P, x, y);
+  return (d >= dmin && d <= dmax) ? d : -INFINITY;
+}
+
+// all K frames at once (blockIdx.y = frame): u16 -> metres -> L reductions -> vertex and normal map of level L
+template <int L>
+__global__ void __launch_bounds__(256) k_align_prep(const uint8_t* __restrict__ frames, size_t frame_stride, const ParamsK P, const Cam c, float dmin, float dmax,
+                                                    float4* __restrict__ vmap, float4* __restrict__ nmap) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int npx = c.W * c.H;
+  if (i >= npx) return;
+  const uint16_t* in = reinterpret_cast<const uint16_t*>(frames + (size_t)blockIdx.y * frame_stride);
+  const int x = i % c.W, y = i / c.W;
+  const float dz = gated_depth<L>(in, P, x, y, dmin, dmax);
+  const bool nb = dz > 0.0f && x + 1 < c.W && y + 1 < c.H;
+  const float dr = nb ? gated_depth<L>(in, P, x + 1, y, dmin, dmax) : 0.0f;
+  const float dd = nb ? gated_depth<L>(in, P, x, y + 1, dmin, dmax) : 0.0f;
+  float4 vo, no;
+  vertex_normal(c, x, y, dz, nb, dr, dd, &vo, &no);
+  const size_t o = (size_t)blockIdx.y * npx + i;
+  vmap[o] = vo;
+  nmap[o] = no;
+}
+
+// one pair per blockIdx.y: association of the source frame's pixels with the target frame's maps and the pair's point-to-plane rows, reduced to one
+// 29-float partial per 256-pixel workgroup; partials[P][nb][32]
+__global__ void __launch_bounds__(256) k_align_assoc(const float4* __restrict__ vmap, const float4* __restrict__ nmap, const PairEntry* __restrict__ table,
+                                                     const Cam c, float dist_thres, float normal_thres, float* __restrict__ partials) {
+  __shared__ float red[4][TK_NSYS];
+  const PairEntry& e = table[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int npx = c.W * c.H;
+  float acc[TK_NSYS];
+#pragma unroll
+  for (int k = 0; k < TK_NSYS; k++) acc[k] = 0.0f;
+  if (e.active && i < npx) {
+    const size_t so = (size_t)e.i * npx, to = (size_t)e.j * npx;
+    const float4 v4 = vmap[so + i], n4 = nmap[so + i];
+    if (v4.z > 0.0f && n4.x > -INFINITY) {
+      const float3 v = make_float3(v4.x, v4.y, v4.z);
+      const float3 p = xf(e.Ti, v), n = rot(e.Ti, make_float3(n4.x, n4.y, n4.z));
+      const float3 pc = xf(e.M, v);
+      if (pc.z > 0.0f) {
+        const float ux = floorf(fmaf(pc.x / pc.z, c.fx, c.mx) + 0.5f), uy = floorf(fmaf(pc.y / pc.z, c.fy, c.my) + 0.5f);
+        if (ux >= 0.0f && ux < (float)c.W && uy >= 0.0f && uy < (float)c.H) {
+          const size_t t = to + (size_t)((int)uy * c.W + (int)ux);
+          const float4 w4 = vmap[t], m4 = nmap[t];
+          if (w4.z > 0.0f && m4.x > -INFINITY) {
+            const float3 q = xf(e.Tj, make_float3(w4.x, w4.y, w4.z)), nm = rot(e.Tj, make_float3(m4.x, m4.y, m4.z));
+            const float3 d = make_float3(p.x - q.x, p.y - q.y, p.z - q.z);
+            if (sqrtf(dot3(d, d)) <= dist_thres && dot3(nm, n) >= normal_thres) row29(p, nm, d, acc);
+          }
+        }
+      }
+    }
+  }
+  reduce256(acc, red, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TK_PSTRIDE);
+}
+
+// one wave per pair: lane k sums value k of the pair's partials in index order, in double; out[P][29]
+__global__ void __launch_bounds__(64) k_align_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
+  const int k = threadIdx.x;
+  if (k >= TK_NSYS) return;
+  const float* p = partials + (size_t)blockIdx.x * nb * TK_PSTRIDE;
+  double s = 0.0;
+#pragma unroll 8
+  for (int b = 0; b < nb; b++) s += (double)p[(size_t)b * TK_PSTRIDE + k];
+  out[(size_t)blockIdx.x * TK_NSYS + k] = s;
+}
+
+}  // namespace
+
+struct AlignWork {
+  size_t in_bytes = 0, map_px = 0, part_floats = 0;
+  int pairs = 0;
+  uint8_t* d_in = nullptr;        // host frames' device copy
+  float4* vmap = nullptr;         // [K][npx]
+  float4* nmap = nullptr;
+  float* partials = nullptr;      // [P][nb][32]
+  PairEntry* d_table = nullptr;
+  PairEntry* h_table = nullptr;   // page-locked
+  double* d_sys = nullptr;        // [P][29]
+  double* h_sys = nullptr;        // page-locked read-back
+};
+
+void sf_align_release(sf_fuser* f) {
+  AlignWork* w = f ? f->align : nullptr;
+  if (!w) return;
+  (void)hipFree(w->d_in); (void)hipFree(w->vmap); (void)hipFree(w->nmap); (void)hipFree(w->partials); (void)hipFree(w->d_table); (void)hipFree(w->d_sys);
+  if (w->h_table) (void)hipHostFree(w->h_table);
+  if (w->h_sys) (void)hipHostFree(w->h_sys);
+  delete w;
+  f->align = nullptr;
+}
+
+namespace {
+
+// what can be checked without a fuser
+int check_align_args(uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a) {
+  if (!a) return sf::fail(SF_ERR_INVALID_ARG, "NULL alignment parameters");
+  if (a->level < 0 || a->level >= TK_MAX_LEVELS) return sf::fail(SF_ERR_INVALID_ARG, "alignment level %d (0..3)", a->level);
+  if (a->down_width < 0 || a->down_height < 0 || (a->down_width == 0) != (a->down_height == 0))
+    return sf::fail(SF_ERR_INVALID_ARG, "alignment down_width x down_height %d x %d: both 0 or both positive", a->down_width, a->down_height);
+  if (a->max_iters < 1 || a->max_iters > 100) return sf::fail(SF_ERR_INVALID_ARG, "alignment max_iters %d (1..100)", a->max_iters);
+  if (!std::isfinite(a->dist_thres) || !(a->dist_thres > 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "alignment dist_thres %g: not a positive finite number", a->dist_thres);
+  if (!(a->normal_thres >= -1.0f && a->normal_thres <= 1.0f)) return sf::fail(SF_ERR_INVALID_ARG, "alignment normal_thres %g (-1..1)", a->normal_thres);
+  if (!std::isfinite(a->depth_min) || !std::isfinite(a->depth_max) || a->depth_min < 0.0f || a->depth_max < a->depth_min)
+    return sf::fail(SF_ERR_INVALID_ARG, "alignment depth range %g .. %g", a->depth_min, a->depth_max);
+  if (!std::isfinite(a->early_out) || !(a->early_out >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "alignment early_out %g: not a finite number >= 0", a->early_out);
+  if (a->min_pair_correspondences < 1) return sf::fail(SF_ERR_INVALID_ARG, "min_pair_correspondences %d (>= 1)", a->min_pair_correspondences);
+  if (!std::isfinite(a->max_translation) || !(a->max_translation > 0.0f) || !std::isfinite(a->max_rotation) || !(a->max_rotation > 0.0f))
+    return sf::fail(SF_ERR_INVALID_ARG, "alignment motion bound %g m, %g rad: not positive finite numbers", a->max_translation, a->max_rotation);
+  if (K < 2 || K > (uint64_t)AL_MAX_FRAMES) return sf::fail(SF_ERR_INVALID_ARG, "alignment of %llu frames (2..%d)", (unsigned long long)K, AL_MAX_FRAMES);
+  if (a->fixed_frame < 0 || (uint64_t)a->fixed_frame >= K) return sf::fail(SF_ERR_INVALID_ARG, "fixed_frame %d of %llu frames", a->fixed_frame, (unsigned long long)K);
+  if (P < 1 || P > (uint64_t)AL_MAX_PAIRS) return sf::fail(SF_ERR_INVALID_ARG, "alignment over %llu pairs (1..%d)", (unsigned long long)P, AL_MAX_PAIRS);
+  if (!poses || !pairs) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  for (uint64_t p = 0; p < P; p++) {
+    const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
+    if (i < 0 || j < 0 || (uint64_t)i >= K || (uint64_t)j >= K || i == j)
+      return sf::fail(SF_ERR_INVALID_ARG, "pair %llu = (%d, %d): two different frames of 0..%llu", (unsigned long long)p, i, j, (unsigned long long)(K - 1));
+  }
+  return SF_OK;
+}
+
+// the level and its camera on this fuser (the tracker's level intrinsics)
+int resolve_level(const sf_fuser* f, const sf_align_params* a, int* level, Cam* cam) {
+  const int W = f->pk.W, H = f->pk.H;
+  int l = a->level;
+  if (a->down_width > 0) {
+    l = -1;
+    for (int k = 0; k < TK_MAX_LEVELS; k++)
+      if ((W >> k) == a->down_width && (H >> k) == a->down_height) { l = k; break; }
+    if (l < 0) return sf::fail(SF_ERR_INVALID_ARG, "alignment down_width x down_height %d x %d is no level 0..3 of %d x %d", a->down_width, a->down_height, W, H);
+  }
+  Cam& c = *cam;
+  c.W = W >> l;
+  c.H = H >> l;
+  if (c.W < 8 || c.H < 8) return sf::fail(SF_ERR_INVALID_ARG, "alignment level %d would be %d x %d (at least 8 x 8)", l, c.W, c.H);
+  const float sx = (float)c.W / (float)W, sy = (float)c.H / (float)H;
+  c.fx = f->pk.fx * sx; c.mx = f->pk.mx * sx;
+  c.fy = f->pk.fy * sy; c.my = f->pk.my * sy;
+  *level = l;
+  return SF_OK;
+}
+
+template <typename T>
+int grow(sf_fuser* f, T** ptr, size_t bytes, bool host) {
+  if (*ptr) { if (host) (void)hipHostFree(*ptr); else (void)hipFree(*ptr); *ptr = nullptr; }
+  const hipError_t e = host ? hipHostMalloc((void**)ptr, bytes, hipHostMallocDefault) : hipMalloc((void**)ptr, bytes);
+  if (e != hipSuccess) { *ptr = nullptr; sf_align_release(f); return sf::fail(SF_ERR_DEVICE, "alignment buffers: %s", hipGetErrorString(e)); }
+  return SF_OK;
+}
+
+int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames) {
+  if (!f->align) f->align = new AlignWork();
+  AlignWork* w = f->align;
+  int rc;
+  const size_t in_bytes = host_frames ? (size_t)K * f->in_px * sizeof(uint16_t) : 0;
+  if (in_bytes > w->in_bytes) { w->in_bytes = 0; if ((rc = grow(f, &w->d_in, in_bytes, false)) != SF_OK) return rc; w->in_bytes = in_bytes; }
+  const size_t map_px = (size_t)K * npx;
+  if (map_px > w->map_px) {
+    w->map_px = 0;
+    if ((rc = grow(f, &w->vmap, map_px * sizeof(float4), false)) != SF_OK || (rc = grow(f, &w->nmap, map_px * sizeof(float4), false)) != SF_OK) return rc;
+    w->map_px = map_px;
+  }
+  const size_t part = (size_t)P * ((npx + 255) / 256) * TK_PSTRIDE;
+  if (part > w->part_floats) { w->part_floats = 0; if ((rc = grow(f, &w->partials, part * sizeof(float), false)) != SF_OK) return rc; w->part_floats = part; }
+  if ((int)P > w->pairs) {
+    w->pairs = 0;
+    if ((rc = grow(f, &w->d_table, P * sizeof(PairEntry), false)) != SF_OK || (rc = grow(f, &w->h_table, P * sizeof(PairEntry), true)) != SF_OK ||
+        (rc = grow(f, &w->d_sys, P * TK_NSYS * sizeof(double), false)) != SF_OK || (rc = grow(f, &w->h_sys, P * TK_NSYS * sizeof(double), true)) != SF_OK)
+      return rc;
+    w->pairs = (int)P;
+  }
+  return SF_OK;
+}
+
+struct Job {
+  uint64_t K, P;
+  const int32_t* pairs;
+  int level;
+  Cam cam;
+  float dmin, dmax;
+};
+
+// the maps of all K frames, queued on f->stream behind everything queued on the handle so far
+int prepare(sf_fuser* f, const void* d_depth, uint64_t stride, const Job& j) {
+  AlignWork* w = f->align;
+  for (hipEvent_t& e : f->ev_raycast)
+    if (!e) SF_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  const hipStream_t fronts[2] = {f->front, f->front_lo};
+  for (int i = 0; i < 2; i++)
+    if (fronts[i]) {
+      SF_HIP_CHECK(hipEventRecord(f->ev_raycast[i], fronts[i]));
+      SF_HIP_CHECK(hipStreamWaitEvent(f->stream, f->ev_raycast[i], 0));
+    }
+  const int npx = j.cam.W * j.cam.H;
+  const dim3 grid((npx + 255) / 256, (unsigned)j.K);
+#define AL_PREP(L)                                                                                                                           \
+  hipLaunchKernelGGL(k_align_prep<L>, grid, dim3(256), 0, f->stream, (const uint8_t*)d_depth, (size_t)stride, f->pk, j.cam, j.dmin, j.dmax, \
+                     w->vmap, w->nmap)
+  switch (j.level) {
+    case 0: AL_PREP(0); break;
+    case 1: AL_PREP(1); break;
+    case 2: AL_PREP(2); break;
+    default: AL_PREP(3); break;
+  }
+#undef AL_PREP
+  SF_HIP_CHECK(hipGetLastError());
+  return SF_OK;
+}
+
+// the P systems at the poses T (K x 12 doubles; valid[k]: the frame takes part) into w->h_sys
+int systems_at(sf_fuser* f, const Job& j, const double* T, const uint8_t* valid, const sf_align_params* a) {
+  AlignWork* w = f->align;
+  for (uint64_t p = 0; p < j.P; p++) {
+    PairEntry& e = w->h_table[p];
+    std::memset(&e, 0, sizeof(e));
+    e.i = j.pairs[2 * p];
+    e.j = j.pairs[2 * p + 1];
+    e.active = valid[e.i] && valid[e.j];
+    if (!e.active) continue;
+    const double *Ti = T + 12 * e.i, *Tj = T + 12 * e.j;
+    for (int k = 0; k < 12; k++) { e.Ti.T[k] = (float)Ti[k]; e.Tj.T[k] = (float)Tj[k]; }
+    compose_ref(Tj, Ti, e.M.T);
+  }
+  SF_HIP_CHECK(hipMemcpyAsync(w->d_table, w->h_table, j.P * sizeof(PairEntry), hipMemcpyHostToDevice, f->stream));
+  const int npx = j.cam.W * j.cam.H, nb = (npx + 255) / 256;
+  hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)j.P), dim3(256), 0, f->stream, w->vmap, w->nmap, w->d_table, j.cam, a->dist_thres, a->normal_thres, w->partials);
+  SF_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_align_final, dim3((unsigned)j.P), dim3(64), 0, f->stream, w->partials, nb, w->d_sys);
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys, w->d_sys, j.P * TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(f->stream));
+  return SF_OK;
+}
+
+int find_root(std::vector<int>& parent, int k) {
+  while (parent[k] != k) k = parent[k] = parent[parent[k]];
+  return k;
+}
+
+// A x = -b for the symmetric N x N system A (row-major, full) by Cholesky in double, sums in index order; false at a pivot <= TK_PIVOT_REL x its diagonal entry
+bool solve_dense(const std::vector<double>& A, const std::vector<double>& b, int N, std::vector<double>& x) {
+  std::vector<double> L((size_t)N * N, 0.0), y(N);
+  for (int j = 0; j < N; j++) {
+    double s = A[(size_t)j * N + j];
+    for (int m = 0; m < j; m++) s -= L[(size_t)j * N + m] * L[(size_t)j * N + m];
+    if (!(s > TK_PIVOT_REL * A[(size_t)j * N + j])) return false;
+    L[(size_t)j * N + j] = std::sqrt(s);
+    for (int i = j + 1; i < N; i++) {
+      double e = A[(size_t)i * N + j];
+      for (int m = 0; m < j; m++) e -= L[(size_t)i * N + m] * L[(size_t)j * N + m];
+      L[(size_t)i * N + j] = e / L[(size_t)j * N + j];
+    }
+  }
+  for (int i = 0; i < N; i++) {
+    double e = -b[i];
+    for (int m = 0; m < i; m++) e -= L[(size_t)i * N + m] * y[m];
+    y[i] = e / L[(size_t)i * N + i];
+  }
+  x.assign(N, 0.0);
+  for (int i = N - 1; i >= 0; i--) {
+    double e = y[i];
+    for (int m = i + 1; m < N; m++) e -= L[(size_t)m * N + i] * x[m];
+    x[i] = e / L[(size_t)i * N + i];
+  }
+  return true;
+}
+
+int align_device(sf_fuser* f, const void* d_depth, uint64_t stride, uint64_t K, const float* poses_in, const Job& j, const sf_align_params* a, float* poses_out,
+                 sf_align_result* res) {
+  int rc;
+  sf_align_result r;
+  std::memset(&r, 0, sizeof(r));
+  std::memcpy(poses_out, poses_in, K * 16 * sizeof(float));
+  std::vector<double> T0(K * 12), T(K * 12);
+  std::vector<uint8_t> valid(K);
+  for (uint64_t k = 0; k < K; k++) {
+    valid[k] = finite12(poses_in + 16 * k);
+    for (int i = 0; i < 12; i++) T0[12 * k + i] = valid[k] ? (double)poses_in[16 * k + i] : 0.0;
+  }
+  T = T0;
+  if ((rc = prepare(f, d_depth, stride, j)) != SF_OK) return rc;
+  const double* sys = f->align->h_sys;
+  const int fixed = a->fixed_frame;
+  std::vector<uint8_t> kept(j.P), conn(K, 0);
+  std::vector<int> parent(K), slot(K);
+  std::vector<double> A, b, xi;
+  for (int it = 0; it < a->max_iters; it++) {
+    if ((rc = systems_at(f, j, T.data(), valid.data(), a)) != SF_OK) return rc;
+    for (uint64_t k = 0; k < K; k++) parent[k] = (int)k;
+    for (uint64_t p = 0; p < j.P; p++) {
+      const int pi = j.pairs[2 * p], pj = j.pairs[2 * p + 1];
+      kept[p] = valid[pi] && valid[pj] && sys[p * TK_NSYS + 28] >= (double)a->min_pair_correspondences;
+      if (!kept[p]) continue;
+      const int ra = find_root(parent, pi), rb = find_root(parent, pj);
+      if (ra != rb) parent[ra > rb ? ra : rb] = ra > rb ? rb : ra;   // the smaller index is the root
+    }
+    const int rf = find_root(parent, fixed);
+    int n = 0, nconn = 0;
+    for (uint64_t k = 0; k < K; k++) {
+      conn[k] = valid[k] && find_root(parent, (int)k) == rf;
+      slot[k] = -1;
+      if (conn[k]) { nconn++; if ((int)k != fixed) slot[k] = n++; }
+    }
+    if (!valid[fixed] || nconn < 2) { r.status = 2; break; }
+    const int N = 6 * n;
+    A.assign((size_t)N * N, 0.0);
+    b.assign(N, 0.0);
+    int used = 0;
+    double corr = 0.0, r2 = 0.0;
+    for (uint64_t p = 0; p < j.P; p++) {
+      const int pi = j.pairs[2 * p], pj = j.pairs[2 * p + 1];
+      if (!kept[p] || !conn[pi]) continue;
+      const double* s = sys + p * TK_NSYS;
+      double Hm[6][6];
+      int k = 0;
+      for (int u = 0; u < 6; u++)
+        for (int v = u; v < 6; v++) Hm[u][v] = Hm[v][u] = s[k++];
+      const int si = slot[pi], sj = slot[pj];
+      for (int u = 0; u < 6; u++) {
+        for (int v = 0; v < 6; v++) {
+          if (si >= 0) A[(size_t)(6 * si + u) * N + 6 * si + v] += Hm[u][v];
+          if (sj >= 0) A[(size_t)(6 * sj + u) * N + 6 * sj + v] += Hm[u][v];
+          if (si >= 0 && sj >= 0) {
+            A[(size_t)(6 * si + u) * N + 6 * sj + v] -= Hm[u][v];
+            A[(size_t)(6 * sj + u) * N + 6 * si + v] -= Hm[u][v];
+          }
+        }
+        if (si >= 0) b[6 * si + u] += s[21 + u];
+        if (sj >= 0) b[6 * sj + u] -= s[21 + u];
+      }
+      used++;
+      r2 += s[27];
+      corr += s[28];
+    }
+    r.pairs_used = used;
+    r.correspondences = (int64_t)corr;
+    r.rms_last = corr > 0.0 ? (float)std::sqrt(r2 / corr) : 0.0f;
+    if (it == 0) r.rms_first = r.rms_last;
+    if (!solve_dense(A, b, N, xi)) { r.status = 1; break; }
+    double mx = 0.0;
+    for (uint64_t k = 0; k < K; k++)
+      if (slot[k] >= 0) apply_update(&xi[6 * slot[k]], &T[12 * k]);
+    for (int k = 0; k < N; k++) mx = std::fmax(mx, std::fabs(xi[k]));
+    r.iterations++;
+    if (mx < (double)a->early_out) break;
+  }
+  // a frame with a finite pose that the last system did not reach, or that moved beyond the bounds, keeps its input pose
+  for (uint64_t k = 0; k < K; k++) {
+    if (!valid[k] || (int)k == fixed) continue;
+    if (!conn[k]) { r.frames_unconnected++; continue; }
+    if (r.status != 0) continue;
+    double dist, ang;
+    motion(&T0[12 * k], &T[12 * k], &dist, &ang);
+    bool fin = true;
+    for (int i = 0; i < 12; i++) fin = fin && std::isfinite(T[12 * k + i]);
+    if (!fin || !(dist <= (double)a->max_translation) || !(ang <= (double)a->max_rotation)) { r.frames_rejected++; continue; }
+    float* o = poses_out + 16 * k;
+    for (int i = 0; i < 12; i++) o[i] = (float)T[12 * k + i];
+    o[12] = o[13] = o[14] = 0.0f;
+    o[15] = 1.0f;
+  }
+  if (res) *res = r;
+  return SF_OK;
+}
+
+int make_job(sf_fuser* f, uint64_t K, const int32_t* pairs, uint64_t P, const sf_align_params* a, Job* j) {
+  j->K = K; j->P = P; j->pairs = pairs;
+  const int rc = resolve_level(f, a, &j->level, &j->cam);
+  if (rc != SF_OK) return rc;
+  const bool own = a->depth_min == 0.0f && a->depth_max == 0.0f;
+  j->dmin = own ? f->pk.dmin : a->depth_min;
+  j->dmax = own ? f->pk.dmax : a->depth_max;
+  return SF_OK;
+}
+
+}  // namespace
+
+SF_API int sf_fuser_align_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
+                                 const sf_align_params* a, float* poses_out, sf_align_result* result) {
+  int rc = check_align_args(K, poses_in, pairs, P, a);
+  if (rc != SF_OK) return rc;
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
+  if (!d_depth || !poses_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (frame_stride_bytes < f->in_px * sizeof(uint16_t) || frame_stride_bytes % sizeof(uint16_t))
+    return sf::fail(SF_ERR_INVALID_ARG, "frame stride %llu bytes for frames of %llu", (unsigned long long)frame_stride_bytes, (unsigned long long)(f->in_px * sizeof(uint16_t)));
+  Job j;
+  if ((rc = make_job(f, K, pairs, P, a, &j)) != SF_OK) return rc;
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, K, P, j.cam.W * j.cam.H, false)) != SF_OK) return rc;
+  return align_device(f, d_depth, frame_stride_bytes, K, poses_in, j, a, poses_out, result);
+}
+
+SF_API int sf_fuser_align(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a,
+                          float* poses_out, sf_align_result* result) {
+  int rc = check_align_args(K, poses_in, pairs, P, a);
+  if (rc != SF_OK) return rc;
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
+  if (!depth || !poses_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  Job j;
+  if ((rc = make_job(f, K, pairs, P, a, &j)) != SF_OK) return rc;
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, K, P, j.cam.W * j.cam.H, true)) != SF_OK) return rc;
+  const size_t stride = f->in_px * sizeof(uint16_t);
+  SF_HIP_CHECK(hipMemcpyAsync(f->align->d_in, depth, K * stride, hipMemcpyHostToDevice, f->stream));
+  return align_device(f, f->align->d_in, stride, K, poses_in, j, a, poses_out, result);
+}
+
+SF_API int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a,
+                                 double* sys) {
+  int rc = check_align_args(K, poses, pairs, P, a);
+  if (rc != SF_OK) return rc;
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
+  if (!depth || !sys) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  Job j;
+  if ((rc = make_job(f, K, pairs, P, a, &j)) != SF_OK) return rc;
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, K, P, j.cam.W * j.cam.H, true)) != SF_OK) return rc;
+  const size_t stride = f->in_px * sizeof(uint16_t);
+  SF_HIP_CHECK(hipMemcpyAsync(f->align->d_in, depth, K * stride, hipMemcpyHostToDevice, f->stream));
+  if ((rc = prepare(f, f->align->d_in, stride, j)) != SF_OK) return rc;
+  std::vector<double> T(K * 12, 0.0);
+  std::vector<uint8_t> valid(K);
+  for (uint64_t k = 0; k < K; k++) {
+    valid[k] = finite12(poses + 16 * k);
+    for (int i = 0; i < 12 && valid[k]; i++) T[12 * k + i] = (double)poses[16 * k + i];
+  }
+  if ((rc = systems_at(f, j, T.data(), valid.data(), a)) != SF_OK) return rc;
+  std::memcpy(sys, f->align->h_sys, P * TK_NSYS * sizeof(double));
+  return SF_OK;
+}
+
+// ======================================================================================================
+// Host only, double precision: the default pair list and the spreading of the keyframes' correction.
+// ======================================================================================================
+SF_API int sf_align_pairs(const float* poses, uint64_t K, const sf_align_params* a, int32_t* pairs_out, uint64_t capacity, uint64_t* n_out) {
+  if (!a || !n_out || (!poses && K > 0) || (!pairs_out && capacity > 0)) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (!(a->pair_max_dist >= 0.0f) || !(a->pair_max_angle >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "sf_align_pairs: pair_max_dist %g, pair_max_angle %g", a->pair_max_dist, a->pair_max_angle);
+  if (K > 0x7FFFFFFFull) return sf::fail(SF_ERR_INVALID_ARG, "sf_align_pairs: %llu frames", (unsigned long long)K);
+  uint64_t n = 0;
+  for (uint64_t i = 0; i < K; i++) {
+    const float* pa = poses + 16 * i;
+    if (!finite12(pa)) continue;
+    for (uint64_t jx = i + 1; jx < K; jx++) {
+      const float* pb = poses + 16 * jx;
+      if (!finite12(pb)) continue;
+      bool take = jx == i + 1;
+      if (!take) {
+        double d2 = 0.0, M[3][3];
+        for (int r = 0; r < 3; r++) {
+          const double dt = (double)pb[4 * r + 3] - (double)pa[4 * r + 3];
+          d2 += dt * dt;
+        }
+        for (int u = 0; u < 3; u++)
+          for (int v = 0; v < 3; v++) {
+            double s = 0.0;
+            for (int k = 0; k < 3; k++) s += (double)pa[4 * k + u] * (double)pb[4 * k + v];
+            M[u][v] = s;
+          }
+        const double x = M[2][1] - M[1][2], y = M[0][2] - M[2][0], z = M[1][0] - M[0][1];
+        const double sn = 0.5 * std::sqrt((x * x + y * y) + z * z);
+        const double cs = 0.5 * (((M[0][0] + M[1][1]) + M[2][2]) - 1.0);
+        take = std::sqrt(d2) <= (double)a->pair_max_dist && std::atan2(sn, cs) <= (double)a->pair_max_angle;
+      }
+      if (!take) continue;
+      if (n < capacity) { pairs_out[2 * n] = (int32_t)i; pairs_out[2 * n + 1] = (int32_t)jx; }
+      n++;
+      if (n < capacity) { pairs_out[2 * n] = (int32_t)jx; pairs_out[2 * n + 1] = (int32_t)i; }
+      n++;
+    }
+  }
+  *n_out = n;
+  return SF_OK;
+}
+
+SF_API int sf_align_spread(const float* poses, uint64_t n, const uint64_t* keyframes, uint64_t K, const float* new_key_poses, float* poses_out) {
+  if ((n > 0 && (!poses || !poses_out)) || (K > 0 && (!keyframes || !new_key_poses))) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  for (uint64_t k = 0; k < K; k++)
+    if (keyframes[k] >= n || (k > 0 && keyframes[k] <= keyframes[k - 1]))
+      return sf::fail(SF_ERR_INVALID_ARG, "sf_align_spread: keyframes must be ascending frame indices below %llu", (unsigned long long)n);
+  // the correction D_k = T_k' T_k^-1 of every usable keyframe, in double
+  std::vector<double> D(K * 12, 0.0);
+  std::vector<uint8_t> usable(K, 0);
+  int64_t first = -1;
+  for (uint64_t k = 0; k < K; k++) {
+    const float* To = poses + 16 * keyframes[k];
+    const float* Tn = new_key_poses + 16 * k;
+    if (!finite12(To) || !finite12(Tn)) continue;
+    usable[k] = 1;
+    if (first < 0) first = (int64_t)k;
+    const double a00 = To[0], a01 = To[1], a02 = To[2], a10 = To[4], a11 = To[5], a12 = To[6], a20 = To[8], a21 = To[9], a22 = To[10];
+    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+    const double det = a00 * c00 + a01 * c01 + a02 * c02;
+    double inv[9];
+    inv[0] = c00 / det; inv[1] = (a02 * a21 - a01 * a22) / det; inv[2] = (a01 * a12 - a02 * a11) / det;
+    inv[3] = c01 / det; inv[4] = (a00 * a22 - a02 * a20) / det; inv[5] = (a02 * a10 - a00 * a12) / det;
+    inv[6] = c02 / det; inv[7] = (a01 * a20 - a00 * a21) / det; inv[8] = (a00 * a11 - a01 * a10) / det;
+    double* d = &D[12 * k];
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) d[4 * r + c] = ((double)Tn[4 * r] * inv[c] + (double)Tn[4 * r + 1] * inv[3 + c]) + (double)Tn[4 * r + 2] * inv[6 + c];
+      d[4 * r + 3] = (double)Tn[4 * r + 3] - ((d[4 * r] * (double)To[3] + d[4 * r + 1] * (double)To[7]) + d[4 * r + 2] * (double)To[11]);
+    }
+  }
+  uint64_t next = 0;        // the first keyframe after frame fi
+  int64_t cur = first;      // the usable keyframe whose correction frame fi takes
+  for (uint64_t fi = 0; fi < n; fi++) {
+    bool is_key = false;
+    while (next < K && keyframes[next] <= fi) {
+      if (usable[next]) cur = (int64_t)next;
+      is_key = keyframes[next] == fi && usable[next];
+      next++;
+    }
+    const float* Tf = poses + 16 * fi;
+    float* o = poses_out + 16 * fi;
+    if (is_key) { std::memcpy(o, new_key_poses + 16 * cur, 16 * sizeof(float)); continue; }
+    if (cur < 0 || !finite12(Tf)) { if (o != Tf) std::memcpy(o, Tf, 16 * sizeof(float)); continue; }
+    const double* d = &D[12 * cur];
+    float out[16];
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) {
+        double s = (d[4 * r] * (double)Tf[c] + d[4 * r + 1] * (double)Tf[4 + c]) + d[4 * r + 2] * (double)Tf[8 + c];
+        if (c == 3) s += d[4 * r + 3];
+        out[4 * r + c] = (float)s;
+      }
+    out[12] = out[13] = out[14] = 0.0f;
+    out[15] = 1.0f;
+    std::memcpy(o, out, sizeof(out));
+  }
+  return SF_OK;
+}

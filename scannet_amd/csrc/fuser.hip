@@ -398,6 +398,7 @@ SF_API void sf_fuser_destroy(sf_fuser* f) {
   if (f->ev_front_switch) (void)hipEventDestroy(f->ev_front_switch);
   for (hipEvent_t e : f->ev_raycast) if (e) (void)hipEventDestroy(e);
   sf_track_release(f);
+  sf_align_release(f);
   for (int q = 0; q < sf_fuser::HOST_RING; q++) {
     (void)hipFree(f->staging_depth[q]); (void)hipFree(f->staging_rgb[q]);
     if (f->pinned_depth[q]) (void)hipHostFree(f->pinned_depth[q]);

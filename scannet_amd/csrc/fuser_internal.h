@@ -338,6 +338,7 @@ struct sf_fuser {
   double mc_timing[12] = {0};   // phases of the most recent sf_fuser_extract_mesh (mc.hip; sf_fuser_mc_timing)
   hipEvent_t ev_raycast[3] = {nullptr, nullptr, nullptr};   // raycast.hip: the two front streams' tails before a ray cast, the ray cast itself (made on first use)
   struct TrackWork* track = nullptr;   // track.hip: the tracker's pyramids, model maps and read-back buffers (made on first use)
+  struct AlignWork* align = nullptr;   // align.hip: the keyframes' maps, the pair table, partials and read-back buffers (made on first use, grown on demand)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
 };
@@ -345,6 +346,7 @@ struct sf_fuser {
 
 hipError_t sf_quiesce(sf_fuser* f);                 // drain both streams
 void sf_track_release(sf_fuser* f);                 // track.hip: frees f->track
+void sf_align_release(sf_fuser* f);                 // align.hip: frees f->align
 bool sf_single_stream_batch(const sf_fuser* f, int n, bool color, int sign);   // run_batch keeps this batch on f->stream alone
 hipStream_t sf_input_stream(const sf_fuser* f, int n, bool color, int sign);   // where the batch's frames must be staged
 int sf_compact_live(sf_fuser* f, int32_t* n_out, int include_ghosts = 1);   // live heap slots -> f->compact, synchronous

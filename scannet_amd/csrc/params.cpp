@@ -255,6 +255,44 @@ SF_API int sf_track_params_load_file(const char* path, sf_track_params* t) {
   return SF_OK;
 }
 
+SF_API void sf_align_params_default(sf_align_params* a) {
+  if (!a) return;
+  std::memset(a, 0, sizeof(*a));
+  a->level = 1;
+  a->max_iters = 8;
+  a->dist_thres = 0.15f;      // s_denseDistThresh (zParametersBundlingScanNet.txt:22)
+  a->normal_thres = 0.7f;     // the tracker's value, not the file's 0.95 (:23): normals of raw depth
+  a->early_out = 1e-5f;
+  a->min_pair_correspondences = 500;
+  a->fixed_frame = 0;
+  a->pair_max_dist = 1.0f;
+  a->pair_max_angle = 0.6f;
+  a->max_translation = 0.5f;
+  a->max_rotation = 0.5f;
+}
+
+// the dense-term keys of zParametersBundlingScanNet.txt:22-44
+SF_API int sf_align_params_load_file(const char* path, sf_align_params* a) {
+  if (!path || !a) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  std::map<std::string, std::vector<std::string>> kv;
+  const int rc = read_param_file(path, kv);
+  if (rc != SF_OK) return rc;
+  const struct { const char* key; float* f; int32_t* i; } keys[] = {
+      {"s_denseDistThresh", &a->dist_thres, nullptr}, {"s_denseNormalThresh", &a->normal_thres, nullptr},
+      {"s_denseDepthMin", &a->depth_min, nullptr}, {"s_denseDepthMax", &a->depth_max, nullptr},
+      {"s_downsampledWidth", nullptr, &a->down_width}, {"s_downsampledHeight", nullptr, &a->down_height},
+      {"s_numGlobalNonLinIterations", nullptr, &a->max_iters}};
+  for (const auto& k : keys) {
+    auto it = kv.find(k.key);
+    if (it == kv.end()) continue;
+    float v;
+    if (it->second.empty() || !parse_float(it->second[0], &v) || !std::isfinite(v)) return sf::fail(SF_ERR_FORMAT, "%s: bad value for %s", path, k.key);
+    if (k.f) *k.f = v;
+    else *k.i = (int32_t)std::strtol(it->second[0].c_str(), nullptr, 10);
+  }
+  return SF_OK;
+}
+
 SF_API void sf_reint_params_default(sf_reint_params* r) {
   if (!r) return;
   std::memset(r, 0, sizeof(*r));

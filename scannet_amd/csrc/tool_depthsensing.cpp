@@ -48,6 +48,11 @@ extern char** environ;
 // --track's frame loop: the same arrangement
 #pragma weak sf_fuser_track
 #pragma weak sf_fuser_integrate
+// --align's solver and the re-integration behind it
+#pragma weak sf_fuser_align
+#pragma weak sf_align_pairs
+#pragma weak sf_align_spread
+#pragma weak sf_fuse_update_trajectory
 
 namespace {
 
@@ -83,7 +88,9 @@ struct Args {
   const char* render_dir = nullptr;   // --render-depth=<dir>: ray-cast depth images of the fused volume (see render_depth below)
   int render_every = 1;
   bool track = false;                 // --track: camera poses from frame-to-model tracking (see track_scan below)
-  const char* write_sens = nullptr;   // --write-sens=<out.sens>: the input with the tracked trajectory
+  const char* write_sens = nullptr;   // --write-sens=<out.sens>: the input with the tracked (and, with --align, corrected) trajectory
+  int align = -1;                     // --align[=N]: keyframes every N-th tracked frame are aligned jointly (see align_scan below); 0: N from the parameter file
+  const char* align_params = nullptr; // --align-params=<file>: zParametersBundlingScanNet.txt
   const char* pos[8];
   int n_pos = 0;
 };
@@ -224,6 +231,81 @@ int render_depth(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_in
   return rc;
 }
 
+// ---- --align[=N] [--align-params=<file>] (after --track): every N-th tracked frame is a keyframe (N: s_submapSize of the file, zParametersBundlingScanNet.txt:31,
+// or 10); the keyframes are aligned jointly over the default pair list (sf_align_pairs, sf_fuser_align), the correction is carried to the frames between
+// them (sf_align_spread) and the volume is moved to the corrected trajectory (sf_fuse_update_trajectory).  traj: n x 16, in: what the volume holds, out: the same.
+int submap_size(const char* path) {
+  FILE* fp = std::fopen(path, "r");
+  if (!fp) return -1;
+  char line[1024];
+  int n = 0;
+  while (std::fgets(line, sizeof line, fp)) {
+    const char* q = line;
+    while (*q == ' ' || *q == '\t') q++;
+    if (std::strncmp(q, "s_submapSize", 12) != 0) continue;
+    q += 12;
+    while (*q == ' ' || *q == '\t') q++;
+    if (*q == '=') n = std::atoi(q + 1);
+  }
+  std::fclose(fp);
+  return n;
+}
+
+int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info& info, bool color, std::vector<float>& traj) {
+  if (!sf_fuser_align || !sf_align_pairs || !sf_align_spread || !sf_fuse_update_trajectory) return die_msg("--align: this libscanfuse has no alignment");
+  sf_align_params ap;
+  sf_align_params_default(&ap);
+  int every = a.align;
+  if (a.align_params) {
+    if (sf_align_params_load_file(a.align_params, &ap) != SF_OK) return die("alignment parameters");
+    if (every == 0) every = submap_size(a.align_params);
+  }
+  if (every == 0) every = 10;
+  if (every < 1) return die_msg("--align: a keyframe stride of %d", every);
+  const uint64_t n = info.num_frames;
+  std::vector<uint64_t> keys;
+  uint64_t tracked = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    bool fin = true;
+    for (int k = 0; k < 12; k++) fin = fin && std::isfinite(traj[16 * i + k]);
+    if (!fin) continue;
+    if (tracked % (uint64_t)every == 0) keys.push_back(i);
+    tracked++;
+  }
+  const uint64_t K = keys.size();
+  if (K < 2) { say("Aligned nothing: %llu keyframes\n", (unsigned long long)K); return 0; }
+  if (K > 256) return die_msg("--align=%d gives %llu keyframes, the solver takes 256: choose a larger stride", every, (unsigned long long)K);
+  const size_t px = (size_t)info.depth_width * info.depth_height;
+  std::vector<uint16_t> depth(K * px);
+  std::vector<float> kp(K * 16), knew(K * 16);
+  for (uint64_t k = 0; k < K; k++) {
+    if (sf_sens_decode_depth(sens, keys[k], depth.data() + k * px) != SF_OK) return die("depth frame");
+    std::memcpy(&kp[16 * k], &traj[16 * keys[k]], 16 * sizeof(float));
+  }
+  std::vector<int32_t> pairs(2 * 4096);
+  uint64_t P = 0;
+  if (sf_align_pairs(kp.data(), K, &ap, pairs.data(), 4096, &P) != SF_OK) return die("pairs");
+  if (P > 4096) return die_msg("--align: %llu pairs, the solver takes 4096: choose a larger stride", (unsigned long long)P);
+  sf_align_result res;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (sf_fuser_align(fuser, depth.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res) != SF_OK) return die("alignment");
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  say("Aligned %llu keyframes (every %d) over %llu pairs in %.1f ms: status %d, %d iterations, %d pairs and %lld correspondences in the last system, rms %.4f -> %.4f m, "
+      "%d unconnected, %d rejected\n", (unsigned long long)K, every, (unsigned long long)P, ms, res.status, res.iterations, res.pairs_used, (long long)res.correspondences,
+      res.rms_first, res.rms_last, res.frames_unconnected, res.frames_rejected);
+  if (res.status != 0) return 0;   // the poses came back as they went in
+  std::vector<float> target(n * 16);
+  if (sf_align_spread(traj.data(), n, keys.data(), K, knew.data(), target.data()) != SF_OK) return die("spread");
+  sf_reint_params rp;
+  sf_reint_params_default(&rp);
+  if (sf_reint_params_load_file(a.pos[1], &rp) != SF_OK) return die("re-integration parameters");
+  sf_reint_stats rs;
+  if (sf_fuse_update_trajectory(fuser, sens, traj.data(), target.data(), &rp, 0, color ? 1 : 0, 0, &rs) != SF_OK) return die("re-integration");
+  say("Re-integrated %llu frames in %llu steps, %.3f s\n", (unsigned long long)(rs.frames_moved + rs.frames_added + rs.frames_removed), (unsigned long long)rs.steps,
+      rs.seconds_total);
+  return 0;
+}
+
 // ---- --track [--write-sens=<out.sens>] (what the reference tool does with its second parameter file: DepthSensing.exe tracks the camera when the
 // trajectory is to be rewritten, zParametersScanNet.txt s_trackingEnabled / s_overwriteOrigSensTrajectory): frame 0 at its pose in the file (identity
 // when that pose is invalid), every later frame tracked against the volume fused so far (sf_fuser_track, starting from the last tracked pose) and
@@ -241,6 +323,7 @@ int track_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
   std::vector<uint16_t> depth((size_t)info.depth_width * info.depth_height);
   std::vector<uint8_t> rgb(color ? (size_t)info.color_width * info.color_height * 3 : 0);
   float last[16], pose[16];
+  std::vector<float> traj((size_t)info.num_frames * 16);
   uint64_t tracked = 0, lost = 0;
   double ms_track = 0.0;
   for (uint64_t i = 0; i < info.num_frames; i++) {
@@ -266,14 +349,17 @@ int track_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
       if (rc != SF_OK && rc != SF_ERR_SKIPPED) return die("integrate");
       std::memcpy(last, pose, sizeof(last));
     }
-    if (a.write_sens && sf_sens_set_pose(sens, i, pose) != SF_OK) return die("pose");
+    std::memcpy(&traj[16 * i], pose, sizeof(pose));
   }
   if (sf_fuser_sync(fuser) != SF_OK) return die("fuse");
   const uint64_t n = info.num_frames > 1 ? info.num_frames - 1 : 0;
   say("Tracked %llu frames, lost %llu, %.3f ms per frame\n", (unsigned long long)tracked, (unsigned long long)lost, n ? ms_track / (double)n : 0.0);
+  if (a.align >= 0 && align_scan(a, fuser, sens, info, color, traj) != 0) return 1;
   if (a.write_sens) {
+    for (uint64_t i = 0; i < info.num_frames; i++)
+      if (sf_sens_set_pose(sens, i, &traj[16 * i]) != SF_OK) return die("pose");
     if (sf_sens_save(sens, a.write_sens) != SF_OK) return die("write-sens");
-    say("Tracked trajectory written to %s\n", a.write_sens);
+    say("%s trajectory written to %s\n", a.align >= 0 ? "Corrected" : "Tracked", a.write_sens);
   }
   return 0;
 }
@@ -551,15 +637,20 @@ int main(int argc, const char** argv_in) {
     else if (!std::strncmp(s, "--render-every=", 15)) a.render_every = std::atoi(s + 15);
     else if (!std::strcmp(s, "--track")) a.track = true;
     else if (!std::strncmp(s, "--write-sens=", 13) && s[13]) a.write_sens = s + 13;
+    else if (!std::strcmp(s, "--align")) a.align = 0;
+    else if (!std::strncmp(s, "--align=", 8)) { a.align = std::atoi(s + 8); if (a.align < 1) bad = true; }
+    else if (!std::strncmp(s, "--align-params=", 15) && s[15]) a.align_params = s + 15;
     else if (i > 0 && !std::strncmp(s, "--", 2)) bad = true;
     else if (a.n_pos < 8) a.pos[a.n_pos++] = s;
   }
   if (a.n_pos < 4 || bad || a.ranks < 1 || a.ranks > 64 || (a.rank >= 0 && (a.rank >= a.ranks || a.ipc.empty()))) {
-    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
+    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--align[=N]] [--align-params=<zParametersBundling.txt>] [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
     return 255;
   }
   if (a.render_dir && a.ranks > 1)
     return die_msg("--render-depth ray-casts one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to render", a.ranks);
+  if ((a.align >= 0 || a.align_params) && !a.track)
+    return die_msg("--align aligns the keyframes of the tracked trajectory: it needs --track");
   if (a.track && a.ranks > 1)
     return die_msg("--track tracks the camera against one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to track", a.ranks);
   if (a.write_sens && !a.track) return die_msg("--write-sens writes the tracked trajectory: it needs --track");

@@ -15,22 +15,12 @@
 #include "common.h"
 #include "fuser_internal.h"
 #include "scanfuse_internal.h"
+#include "track_math.h"
 
 namespace {
 
-constexpr int TK_MAX_LEVELS = 4;
-constexpr int TK_NSYS = 29;         // 21 of J^T J, 6 of J^T r, sum r^2, count
-constexpr int TK_PSTRIDE = 32;      // floats per workgroup partial
-constexpr float TK_DOWN_THRES = 0.03f;   // 2x2 reduction: depths within this many metres of the reference pixel's are averaged
-constexpr double TK_PIVOT_REL = 1e-5;     // a Cholesky pivot at or below this share of its diagonal entry counts as non-positive
+using namespace tk;   // track_math.h: the rules shared with align.hip
 
-struct Cam {
-  int W, H;
-  float fx, fy, mx, my;
-};
-struct Rows {
-  float T[12];   // rows 0..2 of a rigid transform
-};
 struct AssocArgs {
   Cam c;
   int W0, shift;   // the model image (level 0) and the level's subsampling of it
@@ -38,78 +28,31 @@ struct AssocArgs {
   float dist_thres, normal_thres;
 };
 
-__device__ inline float3 xf(const Rows& R, float3 v) {
-  return make_float3(fmaf(R.T[2], v.z, fmaf(R.T[1], v.y, fmaf(R.T[0], v.x, R.T[3]))), fmaf(R.T[6], v.z, fmaf(R.T[5], v.y, fmaf(R.T[4], v.x, R.T[7]))),
-                     fmaf(R.T[10], v.z, fmaf(R.T[9], v.y, fmaf(R.T[8], v.x, R.T[11]))));
-}
-__device__ inline float3 rot(const Rows& R, float3 n) {
-  return make_float3(fmaf(R.T[2], n.z, fmaf(R.T[1], n.y, R.T[0] * n.x)), fmaf(R.T[6], n.z, fmaf(R.T[5], n.y, R.T[4] * n.x)),
-                     fmaf(R.T[10], n.z, fmaf(R.T[9], n.y, R.T[8] * n.x)));
-}
-__device__ inline float dot3(float3 a, float3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline float3 cross3(float3 a, float3 b) { return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ inline float3 unproject(const Cam& c, int x, int y, float d) {
-  return make_float3(((float)x - c.mx) / c.fx * d, ((float)y - c.my) / c.fy * d, d);
-}
-
 // u16 frame at the input size -> metres at the integration size: k_prepass's rule (nearest resample, then the depth range)
 __global__ void __launch_bounds__(256) k_track_depth0(const uint16_t* __restrict__ in, const ParamsK P, float* __restrict__ d0) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P.W * P.H) return;
-  uint16_t u;
-  if (P.inW > 0) {
-    const unsigned xi = (unsigned)((float)(i % P.W) * P.rsx + 0.5f), yi = (unsigned)((float)(i / P.W) * P.rsy + 0.5f);
-    u = (xi < (unsigned)P.inW && yi < (unsigned)P.inH) ? in[(size_t)yi * P.inW + xi] : (uint16_t)0;
-  } else {
-    u = in[i];
-  }
-  float v = (float)u / P.depth_shift;
-  if (u == 0 || v < P.dmin || v > P.dmax) v = -INFINITY;
-  d0[i] = v;
+  d0[i] = depth0_at(in, P, i);
 }
 
-// one 2x2 reduction: the mean of the valid depths of the 2x2 block within TK_DOWN_THRES of its top-left (reference) pixel, in the order
-// (0,0), (1,0), (0,1), (1,1); invalid where the reference pixel is
+// one 2x2 reduction (track_math.h down4)
 __global__ void __launch_bounds__(256) k_track_down(const float* __restrict__ src, int Ws, float* __restrict__ dst, int Wd, int Hd) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= Wd * Hd) return;
   const int x = i % Wd, y = i / Wd;
   const float* s = src + (size_t)(2 * y) * Ws + 2 * x;
-  const float r = s[0];
-  float out = -INFINITY;
-  if (r > 0.0f) {
-    const float v[4] = {s[0], s[1], s[Ws], s[Ws + 1]};
-    float sum = 0.0f, cnt = 0.0f;
-    for (int k = 0; k < 4; k++)
-      if (v[k] > 0.0f && fabsf(v[k] - r) <= TK_DOWN_THRES) {
-        sum = sum + v[k];
-        cnt = cnt + 1.0f;
-      }
-    out = sum / cnt;
-  }
-  dst[i] = out;
+  dst[i] = down4(s[0], s[1], s[Ws], s[Ws + 1]);
 }
 
-// camera-space vertex and normal of every pixel of a level; x = -inf where invalid.  Normal: cross(v(x, y+1) - v, v(x+1, y) - v) normalised
+// camera-space vertex and normal of every pixel of a level; x = -inf where invalid (track_math.h vertex_normal)
 __global__ void __launch_bounds__(256) k_track_vn(const float* __restrict__ d, const Cam c, float4* __restrict__ vmap, float4* __restrict__ nmap) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= c.W * c.H) return;
   const int x = i % c.W, y = i / c.W;
   const float dz = d[i];
-  float4 vo = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f), no = vo;
-  if (dz > 0.0f) {
-    const float3 v = unproject(c, x, y, dz);
-    vo = make_float4(v.x, v.y, v.z, 0.0f);
-    if (x + 1 < c.W && y + 1 < c.H) {
-      const float dr = d[i + 1], dd = d[i + c.W];
-      if (dr > 0.0f && dd > 0.0f) {
-        const float3 vr = unproject(c, x + 1, y, dr), vd = unproject(c, x, y + 1, dd);
-        const float3 n = cross3(make_float3(vd.x - v.x, vd.y - v.y, vd.z - v.z), make_float3(vr.x - v.x, vr.y - v.y, vr.z - v.z));
-        const float len = sqrtf(dot3(n, n));
-        if (len > 0.0f) no = make_float4(n.x / len, n.y / len, n.z / len, 0.0f);
-      }
-    }
-  }
+  const bool nb = dz > 0.0f && x + 1 < c.W && y + 1 < c.H;
+  float4 vo, no;
+  vertex_normal(c, x, y, dz, nb, nb ? d[i + 1] : 0.0f, nb ? d[i + c.W] : 0.0f, &vo, &no);
   vmap[i] = vo;
   nmap[i] = no;
 }
@@ -158,18 +101,7 @@ __global__ void __launch_bounds__(256) k_track_assoc(const float4* __restrict__ 
             const float3 nm = make_float3(m4.x, m4.y, m4.z);
             const float3 d = make_float3(p.x - q4.x, p.y - q4.y, p.z - q4.z);
             if (sqrtf(dot3(d, d)) <= A.dist_thres && dot3(nm, n) >= A.normal_thres) {
-              const float r = dot3(nm, d);
-              const float3 c = cross3(p, nm);
-              const float J[6] = {c.x, c.y, c.z, nm.x, nm.y, nm.z};
-              int k = 0;
-#pragma unroll
-              for (int a = 0; a < 6; a++)
-#pragma unroll
-                for (int b = a; b < 6; b++) acc[k++] = J[a] * J[b];
-#pragma unroll
-              for (int a = 0; a < 6; a++) acc[21 + a] = J[a] * r;
-              acc[27] = r * r;
-              acc[28] = 1.0f;
+              row29(p, nm, d, acc);
               ok = true;
             }
           }
@@ -178,20 +110,7 @@ __global__ void __launch_bounds__(256) k_track_assoc(const float4* __restrict__ 
     }
     if (mask) mask[i] = ok ? 1 : 0;
   }
-  // xor butterfly within the wave: every lane ends with the wave's sum (a + b and b + a are the same float)
-#pragma unroll
-  for (int k = 0; k < TK_NSYS; k++)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc[k] = acc[k] + __shfl_xor(acc[k], off);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < TK_NSYS; k++) red[wave][k] = acc[k];
-  __syncthreads();
-  if (threadIdx.x < TK_NSYS) {
-    const int k = threadIdx.x;
-    partials[(size_t)blockIdx.x * TK_PSTRIDE + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-  }
+  reduce256(acc, red, partials + (size_t)blockIdx.x * TK_PSTRIDE);
 }
 
 // the workgroups' partials summed in index order, in double: lane k sums value k
@@ -305,12 +224,6 @@ int ensure_work(sf_fuser* f, const Cam* cams, int levels) {
   return SF_OK;
 }
 
-bool finite12(const float* T) {
-  for (int i = 0; i < 12; i++)
-    if (!std::isfinite(T[i])) return false;
-  return true;
-}
-
 Rows rows_of(const float* T) {
   Rows r;
   std::memcpy(r.T, T, sizeof(r.T));
@@ -339,22 +252,6 @@ int prepare(sf_fuser* f, const void* d_depth, const float* Tref, const sf_track_
   hipLaunchKernelGGL(k_track_model, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, w->model_depth, w->model_normal, cams[0], rows_of(Tref), w->mq, w->mn);
   SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
-}
-
-// T_ref^-1 (cofactors over the determinant, as the oracle's frame set-up) composed with T, in double: rounded to float once
-void compose_ref(const double* Tref, const double* T, float* M) {
-  const double a00 = Tref[0], a01 = Tref[1], a02 = Tref[2], a10 = Tref[4], a11 = Tref[5], a12 = Tref[6], a20 = Tref[8], a21 = Tref[9], a22 = Tref[10];
-  const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-  const double det = a00 * c00 + a01 * c01 + a02 * c02;
-  double inv[9];
-  inv[0] = c00 / det; inv[1] = (a02 * a21 - a01 * a22) / det; inv[2] = (a01 * a12 - a02 * a11) / det;
-  inv[3] = c01 / det; inv[4] = (a00 * a22 - a02 * a20) / det; inv[5] = (a02 * a10 - a00 * a12) / det;
-  inv[6] = c02 / det; inv[7] = (a01 * a20 - a00 * a21) / det; inv[8] = (a00 * a11 - a01 * a10) / det;
-  const double dt[3] = {T[3] - Tref[3], T[7] - Tref[7], T[11] - Tref[11]};
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) M[4 * r + c] = (float)((inv[3 * r] * T[c] + inv[3 * r + 1] * T[4 + c]) + inv[3 * r + 2] * T[8 + c]);
-    M[4 * r + 3] = (float)((inv[3 * r] * dt[0] + inv[3 * r + 1] * dt[1]) + inv[3 * r + 2] * dt[2]);
-  }
 }
 
 // one level's system at the estimate T (double, rows 0..2 used), summed into w->h_sys; the mask optionally into w->d_mask
@@ -409,30 +306,6 @@ bool solve6(const double* sys, double* xi) {
   return true;
 }
 
-// T <- [Rodrigues(omega) | t] T, xi = (omega, t)
-void apply_update(const double* xi, double* T) {
-  const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
-  const double th = std::sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-  double a = 1.0, b = 0.5;
-  if (th >= 1e-8) {
-    a = std::sin(th) / th;
-    b = (1.0 - std::cos(th)) / (th * th);
-  }
-  const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-  double R[3][3];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
-      R[i][j] = ((i == j ? 1.0 : 0.0) + a * K[i][j]) + b * k2;
-    }
-  double out[12];
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 4; j++) out[4 * i + j] = (R[i][0] * T[j] + R[i][1] * T[4 + j]) + R[i][2] * T[8 + j];
-    out[4 * i + 3] += xi[3 + i];
-  }
-  std::memcpy(T, out, sizeof(out));
-}
-
 void lost_pose(float* pose_out) {
   for (int i = 0; i < 16; i++) pose_out[i] = -INFINITY;
 }
@@ -477,11 +350,8 @@ int track_device(sf_fuser* f, const void* d_depth, const float* guess, const flo
     }
   }
   if (r.lost_reason == 0) {
-    const double dt[3] = {T[3] - G[3], T[7] - G[7], T[11] - G[11]};
-    const double dist = std::sqrt((dt[0] * dt[0] + dt[1] * dt[1]) + dt[2] * dt[2]);
-    double tr = 0.0;   // trace(R_guess^T R)
-    for (int i = 0; i < 3; i++) tr += (G[i] * T[i] + G[4 + i] * T[4 + i]) + G[8 + i] * T[8 + i];
-    const double ang = std::acos(std::fmin(1.0, std::fmax(-1.0, (tr - 1.0) * 0.5)));
+    double dist, ang;
+    motion(G, T, &dist, &ang);
     bool fin = true;
     for (int i = 0; i < 12; i++) fin = fin && std::isfinite(T[i]);
     if (!fin || !(dist <= (double)t->max_translation) || !(ang <= (double)t->max_rotation)) r.lost_reason = 4;

@@ -145,6 +145,102 @@ def load_reint_params(path, base=None):
     return r
 
 
+class SfAlignParams(C.Structure):
+    _fields_ = [("level", C.c_int32), ("down_width", C.c_int32), ("down_height", C.c_int32), ("max_iters", C.c_int32),
+                ("dist_thres", C.c_float), ("normal_thres", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("early_out", C.c_float),
+                ("min_pair_correspondences", C.c_int32), ("fixed_frame", C.c_int32),
+                ("pair_max_dist", C.c_float), ("pair_max_angle", C.c_float), ("max_translation", C.c_float), ("max_rotation", C.c_float),
+                ("reserved", C.c_int32 * 9)]
+
+
+class SfAlignResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("pairs_used", C.c_int32), ("frames_unconnected", C.c_int32),
+                ("frames_rejected", C.c_int32), ("reserved0", C.c_int32), ("correspondences", C.c_int64),
+                ("rms_first", C.c_float), ("rms_last", C.c_float), ("reserved", C.c_int32 * 6)]
+
+    def as_dict(self):
+        return dict(status=int(self.status), iterations=int(self.iterations), pairs_used=int(self.pairs_used),
+                    frames_unconnected=int(self.frames_unconnected), frames_rejected=int(self.frames_rejected),
+                    correspondences=int(self.correspondences), rms_first=float(self.rms_first), rms_last=float(self.rms_last))
+
+
+def default_align_params(**over):
+    """sf_align_params_default (DESIGN.md "Global alignment"); keyword overrides."""
+    a = SfAlignParams()
+    L = _abi.lib()
+    L.sf_align_params_default.argtypes = [C.POINTER(SfAlignParams)]
+    L.sf_align_params_default.restype = None
+    L.sf_align_params_default(C.byref(a))
+    for k, v in over.items():
+        if not hasattr(a, k) or k == "reserved":
+            raise AttributeError("sf_align_params has no field %r" % k)
+        setattr(a, k, v)
+    return a
+
+
+def load_align_params(path, base=None):
+    """The dense-term keys (s_denseDistThresh, s_denseNormalThresh, s_denseDepthMin / Max, s_downsampledWidth / Height,
+    s_numGlobalNonLinIterations) of an mLib ParameterFile such as zParametersBundlingScanNet.txt; absent keys leave the base as it is."""
+    a = base if base is not None else default_align_params()
+    L = _abi.lib()
+    L.sf_align_params_load_file.argtypes = [C.c_char_p, C.POINTER(SfAlignParams)]
+    check(L.sf_align_params_load_file(str(path).encode(), C.byref(a)))
+    return a
+
+
+def align_pairs(poses, params=None, capacity=4096):
+    """sf_align_pairs (host only): the default pair list of K keyframe poses ([K,16] / [K,4,4] camToWorld) -> (int32 [min(count, capacity), 2] of
+    (source, target), the count the rule produces)."""
+    a = params if params is not None else default_align_params()
+    poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+    out = np.zeros((max(int(capacity), 1), 2), np.int32)
+    n = C.c_uint64(0)
+    L = _abi.lib()
+    L.sf_align_pairs.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    check(L.sf_align_pairs(_ptr(poses), len(poses), C.byref(a), _ptr(out), int(capacity), C.byref(n)))
+    return out[:min(n.value, int(capacity))].copy(), int(n.value)
+
+
+def align_spread(poses, keyframes, new_key_poses):
+    """sf_align_spread (host only): the keyframes' correction carried to every frame of the trajectory -> float32 [n,16]."""
+    poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+    keys = np.ascontiguousarray(keyframes, dtype=np.uint64)
+    new = np.ascontiguousarray(new_key_poses, dtype=np.float32).reshape(-1, 16)
+    if len(keys) != len(new):
+        raise ValueError("one new pose per keyframe")
+    out = np.empty_like(poses)
+    L = _abi.lib()
+    L.sf_align_spread.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    check(L.sf_align_spread(_ptr(poses), len(poses), _ptr(keys), len(keys), _ptr(new), _ptr(out)))
+    return out
+
+
+def align_keyframes(poses, every):
+    """Every `every`-th of the frames with a finite pose (rows 0..2), in frame order, starting with the first -> uint64 frame indices."""
+    poses = np.asarray(poses, dtype=np.float32).reshape(-1, 16)
+    good = np.flatnonzero(np.isfinite(poses[:, :12]).all(axis=1))
+    return good[::max(1, int(every))].astype(np.uint64)
+
+
+def align_and_reintegrate(fuser, sensor_data, integrated, every=10, params=None, reint_params=None, colour=False):
+    """The correction loop: keyframes are every `every`-th frame with a finite integrated pose; their depth is decoded, the default pairs built, the
+    keyframes aligned (Fuser.align), the correction spread over the trajectory, and the volume moved there (Fuser.update_trajectory, which updates a
+    float32 C-contiguous `integrated` in place).  -> (target poses float32 [n,16], SfAlignResult, re-integration statistics)."""
+    a = params if params is not None else default_align_params()
+    cur = np.ascontiguousarray(integrated, dtype=np.float32).reshape(-1, 16)
+    keys = align_keyframes(cur, every)
+    if len(keys) < 2:
+        raise ValueError("alignment needs two keyframes, the trajectory has %d" % len(keys))
+    depth = np.stack([np.ascontiguousarray(sensor_data.frames[int(k)].decompress_depth(), dtype=np.uint16).reshape(-1) for k in keys])
+    pairs, count = align_pairs(cur[keys.astype(np.int64)], a)
+    if count > len(pairs):
+        raise ValueError("the pair rule gives %d pairs, the solver takes %d" % (count, len(pairs)))
+    new, res = fuser.align(depth, cur[keys.astype(np.int64)], pairs, a)
+    target = align_spread(cur, keys, new)
+    _, stats = fuser.update_trajectory(sensor_data, integrated, target, params=reint_params, colour=colour)
+    return target, res, stats
+
+
 def plan_reintegration(integrated, target, params=None, capacity=None):
     """sf_reint_plan: one step of the trajectory manager (host only).  integrated / target: [n,16] or [n,4,4] camToWorld, what the volume holds and
     what it should hold (all -inf: not in the volume / lost) -> the frames to re-integrate now (uint64 array, largest pose change first)."""
@@ -509,6 +605,50 @@ class Fuser:
         L = _abi.lib()
         L.sf_fuser_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfRaycastParams), C.c_void_p, C.c_void_p, C.c_void_p]
         check(L.sf_fuser_raycast_device(self._h, _ptr(poses), len(poses), C.byref(r), _ptr(d_depth), _ptr(d_normals), _ptr(d_rgb)))
+
+    # -- global alignment (DESIGN.md "Global alignment") ----------------------------------------------
+    def _align_args(self, poses, pairs, params):
+        a = params if params is not None else default_align_params()
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        return a, poses, pairs
+
+    def align(self, depth, poses, pairs, params=None):
+        """sf_fuser_align: K u16 keyframes (host, [K, H*W] at the fuser's input size) with camToWorld poses [K,16] aligned jointly over the directed
+        pairs [P,2] (source, target).  -> (poses float32 [K,16], SfAlignResult)."""
+        a, poses, pairs = self._align_args(poses, pairs, params)
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if depth.size != len(poses) * self.params.depth_width * self.params.depth_height:
+            raise ValueError("depth holds %d pixels, %d frames of %dx%d expected" % (depth.size, len(poses), self.params.depth_width, self.params.depth_height))
+        out = np.empty_like(poses)
+        res = SfAlignResult()
+        L = _abi.lib()
+        L.sf_fuser_align.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams), C.c_void_p,
+                                     C.POINTER(SfAlignResult)]
+        check(L.sf_fuser_align(self._h, _ptr(depth), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a), _ptr(out), C.byref(res)))
+        return out, res
+
+    def align_device(self, d_depth, frame_stride_bytes, poses, pairs, params=None):
+        """align() for keyframes already in HBM (torch tensor or raw pointer), `frame_stride_bytes` apart, read on self.stream."""
+        a, poses, pairs = self._align_args(poses, pairs, params)
+        out = np.empty_like(poses)
+        res = SfAlignResult()
+        L = _abi.lib()
+        L.sf_fuser_align_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams),
+                                            C.c_void_p, C.POINTER(SfAlignResult)]
+        check(L.sf_fuser_align_device(self._h, _ptr(d_depth), int(frame_stride_bytes), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a),
+                                      _ptr(out), C.byref(res)))
+        return out, res
+
+    def align_system(self, depth, poses, pairs, params=None):
+        """Test hook (scanfuse_internal.h sf_fuser_align_system): the P per-pair 29-value systems (float64 [P,29]) at the given poses."""
+        a, poses, pairs = self._align_args(poses, pairs, params)
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        sys = np.zeros((len(pairs), 29), np.float64)
+        L = _abi.lib()
+        L.sf_fuser_align_system.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams), C.c_void_p]
+        check(L.sf_fuser_align_system(self._h, _ptr(depth), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a), _ptr(sys)))
+        return sys
 
     # -- camera tracking (DESIGN.md "Camera tracking") --------------------------------------------------
     def track(self, depth, guess, ref=None, params=None):
