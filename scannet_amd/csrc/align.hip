@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 #include "scanfuse_internal.h"
 #include "track_math.h"
 
@@ -82,24 +83,15 @@ __global__ void __launch_bounds__(256) k_align_assoc(const float4* __restrict__ 
   for (int k = 0; k < TK_NSYS; k++) acc[k] = 0.0f;
   if (e.active && i < npx) {
     const size_t so = (size_t)e.i * npx, to = (size_t)e.j * npx;
-    const float4 v4 = vmap[so + i], n4 = nmap[so + i];
-    if (v4.z > 0.0f && n4.x > -INFINITY) {
-      const float3 v = make_float3(v4.x, v4.y, v4.z);
-      const float3 p = xf(e.Ti, v), n = rot(e.Ti, make_float3(n4.x, n4.y, n4.z));
-      const float3 pc = xf(e.M, v);
-      if (pc.z > 0.0f) {
-        const float ux = floorf(fmaf(pc.x / pc.z, c.fx, c.mx) + 0.5f), uy = floorf(fmaf(pc.y / pc.z, c.fy, c.my) + 0.5f);
-        if (ux >= 0.0f && ux < (float)c.W && uy >= 0.0f && uy < (float)c.H) {
-          const size_t t = to + (size_t)((int)uy * c.W + (int)ux);
-          const float4 w4 = vmap[t], m4 = nmap[t];
-          if (w4.z > 0.0f && m4.x > -INFINITY) {
-            const float3 q = xf(e.Tj, make_float3(w4.x, w4.y, w4.z)), nm = rot(e.Tj, make_float3(m4.x, m4.y, m4.z));
-            const float3 d = make_float3(p.x - q.x, p.y - q.y, p.z - q.z);
-            if (sqrtf(dot3(d, d)) <= dist_thres && dot3(nm, n) >= normal_thres) row29(p, nm, d, acc);
-          }
-        }
-      }
-    }
+    // the target is frame j's maps at the same level, moved to the world by T_j
+    correspond(c, e.Ti, e.M, vmap[so + i], nmap[so + i], dist_thres, normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
+      const size_t t = to + (size_t)(uy * c.W + ux);
+      const float4 w4 = vmap[t], m4 = nmap[t];
+      if (!(w4.z > 0.0f && m4.x > -INFINITY)) return false;
+      *q = xf(e.Tj, make_float3(w4.x, w4.y, w4.z));
+      *nm = rot(e.Tj, make_float3(m4.x, m4.y, m4.z));
+      return true;
+    }, acc);
   }
   reduce256(acc, red, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TK_PSTRIDE);
 }
@@ -107,36 +99,24 @@ __global__ void __launch_bounds__(256) k_align_assoc(const float4* __restrict__ 
 // one wave per pair: lane k sums value k of the pair's partials in index order, in double; out[P][29]
 __global__ void __launch_bounds__(64) k_align_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
   const int k = threadIdx.x;
-  if (k >= TK_NSYS) return;
-  const float* p = partials + (size_t)blockIdx.x * nb * TK_PSTRIDE;
-  double s = 0.0;
-#pragma unroll 8
-  for (int b = 0; b < nb; b++) s += (double)p[(size_t)b * TK_PSTRIDE + k];
-  out[(size_t)blockIdx.x * TK_NSYS + k] = s;
+  if (k < TK_NSYS) out[(size_t)blockIdx.x * TK_NSYS + k] = sum_partials(partials + (size_t)blockIdx.x * nb * TK_PSTRIDE, nb, k);
 }
 
 }  // namespace
 
-struct AlignWork {
-  size_t in_bytes = 0, map_px = 0, part_floats = 0;
-  int pairs = 0;
-  uint8_t* d_in = nullptr;        // host frames' device copy
-  float4* vmap = nullptr;         // [K][npx]
-  float4* nmap = nullptr;
-  float* partials = nullptr;      // [P][nb][32]
-  PairEntry* d_table = nullptr;
-  PairEntry* h_table = nullptr;   // page-locked
-  double* d_sys = nullptr;        // [P][29]
-  double* h_sys = nullptr;        // page-locked read-back
+struct AlignWork {   // every buffer grows on demand and never shrinks
+  sf::DevBuf d_in;             // u8: host frames' device copy
+  sf::DevBuf vmap, nmap;       // float4 [K][npx]
+  sf::DevBuf partials;         // float [P][nb][32]
+  sf::DevBuf d_table;          // PairEntry [P]
+  sf::HostBuf h_table;         // page-locked
+  sf::DevBuf d_sys;            // double [P][29]
+  sf::HostBuf h_sys;           // page-locked read-back
 };
 
 void sf_align_release(sf_fuser* f) {
-  AlignWork* w = f ? f->align : nullptr;
-  if (!w) return;
-  (void)hipFree(w->d_in); (void)hipFree(w->vmap); (void)hipFree(w->nmap); (void)hipFree(w->partials); (void)hipFree(w->d_table); (void)hipFree(w->d_sys);
-  if (w->h_table) (void)hipHostFree(w->h_table);
-  if (w->h_sys) (void)hipHostFree(w->h_sys);
-  delete w;
+  if (!f) return;
+  delete f->align;
   f->align = nullptr;
 }
 
@@ -169,7 +149,7 @@ int check_align_args(uint64_t K, const float* poses, const int32_t* pairs, uint6
   return SF_OK;
 }
 
-// the level and its camera on this fuser (the tracker's level intrinsics)
+// the level on this fuser and its camera (the tracker's level intrinsics)
 int resolve_level(const sf_fuser* f, const sf_align_params* a, int* level, Cam* cam) {
   const int W = f->pk.W, H = f->pk.H;
   int l = a->level;
@@ -179,50 +159,30 @@ int resolve_level(const sf_fuser* f, const sf_align_params* a, int* level, Cam* 
       if ((W >> k) == a->down_width && (H >> k) == a->down_height) { l = k; break; }
     if (l < 0) return sf::fail(SF_ERR_INVALID_ARG, "alignment down_width x down_height %d x %d is no level 0..3 of %d x %d", a->down_width, a->down_height, W, H);
   }
-  Cam& c = *cam;
-  c.W = W >> l;
-  c.H = H >> l;
-  if (c.W < 8 || c.H < 8) return sf::fail(SF_ERR_INVALID_ARG, "alignment level %d would be %d x %d (at least 8 x 8)", l, c.W, c.H);
-  const float sx = (float)c.W / (float)W, sy = (float)c.H / (float)H;
-  c.fx = f->pk.fx * sx; c.mx = f->pk.mx * sx;
-  c.fy = f->pk.fy * sy; c.my = f->pk.my * sy;
+  if (!level_cam(f->pk, l, cam)) return sf::fail(SF_ERR_INVALID_ARG, "alignment level %d would be %d x %d (at least 8 x 8)", l, cam->W, cam->H);
   *level = l;
-  return SF_OK;
-}
-
-template <typename T>
-int grow(sf_fuser* f, T** ptr, size_t bytes, bool host) {
-  if (*ptr) { if (host) (void)hipHostFree(*ptr); else (void)hipFree(*ptr); *ptr = nullptr; }
-  const hipError_t e = host ? hipHostMalloc((void**)ptr, bytes, hipHostMallocDefault) : hipMalloc((void**)ptr, bytes);
-  if (e != hipSuccess) { *ptr = nullptr; sf_align_release(f); return sf::fail(SF_ERR_DEVICE, "alignment buffers: %s", hipGetErrorString(e)); }
   return SF_OK;
 }
 
 int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames) {
   if (!f->align) f->align = new AlignWork();
   AlignWork* w = f->align;
-  int rc;
-  const size_t in_bytes = host_frames ? (size_t)K * f->in_px * sizeof(uint16_t) : 0;
-  if (in_bytes > w->in_bytes) { w->in_bytes = 0; if ((rc = grow(f, &w->d_in, in_bytes, false)) != SF_OK) return rc; w->in_bytes = in_bytes; }
-  const size_t map_px = (size_t)K * npx;
-  if (map_px > w->map_px) {
-    w->map_px = 0;
-    if ((rc = grow(f, &w->vmap, map_px * sizeof(float4), false)) != SF_OK || (rc = grow(f, &w->nmap, map_px * sizeof(float4), false)) != SF_OK) return rc;
-    w->map_px = map_px;
-  }
-  const size_t part = (size_t)P * ((npx + 255) / 256) * TK_PSTRIDE;
-  if (part > w->part_floats) { w->part_floats = 0; if ((rc = grow(f, &w->partials, part * sizeof(float), false)) != SF_OK) return rc; w->part_floats = part; }
-  if ((int)P > w->pairs) {
-    w->pairs = 0;
-    if ((rc = grow(f, &w->d_table, P * sizeof(PairEntry), false)) != SF_OK || (rc = grow(f, &w->h_table, P * sizeof(PairEntry), true)) != SF_OK ||
-        (rc = grow(f, &w->d_sys, P * TK_NSYS * sizeof(double), false)) != SF_OK || (rc = grow(f, &w->h_sys, P * TK_NSYS * sizeof(double), true)) != SF_OK)
-      return rc;
-    w->pairs = (int)P;
-  }
+  const size_t map_bytes = (size_t)K * npx * sizeof(float4);
+  hipError_t e = w->d_in.reserve(host_frames ? (size_t)K * f->in_px * sizeof(uint16_t) : 0);
+  if (e == hipSuccess) e = w->vmap.reserve(map_bytes);
+  if (e == hipSuccess) e = w->nmap.reserve(map_bytes);
+  if (e == hipSuccess) e = w->partials.reserve((size_t)P * ((npx + 255) / 256) * TK_PSTRIDE * sizeof(float));
+  if (e == hipSuccess) e = w->d_table.reserve(P * sizeof(PairEntry));
+  if (e == hipSuccess) e = w->h_table.reserve(P * sizeof(PairEntry));
+  if (e == hipSuccess) e = w->d_sys.reserve(P * TK_NSYS * sizeof(double));
+  if (e == hipSuccess) e = w->h_sys.reserve(P * TK_NSYS * sizeof(double));
+  if (e != hipSuccess) { sf_align_release(f); return sf::fail(SF_ERR_DEVICE, "alignment buffers: %s", hipGetErrorString(e)); }
   return SF_OK;
 }
 
 struct Job {
+  const void* d_depth;   // the K frames in HBM, stride bytes apart
+  uint64_t stride;
   uint64_t K, P;
   const int32_t* pairs;
   int level;
@@ -231,21 +191,15 @@ struct Job {
 };
 
 // the maps of all K frames, queued on f->stream behind everything queued on the handle so far
-int prepare(sf_fuser* f, const void* d_depth, uint64_t stride, const Job& j) {
+int prepare(sf_fuser* f, const Job& j) {
   AlignWork* w = f->align;
-  for (hipEvent_t& e : f->ev_raycast)
-    if (!e) SF_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  const hipStream_t fronts[2] = {f->front, f->front_lo};
-  for (int i = 0; i < 2; i++)
-    if (fronts[i]) {
-      SF_HIP_CHECK(hipEventRecord(f->ev_raycast[i], fronts[i]));
-      SF_HIP_CHECK(hipStreamWaitEvent(f->stream, f->ev_raycast[i], 0));
-    }
+  // the maps read no volume, so nothing queued later on the front streams has to wait for them
+  if (const int oc = sf_order_behind_fronts(f)) return oc;
   const int npx = j.cam.W * j.cam.H;
   const dim3 grid((npx + 255) / 256, (unsigned)j.K);
 #define AL_PREP(L)                                                                                                                           \
-  hipLaunchKernelGGL(k_align_prep<L>, grid, dim3(256), 0, f->stream, (const uint8_t*)d_depth, (size_t)stride, f->pk, j.cam, j.dmin, j.dmax, \
-                     w->vmap, w->nmap)
+  hipLaunchKernelGGL(k_align_prep<L>, grid, dim3(256), 0, f->stream, (const uint8_t*)j.d_depth, (size_t)j.stride, f->pk, j.cam, j.dmin, j.dmax, \
+                     w->vmap.as<float4>(), w->nmap.as<float4>())
   switch (j.level) {
     case 0: AL_PREP(0); break;
     case 1: AL_PREP(1); break;
@@ -261,7 +215,7 @@ int prepare(sf_fuser* f, const void* d_depth, uint64_t stride, const Job& j) {
 int systems_at(sf_fuser* f, const Job& j, const double* T, const uint8_t* valid, const sf_align_params* a) {
   AlignWork* w = f->align;
   for (uint64_t p = 0; p < j.P; p++) {
-    PairEntry& e = w->h_table[p];
+    PairEntry& e = w->h_table.as<PairEntry>()[p];
     std::memset(&e, 0, sizeof(e));
     e.i = j.pairs[2 * p];
     e.j = j.pairs[2 * p + 1];
@@ -271,13 +225,14 @@ int systems_at(sf_fuser* f, const Job& j, const double* T, const uint8_t* valid,
     for (int k = 0; k < 12; k++) { e.Ti.T[k] = (float)Ti[k]; e.Tj.T[k] = (float)Tj[k]; }
     compose_ref(Tj, Ti, e.M.T);
   }
-  SF_HIP_CHECK(hipMemcpyAsync(w->d_table, w->h_table, j.P * sizeof(PairEntry), hipMemcpyHostToDevice, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(w->d_table.p, w->h_table.p, j.P * sizeof(PairEntry), hipMemcpyHostToDevice, f->stream));
   const int npx = j.cam.W * j.cam.H, nb = (npx + 255) / 256;
-  hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)j.P), dim3(256), 0, f->stream, w->vmap, w->nmap, w->d_table, j.cam, a->dist_thres, a->normal_thres, w->partials);
+  hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)j.P), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
+                     w->d_table.as<const PairEntry>(), j.cam, a->dist_thres, a->normal_thres, w->partials.as<float>());
   SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_align_final, dim3((unsigned)j.P), dim3(64), 0, f->stream, w->partials, nb, w->d_sys);
+  hipLaunchKernelGGL(k_align_final, dim3((unsigned)j.P), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
   SF_HIP_CHECK(hipGetLastError());
-  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys, w->d_sys, j.P * TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, j.P * TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   SF_HIP_CHECK(hipStreamSynchronize(f->stream));
   return SF_OK;
 }
@@ -287,37 +242,9 @@ int find_root(std::vector<int>& parent, int k) {
   return k;
 }
 
-// A x = -b for the symmetric N x N system A (row-major, full) by Cholesky in double, sums in index order; false at a pivot <= TK_PIVOT_REL x its diagonal entry
-bool solve_dense(const std::vector<double>& A, const std::vector<double>& b, int N, std::vector<double>& x) {
-  std::vector<double> L((size_t)N * N, 0.0), y(N);
-  for (int j = 0; j < N; j++) {
-    double s = A[(size_t)j * N + j];
-    for (int m = 0; m < j; m++) s -= L[(size_t)j * N + m] * L[(size_t)j * N + m];
-    if (!(s > TK_PIVOT_REL * A[(size_t)j * N + j])) return false;
-    L[(size_t)j * N + j] = std::sqrt(s);
-    for (int i = j + 1; i < N; i++) {
-      double e = A[(size_t)i * N + j];
-      for (int m = 0; m < j; m++) e -= L[(size_t)i * N + m] * L[(size_t)j * N + m];
-      L[(size_t)i * N + j] = e / L[(size_t)j * N + j];
-    }
-  }
-  for (int i = 0; i < N; i++) {
-    double e = -b[i];
-    for (int m = 0; m < i; m++) e -= L[(size_t)i * N + m] * y[m];
-    y[i] = e / L[(size_t)i * N + i];
-  }
-  x.assign(N, 0.0);
-  for (int i = N - 1; i >= 0; i--) {
-    double e = y[i];
-    for (int m = i + 1; m < N; m++) e -= L[(size_t)m * N + i] * x[m];
-    x[i] = e / L[(size_t)i * N + i];
-  }
-  return true;
-}
-
-int align_device(sf_fuser* f, const void* d_depth, uint64_t stride, uint64_t K, const float* poses_in, const Job& j, const sf_align_params* a, float* poses_out,
-                 sf_align_result* res) {
+int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_params* a, float* poses_out, sf_align_result* res) {
   int rc;
+  const uint64_t K = j.K;
   sf_align_result r;
   std::memset(&r, 0, sizeof(r));
   std::memcpy(poses_out, poses_in, K * 16 * sizeof(float));
@@ -328,8 +255,8 @@ int align_device(sf_fuser* f, const void* d_depth, uint64_t stride, uint64_t K, 
     for (int i = 0; i < 12; i++) T0[12 * k + i] = valid[k] ? (double)poses_in[16 * k + i] : 0.0;
   }
   T = T0;
-  if ((rc = prepare(f, d_depth, stride, j)) != SF_OK) return rc;
-  const double* sys = f->align->h_sys;
+  if ((rc = prepare(f, j)) != SF_OK) return rc;
+  const double* sys = f->align->h_sys.as<const double>();
   const int fixed = a->fixed_frame;
   std::vector<uint8_t> kept(j.P), conn(K, 0);
   std::vector<int> parent(K), slot(K);
@@ -386,7 +313,8 @@ int align_device(sf_fuser* f, const void* d_depth, uint64_t stride, uint64_t K, 
     r.correspondences = (int64_t)corr;
     r.rms_last = corr > 0.0 ? (float)std::sqrt(r2 / corr) : 0.0f;
     if (it == 0) r.rms_first = r.rms_last;
-    if (!solve_dense(A, b, N, xi)) { r.status = 1; break; }
+    xi.resize(N);
+    if (!solve_spd(A.data(), b.data(), N, xi.data())) { r.status = 1; break; }
     double mx = 0.0;
     for (uint64_t k = 0; k < K; k++)
       if (slot[k] >= 0) apply_update(&xi[6 * slot[k]], &T[12 * k]);
@@ -399,27 +327,37 @@ int align_device(sf_fuser* f, const void* d_depth, uint64_t stride, uint64_t K, 
     if (!valid[k] || (int)k == fixed) continue;
     if (!conn[k]) { r.frames_unconnected++; continue; }
     if (r.status != 0) continue;
-    double dist, ang;
-    motion(&T0[12 * k], &T[12 * k], &dist, &ang);
-    bool fin = true;
-    for (int i = 0; i < 12; i++) fin = fin && std::isfinite(T[12 * k + i]);
-    if (!fin || !(dist <= (double)a->max_translation) || !(ang <= (double)a->max_rotation)) { r.frames_rejected++; continue; }
-    float* o = poses_out + 16 * k;
-    for (int i = 0; i < 12; i++) o[i] = (float)T[12 * k + i];
-    o[12] = o[13] = o[14] = 0.0f;
-    o[15] = 1.0f;
+    if (!accept_pose(&T0[12 * k], &T[12 * k], (double)a->max_translation, (double)a->max_rotation)) { r.frames_rejected++; continue; }
+    write_pose16(&T[12 * k], poses_out + 16 * k);
   }
   if (res) *res = r;
   return SF_OK;
 }
 
-int make_job(sf_fuser* f, uint64_t K, const int32_t* pairs, uint64_t P, const sf_align_params* a, Job* j) {
-  j->K = K; j->P = P; j->pairs = pairs;
-  const int rc = resolve_level(f, a, &j->level, &j->cam);
+// what the three entry points share: the checks in their order, the job, the device, the buffers and, for frames on the host, their copy into w->d_in
+int begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool out_ok, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P,
+          const sf_align_params* a, Job* j) {
+  int rc = check_align_args(K, poses, pairs, P, a);
   if (rc != SF_OK) return rc;
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
+  if (!depth || !out_ok) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  const uint64_t frame_bytes = f->in_px * sizeof(uint16_t);
+  if (on_device && (stride < frame_bytes || stride % sizeof(uint16_t)))
+    return sf::fail(SF_ERR_INVALID_ARG, "frame stride %llu bytes for frames of %llu", (unsigned long long)stride, (unsigned long long)frame_bytes);
+  j->K = K; j->P = P; j->pairs = pairs;
+  if ((rc = resolve_level(f, a, &j->level, &j->cam)) != SF_OK) return rc;
   const bool own = a->depth_min == 0.0f && a->depth_max == 0.0f;
   j->dmin = own ? f->pk.dmin : a->depth_min;
   j->dmax = own ? f->pk.dmax : a->depth_max;
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, K, P, j->cam.W * j->cam.H, !on_device)) != SF_OK) return rc;
+  j->d_depth = depth;
+  j->stride = stride;
+  if (!on_device) {
+    j->d_depth = f->align->d_in.p;
+    j->stride = frame_bytes;
+    SF_HIP_CHECK(hipMemcpyAsync(f->align->d_in.p, depth, K * frame_bytes, hipMemcpyHostToDevice, f->stream));
+  }
   return SF_OK;
 }
 
@@ -427,47 +365,23 @@ int make_job(sf_fuser* f, uint64_t K, const int32_t* pairs, uint64_t P, const sf
 
 SF_API int sf_fuser_align_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
                                  const sf_align_params* a, float* poses_out, sf_align_result* result) {
-  int rc = check_align_args(K, poses_in, pairs, P, a);
-  if (rc != SF_OK) return rc;
-  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
-  if (!d_depth || !poses_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  if (frame_stride_bytes < f->in_px * sizeof(uint16_t) || frame_stride_bytes % sizeof(uint16_t))
-    return sf::fail(SF_ERR_INVALID_ARG, "frame stride %llu bytes for frames of %llu", (unsigned long long)frame_stride_bytes, (unsigned long long)(f->in_px * sizeof(uint16_t)));
   Job j;
-  if ((rc = make_job(f, K, pairs, P, a, &j)) != SF_OK) return rc;
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  if ((rc = ensure_work(f, K, P, j.cam.W * j.cam.H, false)) != SF_OK) return rc;
-  return align_device(f, d_depth, frame_stride_bytes, K, poses_in, j, a, poses_out, result);
+  const int rc = begin(f, d_depth, true, frame_stride_bytes, poses_out != nullptr, K, poses_in, pairs, P, a, &j);
+  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
 }
 
 SF_API int sf_fuser_align(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a,
                           float* poses_out, sf_align_result* result) {
-  int rc = check_align_args(K, poses_in, pairs, P, a);
-  if (rc != SF_OK) return rc;
-  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
-  if (!depth || !poses_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   Job j;
-  if ((rc = make_job(f, K, pairs, P, a, &j)) != SF_OK) return rc;
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  if ((rc = ensure_work(f, K, P, j.cam.W * j.cam.H, true)) != SF_OK) return rc;
-  const size_t stride = f->in_px * sizeof(uint16_t);
-  SF_HIP_CHECK(hipMemcpyAsync(f->align->d_in, depth, K * stride, hipMemcpyHostToDevice, f->stream));
-  return align_device(f, f->align->d_in, stride, K, poses_in, j, a, poses_out, result);
+  const int rc = begin(f, depth, false, 0, poses_out != nullptr, K, poses_in, pairs, P, a, &j);
+  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
 }
 
 SF_API int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a,
                                  double* sys) {
-  int rc = check_align_args(K, poses, pairs, P, a);
-  if (rc != SF_OK) return rc;
-  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
-  if (!depth || !sys) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   Job j;
-  if ((rc = make_job(f, K, pairs, P, a, &j)) != SF_OK) return rc;
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  if ((rc = ensure_work(f, K, P, j.cam.W * j.cam.H, true)) != SF_OK) return rc;
-  const size_t stride = f->in_px * sizeof(uint16_t);
-  SF_HIP_CHECK(hipMemcpyAsync(f->align->d_in, depth, K * stride, hipMemcpyHostToDevice, f->stream));
-  if ((rc = prepare(f, f->align->d_in, stride, j)) != SF_OK) return rc;
+  int rc = begin(f, depth, false, 0, sys != nullptr, K, poses, pairs, P, a, &j);
+  if (rc != SF_OK || (rc = prepare(f, j)) != SF_OK) return rc;
   std::vector<double> T(K * 12, 0.0);
   std::vector<uint8_t> valid(K);
   for (uint64_t k = 0; k < K; k++) {
@@ -475,7 +389,7 @@ SF_API int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K,
     for (int i = 0; i < 12 && valid[k]; i++) T[12 * k + i] = (double)poses[16 * k + i];
   }
   if ((rc = systems_at(f, j, T.data(), valid.data(), a)) != SF_OK) return rc;
-  std::memcpy(sys, f->align->h_sys, P * TK_NSYS * sizeof(double));
+  std::memcpy(sys, f->align->h_sys.p, P * TK_NSYS * sizeof(double));
   return SF_OK;
 }
 

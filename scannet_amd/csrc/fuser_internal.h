@@ -1,5 +1,5 @@
 // fuser_internal.h -- device-side layout and the sf_fuser handle, shared by the fusion core (fuser.hip: the host side; fuser_prepass / _alloc / _compact /
-// _integrate / _blocks.hip: one stage each, kernels and their launchers) and by mc.hip, raycast.hip, track.hip, pipeline.hip and calib.hip
+// _integrate / _blocks.hip: one stage each, kernels and their launchers) and by mc.hip, raycast.hip, track.hip, align.hip, pipeline.hip and calib.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -347,6 +347,8 @@ struct sf_fuser {
 hipError_t sf_quiesce(sf_fuser* f);                 // drain both streams
 void sf_track_release(sf_fuser* f);                 // track.hip: frees f->track
 void sf_align_release(sf_fuser* f);                 // align.hip: frees f->align
+int sf_order_behind_fronts(sf_fuser* f);            // raycast.hip: f->stream waits for both front streams' tails (makes f->ev_raycast on first use)
+int sf_order_fronts_behind(sf_fuser* f);            // raycast.hip: ... and both front streams wait for f->stream's
 bool sf_single_stream_batch(const sf_fuser* f, int n, bool color, int sign);   // run_batch keeps this batch on f->stream alone
 hipStream_t sf_input_stream(const sf_fuser* f, int n, bool color, int sign);   // where the batch's frames must be staged
 int sf_compact_live(sf_fuser* f, int32_t* n_out, int include_ghosts = 1);   // live heap slots -> f->compact, synchronous

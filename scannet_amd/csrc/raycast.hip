@@ -253,6 +253,27 @@ bool pose_usable(const float* T) {
 
 }  // namespace
 
+// f->stream waits for what both front streams hold so far: whatever reads the frames' effect on f->stream comes behind every frame queued on the handle
+int sf_order_behind_fronts(sf_fuser* f) {
+  for (hipEvent_t& e : f->ev_raycast)
+    if (!e) SF_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  const hipStream_t fronts[2] = {f->front, f->front_lo};
+  for (int i = 0; i < 2; i++)
+    if (fronts[i]) {
+      SF_HIP_CHECK(hipEventRecord(f->ev_raycast[i], fronts[i]));
+      SF_HIP_CHECK(hipStreamWaitEvent(f->stream, f->ev_raycast[i], 0));
+    }
+  return SF_OK;
+}
+
+// the counterpart, after sf_order_behind_fronts: both front streams wait for what f->stream holds so far
+int sf_order_fronts_behind(sf_fuser* f) {
+  SF_HIP_CHECK(hipEventRecord(f->ev_raycast[2], f->stream));
+  for (hipStream_t s : {f->front, f->front_lo})
+    if (s) SF_HIP_CHECK(hipStreamWaitEvent(s, f->ev_raycast[2], 0));
+  return SF_OK;
+}
+
 SF_API int sf_fuser_raycast_size(sf_fuser* f, const sf_raycast_params* r, int32_t* width, int32_t* height) {
   RayArgs a;
   const int rc = resolve(f, r, &a);
@@ -269,15 +290,8 @@ SF_API int sf_fuser_raycast_device(sf_fuser* f, const float* poses, uint64_t n, 
   if (!poses && n) return sf::fail(SF_ERR_INVALID_ARG, "NULL poses");
   if (n == 0 || (!d_depth && !d_normals_xyz && !d_rgb)) return SF_OK;
   SF_HIP_CHECK(hipSetDevice(f->device));
-  for (hipEvent_t& e : f->ev_raycast)
-    if (!e) SF_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   // behind every frame queued so far, on the main stream and on both front streams ...
-  const hipStream_t fronts[2] = {f->front, f->front_lo};
-  for (int i = 0; i < 2; i++)
-    if (fronts[i]) {
-      SF_HIP_CHECK(hipEventRecord(f->ev_raycast[i], fronts[i]));
-      SF_HIP_CHECK(hipStreamWaitEvent(f->stream, f->ev_raycast[i], 0));
-    }
+  if (const int oc = sf_order_behind_fronts(f)) return oc;
   const size_t npx = (size_t)a.W * a.H;
   const dim3 grid((a.W + 15) / 16, (a.H + 15) / 16, 1);
   for (uint64_t j0 = 0; j0 < n; j0 += RC_MAX_POSES) {
@@ -296,10 +310,7 @@ SF_API int sf_fuser_raycast_device(sf_fuser* f, const float* poses, uint64_t n, 
     SF_HIP_CHECK(hipGetLastError());
   }
   // ... and ahead of everything queued later: the next frame's allocation must not insert into the table while the kernel reads it
-  SF_HIP_CHECK(hipEventRecord(f->ev_raycast[2], f->stream));
-  for (int i = 0; i < 2; i++)
-    if (fronts[i]) SF_HIP_CHECK(hipStreamWaitEvent(fronts[i], f->ev_raycast[2], 0));
-  return SF_OK;
+  return sf_order_fronts_behind(f);
 }
 
 SF_API int sf_fuser_raycast(sf_fuser* f, const float pose[16], const sf_raycast_params* r, float* depth, float* normals_xyz, uint8_t* rgb) {

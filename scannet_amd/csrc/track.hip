@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 #include "scanfuse_internal.h"
 #include "track_math.h"
 
@@ -80,34 +81,20 @@ __global__ void __launch_bounds__(256) k_track_assoc(const float4* __restrict__ 
                                                      uint8_t* __restrict__ mask) {
   __shared__ float red[4][TK_NSYS];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int npx = A.c.W * A.c.H;
   float acc[TK_NSYS];
 #pragma unroll
   for (int k = 0; k < TK_NSYS; k++) acc[k] = 0.0f;
-  bool ok = false;
-  if (i < npx) {
-    const float4 v4 = vmap[i], n4 = nmap[i];
-    if (v4.z > 0.0f && n4.x > -INFINITY) {
-      const float3 v = make_float3(v4.x, v4.y, v4.z);
-      const float3 p = xf(A.T, v), n = rot(A.T, make_float3(n4.x, n4.y, n4.z));
-      const float3 pc = xf(A.M, v);
-      if (pc.z > 0.0f) {
-        const float ux = floorf(fmaf(pc.x / pc.z, A.c.fx, A.c.mx) + 0.5f), uy = floorf(fmaf(pc.y / pc.z, A.c.fy, A.c.my) + 0.5f);
-        if (ux >= 0.0f && ux < (float)A.c.W && uy >= 0.0f && uy < (float)A.c.H) {
-          const size_t j = (size_t)((int)uy << A.shift) * A.W0 + ((int)ux << A.shift);
-          const float4 q4 = mq[j];
-          if (q4.x > -INFINITY) {
-            const float4 m4 = mnorm[j];
-            const float3 nm = make_float3(m4.x, m4.y, m4.z);
-            const float3 d = make_float3(p.x - q4.x, p.y - q4.y, p.z - q4.z);
-            if (sqrtf(dot3(d, d)) <= A.dist_thres && dot3(nm, n) >= A.normal_thres) {
-              row29(p, nm, d, acc);
-              ok = true;
-            }
-          }
-        }
-      }
-    }
+  if (i < A.c.W * A.c.H) {
+    // the target is the model image (level 0) subsampled; its normal is read only where its vertex is valid
+    const bool ok = correspond(A.c, A.T, A.M, vmap[i], nmap[i], A.dist_thres, A.normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
+      const size_t j = (size_t)(uy << A.shift) * A.W0 + (ux << A.shift);
+      const float4 q4 = mq[j];
+      if (!(q4.x > -INFINITY)) return false;
+      const float4 m4 = mnorm[j];
+      *q = make_float3(q4.x, q4.y, q4.z);
+      *nm = make_float3(m4.x, m4.y, m4.z);
+      return true;
+    }, acc);
     if (mask) mask[i] = ok ? 1 : 0;
   }
   reduce256(acc, red, partials + (size_t)blockIdx.x * TK_PSTRIDE);
@@ -116,41 +103,27 @@ __global__ void __launch_bounds__(256) k_track_assoc(const float4* __restrict__ 
 // the workgroups' partials summed in index order, in double: lane k sums value k
 __global__ void __launch_bounds__(64) k_track_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
   const int k = threadIdx.x;
-  if (k >= TK_NSYS) return;
-  double s = 0.0;
-#pragma unroll 8
-  for (int b = 0; b < nb; b++) s += (double)partials[(size_t)b * TK_PSTRIDE + k];
-  out[k] = s;
+  if (k < TK_NSYS) out[k] = sum_partials(partials, nb, k);
 }
 
 }  // namespace
 
 struct TrackWork {
-  int W = 0, H = 0, levels = 0;
-  int in_px = 0;
-  uint16_t* d_in = nullptr;             // a host frame's device copy
-  float* depth[TK_MAX_LEVELS] = {};     // metres per level
-  float4* vmap[TK_MAX_LEVELS] = {};
-  float4* nmap[TK_MAX_LEVELS] = {};
-  float* model_depth = nullptr;         // the ray cast at level-0 size
-  float* model_normal = nullptr;
-  float4* mq = nullptr;                 // world vertices and normals of the model
-  float4* mn = nullptr;
-  float* partials = nullptr;
-  double* d_sys = nullptr;
-  double* h_sys = nullptr;              // page-locked read-back
-  uint8_t* d_mask = nullptr;
+  int levels = 0;
+  sf::DevBuf d_in;                            // u16: a host frame's device copy
+  sf::DevBuf depth[TK_MAX_LEVELS];            // float: metres per level
+  sf::DevBuf vmap[TK_MAX_LEVELS], nmap[TK_MAX_LEVELS];   // float4
+  sf::DevBuf model_depth, model_normal;       // float, 3 floats: the ray cast at level-0 size
+  sf::DevBuf mq, mn;                          // float4: world vertices and normals of the model
+  sf::DevBuf partials;                        // float
+  sf::DevBuf d_sys;                           // double
+  sf::HostBuf h_sys;                          // double: page-locked read-back
+  sf::DevBuf d_mask;                          // u8
 };
 
 void sf_track_release(sf_fuser* f) {
-  TrackWork* w = f ? f->track : nullptr;
-  if (!w) return;
-  (void)hipFree(w->d_in);
-  for (int l = 0; l < TK_MAX_LEVELS; l++) { (void)hipFree(w->depth[l]); (void)hipFree(w->vmap[l]); (void)hipFree(w->nmap[l]); }
-  (void)hipFree(w->model_depth); (void)hipFree(w->model_normal); (void)hipFree(w->mq); (void)hipFree(w->mn);
-  (void)hipFree(w->partials); (void)hipFree(w->d_sys); (void)hipFree(w->d_mask);
-  if (w->h_sys) (void)hipHostFree(w->h_sys);
-  delete w;
+  if (!f) return;
+  delete f->track;
   f->track = nullptr;
 }
 
@@ -175,52 +148,30 @@ int check_track_params(const sf_track_params* t) {
   return SF_OK;
 }
 
-// the level cameras: level 0 the integration camera, level l (W >> l) x (H >> l) with the ray caster's scaled intrinsics
-int level_cams(const sf_fuser* f, int levels, Cam* cams) {
-  const int W = f->pk.W, H = f->pk.H;
-  for (int l = 0; l < levels; l++) {
-    Cam& c = cams[l];
-    c.W = W >> l;
-    c.H = H >> l;
-    if (c.W < 8 || c.H < 8) return sf::fail(SF_ERR_INVALID_ARG, "tracking level %d would be %d x %d (at least 8 x 8)", l, c.W, c.H);
-    const float sx = (float)c.W / (float)W, sy = (float)c.H / (float)H;
-    c.fx = f->pk.fx * sx; c.mx = f->pk.mx * sx;
-    c.fy = f->pk.fy * sy; c.my = f->pk.my * sy;
-  }
-  return SF_OK;
-}
-
+// the buffers of `levels` levels, made on first use and again only when more levels are asked for than the set holds
 int ensure_work(sf_fuser* f, const Cam* cams, int levels) {
-  TrackWork* w = f->track;
-  if (w && w->levels >= levels) return SF_OK;
+  if (f->track && f->track->levels >= levels) return SF_OK;
   sf_track_release(f);
-  w = new TrackWork();
-  f->track = w;
-  w->W = cams[0].W; w->H = cams[0].H; w->levels = levels;
-  w->in_px = (int)f->in_px;
-  const size_t n0 = (size_t)w->W * w->H;
-#define TK_ALLOC(ptr, bytes)                                                                                                  \
-  do {                                                                                                                        \
-    const hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                                                                 \
-    if (e_ != hipSuccess) { sf_track_release(f); return sf::fail(SF_ERR_DEVICE, "tracking buffers: %s", hipGetErrorString(e_)); } \
-  } while (0)
-  TK_ALLOC(w->d_in, f->in_px * sizeof(uint16_t));
+  TrackWork* w = f->track = new TrackWork();
+  w->levels = levels;
+  const size_t n0 = (size_t)cams[0].W * cams[0].H;
+  hipError_t e = w->d_in.reserve(f->in_px * sizeof(uint16_t));
+  const auto dev = [&e](sf::DevBuf& b, size_t bytes) { if (e == hipSuccess) e = b.reserve(bytes); };
   for (int l = 0; l < levels; l++) {
     const size_t n = (size_t)cams[l].W * cams[l].H;
-    TK_ALLOC(w->depth[l], n * sizeof(float));
-    TK_ALLOC(w->vmap[l], n * sizeof(float4));
-    TK_ALLOC(w->nmap[l], n * sizeof(float4));
+    dev(w->depth[l], n * sizeof(float));
+    dev(w->vmap[l], n * sizeof(float4));
+    dev(w->nmap[l], n * sizeof(float4));
   }
-  TK_ALLOC(w->model_depth, n0 * sizeof(float));
-  TK_ALLOC(w->model_normal, n0 * 3 * sizeof(float));
-  TK_ALLOC(w->mq, n0 * sizeof(float4));
-  TK_ALLOC(w->mn, n0 * sizeof(float4));
-  TK_ALLOC(w->partials, ((n0 + 255) / 256) * TK_PSTRIDE * sizeof(float));
-  TK_ALLOC(w->d_sys, TK_PSTRIDE * sizeof(double));
-  TK_ALLOC(w->d_mask, n0);
-#undef TK_ALLOC
-  const hipError_t e = hipHostMalloc((void**)&w->h_sys, TK_PSTRIDE * sizeof(double), hipHostMallocDefault);
-  if (e != hipSuccess) { w->h_sys = nullptr; sf_track_release(f); return sf::fail(SF_ERR_DEVICE, "tracking read-back buffer: %s", hipGetErrorString(e)); }
+  dev(w->model_depth, n0 * sizeof(float));
+  dev(w->model_normal, n0 * 3 * sizeof(float));
+  dev(w->mq, n0 * sizeof(float4));
+  dev(w->mn, n0 * sizeof(float4));
+  dev(w->partials, ((n0 + 255) / 256) * TK_PSTRIDE * sizeof(float));
+  dev(w->d_sys, TK_PSTRIDE * sizeof(double));
+  dev(w->d_mask, n0);
+  if (e == hipSuccess) e = w->h_sys.reserve(TK_PSTRIDE * sizeof(double));
+  if (e != hipSuccess) { sf_track_release(f); return sf::fail(SF_ERR_DEVICE, "tracking buffers: %s", hipGetErrorString(e)); }
   return SF_OK;
 }
 
@@ -234,22 +185,25 @@ Rows rows_of(const float* T) {
 int prepare(sf_fuser* f, const void* d_depth, const float* Tref, const sf_track_params* t, const Cam* cams) {
   TrackWork* w = f->track;
   const int n0 = cams[0].W * cams[0].H;
-  hipLaunchKernelGGL(k_track_depth0, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, (const uint16_t*)d_depth, f->pk, w->depth[0]);
+  hipLaunchKernelGGL(k_track_depth0, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, (const uint16_t*)d_depth, f->pk, w->depth[0].as<float>());
   SF_HIP_CHECK(hipGetLastError());
   for (int l = 1; l < t->levels; l++) {
     const int n = cams[l].W * cams[l].H;
-    hipLaunchKernelGGL(k_track_down, dim3((n + 255) / 256), dim3(256), 0, f->stream, w->depth[l - 1], cams[l - 1].W, w->depth[l], cams[l].W, cams[l].H);
+    hipLaunchKernelGGL(k_track_down, dim3((n + 255) / 256), dim3(256), 0, f->stream, w->depth[l - 1].as<const float>(), cams[l - 1].W, w->depth[l].as<float>(),
+                       cams[l].W, cams[l].H);
     SF_HIP_CHECK(hipGetLastError());
   }
   for (int l = 0; l < t->levels; l++) {
     const int n = cams[l].W * cams[l].H;
-    hipLaunchKernelGGL(k_track_vn, dim3((n + 255) / 256), dim3(256), 0, f->stream, w->depth[l], cams[l], w->vmap[l], w->nmap[l]);
+    hipLaunchKernelGGL(k_track_vn, dim3((n + 255) / 256), dim3(256), 0, f->stream, w->depth[l].as<const float>(), cams[l], w->vmap[l].as<float4>(),
+                       w->nmap[l].as<float4>());
     SF_HIP_CHECK(hipGetLastError());
   }
   // the ray cast orders itself behind both front streams and blocks later front-chain work (raycast.hip)
-  const int rc = sf_fuser_raycast_device(f, Tref, 1, &t->raycast, w->model_depth, w->model_normal, nullptr);
+  const int rc = sf_fuser_raycast_device(f, Tref, 1, &t->raycast, w->model_depth.p, w->model_normal.p, nullptr);
   if (rc != SF_OK) return rc;
-  hipLaunchKernelGGL(k_track_model, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, w->model_depth, w->model_normal, cams[0], rows_of(Tref), w->mq, w->mn);
+  hipLaunchKernelGGL(k_track_model, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, w->model_depth.as<const float>(), w->model_normal.as<const float>(), cams[0],
+                     rows_of(Tref), w->mq.as<float4>(), w->mn.as<float4>());
   SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }
@@ -266,72 +220,60 @@ int system_at(sf_fuser* f, int l, const Cam* cams, const double* T, const double
   A.dist_thres = t->dist_thres[l];
   A.normal_thres = t->normal_thres[l];
   const int n = cams[l].W * cams[l].H, nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_track_assoc, dim3(nb), dim3(256), 0, f->stream, w->vmap[l], w->nmap[l], w->mq, w->mn, A, w->partials, want_mask ? w->d_mask : nullptr);
+  hipLaunchKernelGGL(k_track_assoc, dim3(nb), dim3(256), 0, f->stream, w->vmap[l].as<const float4>(), w->nmap[l].as<const float4>(), w->mq.as<const float4>(),
+                     w->mn.as<const float4>(), A, w->partials.as<float>(), want_mask ? w->d_mask.as<uint8_t>() : nullptr);
   SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_track_final, dim3(1), dim3(64), 0, f->stream, w->partials, nb, w->d_sys);
+  hipLaunchKernelGGL(k_track_final, dim3(1), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
   SF_HIP_CHECK(hipGetLastError());
-  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys, w->d_sys, TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   SF_HIP_CHECK(hipStreamSynchronize(f->stream));
   return SF_OK;
 }
 
-// A xi = -b by Cholesky, in double; false at a pivot <= TK_PIVOT_REL x its diagonal entry
+// the 6x6 system of the 29 values: A xi = -b
 bool solve6(const double* sys, double* xi) {
-  double A[6][6], L[6][6] = {};
+  double A[6][6];
   int k = 0;
   for (int a = 0; a < 6; a++)
     for (int b = a; b < 6; b++) A[a][b] = A[b][a] = sys[k++];
-  for (int j = 0; j < 6; j++) {
-    double s = A[j][j];
-    for (int m = 0; m < j; m++) s -= L[j][m] * L[j][m];
-    if (!(s > TK_PIVOT_REL * A[j][j])) return false;
-    L[j][j] = std::sqrt(s);
-    for (int i = j + 1; i < 6; i++) {
-      double e = A[i][j];
-      for (int m = 0; m < j; m++) e -= L[i][m] * L[j][m];
-      L[i][j] = e / L[j][j];
-    }
-  }
-  double y[6];
-  for (int i = 0; i < 6; i++) {
-    double e = -sys[21 + i];
-    for (int m = 0; m < i; m++) e -= L[i][m] * y[m];
-    y[i] = e / L[i][i];
-  }
-  for (int i = 5; i >= 0; i--) {
-    double e = y[i];
-    for (int m = i + 1; m < 6; m++) e -= L[m][i] * xi[m];
-    xi[i] = e / L[i][i];
-  }
-  return true;
+  return solve_spd(&A[0][0], sys + 21, 6, xi);
 }
 
-void lost_pose(float* pose_out) {
-  for (int i = 0; i < 16; i++) pose_out[i] = -INFINITY;
-}
-
-int track_device(sf_fuser* f, const void* d_depth, const float* guess, const float* ref, const sf_track_params* t, float* pose_out, sf_track_result* res) {
+// what the three entry points share: the checks in their order (own_checks: the caller's own, behind the NULL checks), the level cameras, the device, the
+// buffers and, for a host frame, its copy into w->d_in
+template <typename Checks>
+int begin(sf_fuser* f, const sf_track_params* t, bool args_ok, Checks own_checks, Cam* cams, const uint16_t* host_depth) {
   int rc = check_track_params(t);
   if (rc != SF_OK) return rc;
   if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
-  if (!d_depth || !guess || !pose_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (!args_ok) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if ((rc = own_checks()) != SF_OK) return rc;
+  for (int l = 0; l < t->levels; l++)
+    if (!level_cam(f->pk, l, &cams[l])) return sf::fail(SF_ERR_INVALID_ARG, "tracking level %d would be %d x %d (at least 8 x 8)", l, cams[l].W, cams[l].H);
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
+  if (host_depth) SF_HIP_CHECK(hipMemcpyAsync(f->track->d_in.p, host_depth, f->in_px * sizeof(uint16_t), hipMemcpyHostToDevice, f->stream));
+  return SF_OK;
+}
+
+// depth: a frame in HBM (on_device) or on the host
+int track(sf_fuser* f, const void* depth, bool on_device, const float* guess, const float* ref, const sf_track_params* t, float* pose_out, sf_track_result* res) {
+  Cam cams[TK_MAX_LEVELS];
+  int rc = begin(f, t, depth && guess && pose_out, [] { return (int)SF_OK; }, cams, on_device ? nullptr : (const uint16_t*)depth);
+  if (rc != SF_OK) return rc;
   sf_track_result r;
   std::memset(&r, 0, sizeof(r));
-  lost_pose(pose_out);
+  for (int i = 0; i < 16; i++) pose_out[i] = -INFINITY;   // the "tracking lost" pose
   if (!ref) ref = guess;
-  Cam cams[TK_MAX_LEVELS];
-  if ((rc = level_cams(f, t->levels, cams)) != SF_OK) return rc;
   if (!finite12(guess) || !finite12(ref)) {
     r.lost_reason = 1;
     if (res) *res = r;
     return SF_OK;
   }
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
-  if ((rc = prepare(f, d_depth, ref, t, cams)) != SF_OK) return rc;
+  if ((rc = prepare(f, on_device ? depth : f->track->d_in.p, ref, t, cams)) != SF_OK) return rc;
   double T[12], Tref[12], G[12];
   for (int i = 0; i < 12; i++) { T[i] = guess[i]; G[i] = guess[i]; Tref[i] = ref[i]; }
-  const double* sys = f->track->h_sys;
+  const double* sys = f->track->h_sys.as<const double>();
   for (int l = t->levels - 1; l >= 0 && r.lost_reason == 0; l--) {
     for (int it = 0; it < t->max_iters[l]; it++) {
       if ((rc = system_at(f, l, cams, T, Tref, t, false)) != SF_OK) return rc;
@@ -349,18 +291,10 @@ int track_device(sf_fuser* f, const void* d_depth, const float* guess, const flo
       if (mx < (double)t->early_out) break;
     }
   }
-  if (r.lost_reason == 0) {
-    double dist, ang;
-    motion(G, T, &dist, &ang);
-    bool fin = true;
-    for (int i = 0; i < 12; i++) fin = fin && std::isfinite(T[i]);
-    if (!fin || !(dist <= (double)t->max_translation) || !(ang <= (double)t->max_rotation)) r.lost_reason = 4;
-  }
+  if (r.lost_reason == 0 && !accept_pose(G, T, (double)t->max_translation, (double)t->max_rotation)) r.lost_reason = 4;
   if (r.lost_reason == 0) {
     r.tracked = 1;
-    for (int i = 0; i < 12; i++) pose_out[i] = (float)T[i];
-    pose_out[12] = pose_out[13] = pose_out[14] = 0.0f;
-    pose_out[15] = 1.0f;
+    write_pose16(T, pose_out);
   }
   if (res) *res = r;
   return SF_OK;
@@ -370,42 +304,29 @@ int track_device(sf_fuser* f, const void* d_depth, const float* guess, const flo
 
 SF_API int sf_fuser_track_device(sf_fuser* f, const void* d_depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
                                  sf_track_result* result) {
-  return track_device(f, d_depth, guess, ref, t, pose_out, result);
+  return track(f, d_depth, true, guess, ref, t, pose_out, result);
 }
 
 SF_API int sf_fuser_track(sf_fuser* f, const uint16_t* depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
                           sf_track_result* result) {
-  int rc = check_track_params(t);
-  if (rc != SF_OK) return rc;
-  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
-  if (!depth || !guess || !pose_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  Cam cams[TK_MAX_LEVELS];
-  if ((rc = level_cams(f, t->levels, cams)) != SF_OK) return rc;
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
-  SF_HIP_CHECK(hipMemcpyAsync(f->track->d_in, depth, f->in_px * sizeof(uint16_t), hipMemcpyHostToDevice, f->stream));
-  return track_device(f, f->track->d_in, guess, ref, t, pose_out, result);
+  return track(f, depth, false, guess, ref, t, pose_out, result);
 }
 
 SF_API int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, const float T[16], const float T_ref[16], const sf_track_params* t,
                                  double sys[29], uint8_t* mask) {
-  int rc = check_track_params(t);
-  if (rc != SF_OK) return rc;
-  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
-  if (!depth || !T || !T_ref || !sys) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  if (level < 0 || level >= t->levels) return sf::fail(SF_ERR_INVALID_ARG, "level %d of %d", level, t->levels);
-  if (!finite12(T) || !finite12(T_ref)) return sf::fail(SF_ERR_INVALID_ARG, "non-finite pose");
   Cam cams[TK_MAX_LEVELS];
-  if ((rc = level_cams(f, t->levels, cams)) != SF_OK) return rc;
-  SF_HIP_CHECK(hipSetDevice(f->device));
-  if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
+  int rc = begin(f, t, depth && T && T_ref && sys, [&] {
+    if (level < 0 || level >= t->levels) return sf::fail(SF_ERR_INVALID_ARG, "level %d of %d", level, t->levels);
+    if (!finite12(T) || !finite12(T_ref)) return sf::fail(SF_ERR_INVALID_ARG, "non-finite pose");
+    return (int)SF_OK;
+  }, cams, depth);
+  if (rc != SF_OK) return rc;
   TrackWork* w = f->track;
-  SF_HIP_CHECK(hipMemcpyAsync(w->d_in, depth, f->in_px * sizeof(uint16_t), hipMemcpyHostToDevice, f->stream));
-  if ((rc = prepare(f, w->d_in, T_ref, t, cams)) != SF_OK) return rc;
+  if ((rc = prepare(f, w->d_in.p, T_ref, t, cams)) != SF_OK) return rc;
   double Td[12], Rd[12];
   for (int i = 0; i < 12; i++) { Td[i] = T[i]; Rd[i] = T_ref[i]; }
   if ((rc = system_at(f, level, cams, Td, Rd, t, mask != nullptr)) != SF_OK) return rc;
-  for (int k = 0; k < TK_NSYS; k++) sys[k] = w->h_sys[k];
-  if (mask) SF_HIP_CHECK(hipMemcpy(mask, w->d_mask, (size_t)cams[level].W * cams[level].H, hipMemcpyDeviceToHost));
+  for (int k = 0; k < TK_NSYS; k++) sys[k] = w->h_sys.as<const double>()[k];
+  if (mask) SF_HIP_CHECK(hipMemcpy(mask, w->d_mask.p, (size_t)cams[level].W * cams[level].H, hipMemcpyDeviceToHost));
   return SF_OK;
 }

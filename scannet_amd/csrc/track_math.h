@@ -1,5 +1,6 @@
 // track_math.h -- the per-pixel rules the camera tracker (track.hip) and the global alignment (align.hip) share: metres from a u16 frame, the 2x2
-// reduction, camera-space vertices and normals, the point-to-plane row with its 29 values, and their reduction over a 256-pixel workgroup
+// reduction, camera-space vertices and normals, the correspondence rule, the point-to-plane row with its 29 values and their reduction over a 256-pixel
+// workgroup; and the host's side of a Gauss-Newton step: the level camera, the Cholesky solve, the pose update and its acceptance
 // (DESIGN.md "Camera tracking" and "Global alignment").  Every operation is written as the specification states it; nothing here contracts.
 #ifndef SCANFUSE_TRACK_MATH_H
 #define SCANFUSE_TRACK_MATH_H
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <vector>
 
 #include "fuser_internal.h"
 
@@ -105,6 +107,33 @@ __device__ inline void row29(float3 p, float3 nm, float3 d, float (&acc)[TK_NSYS
   acc[28] = 1.0f;
 }
 
+// one source pixel (camera-space vertex v4, normal n4) against a target: T the source's pose, M the source in the target's camera, c that camera at the
+// level.  target(ux, uy, &q, &nm) looks up the world point and normal of target pixel (ux, uy) and returns false where it has none.  Fills acc and
+// returns true where the pixel is a correspondence
+template <typename Target>
+__device__ inline bool correspond(const Cam& c, const Rows& T, const Rows& M, float4 v4, float4 n4, float dist_thres, float normal_thres, Target target,
+                                  float (&acc)[TK_NSYS]) {
+  if (v4.z > 0.0f && n4.x > -INFINITY) {
+    const float3 v = make_float3(v4.x, v4.y, v4.z);
+    const float3 p = xf(T, v), n = rot(T, make_float3(n4.x, n4.y, n4.z));
+    const float3 pc = xf(M, v);
+    if (pc.z > 0.0f) {
+      const float ux = floorf(fmaf(pc.x / pc.z, c.fx, c.mx) + 0.5f), uy = floorf(fmaf(pc.y / pc.z, c.fy, c.my) + 0.5f);
+      if (ux >= 0.0f && ux < (float)c.W && uy >= 0.0f && uy < (float)c.H) {
+        float3 q, nm;
+        if (target((int)ux, (int)uy, &q, &nm)) {
+          const float3 d = make_float3(p.x - q.x, p.y - q.y, p.z - q.z);
+          if (sqrtf(dot3(d, d)) <= dist_thres && dot3(nm, n) >= normal_thres) {
+            row29(p, nm, d, acc);
+            return true;
+          }
+        }
+      }
+    }
+  }
+  return false;
+}
+
 // the workgroup's 256 lanes reduced to one 29-float partial: xor butterfly 32 .. 1 within the wave (every lane ends with the wave's sum: a + b and
 // b + a are the same float), (w0 + w1) + (w2 + w3) across the four waves.  No atomics.
 __device__ inline void reduce256(float (&acc)[TK_NSYS], float (&red)[4][TK_NSYS], float* __restrict__ partial) {
@@ -123,7 +152,52 @@ __device__ inline void reduce256(float (&acc)[TK_NSYS], float (&red)[4][TK_NSYS]
   }
 }
 
+// value k of nb workgroup partials summed in index order, in double
+__device__ inline double sum_partials(const float* __restrict__ partials, int nb, int k) {
+  double s = 0.0;
+#pragma unroll 8
+  for (int b = 0; b < nb; b++) s += (double)partials[(size_t)b * TK_PSTRIDE + k];
+  return s;
+}
+
 // ---- host, double: shared by the two solvers ---------------------------------------------------------------------------------------------------
+
+// the camera of level l: (W >> l) x (H >> l) with the ray caster's scaled intrinsics; false below 8 x 8
+inline bool level_cam(const ParamsK& P, int l, Cam* c) {
+  c->W = P.W >> l;
+  c->H = P.H >> l;
+  const float sx = (float)c->W / (float)P.W, sy = (float)c->H / (float)P.H;
+  c->fx = P.fx * sx; c->mx = P.mx * sx;
+  c->fy = P.fy * sy; c->my = P.my * sy;
+  return c->W >= 8 && c->H >= 8;
+}
+
+// A x = -b for the symmetric N x N system A (row-major, full) by Cholesky in double, sums in index order; false at a pivot <= TK_PIVOT_REL x its diagonal entry
+inline bool solve_spd(const double* A, const double* b, int N, double* x) {
+  std::vector<double> L((size_t)N * N, 0.0), y(N);
+  for (int j = 0; j < N; j++) {
+    double s = A[(size_t)j * N + j];
+    for (int m = 0; m < j; m++) s -= L[(size_t)j * N + m] * L[(size_t)j * N + m];
+    if (!(s > TK_PIVOT_REL * A[(size_t)j * N + j])) return false;
+    L[(size_t)j * N + j] = std::sqrt(s);
+    for (int i = j + 1; i < N; i++) {
+      double e = A[(size_t)i * N + j];
+      for (int m = 0; m < j; m++) e -= L[(size_t)i * N + m] * L[(size_t)j * N + m];
+      L[(size_t)i * N + j] = e / L[(size_t)j * N + j];
+    }
+  }
+  for (int i = 0; i < N; i++) {
+    double e = -b[i];
+    for (int m = 0; m < i; m++) e -= L[(size_t)i * N + m] * y[m];
+    y[i] = e / L[(size_t)i * N + i];
+  }
+  for (int i = N - 1; i >= 0; i--) {
+    double e = y[i];
+    for (int m = i + 1; m < N; m++) e -= L[(size_t)m * N + i] * x[m];
+    x[i] = e / L[(size_t)i * N + i];
+  }
+  return true;
+}
 
 // T_ref^-1 (cofactors over the determinant, as the oracle's frame set-up) composed with T, in double: rounded to float once
 inline void compose_ref(const double* Tref, const double* T, float* M) {
@@ -178,6 +252,21 @@ inline bool finite12(const float* T) {
   for (int i = 0; i < 12; i++)
     if (!std::isfinite(T[i])) return false;
   return true;
+}
+
+// a solved pose T is taken when all of it is finite and it lies within both motion bounds of where it started, T0
+inline bool accept_pose(const double* T0, const double* T, double max_t, double max_r) {
+  double dist, ang;
+  motion(T0, T, &dist, &ang);
+  bool fin = true;
+  for (int i = 0; i < 12; i++) fin = fin && std::isfinite(T[i]);
+  return fin && dist <= max_t && ang <= max_r;
+}
+
+inline void write_pose16(const double* T, float* out) {
+  for (int i = 0; i < 12; i++) out[i] = (float)T[i];
+  out[12] = out[13] = out[14] = 0.0f;
+  out[15] = 1.0f;
 }
 
 }  // namespace tk

@@ -562,6 +562,25 @@ def test_gpu_systems_bit_exact(chk, room, gpu_fuser, level):
 
 
 @pytest.mark.gpu
+def test_gpu_buffers_grow_on_demand_and_never_go_stale(chk, room):
+    """One fuser's alignment buffers through their three states: made for K = 2, P = 2 at level 2 (80 x 60: a partial last workgroup), every one of them
+    grown for K = 4, P = 7 at level 0, and the small problem again in the larger buffers."""
+    from scannet_amd import fusion
+    depth, truth, start = room
+    small = (depth[:2], start[:2], np.array([[0, 1], [1, 0]], np.int32), fusion.default_align_params(level=2))
+    big = (depth[[0, 2, 5, 7]], start[[0, 2, 5, 7]], np.array([[0, 1], [1, 0], [1, 2], [2, 1], [0, 2], [2, 0], [0, 3]], np.int32),
+           fusion.default_align_params(level=0))
+    want = {}
+    for name, (d, poses, pairs, a) in (("small", small), ("big", big)):
+        rc, want[name] = cpu_system(chk, d, poses, pairs, a)
+        assert rc == 0 and (want[name][:2, 28] > 1000 >> (2 * a.level)).all(), want[name][:, 28]   # the comparison is not of empty systems
+    with fusion.Fuser(fuser_params(), device=0) as f:
+        for step, (name, (d, poses, pairs, a)) in enumerate((("small", small), ("big", big), ("small", small))):
+            got = f.align_system(d, poses, pairs, a)
+            assert got.shape == want[name].shape and got.tobytes() == want[name].tobytes(), (step, name, np.abs(got - want[name]).max())
+
+
+@pytest.mark.gpu
 def test_gpu_a_size_that_is_no_level_is_refused(room, gpu_fuser):
     from scannet_amd import fusion
     depth, truth, start = room

@@ -495,6 +495,32 @@ def test_gpu_system_bit_exact_every_level(chk, oracle, voxel):
         f.close()
 
 
+@pytest.mark.gpu
+def test_gpu_buffers_are_remade_for_more_levels(chk, oracle):
+    """One fuser's tracking buffers through their three states: made for one level, re-made when three are asked for (level 2 is 80 x 60 = 4 800 pixels =
+    18.75 workgroups: the last one is partial), and kept when one level is asked for again."""
+    from scannet_amd import fusion
+    op, gp = params_pair(oracle)
+    frames = corner_frames()
+    depth, truth = frames[0]
+    T = perturb(truth, 0.01, 1.0)
+    with fusion.Fuser(gp, device=0) as f:
+        for d, p in frames:
+            assert f.integrate(d, p)
+        f.sync()
+        blocks = f.export_blocks()
+        want = {}
+        for step, (levels, level) in enumerate(((1, 0), (3, 2), (1, 0))):
+            t = fusion.default_track_params(levels=levels)
+            if (levels, level) not in want:
+                want[levels, level] = cpu_system(chk, blocks, op, depth, level, T, truth, t)
+            wsys, wmask = want[levels, level]
+            got, gmask = f.track_system(depth, level, T, truth, t, mask=True)
+            assert np.array_equal(gmask, wmask), (step, int((gmask != wmask).sum()))
+            assert got.tobytes() == wsys.tobytes(), (step, got, wsys)
+            assert wsys[28] > 100, (step, wsys[28])
+
+
 @pytest.fixture(scope="module")
 def gpu_room10(oracle):
     op, vol, f = _room_pair(oracle, 10, 0.004)
