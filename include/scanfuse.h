@@ -308,8 +308,8 @@ int sf_fuser_track_device(sf_fuser* f, const void* d_depth, const float guess[16
  * happens.  sf_stats moves as that sequence moves it -- every all -inf pose is one skipped call of it, hence one count in frames_skipped, every other
  * pose one in frames_integrated -- except total_pass_tiles, which counts what the passes really read.  d_rgb may be NULL (geometry only).  Up to
  * sf_fuser_batch_frames() operations share a pass, the two of a frame always do.  Revised poses come from sf_fuser_align below (a dense-depth solver
- * over keyframes) or from the caller (sf_sens_apply_transform on part of a scan, a second tracking sweep, a solver of its own): BundleFusion's SIFT
- * matching, colour term, loop detection and local / global hierarchy are not in this library. */
+ * over keyframes, with BundleFusion's dense colour term through sf_fuser_align_rgbd) or from the caller (sf_sens_apply_transform on part of a scan, a
+ * second tracking sweep, a solver of its own): BundleFusion's SIFT matching, loop detection and local / global hierarchy are not in this library. */
 int sf_fuser_reintegrate_batch_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes,
                                       const float* old_poses, const float* new_poses, uint64_t n);
 /* one frame from host buffers (as sf_fuser_integrate takes them); SF_ERR_SKIPPED when both poses are all -inf */
@@ -347,8 +347,11 @@ int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float* integ
 /* Global alignment: the producer of the revised poses above.  K keyframes (u16 depth at the fuser's input size, camToWorld poses) are aligned jointly
  * over a list of directed frame pairs by a depth-only projective point-to-plane term, BundleFusion's dense depth term between keyframes (the keys of
  * Server/tools/recons/zParametersBundlingScanNet.txt:22-44; the code that reads them is not in the reference tree).  The semantics, per pixel, per pair
- * and per Gauss-Newton iteration, are DESIGN.md section 4e "Global alignment".  SIFT matching, the colour term, loop detection, the bilateral depth
- * filter and the local / global hierarchy of BundleFusion are not built.  An alignment changes nothing in the volume, its counters or frame numbering. */
+ * and per Gauss-Newton iteration, are DESIGN.md section 4e "Global alignment".  sf_fuser_align_rgbd* add BundleFusion's dense colour term to every
+ * depth correspondence (s_denseColorThresh, s_denseColorGradientMin, :24-25): it pins the motion inside a plane, which depth
+ * alone leaves free.  SIFT matching, loop detection, the bilateral depth filter, the Gaussian pre-filter of the colour frames (s_colorDownSigma), the
+ * local / global hierarchy of BundleFusion and a colour term in the tracker are not built.  An alignment changes nothing in the volume, its counters
+ * or frame numbering. */
 typedef struct sf_align_params {
   int32_t level;                    /* the one image size the solver works at, (W >> level) x (H >> level), 0..3: 1                 */
   int32_t down_width, down_height;  /* s_downsampledWidth / Height (:44-45); both 0: `level` decides, else the level of that size   */
@@ -363,10 +366,14 @@ typedef struct sf_align_params {
   float pair_max_angle;             /* sf_align_pairs: radians between two orientations, >= 0: 0.6                                  */
   float max_translation;            /* metres between a frame's input pose and its result, > 0: 0.5                                 */
   float max_rotation;               /* radians between them, > 0: 0.5                                                               */
-  int32_t reserved[9];
+  /* the colour term: read by sf_fuser_align_rgbd* only, sf_fuser_align* ignore the three */
+  float colour_weight;              /* weight of the squared intensity residual beside the squared metres, finite, >= 0: 0 (off)    */
+  float colour_thres;               /* s_denseColorThresh: largest |intensity residual| (intensity in 0..1), finite, >= 0: 0.1      */
+  float colour_gradient_min;        /* s_denseColorGradientMin: smallest gradient length per level pixel, finite, >= 0: 0.005       */
+  int32_t reserved[6];
 } sf_align_params;
 void sf_align_params_default(sf_align_params* a);
-/* s_denseDistThresh, s_denseNormalThresh, s_denseDepthMin / Max, s_downsampledWidth / Height and s_numGlobalNonLinIterations of an mLib ParameterFile
+/* s_denseDistThresh, s_denseNormalThresh, s_denseColorThresh, s_denseColorGradientMin, s_denseDepthMin / Max, s_downsampledWidth / Height and s_numGlobalNonLinIterations of an mLib ParameterFile
  * (zParametersBundlingScanNet.txt:22-44); keys that are absent leave *a as it is.  s_submapSize (:31) is the tool's keyframe stride, not a field. */
 int sf_align_params_load_file(const char* path, sf_align_params* a);
 typedef struct sf_align_result {
@@ -378,7 +385,9 @@ typedef struct sf_align_result {
   int32_t reserved0;
   int64_t correspondences;          /* of the last system                                                                           */
   float rms_first, rms_last;        /* sqrt(sum r^2 / correspondences) of the first and of the last system                          */
-  int32_t reserved[6];
+  int64_t colour_correspondences;   /* sf_fuser_align_rgbd*: correspondences of the last system that also gave a colour row (else 0) */
+  float colour_rms_first, colour_rms_last;   /* sqrt(sum r_c^2 / colour_correspondences), intensity in 0..1, first and last system  */
+  int32_t reserved[2];
 } sf_align_result;
 /* The default pair list (host only, double): for i < j both (i, j) and (j, i) when j = i + 1, or when the camera centres are within pair_max_dist and the
  * orientations within pair_max_angle (sf_reint_plan's angle); ascending i, then j, the forward pair first.  A frame whose pose has a non-finite element
@@ -397,6 +406,16 @@ int sf_fuser_align_device(sf_fuser* f, const void* d_depth, uint64_t frame_strid
 /* The same from host frames (K x input-size u16, one after the other). */
 int sf_fuser_align(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a,
                    float* poses_out, sf_align_result* result);
+/* The same with the keyframes' colour pictures: K RGB8 pictures `rgb_stride_bytes` apart, at the size the fuser fuses colour at
+ * (color_width x color_height, or depth_width x depth_height -- the size of the depth frames themselves, also where s_integrationWidth / Height resample them -- when color_width is 0).  Every depth correspondence whose source and target have an intensity
+ * (and the target a gradient) adds colour_weight x a photometric row to the pair's normal equations; the solve, the pair rule and every other field of
+ * the result are sf_fuser_align_device's, and with colour_weight 0 so are all their bits.  d_rgb may be NULL when colour_weight is 0 (no colour rows
+ * are counted then); NULL with colour_weight > 0, a negative or non-finite weight, threshold or gradient bound: SF_ERR_INVALID_ARG. */
+int sf_fuser_align_rgbd_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K,
+                               const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a, float* poses_out, sf_align_result* result);
+/* The same from host frames (K x input-size u16 and K x colour-size RGB8, one after the other). */
+int sf_fuser_align_rgbd(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
+                        const sf_align_params* a, float* poses_out, sf_align_result* result);
 
 /* Host <-> device helpers so that callers without a HIP binding can stage inputs in HBM. */
 int sf_device_malloc(int device, uint64_t bytes, void** out);

@@ -124,6 +124,11 @@ int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, const f
  * (DESIGN.md section 4e), summed as sf_fuser_align sums them, without solving.  depth: K host frames, u16 at the input size; sys: P x 29 doubles. */
 int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a,
                           double* sys);
+/* Its twin with the colour term (tests/test_align_colour.py): the P per-pair 31-value systems as sf_fuser_align_rgbd sums them --
+ * the 27 weighted sums, the depth term's sum r^2 and count, the colour term's sum r_c^2 and count.  rgb: K host pictures (NULL: colour_weight must be 0);
+ * sys: P x 31 doubles. */
+int sf_fuser_align_rgbd_system(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P,
+                               const sf_align_params* a, double* sys);
 
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);

@@ -6,18 +6,17 @@
 // pairs every source pixel of every pair with the target pixel it projects to and reduces the pair's 29 values per 256-pixel workgroup (no atomics);
 // k_align_final sums a pair's partials in index order in double; one read-back.  The host drops thin pairs, finds the frames connected to the fixed
 // frame, assembles the sparse-by-blocks normal equations densely and solves them by Cholesky in double.  Every step is deterministic and
-// tests/align_checker.c restates it bit for bit.
+// tests/align_checker.c restates it bit for bit.  sf_fuser_align_rgbd* run the same host loop over align_colour.hip's kernels, which add the dense
+// colour term's row to every correspondence and two sums to the pair's values (tests/align_colour_checker.c).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "align_internal.h"
 #include "common.h"
-#include "fuser_internal.h"
-#include "hip_util.h"
 #include "scanfuse_internal.h"
-#include "track_math.h"
 
 namespace {
 
@@ -26,10 +25,7 @@ using namespace tk;
 constexpr int AL_MAX_FRAMES = 256;
 constexpr int AL_MAX_PAIRS = 4096;
 
-struct PairEntry {   // one row of the device table; read through the scalar unit (the index is blockIdx.y)
-  int32_t i, j, active, pad;
-  Rows Ti, Tj, M;    // source pose, target pose, T_j^-1 T_i
-};
+using PairEntry = AlignPair;   // one row of the device table; read through the scalar unit (the index is blockIdx.y)
 
 // depth of pixel (x, y) of level L of a frame in metres: level 0 from the u16 frame, level L the 2x2 reduction of level L - 1
 template <int L>
@@ -104,16 +100,6 @@ __global__ void __launch_bounds__(64) k_align_final(const float* __restrict__ pa
 
 }  // namespace
 
-struct AlignWork {   // every buffer grows on demand and never shrinks
-  sf::DevBuf d_in;             // u8: host frames' device copy
-  sf::DevBuf vmap, nmap;       // float4 [K][npx]
-  sf::DevBuf partials;         // float [P][nb][32]
-  sf::DevBuf d_table;          // PairEntry [P]
-  sf::HostBuf h_table;         // page-locked
-  sf::DevBuf d_sys;            // double [P][29]
-  sf::HostBuf h_sys;           // page-locked read-back
-};
-
 void sf_align_release(sf_fuser* f) {
   if (!f) return;
   delete f->align;
@@ -164,18 +150,24 @@ int resolve_level(const sf_fuser* f, const sf_align_params* a, int* level, Cam* 
   return SF_OK;
 }
 
-int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames) {
+// the colour pictures the fuser fuses: color_width x color_height, or the integration size
+uint64_t picture_bytes(const sf_fuser* f) { return (f->pk.cW ? (uint64_t)f->pk.cW * f->pk.cH : (uint64_t)f->pk.W * f->pk.H) * 3; }
+
+// nsys: 29, or 31 with the colour term's sums; host_rgb / photo: the pictures come from the host / there are pictures at all
+int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames, int nsys = TK_NSYS, bool host_rgb = false, bool photo = false) {
   if (!f->align) f->align = new AlignWork();
   AlignWork* w = f->align;
   const size_t map_bytes = (size_t)K * npx * sizeof(float4);
   hipError_t e = w->d_in.reserve(host_frames ? (size_t)K * f->in_px * sizeof(uint16_t) : 0);
+  if (e == hipSuccess) e = w->d_rgb.reserve(host_rgb ? (size_t)K * picture_bytes(f) : 0);
+  if (e == hipSuccess) e = w->photo.reserve(photo ? map_bytes : 0);
   if (e == hipSuccess) e = w->vmap.reserve(map_bytes);
   if (e == hipSuccess) e = w->nmap.reserve(map_bytes);
   if (e == hipSuccess) e = w->partials.reserve((size_t)P * ((npx + 255) / 256) * TK_PSTRIDE * sizeof(float));
   if (e == hipSuccess) e = w->d_table.reserve(P * sizeof(PairEntry));
   if (e == hipSuccess) e = w->h_table.reserve(P * sizeof(PairEntry));
-  if (e == hipSuccess) e = w->d_sys.reserve(P * TK_NSYS * sizeof(double));
-  if (e == hipSuccess) e = w->h_sys.reserve(P * TK_NSYS * sizeof(double));
+  if (e == hipSuccess) e = w->d_sys.reserve(P * nsys * sizeof(double));
+  if (e == hipSuccess) e = w->h_sys.reserve(P * nsys * sizeof(double));
   if (e != hipSuccess) { sf_align_release(f); return sf::fail(SF_ERR_DEVICE, "alignment buffers: %s", hipGetErrorString(e)); }
   return SF_OK;
 }
@@ -188,6 +180,9 @@ struct Job {
   int level;
   Cam cam;
   float dmin, dmax;
+  int nsys = TK_NSYS;            // values per pair: 29, or 31 through sf_fuser_align_rgbd* (align_colour.hip's kernels)
+  const void* d_rgb = nullptr;   // the K colour pictures in HBM, rgb_stride bytes apart; nullptr: none
+  uint64_t rgb_stride = 0;
 };
 
 // the maps of all K frames, queued on f->stream behind everything queued on the handle so far
@@ -208,7 +203,7 @@ int prepare(sf_fuser* f, const Job& j) {
   }
 #undef AL_PREP
   SF_HIP_CHECK(hipGetLastError());
-  return SF_OK;
+  return j.d_rgb ? sf_photo_prepare(f, j.d_rgb, j.rgb_stride, j.K, j.level, j.cam) : SF_OK;
 }
 
 // the P systems at the poses T (K x 12 doubles; valid[k]: the frame takes part) into w->h_sys
@@ -226,13 +221,17 @@ int systems_at(sf_fuser* f, const Job& j, const double* T, const uint8_t* valid,
     compose_ref(Tj, Ti, e.M.T);
   }
   SF_HIP_CHECK(hipMemcpyAsync(w->d_table.p, w->h_table.p, j.P * sizeof(PairEntry), hipMemcpyHostToDevice, f->stream));
-  const int npx = j.cam.W * j.cam.H, nb = (npx + 255) / 256;
-  hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)j.P), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
-                     w->d_table.as<const PairEntry>(), j.cam, a->dist_thres, a->normal_thres, w->partials.as<float>());
-  SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_align_final, dim3((unsigned)j.P), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
-  SF_HIP_CHECK(hipGetLastError());
-  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, j.P * TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  if (j.nsys == AL_NSYS_RGBD) {
+    if (const int rc = sf_photo_systems(f, j.P, j.cam, a, j.d_rgb != nullptr)) return rc;
+  } else {
+    const int npx = j.cam.W * j.cam.H, nb = (npx + 255) / 256;
+    hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)j.P), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
+                       w->d_table.as<const PairEntry>(), j.cam, a->dist_thres, a->normal_thres, w->partials.as<float>());
+    SF_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_align_final, dim3((unsigned)j.P), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
+    SF_HIP_CHECK(hipGetLastError());
+  }
+  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, j.P * j.nsys * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   SF_HIP_CHECK(hipStreamSynchronize(f->stream));
   return SF_OK;
 }
@@ -258,6 +257,7 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
   if ((rc = prepare(f, j)) != SF_OK) return rc;
   const double* sys = f->align->h_sys.as<const double>();
   const int fixed = a->fixed_frame;
+  const size_t ns = (size_t)j.nsys;   // the loop reads a pair's first 29 values; the colour term's two only for the result
   std::vector<uint8_t> kept(j.P), conn(K, 0);
   std::vector<int> parent(K), slot(K);
   std::vector<double> A, b, xi;
@@ -266,7 +266,7 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
     for (uint64_t k = 0; k < K; k++) parent[k] = (int)k;
     for (uint64_t p = 0; p < j.P; p++) {
       const int pi = j.pairs[2 * p], pj = j.pairs[2 * p + 1];
-      kept[p] = valid[pi] && valid[pj] && sys[p * TK_NSYS + 28] >= (double)a->min_pair_correspondences;
+      kept[p] = valid[pi] && valid[pj] && sys[p * ns + 28] >= (double)a->min_pair_correspondences;
       if (!kept[p]) continue;
       const int ra = find_root(parent, pi), rb = find_root(parent, pj);
       if (ra != rb) parent[ra > rb ? ra : rb] = ra > rb ? rb : ra;   // the smaller index is the root
@@ -283,11 +283,11 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
     A.assign((size_t)N * N, 0.0);
     b.assign(N, 0.0);
     int used = 0;
-    double corr = 0.0, r2 = 0.0;
+    double corr = 0.0, r2 = 0.0, ccorr = 0.0, cr2 = 0.0;
     for (uint64_t p = 0; p < j.P; p++) {
       const int pi = j.pairs[2 * p], pj = j.pairs[2 * p + 1];
       if (!kept[p] || !conn[pi]) continue;
-      const double* s = sys + p * TK_NSYS;
+      const double* s = sys + p * ns;
       double Hm[6][6];
       int k = 0;
       for (int u = 0; u < 6; u++)
@@ -308,11 +308,15 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
       used++;
       r2 += s[27];
       corr += s[28];
+      if (j.nsys == AL_NSYS_RGBD) { cr2 += s[29]; ccorr += s[30]; }
     }
     r.pairs_used = used;
     r.correspondences = (int64_t)corr;
     r.rms_last = corr > 0.0 ? (float)std::sqrt(r2 / corr) : 0.0f;
     if (it == 0) r.rms_first = r.rms_last;
+    r.colour_correspondences = (int64_t)ccorr;
+    r.colour_rms_last = ccorr > 0.0 ? (float)std::sqrt(cr2 / ccorr) : 0.0f;
+    if (it == 0) r.colour_rms_first = r.colour_rms_last;
     xi.resize(N);
     if (!solve_spd(A.data(), b.data(), N, xi.data())) { r.status = 1; break; }
     double mx = 0.0;
@@ -334,13 +338,27 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
   return SF_OK;
 }
 
-// what the three entry points share: the checks in their order, the job, the device, the buffers and, for frames on the host, their copy into w->d_in
+// the colour term's three parameters, which only the rgbd entry points read
+int check_colour_args(const sf_align_params* a, const void* rgb) {
+  if (!std::isfinite(a->colour_weight) || !(a->colour_weight >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "alignment colour_weight %g: not a finite number >= 0", a->colour_weight);
+  if (!std::isfinite(a->colour_thres) || !(a->colour_thres >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "alignment colour_thres %g: not a finite number >= 0", a->colour_thres);
+  if (!std::isfinite(a->colour_gradient_min) || !(a->colour_gradient_min >= 0.0f))
+    return sf::fail(SF_ERR_INVALID_ARG, "alignment colour_gradient_min %g: not a finite number >= 0", a->colour_gradient_min);
+  if (!rgb && a->colour_weight > 0.0f) return sf::fail(SF_ERR_INVALID_ARG, "alignment colour_weight %g without colour pictures", a->colour_weight);
+  return SF_OK;
+}
+
+// what the entry points share: the checks in their order, the job, the device, the buffers and, for frames on the host, their copy into w->d_in (and
+// w->d_rgb).  rgbd: the call is one of sf_fuser_align_rgbd*; rgb may still be NULL (colour_weight 0)
 int begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool out_ok, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P,
-          const sf_align_params* a, Job* j) {
+          const sf_align_params* a, Job* j, bool rgbd = false, const void* rgb = nullptr, uint64_t rgb_stride = 0) {
   int rc = check_align_args(K, poses, pairs, P, a);
   if (rc != SF_OK) return rc;
+  if (rgbd && (rc = check_colour_args(a, rgb)) != SF_OK) return rc;
   if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
   if (!depth || !out_ok) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (rgb && on_device && rgb_stride < picture_bytes(f))
+    return sf::fail(SF_ERR_INVALID_ARG, "picture stride %llu bytes for pictures of %llu", (unsigned long long)rgb_stride, (unsigned long long)picture_bytes(f));
   const uint64_t frame_bytes = f->in_px * sizeof(uint16_t);
   if (on_device && (stride < frame_bytes || stride % sizeof(uint16_t)))
     return sf::fail(SF_ERR_INVALID_ARG, "frame stride %llu bytes for frames of %llu", (unsigned long long)stride, (unsigned long long)frame_bytes);
@@ -350,13 +368,21 @@ int begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool 
   j->dmin = own ? f->pk.dmin : a->depth_min;
   j->dmax = own ? f->pk.dmax : a->depth_max;
   SF_HIP_CHECK(hipSetDevice(f->device));
-  if ((rc = ensure_work(f, K, P, j->cam.W * j->cam.H, !on_device)) != SF_OK) return rc;
+  j->nsys = rgbd ? AL_NSYS_RGBD : TK_NSYS;
+  if ((rc = ensure_work(f, K, P, j->cam.W * j->cam.H, !on_device, j->nsys, rgb && !on_device, rgb != nullptr)) != SF_OK) return rc;
   j->d_depth = depth;
   j->stride = stride;
+  j->d_rgb = rgb;
+  j->rgb_stride = rgb_stride;
   if (!on_device) {
     j->d_depth = f->align->d_in.p;
     j->stride = frame_bytes;
     SF_HIP_CHECK(hipMemcpyAsync(f->align->d_in.p, depth, K * frame_bytes, hipMemcpyHostToDevice, f->stream));
+    if (rgb) {
+      j->d_rgb = f->align->d_rgb.p;
+      j->rgb_stride = picture_bytes(f);
+      SF_HIP_CHECK(hipMemcpyAsync(f->align->d_rgb.p, rgb, K * picture_bytes(f), hipMemcpyHostToDevice, f->stream));
+    }
   }
   return SF_OK;
 }
@@ -377,11 +403,27 @@ SF_API int sf_fuser_align(sf_fuser* f, const uint16_t* depth, uint64_t K, const 
   return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
 }
 
-SF_API int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a,
-                                 double* sys) {
+SF_API int sf_fuser_align_rgbd_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K,
+                                      const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a, float* poses_out, sf_align_result* result) {
   Job j;
-  int rc = begin(f, depth, false, 0, sys != nullptr, K, poses, pairs, P, a, &j);
-  if (rc != SF_OK || (rc = prepare(f, j)) != SF_OK) return rc;
+  const int rc = begin(f, d_depth, true, frame_stride_bytes, poses_out != nullptr, K, poses_in, pairs, P, a, &j, true, d_rgb, rgb_stride_bytes);
+  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
+}
+
+SF_API int sf_fuser_align_rgbd(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
+                               const sf_align_params* a, float* poses_out, sf_align_result* result) {
+  Job j;
+  const int rc = begin(f, depth, false, 0, poses_out != nullptr, K, poses_in, pairs, P, a, &j, true, rgb, 0);
+  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
+}
+
+namespace {
+
+// the test exports: the P systems at the given poses, j.nsys doubles each
+int systems_only(sf_fuser* f, const Job& j, const float* poses, const sf_align_params* a, double* sys) {
+  int rc = prepare(f, j);
+  if (rc != SF_OK) return rc;
+  const uint64_t K = j.K;
   std::vector<double> T(K * 12, 0.0);
   std::vector<uint8_t> valid(K);
   for (uint64_t k = 0; k < K; k++) {
@@ -389,8 +431,24 @@ SF_API int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K,
     for (int i = 0; i < 12 && valid[k]; i++) T[12 * k + i] = (double)poses[16 * k + i];
   }
   if ((rc = systems_at(f, j, T.data(), valid.data(), a)) != SF_OK) return rc;
-  std::memcpy(sys, f->align->h_sys.p, P * TK_NSYS * sizeof(double));
+  std::memcpy(sys, f->align->h_sys.p, j.P * j.nsys * sizeof(double));
   return SF_OK;
+}
+
+}  // namespace
+
+SF_API int sf_fuser_align_rgbd_system(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P,
+                                      const sf_align_params* a, double* sys) {
+  Job j;
+  const int rc = begin(f, depth, false, 0, sys != nullptr, K, poses, pairs, P, a, &j, true, rgb, 0);
+  return rc != SF_OK ? rc : systems_only(f, j, poses, a, sys);
+}
+
+SF_API int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a,
+                                 double* sys) {
+  Job j;
+  const int rc = begin(f, depth, false, 0, sys != nullptr, K, poses, pairs, P, a, &j);
+  return rc != SF_OK ? rc : systems_only(f, j, poses, a, sys);
 }
 
 // ======================================================================================================

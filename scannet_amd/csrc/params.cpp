@@ -269,6 +269,9 @@ SF_API void sf_align_params_default(sf_align_params* a) {
   a->pair_max_angle = 0.6f;
   a->max_translation = 0.5f;
   a->max_rotation = 0.5f;
+  a->colour_weight = 0.0f;            // the colour term is off: metres and intensity have no common unit (DESIGN.md 4f has the working weight)
+  a->colour_thres = 0.1f;             // s_denseColorThresh (:24)
+  a->colour_gradient_min = 0.005f;    // s_denseColorGradientMin (:25)
 }
 
 // the dense-term keys of zParametersBundlingScanNet.txt:22-44
@@ -279,6 +282,7 @@ SF_API int sf_align_params_load_file(const char* path, sf_align_params* a) {
   if (rc != SF_OK) return rc;
   const struct { const char* key; float* f; int32_t* i; } keys[] = {
       {"s_denseDistThresh", &a->dist_thres, nullptr}, {"s_denseNormalThresh", &a->normal_thres, nullptr},
+      {"s_denseColorThresh", &a->colour_thres, nullptr}, {"s_denseColorGradientMin", &a->colour_gradient_min, nullptr},
       {"s_denseDepthMin", &a->depth_min, nullptr}, {"s_denseDepthMax", &a->depth_max, nullptr},
       {"s_downsampledWidth", nullptr, &a->down_width}, {"s_downsampledHeight", nullptr, &a->down_height},
       {"s_numGlobalNonLinIterations", nullptr, &a->max_iters}};

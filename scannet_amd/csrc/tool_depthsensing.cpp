@@ -50,6 +50,7 @@ extern char** environ;
 #pragma weak sf_fuser_integrate
 // --align's solver and the re-integration behind it
 #pragma weak sf_fuser_align
+#pragma weak sf_fuser_align_rgbd
 #pragma weak sf_align_pairs
 #pragma weak sf_align_spread
 #pragma weak sf_fuse_update_trajectory
@@ -91,6 +92,7 @@ struct Args {
   const char* write_sens = nullptr;   // --write-sens=<out.sens>: the input with the tracked (and, with --align, corrected) trajectory
   int align = -1;                     // --align[=N]: keyframes every N-th tracked frame are aligned jointly (see align_scan below); 0: N from the parameter file
   const char* align_params = nullptr; // --align-params=<file>: zParametersBundlingScanNet.txt
+  float align_colour = -1.0f;         // --align-colour[=w]: --align's solver with the dense colour term at weight w; < 0: depth only
   const char* pos[8];
   int n_pos = 0;
 };
@@ -234,6 +236,8 @@ int render_depth(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_in
 // ---- --align[=N] [--align-params=<file>] (after --track): every N-th tracked frame is a keyframe (N: s_submapSize of the file, zParametersBundlingScanNet.txt:31,
 // or 10); the keyframes are aligned jointly over the default pair list (sf_align_pairs, sf_fuser_align), the correction is carried to the frames between
 // them (sf_align_spread) and the volume is moved to the corrected trajectory (sf_fuse_update_trajectory).  traj: n x 16, in: what the volume holds, out: the same.
+// --align-colour[=w]: the keyframes' colour frames go with their depth and the solver adds the dense colour term at weight w (sf_fuser_align_rgbd).
+constexpr float ALIGN_COLOUR_WEIGHT = 0.1f;   // --align-colour without a value: the working weight (DESIGN.md 4f has the sweep)
 int submap_size(const char* path) {
   FILE* fp = std::fopen(path, "r");
   if (!fp) return -1;
@@ -253,6 +257,8 @@ int submap_size(const char* path) {
 
 int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info& info, bool color, std::vector<float>& traj) {
   if (!sf_fuser_align || !sf_align_pairs || !sf_align_spread || !sf_fuse_update_trajectory) return die_msg("--align: this libscanfuse has no alignment");
+  const bool photo = a.align_colour >= 0.0f;
+  if (photo && !sf_fuser_align_rgbd) return die_msg("--align-colour: this libscanfuse has no colour term");
   sf_align_params ap;
   sf_align_params_default(&ap);
   int every = a.align;
@@ -262,6 +268,7 @@ int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
   }
   if (every == 0) every = 10;
   if (every < 1) return die_msg("--align: a keyframe stride of %d", every);
+  if (photo) ap.colour_weight = a.align_colour;
   const uint64_t n = info.num_frames;
   std::vector<uint64_t> keys;
   uint64_t tracked = 0;
@@ -276,10 +283,13 @@ int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
   if (K < 2) { say("Aligned nothing: %llu keyframes\n", (unsigned long long)K); return 0; }
   if (K > 256) return die_msg("--align=%d gives %llu keyframes, the solver takes 256: choose a larger stride", every, (unsigned long long)K);
   const size_t px = (size_t)info.depth_width * info.depth_height;
+  const size_t cpx = (size_t)info.color_width * info.color_height * 3;
   std::vector<uint16_t> depth(K * px);
+  std::vector<uint8_t> rgb(photo ? K * cpx : 0);
   std::vector<float> kp(K * 16), knew(K * 16);
   for (uint64_t k = 0; k < K; k++) {
     if (sf_sens_decode_depth(sens, keys[k], depth.data() + k * px) != SF_OK) return die("depth frame");
+    if (photo && sf_sens_decode_color(sens, keys[k], rgb.data() + k * cpx) != SF_OK) return die("colour frame");
     std::memcpy(&kp[16 * k], &traj[16 * keys[k]], 16 * sizeof(float));
   }
   std::vector<int32_t> pairs(2 * 4096);
@@ -288,11 +298,16 @@ int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
   if (P > 4096) return die_msg("--align: %llu pairs, the solver takes 4096: choose a larger stride", (unsigned long long)P);
   sf_align_result res;
   const auto t0 = std::chrono::steady_clock::now();
-  if (sf_fuser_align(fuser, depth.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res) != SF_OK) return die("alignment");
+  if ((photo ? sf_fuser_align_rgbd(fuser, depth.data(), rgb.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res)
+             : sf_fuser_align(fuser, depth.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res)) != SF_OK)
+    return die("alignment");
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   say("Aligned %llu keyframes (every %d) over %llu pairs in %.1f ms: status %d, %d iterations, %d pairs and %lld correspondences in the last system, rms %.4f -> %.4f m, "
       "%d unconnected, %d rejected\n", (unsigned long long)K, every, (unsigned long long)P, ms, res.status, res.iterations, res.pairs_used, (long long)res.correspondences,
       res.rms_first, res.rms_last, res.frames_unconnected, res.frames_rejected);
+  if (photo)
+    say("Colour term at weight %g: %lld colour correspondences in the last system, rms %.4f -> %.4f of the intensity range\n", ap.colour_weight,
+        (long long)res.colour_correspondences, res.colour_rms_first, res.colour_rms_last);
   if (res.status != 0) return 0;   // the poses came back as they went in
   std::vector<float> target(n * 16);
   if (sf_align_spread(traj.data(), n, keys.data(), K, knew.data(), target.data()) != SF_OK) return die("spread");
@@ -398,6 +413,10 @@ int fuse_scan(const Args& a) {
     p.color_width = (int32_t)info.color_width; p.color_height = (int32_t)info.color_height;
     p.cfx = info.color_intrinsic[0]; p.cfy = info.color_intrinsic[5]; p.cmx = info.color_intrinsic[2]; p.cmy = info.color_intrinsic[6];
   }
+  if (a.align_colour >= 0.0f && !(info.color_width > 0 && info.color_height > 0 &&
+                                  (p.color_width > 0 || (info.color_width == info.depth_width && info.color_height == info.depth_height))))
+    return die_msg("--align-colour adds a colour term to --align: %s has no colour frames the fuser can use (%u x %u); run --align without --align-colour", sens_path,
+                   info.color_width, info.color_height);
   const int device = std::getenv("SF_DEVICE") ? std::atoi(std::getenv("SF_DEVICE")) : 0;
   (void)sf_fuse_run_prepare(sens, &p, device);   // the run's streams and rings, sized for this file, made beside the fuser's own allocations (an optimisation: failures surface in sf_fuser_create)
   sf_fuser* fuser = nullptr;
@@ -640,15 +659,23 @@ int main(int argc, const char** argv_in) {
     else if (!std::strcmp(s, "--align")) a.align = 0;
     else if (!std::strncmp(s, "--align=", 8)) { a.align = std::atoi(s + 8); if (a.align < 1) bad = true; }
     else if (!std::strncmp(s, "--align-params=", 15) && s[15]) a.align_params = s + 15;
+    else if (!std::strcmp(s, "--align-colour")) a.align_colour = ALIGN_COLOUR_WEIGHT;
+    else if (!std::strncmp(s, "--align-colour=", 15) && s[15]) {
+      char* end = nullptr;
+      a.align_colour = std::strtof(s + 15, &end);
+      if (*end || !std::isfinite(a.align_colour) || a.align_colour < 0.0f) bad = true;
+    }
     else if (i > 0 && !std::strncmp(s, "--", 2)) bad = true;
     else if (a.n_pos < 8) a.pos[a.n_pos++] = s;
   }
   if (a.n_pos < 4 || bad || a.ranks < 1 || a.ranks > 64 || (a.rank >= 0 && (a.rank >= a.ranks || a.ipc.empty()))) {
-    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--align[=N]] [--align-params=<zParametersBundling.txt>] [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
+    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--align[=N] [--align-colour[=w]]] [--align-params=<zParametersBundling.txt>] [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
     return 255;
   }
   if (a.render_dir && a.ranks > 1)
     return die_msg("--render-depth ray-casts one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to render", a.ranks);
+  if (a.align_colour >= 0.0f && a.align < 0)
+    return die_msg("--align-colour adds the dense colour term to --align's solver: it needs --track --align");
   if ((a.align >= 0 || a.align_params) && !a.track)
     return die_msg("--align aligns the keyframes of the tracked trajectory: it needs --track");
   if (a.track && a.ranks > 1)

@@ -91,8 +91,11 @@ __device__ inline void vertex_normal(const Cam& c, int x, int y, float dz, bool 
   }
 }
 
-// the 29 values of one correspondence: world point p, model normal nm, d = p - q.  J = (p x nm, nm), r = nm . d
-__device__ inline void row29(float3 p, float3 nm, float3 d, float (&acc)[TK_NSYS]) {
+// the 29 values of one correspondence: world point p, model normal nm, d = p - q.  J = (p x nm, nm), r = nm . d.  (acc may be longer: the colour term's
+// two sums follow the 29, align_colour.hip)
+template <int N>
+__device__ inline void row29(float3 p, float3 nm, float3 d, float (&acc)[N]) {
+  static_assert(N >= TK_NSYS, "the row has TK_NSYS values");
   const float r = dot3(nm, d);
   const float3 c = cross3(p, nm);
   const float J[6] = {c.x, c.y, c.z, nm.x, nm.y, nm.z};
@@ -110,9 +113,9 @@ __device__ inline void row29(float3 p, float3 nm, float3 d, float (&acc)[TK_NSYS
 // one source pixel (camera-space vertex v4, normal n4) against a target: T the source's pose, M the source in the target's camera, c that camera at the
 // level.  target(ux, uy, &q, &nm) looks up the world point and normal of target pixel (ux, uy) and returns false where it has none.  Fills acc and
 // returns true where the pixel is a correspondence
-template <typename Target>
+template <typename Target, int N>
 __device__ inline bool correspond(const Cam& c, const Rows& T, const Rows& M, float4 v4, float4 n4, float dist_thres, float normal_thres, Target target,
-                                  float (&acc)[TK_NSYS]) {
+                                  float (&acc)[N]) {
   if (v4.z > 0.0f && n4.x > -INFINITY) {
     const float3 v = make_float3(v4.x, v4.y, v4.z);
     const float3 p = xf(T, v), n = rot(T, make_float3(n4.x, n4.y, n4.z));
@@ -134,19 +137,21 @@ __device__ inline bool correspond(const Cam& c, const Rows& T, const Rows& M, fl
   return false;
 }
 
-// the workgroup's 256 lanes reduced to one 29-float partial: xor butterfly 32 .. 1 within the wave (every lane ends with the wave's sum: a + b and
-// b + a are the same float), (w0 + w1) + (w2 + w3) across the four waves.  No atomics.
-__device__ inline void reduce256(float (&acc)[TK_NSYS], float (&red)[4][TK_NSYS], float* __restrict__ partial) {
+// the workgroup's 256 lanes reduced to one N-float partial (N = 29; 31 with the colour term's two sums, align_colour.hip): xor butterfly 32 .. 1 within
+// the wave (every lane ends with the wave's sum: a + b and b + a are the same float), (w0 + w1) + (w2 + w3) across the four waves.  No atomics.
+template <int N>
+__device__ inline void reduce256(float (&acc)[N], float (&red)[4][N], float* __restrict__ partial) {
+  static_assert(N <= TK_PSTRIDE, "a partial holds TK_PSTRIDE floats");
 #pragma unroll
-  for (int k = 0; k < TK_NSYS; k++)
+  for (int k = 0; k < N; k++)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc[k] = acc[k] + __shfl_xor(acc[k], off);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
-    for (int k = 0; k < TK_NSYS; k++) red[wave][k] = acc[k];
+    for (int k = 0; k < N; k++) red[wave][k] = acc[k];
   __syncthreads();
-  if (threadIdx.x < TK_NSYS) {
+  if (threadIdx.x < N) {
     const int k = threadIdx.x;
     partial[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
   }

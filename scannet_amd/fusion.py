@@ -150,18 +150,22 @@ class SfAlignParams(C.Structure):
                 ("dist_thres", C.c_float), ("normal_thres", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("early_out", C.c_float),
                 ("min_pair_correspondences", C.c_int32), ("fixed_frame", C.c_int32),
                 ("pair_max_dist", C.c_float), ("pair_max_angle", C.c_float), ("max_translation", C.c_float), ("max_rotation", C.c_float),
-                ("reserved", C.c_int32 * 9)]
+                ("colour_weight", C.c_float), ("colour_thres", C.c_float), ("colour_gradient_min", C.c_float),
+                ("reserved", C.c_int32 * 6)]
 
 
 class SfAlignResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("pairs_used", C.c_int32), ("frames_unconnected", C.c_int32),
                 ("frames_rejected", C.c_int32), ("reserved0", C.c_int32), ("correspondences", C.c_int64),
-                ("rms_first", C.c_float), ("rms_last", C.c_float), ("reserved", C.c_int32 * 6)]
+                ("rms_first", C.c_float), ("rms_last", C.c_float), ("colour_correspondences", C.c_int64),
+                ("colour_rms_first", C.c_float), ("colour_rms_last", C.c_float), ("reserved", C.c_int32 * 2)]
 
     def as_dict(self):
         return dict(status=int(self.status), iterations=int(self.iterations), pairs_used=int(self.pairs_used),
                     frames_unconnected=int(self.frames_unconnected), frames_rejected=int(self.frames_rejected),
-                    correspondences=int(self.correspondences), rms_first=float(self.rms_first), rms_last=float(self.rms_last))
+                    correspondences=int(self.correspondences), rms_first=float(self.rms_first), rms_last=float(self.rms_last),
+                    colour_correspondences=int(self.colour_correspondences), colour_rms_first=float(self.colour_rms_first),
+                    colour_rms_last=float(self.colour_rms_last))
 
 
 def default_align_params(**over):
@@ -179,7 +183,7 @@ def default_align_params(**over):
 
 
 def load_align_params(path, base=None):
-    """The dense-term keys (s_denseDistThresh, s_denseNormalThresh, s_denseDepthMin / Max, s_downsampledWidth / Height,
+    """The dense-term keys (s_denseDistThresh, s_denseNormalThresh, s_denseColorThresh, s_denseColorGradientMin, s_denseDepthMin / Max, s_downsampledWidth / Height,
     s_numGlobalNonLinIterations) of an mLib ParameterFile such as zParametersBundlingScanNet.txt; absent keys leave the base as it is."""
     a = base if base is not None else default_align_params()
     L = _abi.lib()
@@ -222,11 +226,20 @@ def align_keyframes(poses, every):
     return good[::max(1, int(every))].astype(np.uint64)
 
 
-def align_and_reintegrate(fuser, sensor_data, integrated, every=10, params=None, reint_params=None, colour=False):
+ALIGN_COLOUR_WEIGHT = 0.1   # the working weight of the colour term (DESIGN.md 4f has the sweep); sf_align_params_default keeps 0, the term off
+
+
+def align_and_reintegrate(fuser, sensor_data, integrated, every=10, params=None, reint_params=None, colour=False, with_colour=False, colour_weight=None):
     """The correction loop: keyframes are every `every`-th frame with a finite integrated pose; their depth is decoded, the default pairs built, the
     keyframes aligned (Fuser.align), the correction spread over the trajectory, and the volume moved there (Fuser.update_trajectory, which updates a
-    float32 C-contiguous `integrated` in place).  -> (target poses float32 [n,16], SfAlignResult, re-integration statistics)."""
+    float32 C-contiguous `integrated` in place).  with_colour: the keyframes' colour pictures are decoded too and the aligner runs its colour term
+     with `colour_weight` (None: the parameters' own when positive, else ALIGN_COLOUR_WEIGHT).  `colour` is the re-integration's:
+    the file's colour frames go back into the volume with the depth.  -> (target poses float32 [n,16], SfAlignResult, re-integration statistics)."""
     a = params if params is not None else default_align_params()
+    if with_colour:
+        b = SfAlignParams.from_buffer_copy(a)
+        b.colour_weight = float(colour_weight) if colour_weight is not None else (a.colour_weight if a.colour_weight > 0 else ALIGN_COLOUR_WEIGHT)
+        a = b
     cur = np.ascontiguousarray(integrated, dtype=np.float32).reshape(-1, 16)
     keys = align_keyframes(cur, every)
     if len(keys) < 2:
@@ -235,7 +248,10 @@ def align_and_reintegrate(fuser, sensor_data, integrated, every=10, params=None,
     pairs, count = align_pairs(cur[keys.astype(np.int64)], a)
     if count > len(pairs):
         raise ValueError("the pair rule gives %d pairs, the solver takes %d" % (count, len(pairs)))
-    new, res = fuser.align(depth, cur[keys.astype(np.int64)], pairs, a)
+    rgb = None
+    if with_colour:
+        rgb = np.stack([np.ascontiguousarray(sensor_data.frames[int(k)].decompress_color(), dtype=np.uint8).reshape(-1) for k in keys])
+    new, res = fuser.align(depth, cur[keys.astype(np.int64)], pairs, a, rgb=rgb)
     target = align_spread(cur, keys, new)
     _, stats = fuser.update_trajectory(sensor_data, integrated, target, params=reint_params, colour=colour)
     return target, res, stats
@@ -613,9 +629,20 @@ class Fuser:
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         return a, poses, pairs
 
-    def align(self, depth, poses, pairs, params=None):
+    def _align_rgb(self, rgb, K):
+        """K RGB8 pictures at the size the fuser fuses colour at (color_width x color_height, else the size of the depth frames given to it), contiguous."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        p = self.params
+        cw, ch = (p.color_width, p.color_height) if p.color_width > 0 and p.color_height > 0 else (p.depth_width, p.depth_height)
+        if rgb.size != K * cw * ch * 3:
+            raise ValueError("rgb holds %d bytes, %d pictures of %dx%dx3 expected" % (rgb.size, K, cw, ch))
+        return rgb
+
+    def align(self, depth, poses, pairs, params=None, rgb=None):
         """sf_fuser_align: K u16 keyframes (host, [K, H*W] at the fuser's input size) with camToWorld poses [K,16] aligned jointly over the directed
-        pairs [P,2] (source, target).  -> (poses float32 [K,16], SfAlignResult)."""
+        pairs [P,2] (source, target).  rgb: the keyframes' RGB8 pictures ([K, h*w*3] at the size the fuser fuses colour at, color_width x color_height, else
+        the depth frames' own size): sf_fuser_align_rgbd, the
+        colour term of DESIGN.md 4f with the parameters' colour_weight.  -> (poses float32 [K,16], SfAlignResult)."""
         a, poses, pairs = self._align_args(poses, pairs, params)
         depth = np.ascontiguousarray(depth, dtype=np.uint16)
         if depth.size != len(poses) * self.params.depth_width * self.params.depth_height:
@@ -623,17 +650,30 @@ class Fuser:
         out = np.empty_like(poses)
         res = SfAlignResult()
         L = _abi.lib()
+        if rgb is not None:
+            rgb = self._align_rgb(rgb, len(poses))
+            L.sf_fuser_align_rgbd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams),
+                                              C.c_void_p, C.POINTER(SfAlignResult)]
+            check(L.sf_fuser_align_rgbd(self._h, _ptr(depth), _ptr(rgb), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a), _ptr(out), C.byref(res)))
+            return out, res
         L.sf_fuser_align.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams), C.c_void_p,
                                      C.POINTER(SfAlignResult)]
         check(L.sf_fuser_align(self._h, _ptr(depth), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a), _ptr(out), C.byref(res)))
         return out, res
 
-    def align_device(self, d_depth, frame_stride_bytes, poses, pairs, params=None):
-        """align() for keyframes already in HBM (torch tensor or raw pointer), `frame_stride_bytes` apart, read on self.stream."""
+    def align_device(self, d_depth, frame_stride_bytes, poses, pairs, params=None, d_rgb=None, rgb_stride_bytes=0):
+        """align() for keyframes already in HBM (torch tensor or raw pointer), `frame_stride_bytes` apart, read on self.stream.  d_rgb: the
+        keyframes' pictures in HBM, `rgb_stride_bytes` apart (sf_fuser_align_rgbd_device)."""
         a, poses, pairs = self._align_args(poses, pairs, params)
         out = np.empty_like(poses)
         res = SfAlignResult()
         L = _abi.lib()
+        if d_rgb is not None:
+            L.sf_fuser_align_rgbd_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                     C.POINTER(SfAlignParams), C.c_void_p, C.POINTER(SfAlignResult)]
+            check(L.sf_fuser_align_rgbd_device(self._h, _ptr(d_depth), int(frame_stride_bytes), _ptr(d_rgb),
+                                               int(rgb_stride_bytes), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a), _ptr(out), C.byref(res)))
+            return out, res
         L.sf_fuser_align_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams),
                                             C.c_void_p, C.POINTER(SfAlignResult)]
         check(L.sf_fuser_align_device(self._h, _ptr(d_depth), int(frame_stride_bytes), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a),
@@ -648,6 +688,21 @@ class Fuser:
         L = _abi.lib()
         L.sf_fuser_align_system.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams), C.c_void_p]
         check(L.sf_fuser_align_system(self._h, _ptr(depth), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a), _ptr(sys)))
+        return sys
+
+    def align_rgbd_system(self, depth, rgb, poses, pairs, params=None):
+        """Test hook (scanfuse_internal.h sf_fuser_align_rgbd_system): the P per-pair 31-value systems (float64 [P,31]) at the given poses; rgb may be
+        None when colour_weight is 0."""
+        a, poses, pairs = self._align_args(poses, pairs, params)
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if rgb is not None:
+            rgb = self._align_rgb(rgb, len(poses))
+        sys = np.zeros((len(pairs), 31), np.float64)
+        L = _abi.lib()
+        L.sf_fuser_align_rgbd_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams),
+                                                 C.c_void_p]
+        check(L.sf_fuser_align_rgbd_system(self._h, _ptr(depth), _ptr(rgb) if rgb is not None else None, len(poses), _ptr(poses), _ptr(pairs), len(pairs),
+                                           C.byref(a), _ptr(sys)))
         return sys
 
     # -- camera tracking (DESIGN.md "Camera tracking") --------------------------------------------------

@@ -4,8 +4,10 @@ their poses drifted k x (2 mm, 1 mrad) so that the solver has something to do.  
 
     python tools/align_bench.py                  # the table below, on stdout
     python tools/align_bench.py --profile DIR    # the same command under rocprofv3 --kernel-trace --stats (a run of its own), per-kernel device time appended
+    python tools/align_bench.py --colour         # the depth-only call, then sf_fuser_align_rgbd_device with the colour term on the same frames, poses and pairs
+                                                 # (a sinusoid texture painted on by world position); --profile DIR goes with it
 
-The numbers in profiles/align.txt are this tool's output (DESIGN.md "Global alignment").
+The numbers in profiles/align.txt and, with --colour, profiles/align_colour.txt are this tool's output (DESIGN.md "Global alignment", 4e and 4f).
 """
 import argparse
 import csv
@@ -33,7 +35,25 @@ def drift(pose, dt, rad, axis=(0.3, -0.5, 0.8), tdir=(0.6, 0.64, -0.48)):
     return out.astype(np.float32)
 
 
-def run(calls):
+def paint(depth, pose, fx, fy, mx, my):
+    """RGB8 [H*W*3] of one frame: a sum of sinusoids at each pixel's world position (wavelengths of 16 .. 64 level-1 pixels at 2.5 m)."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    d = depth.reshape(H, W).astype(np.float64) / 1000.0
+    cam = np.stack([(xx - mx) / fx * d, (yy - my) / fy * d, d], -1)
+    p = np.asarray(pose, np.float64).reshape(4, 4)
+    wp = cam @ p[:3, :3].T + p[:3, 3]
+    X, Y = wp[..., 0] + 0.7 * wp[..., 2], wp[..., 1] - 0.7 * wp[..., 2]
+    foot = 2.5 / (fx / 2)
+    out = []
+    for amps in ((0.06, 0.10, 0.12, 0.12), (0.05, 0.12, 0.10, 0.14), (0.10, 0.06, 0.14, 0.08)):
+        v = np.full(X.shape, 0.5)
+        for (lam, th, ph), a in zip(((16.0, 0.3, 0.0), (24.0, 1.9, 1.0), (40.0, 2.6, 2.0), (64.0, 1.1, 4.0)), amps):
+            v = v + a * np.sin(2 * np.pi * (X * np.cos(th) + Y * np.sin(th)) / (lam * foot) + ph)
+        out.append(v)
+    return np.clip(np.rint(np.stack(out, -1) * 255.0), 0, 255).astype(np.uint8).reshape(-1)
+
+
+def run(calls, colour=False):
     import torch
     from scannet_amd import fusion, synth
     fx, fy, mx, my = synth.intrinsics(W, H)
@@ -52,6 +72,17 @@ def run(calls):
             out, res = f.align_device(d, W * H * 2, start, pairs, a)
             if i:
                 times.append((time.perf_counter() - t0) * 1e3)
+        if colour:
+            host = d.cpu().numpy().view(np.uint16)
+            c = torch.from_numpy(np.stack([paint(host[k], truth[k], fx, fy, mx, my) for k in range(K)])).to("cuda:0")
+            torch.cuda.synchronize()
+            ac = fusion.default_align_params(colour_weight=fusion.ALIGN_COLOUR_WEIGHT)
+            ctimes = []
+            for i in range(calls + 1):
+                t0 = time.perf_counter()
+                cout, cres = f.align_device(d, W * H * 2, start, pairs, ac, d_rgb=c, rgb_stride_bytes=W * H * 3)
+                if i:
+                    ctimes.append((time.perf_counter() - t0) * 1e3)
         err0 = max(float(np.linalg.norm(s.reshape(4, 4)[:3, 3] - t.reshape(4, 4)[:3, 3])) for s, t in zip(start, truth))
         err1 = max(float(np.linalg.norm(o.reshape(4, 4)[:3, 3] - t.reshape(4, 4)[:3, 3])) for o, t in zip(out, truth))
     t = sorted(times)
@@ -61,11 +92,23 @@ def run(calls):
         res.iterations, res.pairs_used, res.correspondences, res.rms_first, res.rms_last, res.status, res.frames_unconnected, res.frames_rejected))
     print("per iteration: %.2f ms (median call / iterations, preparation included)" % (t[len(t) // 2] / max(1, res.iterations)))
     print("worst keyframe translation error: %.1f mm at the start, %.1f mm after" % (err0 * 1e3, err1 * 1e3))
+    if colour:
+        ct = sorted(ctimes)
+        errc = max(float(np.linalg.norm(o.reshape(4, 4)[:3, 3] - t.reshape(4, 4)[:3, 3])) for o, t in zip(cout, truth))
+        print("sf_fuser_align_rgbd_device: the same frames, poses and pairs with %d x %d pictures, colour_weight %g" % (W, H, ac.colour_weight))
+        print("whole call, %d calls after a warm-up: min %.2f ms, median %.2f ms, max %.2f ms" % (len(ct), ct[0], ct[len(ct) // 2], ct[-1]))
+        print("iterations %d, pairs in the last system %d, correspondences %d (%d with a colour row), rms %.5f -> %.5f m, colour rms %.5f -> %.5f, status %d, "
+              "unconnected %d, rejected %d" % (cres.iterations, cres.pairs_used, cres.correspondences, cres.colour_correspondences, cres.rms_first, cres.rms_last,
+                                               cres.colour_rms_first, cres.colour_rms_last, cres.status, cres.frames_unconnected, cres.frames_rejected))
+        print("per iteration: %.2f ms (median call / iterations, preparation included)" % (ct[len(ct) // 2] / max(1, cres.iterations)))
+        print("worst keyframe translation error: %.1f mm after" % (errc * 1e3))
 
 
-def profile(outdir):
+def profile(outdir, colour=False):
     os.makedirs(outdir, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", outdir, "--", sys.executable, os.path.abspath(__file__), "--calls", "1"]
+    if colour:
+        cmd.append("--colour")
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         print("rocprofv3 failed (%d):\n%s" % (r.returncode, (r.stdout + r.stderr)[-2000:]))
@@ -76,7 +119,7 @@ def profile(outdir):
     print("per-kernel device time (rocprofv3 --kernel-trace --stats, a run of its own: warm-up + 1 call):")
     for row in rows:
         name = row.get("Name", "")
-        if "k_align" in name or "k_synth" in name:
+        if "k_align" in name or "k_photo" in name or "k_synth" in name:
             print("  %-60s calls %6s  total %10.1f us  average %9.1f us" % (name[:60], row.get("Calls"), float(row.get("TotalDurationNs", 0)) / 1e3,
                                                                             float(row.get("AverageNs", 0)) / 1e3))
     return 0
@@ -86,7 +129,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=REPEATS)
     ap.add_argument("--profile", metavar="DIR")
+    ap.add_argument("--colour", action="store_true")
     args = ap.parse_args()
     if args.profile:
-        sys.exit(profile(args.profile))
-    run(args.calls)
+        sys.exit(profile(args.profile, args.colour))
+    run(args.calls, args.colour)
