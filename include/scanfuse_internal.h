@@ -130,6 +130,32 @@ int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const 
 int sf_fuser_align_rgbd_system(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P,
                                const sf_align_params* a, double* sys);
 
+/* Stage hooks of the 2-D annotation filter (tests/test_filter2d_stages.py; scannet_amd/csrc/filter2d.hip): each call runs ONE kernel of the filter on host
+ * arrays on GPU `device`, through the launcher sf_filter2d_frame uses for it (same grid, same workgroup, same dynamic LDS), and returns the output to the
+ * host.  Images are row-major, w x h.  Sides are 1 .. 16384 (2 .. 16384 for the resamples, whose scale divides by side - 1).
+ * Window radius: at most 35 -- what k_f2d_vote's dynamic-LDS budget holds (the 80 x 256 x 4 B histogram + (2r + 1)^2 x 4 B spatial table <= 100 KiB;
+ * r = 36 would need 103 236 B); the bilateral hook takes the same bound on its radius ceil(2 sigma_d), i.e. sigma_d <= 17.5.  Anything else is
+ * SF_ERR_INVALID_ARG, not a launch.
+ *   prepare          depth16[dn] (mm) -> depth_out[dn] (m, 0 -> -inf), rgb[3 cn] -> intensity_out[cn]
+ *   bilateral        in -> out, radius ceil(2 sigma_d)
+ *   resample_float / resample_uchar
+ *                    `out` (ow x oh) is BOTH the initial contents of the output and the result: pixels whose source position rounds outside keep it
+ *   vote             one pass of the weighted vote over a (2 radius + 1)^2 window
+ *   to_label         label_out[i] = instance_to_label[instance[i]] */
+int sf_filter2d_stage_prepare(int device, const uint16_t* depth16, int dn, const uint8_t* rgb, int cn, float* depth_out, float* intensity_out);
+int sf_filter2d_stage_bilateral(int device, const float* in, float sigma_d, float sigma_r, int w, int h, float* out);
+int sf_filter2d_stage_resample_float(int device, const float* in, int iw, int ih, float* out, int ow, int oh);
+int sf_filter2d_stage_resample_uchar(int device, const uint8_t* in, int iw, int ih, uint8_t* out, int ow, int oh);
+int sf_filter2d_stage_vote(int device, const uint8_t* instance_in, const float* depth, const float* intensity, const uint8_t instance_to_idx[256],
+                           const uint8_t idx_to_instance[80], int radius, int w, int h, float sigma_d, float sigma_r, float intensity_scale,
+                           uint8_t* instance_out);
+int sf_filter2d_stage_to_label(int device, const uint8_t* instance, const uint16_t instance_to_label[256], int n, uint16_t* label_out);
+/* Element-wise probe of the filter's two Gaussians as the kernels evaluate them (exp table in LDS; the range Gaussian through its three-operation
+ * quotient): out_r[i] = gaussR(sigma, dist[i]), out_d[i] = gaussD(sigma, dx[i], dy[i]).  Either group (dist + out_r, or dx + dy + out_d) may be NULL.
+ * dist[i]^2 must be finite in binary32 (|dist| < 1.8e19): the pipeline forms no distance above 65.535 (metres of depth) or 10 (scaled intensity), and
+ * the quotient scheme is not defined for an infinite dividend. */
+int sf_filter2d_selftest_gauss(int device, float sigma, const float* dist, const int32_t* dx, const int32_t* dy, uint64_t n, float* out_r, float* out_d);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

@@ -81,6 +81,15 @@ static float gauss_r(float sigma, float dist) { /* filter.cu:190-193: (dist*dist
 static float gauss_d2(float sigma, int x, int y) { /* filter.cu:200-203: all float; exp on a float argument */
   return (float)or_exp64((double)(-((float)(x * x + y * y) / (2.0f * sigma * sigma))));
 }
+/* the two Gaussians for tests/test_filter2d_stages.py (the device probe sf_filter2d_selftest_gauss is held to them), one value and n values */
+float or_f2d_gauss_r(float sigma, float dist) { return gauss_r(sigma, dist); }
+float or_f2d_gauss_d2(float sigma, int x, int y) { return gauss_d2(sigma, x, y); }
+void or_f2d_gauss_r_n(float sigma, const float* dist, float* out, size_t n) {
+  for (size_t i = 0; i < n; i++) out[i] = gauss_r(sigma, dist[i]);
+}
+void or_f2d_gauss_d2_n(float sigma, const int* x, const int* y, float* out, size_t n) {
+  for (size_t i = 0; i < n; i++) out[i] = gauss_d2(sigma, x[i], y[i]);
+}
 
 void or_f2d_bilateral(float* out, const float* in, float sigma_d, float sigma_r, int w, int h) {
   const int radius = (int)ceil(2.0 * (double)sigma_d);

@@ -331,6 +331,11 @@ def f2d_lib():
     vp = C.c_void_p
     L.or_exp64.restype = C.c_double
     L.or_exp64.argtypes = [C.c_double]
+    L.or_f2d_gauss_r.restype = L.or_f2d_gauss_d2.restype = C.c_float
+    L.or_f2d_gauss_r.argtypes = [C.c_float, C.c_float]
+    L.or_f2d_gauss_d2.argtypes = [C.c_float, C.c_int, C.c_int]
+    L.or_f2d_gauss_r_n.argtypes = [C.c_float, vp, vp, C.c_size_t]
+    L.or_f2d_gauss_d2_n.argtypes = [C.c_float, vp, vp, vp, C.c_size_t]
     L.or_f2d_bilateral.argtypes = [vp, vp, C.c_float, C.c_float, C.c_int, C.c_int]
     L.or_f2d_resample_float.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]
     L.or_f2d_resample_uchar.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]

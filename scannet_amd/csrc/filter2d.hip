@@ -25,6 +25,13 @@ namespace {
 
 constexpr int F2D_LABELS = 80;  // MAX_NUM_LABELS_PER_SCENE, GlobalDefines.h:12
 #define F2D_MINF (-INFINITY)
+// k_f2d_vote's dynamic LDS (the 80 KiB histogram + the spatial table) is raised to F2D_VOTE_LDS_BUDGET per device; a window radius fits while
+// 80 * 256 * 4 + (2r + 1)^2 * 4 <= 100 KiB, i.e. r <= F2D_MAX_RADIUS = 35 (side 71: 102 084 B; side 73 would need 103 236 B).  The bilateral
+// kernel's table alone stays under the default 64 KiB far beyond that; the hooks hold both kernels to the one bound.
+constexpr size_t F2D_VOTE_LDS_BUDGET = 100 * 1024;
+constexpr int F2D_MAX_RADIUS = 35;
+static_assert((size_t)F2D_LABELS * 256 * 4 + (size_t)(2 * F2D_MAX_RADIUS + 1) * (2 * F2D_MAX_RADIUS + 1) * 4 <= F2D_VOTE_LDS_BUDGET, "radius bound");
+static_assert((size_t)F2D_LABELS * 256 * 4 + (size_t)(2 * F2D_MAX_RADIUS + 3) * (2 * F2D_MAX_RADIUS + 3) * 4 > F2D_VOTE_LDS_BUDGET, "radius bound is tight");
 
 // exp(-(double)(dist * dist) / (2.0 * sigma * sigma)) (filter.cu:190-193) with the divisor c = 2 sigma^2 and rc = RN(1 / c) fixed per
 // launch: q = a * rc, r = fma(-c, q, a) (exact), q + r * rc is the correctly rounded quotient a / c (Markstein; rc is the correctly
@@ -259,7 +266,7 @@ SF_API int sf_filter2d_create(int depth_width, int depth_height, int color_width
   SF_HIP_CHECK(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
   SF_HIP_CHECK(hipEventCreate(&f->e0));
   SF_HIP_CHECK(hipEventCreate(&f->e1));
-  SF_HIP_CHECK(hipFuncSetAttribute((const void*)k_f2d_vote, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+  SF_HIP_CHECK(hipFuncSetAttribute((const void*)k_f2d_vote, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F2D_VOTE_LDS_BUDGET));
   *out = f;
   return SF_OK;
 }
@@ -277,6 +284,32 @@ SF_API int sf_filter2d_set_tables(sf_filter2d* f, const uint8_t instance_to_idx[
 
 namespace {
 inline dim3 tiles(int w, int h) { return dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)); }
+
+// The launch of each kernel: geometry and dynamic LDS in one place, for sf_filter2d_frame and for the stage hooks at the end of the file.
+inline int bilateral_radius(float sigma_d) { return (int)std::ceil(2.0 * (double)sigma_d); }   // filter.cu:217
+
+inline void launch_prepare(hipStream_t s, const uint16_t* depth16, float* depth, size_t dn, const uint8_t* rgb, float* intensity, size_t cn) {
+  hipLaunchKernelGGL(k_f2d_prepare, dim3((unsigned)((std::max(dn, cn) + 255) / 256)), dim3(256), 0, s, depth16, depth, (int)dn, rgb, intensity, (int)cn);
+}
+inline void launch_bilateral(hipStream_t s, float* out, const float* in, float sd, float sr, int w, int h) {
+  const int radius = bilateral_radius(sd);
+  const size_t lds = (size_t)(2 * radius + 1) * (2 * radius + 1) * 4;
+  hipLaunchKernelGGL(k_f2d_bilateral, tiles(w, h), dim3(256), lds, s, out, in, sd, sr, w, h, radius);
+}
+inline void launch_resample_float(hipStream_t s, float* out, int ow, int oh, const float* in, int iw, int ih) {
+  hipLaunchKernelGGL(k_f2d_resample_float, tiles(ow, oh), dim3(256), 0, s, out, ow, oh, in, iw, ih);
+}
+inline void launch_resample_uchar(hipStream_t s, uint8_t* out, int ow, int oh, const uint8_t* in, int iw, int ih) {
+  hipLaunchKernelGGL(k_f2d_resample_uchar, tiles(ow, oh), dim3(256), 0, s, out, ow, oh, in, iw, ih);
+}
+inline void launch_vote(hipStream_t s, uint8_t* out, const uint8_t* in, const float* depth, const float* intensity, const uint8_t* to_idx, const uint8_t* to_inst,
+                        int r, int w, int h, float sigma_d, float sigma_r, float intensity_scale) {
+  const size_t lds = (size_t)F2D_LABELS * 256 * 4 + (size_t)(2 * r + 1) * (2 * r + 1) * 4;
+  hipLaunchKernelGGL(k_f2d_vote, tiles(w, h), dim3(256), lds, s, out, in, depth, intensity, to_idx, to_inst, r, w, h, sigma_d, sigma_r, intensity_scale);
+}
+inline void launch_to_label(hipStream_t s, uint16_t* out, const uint8_t* instance, const uint16_t* lut, size_t n) {
+  hipLaunchKernelGGL(k_f2d_to_label, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, instance, lut, (int)n);
+}
 }
 
 // One frame: Filter2dAnnotations.cpp:326-397.  Host buffers: depth dw*dh u16 (mm), rgb cw*ch*3, instance_in cw*ch u8 (the rendered
@@ -294,44 +327,36 @@ SF_API int sf_filter2d_frame(sf_filter2d* f, const uint16_t* depth, const uint8_
   SF_HIP_CHECK(hipEventRecord(f->e0, s));
   float *dep = f->depth, *dep_h = f->depth_h, *inten = f->inten, *inten_h = f->inten_h;
   uint8_t *inst = f->inst, *inst_h = f->inst_h;
-  hipLaunchKernelGGL(k_f2d_prepare, dim3((unsigned)((std::max(dn, cn) + 255) / 256)), dim3(256), 0, s, f->d_depth16, dep, (int)dn, f->d_rgb, inten, (int)cn);
+  launch_prepare(s, f->d_depth16, dep, dn, f->d_rgb, inten, cn);
   SF_HIP_CHECK(hipMemcpyAsync(f->depth_orig, dep, dn * 4, hipMemcpyDeviceToDevice, s));
   SF_HIP_CHECK(hipMemcpyAsync(f->inten_orig, inten, cn * 4, hipMemcpyDeviceToDevice, s));
-  auto bilateral = [&](float* out, const float* in, float sd, float sr, int w, int h) {
-    const int radius = (int)std::ceil(2.0 * (double)sd);
-    const size_t lds = (size_t)(2 * radius + 1) * (2 * radius + 1) * 4;
-    hipLaunchKernelGGL(k_f2d_bilateral, tiles(w, h), dim3(256), lds, s, out, in, sd, sr, w, h, radius);
-  };
-  bilateral(inten_h, inten, 6.0f, 0.1f, cw, ch);   // :334
-  bilateral(dep_h, dep, 2.0f, 0.1f, dw, dh);       // :335
+  launch_bilateral(s, inten_h, inten, 6.0f, 0.1f, cw, ch);   // :334
+  launch_bilateral(s, dep_h, dep, 2.0f, 0.1f, dw, dh);       // :335
   const int fw[2] = {320, cw}, fh[2] = {240, ch}, radii[2] = {12, 10};
   const float iscale[2] = {10.0f, 4.0f};
   int cur_dw = dw, cur_cw = cw;
-  if (fw[0] != cw) hipLaunchKernelGGL(k_f2d_resample_uchar, tiles(fw[0], fh[0]), dim3(256), 0, s, inst, fw[0], fh[0], inst_h, cw, ch);
+  if (fw[0] != cw) launch_resample_uchar(s, inst, fw[0], fh[0], inst_h, cw, ch);
   else SF_HIP_CHECK(hipMemcpyAsync(inst, inst_h, cn, hipMemcpyDeviceToDevice, s));
   for (int iter = 0; iter < 2; iter++) {
     if (cur_dw != fw[iter]) {
       if (fw[iter] == dw) {
         if (iter + 1 == 2) std::swap(dep, dep_h);
         else SF_HIP_CHECK(hipMemcpyAsync(dep, f->depth_orig, dn * 4, hipMemcpyDeviceToDevice, s));
-      } else hipLaunchKernelGGL(k_f2d_resample_float, tiles(fw[iter], fh[iter]), dim3(256), 0, s, dep, fw[iter], fh[iter], dep_h, dw, dh);
+      } else launch_resample_float(s, dep, fw[iter], fh[iter], dep_h, dw, dh);
       cur_dw = fw[iter];
     }
     if (cur_cw != fw[iter]) {
       if (fw[iter] == cw) {
         if (iter + 1 == 2) std::swap(inten, inten_h);
         else SF_HIP_CHECK(hipMemcpyAsync(inten, f->inten_orig, cn * 4, hipMemcpyDeviceToDevice, s));
-      } else hipLaunchKernelGGL(k_f2d_resample_float, tiles(fw[iter], fh[iter]), dim3(256), 0, s, inten, fw[iter], fh[iter], inten_h, cw, ch);
+      } else launch_resample_float(s, inten, fw[iter], fh[iter], inten_h, cw, ch);
       cur_cw = fw[iter];
     }
-    const int r = radii[iter];
-    const size_t lds = (size_t)F2D_LABELS * 256 * 4 + (size_t)(2 * r + 1) * (2 * r + 1) * 4;
-    hipLaunchKernelGGL(k_f2d_vote, tiles(fw[iter], fh[iter]), dim3(256), lds, s, inst_h, inst, dep, inten, f->to_idx, f->to_inst, r, fw[iter], fh[iter], 5.0f,
-                       0.1f, iscale[iter]);
+    launch_vote(s, inst_h, inst, dep, inten, f->to_idx, f->to_inst, radii[iter], fw[iter], fh[iter], 5.0f, 0.1f, iscale[iter]);
     if (iter + 1 == 2) std::swap(inst_h, inst);
-    else hipLaunchKernelGGL(k_f2d_resample_uchar, tiles(fw[iter + 1], fh[iter + 1]), dim3(256), 0, s, inst, fw[iter + 1], fh[iter + 1], inst_h, fw[iter], fh[iter]);
+    else launch_resample_uchar(s, inst, fw[iter + 1], fh[iter + 1], inst_h, fw[iter], fh[iter]);
   }
-  hipLaunchKernelGGL(k_f2d_to_label, dim3((unsigned)((cn + 255) / 256)), dim3(256), 0, s, f->label, inst, f->to_label, (int)cn);
+  launch_to_label(s, f->label, inst, f->to_label, cn);
   SF_HIP_CHECK(hipGetLastError());
   SF_HIP_CHECK(hipEventRecord(f->e1, s));
   SF_HIP_CHECK(hipMemcpyAsync(instance_out, inst, cn, hipMemcpyDeviceToHost, s));
@@ -342,5 +367,162 @@ SF_API int sf_filter2d_frame(sf_filter2d* f, const uint16_t* depth, const uint8_
     SF_HIP_CHECK(hipEventElapsedTime(&ms, f->e0, f->e1));
     *kernel_us = ms * 1e3f;
   }
+  return SF_OK;
+}
+
+// ---- Stage hooks (include/scanfuse_internal.h; tests/test_filter2d_stages.py): ONE kernel of this file on host arrays, launched by the launchers
+// sf_filter2d_frame uses (same geometry, same dynamic LDS), the output back on the host.  Test entry points, not product ABI.
+namespace {
+
+// gauss_r / gauss_d2 per lane, the exp table in LDS as in the kernels.  dist * dist must be finite (|dist| < 1.8e19): the pipeline's distances
+// are below 65.536 (depth, metres) and 10 (scaled intensity); beyond that a = -inf and r = fma(-c, q, a) is inf - inf, where the scheme is not
+// defined (the checker's division gives exp(-inf) = 0).
+__global__ __launch_bounds__(256) void k_f2d_selftest_gauss(float sigma, const float* __restrict__ dist, const int* __restrict__ dx, const int* __restrict__ dy,
+                                                            float* __restrict__ out_r, float* __restrict__ out_d, unsigned n) {
+  __shared__ double s_exp[32][2];
+  load_exp_table(s_exp);
+  __syncthreads();
+  const GaussR gr = gauss_r_setup(sigma);
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (dist) out_r[i] = gauss_r(gr, dist[i], s_exp);
+  if (dx) out_d[i] = gauss_d2(sigma, dx[i], dy[i], s_exp);
+}
+
+// device buffers of one hook call: freed when the call returns, whichever way
+struct StageBufs {
+  void* p[8] = {};
+  int n = 0;
+  ~StageBufs() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
+  template <class T> hipError_t put(T** out, const T* host, size_t count) {   // allocate, and upload `host` when given
+    hipError_t e = hipMalloc((void**)out, std::max(count, (size_t)1) * sizeof(T));
+    if (e != hipSuccess) return e;
+    p[n++] = *out;
+    return host && count ? hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+  }
+};
+template <class T> hipError_t stage_finish(T* host, const T* dev, size_t count) {   // launch error, then the (synchronising) download
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost);
+}
+int stage_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: libscanfuse has no CPU fallback, the annotation filter needs an MI355X");
+  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
+  SF_HIP_CHECK(hipSetDevice(device));
+  return SF_OK;
+}
+constexpr int F2D_MAX_SIDE = 1 << 14;   // keeps every pixel count of a hook call inside an int
+#define F2D_STAGE_DEVICE(device)                          \
+  do {                                                    \
+    const int rc_ = stage_device(device);                 \
+    if (rc_ != SF_OK) return rc_;                         \
+  } while (0)
+inline bool side_ok(int w, int h, int least) { return w >= least && h >= least && w <= F2D_MAX_SIDE && h <= F2D_MAX_SIDE; }
+
+}  // namespace
+
+SF_API int sf_filter2d_stage_prepare(int device, const uint16_t* depth16, int dn, const uint8_t* rgb, int cn, float* depth_out, float* intensity_out) {
+  if (!depth16 || !rgb || !depth_out || !intensity_out || dn < 1 || cn < 1 || dn > F2D_MAX_SIDE * F2D_MAX_SIDE || cn > F2D_MAX_SIDE * F2D_MAX_SIDE)
+    return sf::fail(SF_ERR_INVALID_ARG, "invalid argument");
+  F2D_STAGE_DEVICE(device);
+  StageBufs b;
+  uint16_t* d16; uint8_t* c; float *d, *in;
+  SF_HIP_CHECK(b.put(&d16, depth16, (size_t)dn));
+  SF_HIP_CHECK(b.put(&c, rgb, (size_t)cn * 3));
+  SF_HIP_CHECK(b.put(&d, (const float*)nullptr, (size_t)dn));
+  SF_HIP_CHECK(b.put(&in, (const float*)nullptr, (size_t)cn));
+  launch_prepare(nullptr, d16, d, (size_t)dn, c, in, (size_t)cn);
+  SF_HIP_CHECK(stage_finish(depth_out, d, (size_t)dn));
+  SF_HIP_CHECK(stage_finish(intensity_out, in, (size_t)cn));
+  return SF_OK;
+}
+
+SF_API int sf_filter2d_stage_bilateral(int device, const float* in, float sigma_d, float sigma_r, int w, int h, float* out) {
+  if (!in || !out || !side_ok(w, h, 1) || !(sigma_d > 0.0f) || !(sigma_r > 0.0f) || !(sigma_d <= 0.5f * F2D_MAX_RADIUS))
+    return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (the window radius ceil(2 sigma_d) is at most %d)", F2D_MAX_RADIUS);
+  F2D_STAGE_DEVICE(device);
+  StageBufs b;
+  float *di, *dout;
+  const size_t n = (size_t)w * h;
+  SF_HIP_CHECK(b.put(&di, in, n));
+  SF_HIP_CHECK(b.put(&dout, (const float*)nullptr, n));
+  launch_bilateral(nullptr, dout, di, sigma_d, sigma_r, w, h);
+  SF_HIP_CHECK(stage_finish(out, dout, n));
+  return SF_OK;
+}
+
+SF_API int sf_filter2d_stage_resample_float(int device, const float* in, int iw, int ih, float* out, int ow, int oh) {
+  if (!in || !out || !side_ok(iw, ih, 2) || !side_ok(ow, oh, 2)) return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (every side is at least 2)");
+  F2D_STAGE_DEVICE(device);
+  StageBufs b;
+  float *di, *dout;
+  SF_HIP_CHECK(b.put(&di, in, (size_t)iw * ih));
+  SF_HIP_CHECK(b.put(&dout, out, (size_t)ow * oh));
+  launch_resample_float(nullptr, dout, ow, oh, di, iw, ih);
+  SF_HIP_CHECK(stage_finish(out, dout, (size_t)ow * oh));
+  return SF_OK;
+}
+
+SF_API int sf_filter2d_stage_resample_uchar(int device, const uint8_t* in, int iw, int ih, uint8_t* out, int ow, int oh) {
+  if (!in || !out || !side_ok(iw, ih, 2) || !side_ok(ow, oh, 2)) return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (every side is at least 2)");
+  F2D_STAGE_DEVICE(device);
+  StageBufs b;
+  uint8_t *di, *dout;
+  SF_HIP_CHECK(b.put(&di, in, (size_t)iw * ih));
+  SF_HIP_CHECK(b.put(&dout, out, (size_t)ow * oh));
+  launch_resample_uchar(nullptr, dout, ow, oh, di, iw, ih);
+  SF_HIP_CHECK(stage_finish(out, dout, (size_t)ow * oh));
+  return SF_OK;
+}
+
+SF_API int sf_filter2d_stage_vote(int device, const uint8_t* instance_in, const float* depth, const float* intensity, const uint8_t instance_to_idx[256],
+                                  const uint8_t idx_to_instance[80], int radius, int w, int h, float sigma_d, float sigma_r, float intensity_scale,
+                                  uint8_t* instance_out) {
+  if (!instance_in || !depth || !intensity || !instance_to_idx || !idx_to_instance || !instance_out || !side_ok(w, h, 1) || radius < 0 || radius > F2D_MAX_RADIUS ||
+      !(sigma_d > 0.0f) || !(sigma_r > 0.0f))
+    return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (the window radius is at most %d)", F2D_MAX_RADIUS);
+  F2D_STAGE_DEVICE(device);
+  SF_HIP_CHECK(hipFuncSetAttribute((const void*)k_f2d_vote, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F2D_VOTE_LDS_BUDGET));   // as sf_filter2d_create
+  StageBufs b;
+  uint8_t *din, *dout, *ti, *tn;
+  float *dd, *dint;
+  const size_t n = (size_t)w * h;
+  SF_HIP_CHECK(b.put(&din, instance_in, n));
+  SF_HIP_CHECK(b.put(&dd, depth, n));
+  SF_HIP_CHECK(b.put(&dint, intensity, n));
+  SF_HIP_CHECK(b.put(&ti, instance_to_idx, (size_t)256));
+  SF_HIP_CHECK(b.put(&tn, idx_to_instance, (size_t)F2D_LABELS));
+  SF_HIP_CHECK(b.put(&dout, (const uint8_t*)nullptr, n));
+  launch_vote(nullptr, dout, din, dd, dint, ti, tn, radius, w, h, sigma_d, sigma_r, intensity_scale);
+  SF_HIP_CHECK(stage_finish(instance_out, dout, n));
+  return SF_OK;
+}
+
+SF_API int sf_filter2d_stage_to_label(int device, const uint8_t* instance, const uint16_t instance_to_label[256], int n, uint16_t* label_out) {
+  if (!instance || !instance_to_label || !label_out || n < 1 || n > F2D_MAX_SIDE * F2D_MAX_SIDE) return sf::fail(SF_ERR_INVALID_ARG, "invalid argument");
+  F2D_STAGE_DEVICE(device);
+  StageBufs b;
+  uint8_t* di; uint16_t *lut, *dout;
+  SF_HIP_CHECK(b.put(&di, instance, (size_t)n));
+  SF_HIP_CHECK(b.put(&lut, instance_to_label, (size_t)256));
+  SF_HIP_CHECK(b.put(&dout, (const uint16_t*)nullptr, (size_t)n));
+  launch_to_label(nullptr, dout, di, lut, (size_t)n);
+  SF_HIP_CHECK(stage_finish(label_out, dout, (size_t)n));
+  return SF_OK;
+}
+
+SF_API int sf_filter2d_selftest_gauss(int device, float sigma, const float* dist, const int32_t* dx, const int32_t* dy, uint64_t n, float* out_r, float* out_d) {
+  if (!(sigma > 0.0f) || n < 1 || n > (1u << 30) || (!dist && !dx) || (dist && !out_r) || (dx && (!dy || !out_d)) || (!dx && dy))
+    return sf::fail(SF_ERR_INVALID_ARG, "invalid argument");
+  F2D_STAGE_DEVICE(device);
+  StageBufs b;
+  float *dd = nullptr, *dr = nullptr, *dg = nullptr;
+  int32_t *x = nullptr, *y = nullptr;
+  if (dist) { SF_HIP_CHECK(b.put(&dd, dist, (size_t)n)); SF_HIP_CHECK(b.put(&dr, (const float*)nullptr, (size_t)n)); }
+  if (dx) { SF_HIP_CHECK(b.put(&x, dx, (size_t)n)); SF_HIP_CHECK(b.put(&y, dy, (size_t)n)); SF_HIP_CHECK(b.put(&dg, (const float*)nullptr, (size_t)n)); }
+  hipLaunchKernelGGL(k_f2d_selftest_gauss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, sigma, dd, x, y, dr, dg, (unsigned)n);
+  if (dist) SF_HIP_CHECK(stage_finish(out_r, dr, (size_t)n));
+  if (dx) SF_HIP_CHECK(stage_finish(out_d, dg, (size_t)n));
   return SF_OK;
 }

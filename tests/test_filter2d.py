@@ -1,7 +1,10 @@
 """2-D annotation filter: the kernels of AnnotationTools/Filter2dAnnotations/filter.cu that the tool calls.
 CPU part: the checker oracle/filter2d_oracle.c (closed-form cases, its exp against libm, a golden digest).  GPU part (-m gpu):
-scannet_amd/csrc/filter2d.hip against the checker, bit for bit.  PARITY UNPINNED against the reference binary (CUDA + mLib +
-FreeImage; nvcc contraction and libdevice exp are not reproducible here)."""
+scannet_amd/csrc/filter2d.hip against the checker, bit for bit, on whole frames: the original pair of sizes, the command-line tool, and one pair of
+sizes for every branch of the host sequence (test_gpu_frame_branches: an image already at 320 x 240 whose vote reads the unfiltered map, the
+device-to-device copy of the instance image, both swaps of the second pass, down-sampling), two frames through one object each, the second
+without any depth.  The kernels one by one, the device's Gaussians and an independent float64 statement of the filters: tests/test_filter2d_stages.py.
+PARITY UNPINNED against the reference binary (CUDA + mLib + FreeImage; nvcc contraction and libdevice exp are not reproducible here)."""
 import ctypes as C
 import hashlib
 import json
@@ -19,9 +22,10 @@ GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "filter2d_golden.j
 DW, DH, CW, CH = 80, 60, 162, 121     # small on purpose: the checker evaluates ~1e8 double exponentials per frame at this size
 
 
-def _scene(seed=3):
+def _scene(seed=3, depth_wh=(DW, DH), color_wh=(CW, CH)):
     """A depth ramp with a step and holes, a two-tone colour image with noise, an instance image whose borders are ragged
     (what projecting a coarse annotated mesh produces: the filter's job is to snap them to depth / intensity edges)."""
+    (DW, DH), (CW, CH) = depth_wh, color_wh
     rng = np.random.default_rng(seed)
     yy, xx = np.mgrid[0:DH, 0:DW]
     depth = (1500 + 6 * xx + np.where(xx > DW // 2, 700, 0) + rng.integers(0, 4, (DH, DW))).astype(np.uint16)
@@ -212,3 +216,27 @@ def test_gpu_matches_the_checker_bit_for_bit():
         io2, lo2, _ = f.frame(d2, r2, i2)
         oi2, ol2 = orc.f2d_frame(d2, r2, i2, *tables)
         assert np.array_equal(io2, oi2) and np.array_equal(lo2, ol2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("depth_wh,color_wh", [((320, 240), (162, 121)), ((80, 60), (320, 240)), ((96, 72), (96, 72)), ((336, 252), (400, 300))])
+def test_gpu_frame_branches(depth_wh, color_wh):
+    """The branches of the host sequence (Filter2dAnnotations.cpp:353-394) the 80 x 60 / 162 x 121 frame never takes:
+      depth 320 x 240, colour 162 x 121   no depth resample before the first vote, which reads the UNFILTERED depth; depth down-sampled for the second; colour swap
+      depth 80 x 60, colour 320 x 240     the instance image copied device to device; both votes read the unfiltered intensity; depth resampled once
+      96 x 72 both                        both maps up-sampled, then both swapped to their filtered originals
+      depth 336 x 252, colour 400 x 300   both maps DOWN-sampled to 320 x 240 (ScanNet's direction), depth up-sampled for the second vote
+    Each pair takes two frames through one Filter2d; the second has no depth at all, so anything the first left in the reused buffers would show.
+    The checker's share (a 320 x 240 vote per frame, ~1e8 exponentials, plus the colour-sized filter and vote) with 8 CPU threads, both frames together:
+    1.2 s, 1.9 s, 1.0 s and 2.7 s; the two frames of the existing 80 x 60 / 162 x 121 test: 2.1 s."""
+    tables = _tables()
+    frames = [_scene(3, depth_wh, color_wh), _scene(11, depth_wh, color_wh)]
+    frames[1] = (np.zeros_like(frames[1][0]),) + frames[1][1:]
+    with filter2d.Filter2d(depth_wh, color_wh) as f:
+        f.set_tables(*tables)
+        for k, (depth, rgb, inst) in enumerate(frames):
+            io, lo, _ = f.frame(depth, rgb, inst)
+            oi, ol = orc.f2d_frame(depth, rgb, inst, *tables)
+            assert np.array_equal(io, oi), "frame %d: %d instance pixels differ" % (k, (io != oi).sum())
+            assert np.array_equal(lo, ol), k
+            assert len(np.unique(oi)) >= 3, "the scene's labels survive the filter"
