@@ -263,10 +263,12 @@ int sf_fuser_raycast(sf_fuser* f, const float pose[16], const sf_raycast_params*
  * every frame queued on the handle before it, and ahead of everything queued after it. */
 int sf_fuser_raycast_device(sf_fuser* f, const float* poses, uint64_t n, const sf_raycast_params* r, void* d_depth, void* d_normals_xyz, void* d_rgb);
 
-/* Camera tracking: depth-only, frame-to-model projective point-to-plane ICP over an image pyramid (what DepthSensing.exe does with the keys of
- * zParametersTrackingDefault.txt, the second argument of scan_processor.py:126).  The semantics, per pixel and per iteration, are DESIGN.md section
- * "Camera tracking".  The key names below are VoxelHashing's as remembered (the upstream tracker is not in the reference tree).  Lists are finest
- * level first.  A track changes nothing in the volume, its counters or frame numbering. */
+/* Camera tracking: frame-to-model projective point-to-plane ICP over an image pyramid (what DepthSensing.exe does with the keys of
+ * zParametersTrackingDefault.txt, the second argument of scan_processor.py:126), depth only through sf_fuser_track*, with a dense colour row on every
+ * depth correspondence through sf_fuser_track_rgbd* (it pins the motion inside a plane, which depth alone leaves free).  The semantics, per pixel and
+ * per iteration, are DESIGN.md section "Camera tracking" (4c) and "The colour term of the tracker" (4g).  The key names below are VoxelHashing's as
+ * remembered (the upstream tracker is not in the reference tree).  Lists are finest level first.  A track changes nothing in the volume, its counters
+ * or frame numbering. */
 typedef struct sf_track_params {
   int32_t levels;                   /* s_maxLevels: pyramid levels, 1..4: 3                                                      */
   int32_t max_iters[4];             /* s_maxOuterIter: iterations per level, 1..100: 10 5 4 4                                   */
@@ -277,7 +279,11 @@ typedef struct sf_track_params {
   float max_translation;            /* s_maxTranslation: metres between the guess and the result, > 0: 0.3                       */
   float max_rotation;               /* s_maxRotation: radians between the guess and the result, > 0: 0.5                         */
   sf_raycast_params raycast;        /* the model render: width, height and intrinsics must be 0 (the fuser's integration camera)  */
-  int32_t reserved[8];
+  /* the colour term: read by sf_fuser_track_rgbd* only, sf_fuser_track* ignore the three; sf_track_params_load_file reads no key for them */
+  float colour_weight;              /* weight of the squared intensity residual beside the squared metres, finite, >= 0: 0 (off)  */
+  float colour_thres;               /* largest |intensity residual| (intensity in 0..1), finite, >= 0: 0.1                        */
+  float colour_gradient_min;        /* smallest gradient length per level pixel, finite, >= 0: 0.005                              */
+  int32_t reserved[5];
 } sf_track_params;
 void sf_track_params_default(sf_track_params* t);
 /* the keys above from an mLib ParameterFile (zParametersTrackingDefault.txt); keys that are absent leave *t as it is; t->raycast is not touched */
@@ -288,7 +294,9 @@ typedef struct sf_track_result {
   int32_t correspondences;          /* of the last level-0 system                                                               */
   float rms_residual;               /* sqrt(sum r^2 / correspondences) of that system                                           */
   int32_t lost_reason;              /* 0 tracked, 1 no usable guess / reference pose, 2 too few correspondences, 3 singular system, 4 motion above the bound */
-  int32_t reserved[6];
+  int32_t colour_correspondences;   /* sf_fuser_track_rgbd*: correspondences of the last level-0 system that also gave a colour row (else 0) */
+  float colour_rms_residual;        /* sqrt(sum r_c^2 / colour_correspondences) of that system, intensity in 0..1                 */
+  int32_t reserved[4];
 } sf_track_result;
 /* One depth frame (host, u16, the fuser's input size; the fuser's pre-pass rule makes metres at the integration size) tracked against the volume:
  * the model is ray-cast once at ref (NULL: the guess), the estimate starts at guess; pose_out row-major camToWorld.  Synchronous.  Sees every frame
@@ -299,6 +307,16 @@ int sf_fuser_track(sf_fuser* f, const uint16_t* depth, const float guess[16], co
 /* The same for a depth frame already in HBM (read on sf_fuser_stream(f)). */
 int sf_fuser_track_device(sf_fuser* f, const void* d_depth, const float guess[16], const float ref[16], const sf_track_params* t, float pose_out[16],
                           sf_track_result* result);
+/* The same with the frame's colour picture: RGB8 at the size the fuser fuses colour at (color_width x color_height, else the
+ * depth frames' own size).  Every depth correspondence whose pixel has an intensity, and whose four taps in the model's rendered colour have an intensity
+ * and a gradient, adds colour_weight x the photometric row to the 6x6 system.  With colour_weight == 0 the pose, the result's fields above and the
+ * system are sf_fuser_track's bits.  rgb == NULL is allowed only then.  SF_ERR_INVALID_ARG also for one of the three colour parameters negative or not
+ * finite, and for a positive colour_weight on a fuser whose colour intrinsics cannot map a picture (cfx or cfy not a positive finite number). */
+int sf_fuser_track_rgbd(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, const float guess[16], const float ref[16], const sf_track_params* t,
+                        float pose_out[16], sf_track_result* result);
+/* The same for a depth frame and a picture already in HBM (read on sf_fuser_stream(f)). */
+int sf_fuser_track_rgbd_device(sf_fuser* f, const void* d_depth, const void* d_rgb, const float guess[16], const float ref[16], const sf_track_params* t,
+                               float pose_out[16], sf_track_result* result);
 
 /* Re-integration: the volume-side half of a trajectory correction.  sf_fuser_deintegrate* exists "when a frame's pose is revised" (SURVEY App. C;
  * BundleFusion's main loop takes up to s_maxFrameFixes frames per step out at their old pose and puts them back at the new one); these calls
@@ -350,7 +368,7 @@ int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float* integ
  * and per Gauss-Newton iteration, are DESIGN.md section 4e "Global alignment".  sf_fuser_align_rgbd* add BundleFusion's dense colour term to every
  * depth correspondence (s_denseColorThresh, s_denseColorGradientMin, :24-25): it pins the motion inside a plane, which depth
  * alone leaves free.  SIFT matching, loop detection, the bilateral depth filter, the Gaussian pre-filter of the colour frames (s_colorDownSigma), the
- * local / global hierarchy of BundleFusion and a colour term in the tracker are not built.  An alignment changes nothing in the volume, its counters
+ * local / global hierarchy of BundleFusion are not built.  An alignment changes nothing in the volume, its counters
  * or frame numbering. */
 typedef struct sf_align_params {
   int32_t level;                    /* the one image size the solver works at, (W >> level) x (H >> level), 0..3: 1                 */

@@ -120,6 +120,11 @@ int sf_fuser_calib_tile_rmw_ex(sf_fuser* f, int mode, int iters, double* avg_us,
 int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, const float T[16], const float T_ref[16], const sf_track_params* t,
                           double sys[29], uint8_t* mask);
 
+/* Its twin with the colour term (tests/test_track_colour.py): the level's 31-value system as sf_fuser_track_rgbd sums it -- the 27
+ * weighted sums, the depth term's sum r^2 and count, the colour term's sum r_c^2 and count.  rgb: the host picture (NULL: colour_weight must be 0). */
+int sf_fuser_track_rgbd_system(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, int level, const float T[16], const float T_ref[16],
+                               const sf_track_params* t, double sys[31], uint8_t* mask);
+
 /* Test hook of the global alignment (tests/test_align.py), the twin of sf_fuser_track_system: the P per-pair 29-value systems at the given poses
  * (DESIGN.md section 4e), summed as sf_fuser_align sums them, without solving.  depth: K host frames, u16 at the input size; sys: P x 29 doubles. */
 int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a,

@@ -10,37 +10,11 @@
 
 #include "align_internal.h"
 #include "common.h"
+#include "photo_math.h"
 
 namespace {
 
-using namespace tk;
-
-// intensity of pixel (x, y) of the integration image, in [0, 1]: the colour pixel under the same ray by the pre-pass's rule (nearest); -inf outside the picture
-__device__ inline float intensity0_at(const uint8_t* __restrict__ rgb, const ParamsK& P, int x, int y) {
-  int cx = x, cy = y, cw = P.W;
-  if (P.cW > 0) {
-    const float u = fmaf(((float)x - P.mx) / P.fx, P.cfx, P.cmx) + 0.5f;
-    const float v = fmaf(((float)y - P.my) / P.fy, P.cfy, P.cmy) + 0.5f;
-    if (!(u >= 0.0f && u < (float)P.cW && v >= 0.0f && v < (float)P.cH)) return -INFINITY;
-    cx = (int)u;
-    cy = (int)v;
-    cw = P.cW;
-  }
-  const uint8_t* q = rgb + 3 * ((size_t)cy * (size_t)cw + (size_t)cx);
-  return ((0.299f * (float)q[0] + 0.587f * (float)q[1]) + 0.114f * (float)q[2]) / 255.0f;
-}
-
-// level L: the mean of the 2x2 block of level L - 1 in the order (0,0), (1,0), (0,1), (1,1); invalid if one of the four is
-template <int L>
-__device__ inline float level_intensity(const uint8_t* __restrict__ rgb, const ParamsK& P, int x, int y) {
-  if constexpr (L == 0) {
-    return intensity0_at(rgb, P, x, y);
-  } else {
-    const float s00 = level_intensity<L - 1>(rgb, P, 2 * x, 2 * y), s10 = level_intensity<L - 1>(rgb, P, 2 * x + 1, 2 * y);
-    const float s01 = level_intensity<L - 1>(rgb, P, 2 * x, 2 * y + 1), s11 = level_intensity<L - 1>(rgb, P, 2 * x + 1, 2 * y + 1);
-    return (s00 >= 0.0f && s10 >= 0.0f && s01 >= 0.0f && s11 >= 0.0f) ? (((s00 + s10) + s01) + s11) * 0.25f : -INFINITY;
-  }
-}
+using namespace tk;   // photo_math.h: the intensity rule, the level means, the bilinear tap and the colour row, shared with track_colour.hip
 
 // all K pictures at once (blockIdx.y = frame): RGB8 -> intensity -> L reductions -> {I, gx, gy, 0} of level L, the gradient by central differences
 // (-inf on the border and where one of the four neighbours has no intensity)
@@ -66,18 +40,7 @@ __global__ void __launch_bounds__(256) k_photo_prep(const uint8_t* __restrict__ 
     yu = t == 3 ? s : yu;
     yd = t == 4 ? s : yd;
   }
-  float4 o = make_float4(I, -INFINITY, -INFINITY, 0.0f);
-  if (inner && xl >= 0.0f && xr >= 0.0f && yu >= 0.0f && yd >= 0.0f) {
-    o.y = (xr - xl) * 0.5f;
-    o.z = (yd - yu) * 0.5f;
-  }
-  photo[(size_t)blockIdx.y * npx + i] = o;
-}
-
-// bilinear sample of one component: the two rows along x, then along y
-__device__ inline float bilin(float t00, float t10, float t01, float t11, float ax, float ay) {
-  const float top = fmaf(ax, t10 - t00, t00), bot = fmaf(ax, t11 - t01, t01);
-  return fmaf(ay, bot - top, top);
+  photo[(size_t)blockIdx.y * npx + i] = photo_texel(I, inner, xl, xr, yu, yd);
 }
 
 // one pair per blockIdx.y: k_align_assoc's association and depth row, and in the same lane the colour row of the correspondence; one 31-float partial
@@ -106,40 +69,7 @@ __global__ void __launch_bounds__(256) k_photo_assoc(const float4* __restrict__ 
     if (hit && photo) {
       const float Is = photo[so + i].x;
       const float3 v = make_float3(v4.x, v4.y, v4.z);
-      const float3 p = xf(e.Ti, v), pc = xf(e.M, v);   // a correspondence has pc.z > 0
-      const float uf = fmaf(pc.x / pc.z, c.fx, c.mx), vf = fmaf(pc.y / pc.z, c.fy, c.my);
-      // the four taps (x0, y0) .. (x0 + 1, y0 + 1) lie inside the image: compared in float before any conversion, so that a huge or non-finite
-      // projection forms no address
-      if (Is >= 0.0f && uf >= 0.0f && uf < (float)(c.W - 1) && vf >= 0.0f && vf < (float)(c.H - 1)) {
-        const float xf0 = floorf(uf), yf0 = floorf(vf);
-        const float4* t = photo + to + (size_t)((int)yf0 * c.W + (int)xf0);
-        const float4 t00 = t[0], t10 = t[1], t01 = t[c.W], t11 = t[c.W + 1];
-        if (t00.x >= 0.0f && t00.y > -INFINITY && t10.x >= 0.0f && t10.y > -INFINITY && t01.x >= 0.0f && t01.y > -INFINITY && t11.x >= 0.0f &&
-            t11.y > -INFINITY) {
-          const float ax = uf - xf0, ay = vf - yf0;
-          const float It = bilin(t00.x, t10.x, t01.x, t11.x, ax, ay);
-          const float gx = bilin(t00.y, t10.y, t01.y, t11.y, ax, ay), gy = bilin(t00.z, t10.z, t01.z, t11.z, ax, ay);
-          const float r = It - Is;
-          if (!(fabsf(r) > colour_thres || sqrtf(gx * gx + gy * gy) < gradient_min)) {
-            const float gxf = gx * c.fx, gyf = gy * c.fy;
-            const float3 g = make_float3(gxf / pc.z, gyf / pc.z, -((gxf * pc.x + gyf * pc.y) / (pc.z * pc.z)));
-            const float3 a = rot(e.Tj, g);
-            const float3 cr = cross3(p, a);
-            const float J[6] = {cr.x, cr.y, cr.z, a.x, a.y, a.z};
-            if (weight != 0.0f) {   // weight 0: the depth term's sums stay as they are, whatever the colour row holds
-              int k = 0;
-#pragma unroll
-              for (int u = 0; u < 6; u++)
-#pragma unroll
-                for (int w = u; w < 6; w++, k++) acc[k] = acc[k] + weight * (J[u] * J[w]);
-#pragma unroll
-              for (int u = 0; u < 6; u++) acc[21 + u] = acc[21 + u] + weight * (J[u] * r);
-            }
-            acc[29] = r * r;
-            acc[30] = 1.0f;
-          }
-        }
-      }
+      colour_row(photo + to, c, e.Tj, Is, xf(e.Ti, v), xf(e.M, v), weight, colour_thres, gradient_min, acc);
     }
   }
   reduce256(acc, red, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TK_PSTRIDE);

@@ -228,6 +228,9 @@ SF_API void sf_track_params_default(sf_track_params* t) {
   t->max_translation = 0.3f;
   t->max_rotation = 0.5f;
   sf_raycast_params_default(&t->raycast);
+  t->colour_weight = 0.0f;   // off: sf_fuser_track_rgbd* with the default parameters is sf_fuser_track*
+  t->colour_thres = 0.1f;
+  t->colour_gradient_min = 0.005f;
 }
 
 // the tracking keys of zParametersTrackingDefault.txt (names as remembered from VoxelHashing); a list sets the levels it names, finest first

@@ -47,6 +47,7 @@ extern char** environ;
 #pragma weak sf_device_free
 // --track's frame loop: the same arrangement
 #pragma weak sf_fuser_track
+#pragma weak sf_fuser_track_rgbd
 #pragma weak sf_fuser_integrate
 // --align's solver and the re-integration behind it
 #pragma weak sf_fuser_align
@@ -93,6 +94,7 @@ struct Args {
   int align = -1;                     // --align[=N]: keyframes every N-th tracked frame are aligned jointly (see align_scan below); 0: N from the parameter file
   const char* align_params = nullptr; // --align-params=<file>: zParametersBundlingScanNet.txt
   float align_colour = -1.0f;         // --align-colour[=w]: --align's solver with the dense colour term at weight w; < 0: depth only
+  float track_colour = -1.0f;         // --track-colour[=w]: --track's tracker with the dense colour term at weight w; < 0: depth only
   const char* pos[8];
   int n_pos = 0;
 };
@@ -238,6 +240,7 @@ int render_depth(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_in
 // them (sf_align_spread) and the volume is moved to the corrected trajectory (sf_fuse_update_trajectory).  traj: n x 16, in: what the volume holds, out: the same.
 // --align-colour[=w]: the keyframes' colour frames go with their depth and the solver adds the dense colour term at weight w (sf_fuser_align_rgbd).
 constexpr float ALIGN_COLOUR_WEIGHT = 0.1f;   // --align-colour without a value: the working weight (DESIGN.md 4f has the sweep)
+constexpr float TRACK_COLOUR_WEIGHT = 0.1f;   // --track-colour without a value: the working weight (DESIGN.md 4g has the sweep)
 int submap_size(const char* path) {
   FILE* fp = std::fopen(path, "r");
   if (!fp) return -1;
@@ -327,12 +330,15 @@ int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
 // fused at the pose found.  A lost frame is not fused and gets the -inf pose.  One frame after the other: frame k's pose needs the volume through k - 1.
 int track_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info& info, const sf_params& p) {
   if (!sf_fuser_track || !sf_fuser_integrate) return die_msg("--track: this libscanfuse has no tracker");
+  const bool photo = a.track_colour >= 0.0f;
+  if (photo && !sf_fuser_track_rgbd) return die_msg("--track-colour: this libscanfuse has no colour term in its tracker");
   sf_track_params tp;
   sf_track_params_default(&tp);
   if (sf_track_params_load_file(a.pos[2], &tp) != SF_OK) return die("tracking parameters");
   if (sf_raycast_params_load_file(a.pos[1], &tp.raycast) != SF_OK) return die("ray-cast parameters");
   tp.raycast.width = tp.raycast.height = 0;   // the tracker casts at the integration size with the integration camera
   tp.raycast.fx = tp.raycast.fy = tp.raycast.mx = tp.raycast.my = 0.0f;
+  if (photo) tp.colour_weight = a.track_colour;
   const bool color = info.color_width > 0 && info.color_height > 0 &&
                      (p.color_width > 0 || (info.color_width == info.depth_width && info.color_height == info.depth_height));
   std::vector<uint16_t> depth((size_t)info.depth_width * info.depth_height);
@@ -353,7 +359,9 @@ int track_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
     } else {
       sf_track_result res;
       const auto t0 = std::chrono::steady_clock::now();
-      if (sf_fuser_track(fuser, depth.data(), last, nullptr, &tp, pose, &res) != SF_OK) return die("tracking");
+      const int rc = photo ? sf_fuser_track_rgbd(fuser, depth.data(), rgb.data(), last, nullptr, &tp, pose, &res)   // fuse_scan saw to it that there are colour frames
+                           : sf_fuser_track(fuser, depth.data(), last, nullptr, &tp, pose, &res);
+      if (rc != SF_OK) return die("tracking");
       ms_track += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       ok = res.tracked != 0;
       if (ok) tracked++;
@@ -416,6 +424,10 @@ int fuse_scan(const Args& a) {
   if (a.align_colour >= 0.0f && !(info.color_width > 0 && info.color_height > 0 &&
                                   (p.color_width > 0 || (info.color_width == info.depth_width && info.color_height == info.depth_height))))
     return die_msg("--align-colour adds a colour term to --align: %s has no colour frames the fuser can use (%u x %u); run --align without --align-colour", sens_path,
+                   info.color_width, info.color_height);
+  if (a.track_colour >= 0.0f && !(info.color_width > 0 && info.color_height > 0 &&
+                                  (p.color_width > 0 || (info.color_width == info.depth_width && info.color_height == info.depth_height))))
+    return die_msg("--track-colour adds a colour term to --track: %s has no colour frames the fuser can use (%u x %u); run --track without --track-colour", sens_path,
                    info.color_width, info.color_height);
   const int device = std::getenv("SF_DEVICE") ? std::atoi(std::getenv("SF_DEVICE")) : 0;
   (void)sf_fuse_run_prepare(sens, &p, device);   // the run's streams and rings, sized for this file, made beside the fuser's own allocations (an optimisation: failures surface in sf_fuser_create)
@@ -665,17 +677,25 @@ int main(int argc, const char** argv_in) {
       a.align_colour = std::strtof(s + 15, &end);
       if (*end || !std::isfinite(a.align_colour) || a.align_colour < 0.0f) bad = true;
     }
+    else if (!std::strcmp(s, "--track-colour")) a.track_colour = TRACK_COLOUR_WEIGHT;
+    else if (!std::strncmp(s, "--track-colour=", 15) && s[15]) {
+      char* end = nullptr;
+      a.track_colour = std::strtof(s + 15, &end);
+      if (*end || !std::isfinite(a.track_colour) || a.track_colour < 0.0f) bad = true;
+    }
     else if (i > 0 && !std::strncmp(s, "--", 2)) bad = true;
     else if (a.n_pos < 8) a.pos[a.n_pos++] = s;
   }
   if (a.n_pos < 4 || bad || a.ranks < 1 || a.ranks > 64 || (a.rank >= 0 && (a.rank >= a.ranks || a.ipc.empty()))) {
-    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--align[=N] [--align-colour[=w]]] [--align-params=<zParametersBundling.txt>] [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
+    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--track-colour[=w]] [--align[=N] [--align-colour[=w]]] [--align-params=<zParametersBundling.txt>] [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
     return 255;
   }
   if (a.render_dir && a.ranks > 1)
     return die_msg("--render-depth ray-casts one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to render", a.ranks);
   if (a.align_colour >= 0.0f && a.align < 0)
     return die_msg("--align-colour adds the dense colour term to --align's solver: it needs --track --align");
+  if (a.track_colour >= 0.0f && !a.track)
+    return die_msg("--track-colour adds the dense colour term to --track's tracker: it needs --track");
   if ((a.align >= 0 || a.align_params) && !a.track)
     return die_msg("--align aligns the keyframes of the tracked trajectory: it needs --track");
   if (a.track && a.ranks > 1)

@@ -6,7 +6,8 @@
 // Per iteration: k_track_assoc pairs every input pixel with the model pixel it projects to, builds its point-to-plane row and reduces the 29 values
 // of the normal equations of its 256-pixel workgroup (xor butterfly in the wave, (w0 + w1) + (w2 + w3) across waves: no atomics); k_track_final
 // sums the partials in index order in double.  The host solves the 6x6 system in double and updates the pose.  Every step is deterministic and
-// tests/track_checker.c restates it bit for bit.
+// tests/track_checker.c restates it bit for bit.  sf_fuser_track_rgbd* run the same host loop over track_colour.hip's kernels, which add the dense
+// colour term's row to every correspondence and two sums to the system's values (tests/track_colour_checker.c).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,7 +16,9 @@
 #include "common.h"
 #include "fuser_internal.h"
 #include "hip_util.h"
+#include "photo_math.h"
 #include "scanfuse_internal.h"
+#include "track_internal.h"
 #include "track_math.h"
 
 namespace {
@@ -108,19 +111,6 @@ __global__ void __launch_bounds__(64) k_track_final(const float* __restrict__ pa
 
 }  // namespace
 
-struct TrackWork {
-  int levels = 0;
-  sf::DevBuf d_in;                            // u16: a host frame's device copy
-  sf::DevBuf depth[TK_MAX_LEVELS];            // float: metres per level
-  sf::DevBuf vmap[TK_MAX_LEVELS], nmap[TK_MAX_LEVELS];   // float4
-  sf::DevBuf model_depth, model_normal;       // float, 3 floats: the ray cast at level-0 size
-  sf::DevBuf mq, mn;                          // float4: world vertices and normals of the model
-  sf::DevBuf partials;                        // float
-  sf::DevBuf d_sys;                           // double
-  sf::HostBuf h_sys;                          // double: page-locked read-back
-  sf::DevBuf d_mask;                          // u8
-};
-
 void sf_track_release(sf_fuser* f) {
   if (!f) return;
   delete f->track;
@@ -145,6 +135,16 @@ int check_track_params(const sf_track_params* t) {
   const sf_raycast_params& r = t->raycast;
   if (r.width != 0 || r.height != 0 || r.fx != 0.0f || r.fy != 0.0f || r.mx != 0.0f || r.my != 0.0f)
     return sf::fail(SF_ERR_INVALID_ARG, "tracking ray cast: the image size and intrinsics must be 0 (the integration camera)");
+  return SF_OK;
+}
+
+// the colour term's three parameters and its picture, which only the rgbd entry points read
+int check_colour_args(const sf_track_params* t, const void* rgb) {
+  if (!std::isfinite(t->colour_weight) || !(t->colour_weight >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "tracking colour_weight %g: not a finite number >= 0", t->colour_weight);
+  if (!std::isfinite(t->colour_thres) || !(t->colour_thres >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "tracking colour_thres %g: not a finite number >= 0", t->colour_thres);
+  if (!std::isfinite(t->colour_gradient_min) || !(t->colour_gradient_min >= 0.0f))
+    return sf::fail(SF_ERR_INVALID_ARG, "tracking colour_gradient_min %g: not a finite number >= 0", t->colour_gradient_min);
+  if (!rgb && t->colour_weight > 0.0f) return sf::fail(SF_ERR_INVALID_ARG, "tracking colour_weight %g without a colour picture", t->colour_weight);
   return SF_OK;
 }
 
@@ -182,7 +182,8 @@ Rows rows_of(const float* T) {
 }
 
 // the input pyramid of a frame in HBM and the model of the volume at T_ref, queued on f->stream
-int prepare(sf_fuser* f, const void* d_depth, const float* Tref, const sf_track_params* t, const Cam* cams) {
+// d_rgb: the frame's picture in HBM, and the model is cast with its colour; nullptr: depth only
+int prepare(sf_fuser* f, const void* d_depth, const float* Tref, const sf_track_params* t, const Cam* cams, const void* d_rgb = nullptr) {
   TrackWork* w = f->track;
   const int n0 = cams[0].W * cams[0].H;
   hipLaunchKernelGGL(k_track_depth0, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, (const uint16_t*)d_depth, f->pk, w->depth[0].as<float>());
@@ -200,17 +201,29 @@ int prepare(sf_fuser* f, const void* d_depth, const float* Tref, const sf_track_
     SF_HIP_CHECK(hipGetLastError());
   }
   // the ray cast orders itself behind both front streams and blocks later front-chain work (raycast.hip)
-  const int rc = sf_fuser_raycast_device(f, Tref, 1, &t->raycast, w->model_depth.p, w->model_normal.p, nullptr);
+  const int rc = sf_fuser_raycast_device(f, Tref, 1, &t->raycast, w->model_depth.p, w->model_normal.p, d_rgb ? w->model_rgb.p : nullptr);
   if (rc != SF_OK) return rc;
   hipLaunchKernelGGL(k_track_model, dim3((n0 + 255) / 256), dim3(256), 0, f->stream, w->model_depth.as<const float>(), w->model_normal.as<const float>(), cams[0],
                      rows_of(Tref), w->mq.as<float4>(), w->mn.as<float4>());
   SF_HIP_CHECK(hipGetLastError());
-  return SF_OK;
+  return d_rgb ? sf_track_photo_prepare(f, d_rgb, cams, t->levels) : SF_OK;
 }
 
 // one level's system at the estimate T (double, rows 0..2 used), summed into w->h_sys; the mask optionally into w->d_mask
-int system_at(sf_fuser* f, int l, const Cam* cams, const double* T, const double* Tref, const sf_track_params* t, bool want_mask) {
+// rgbd: the 31 values of track_colour.hip's kernels, with colour rows when photo
+int system_at(sf_fuser* f, int l, const Cam* cams, const double* T, const double* Tref, const sf_track_params* t, bool want_mask, bool rgbd = false,
+              bool photo = false) {
   TrackWork* w = f->track;
+  if (rgbd) {
+    Rows Tf, M, Rf;
+    for (int i = 0; i < 12; i++) { Tf.T[i] = (float)T[i]; Rf.T[i] = (float)Tref[i]; }
+    compose_ref(Tref, T, M.T);
+    const int rc = sf_track_photo_system(f, l, cams, Tf, M, Rf, t, photo, want_mask ? w->d_mask.as<uint8_t>() : nullptr);
+    if (rc != SF_OK) return rc;
+    SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, TK_NSYS_RGBD * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    SF_HIP_CHECK(hipStreamSynchronize(f->stream));
+    return SF_OK;
+  }
   AssocArgs A;
   A.c = cams[l];
   A.W0 = cams[0].W;
@@ -241,26 +254,37 @@ bool solve6(const double* sys, double* xi) {
 
 // what the three entry points share: the checks in their order (own_checks: the caller's own, behind the NULL checks), the level cameras, the device, the
 // buffers and, for a host frame, its copy into w->d_in
+// rgbd: the call is one of sf_fuser_track_rgbd*; rgb (its picture, on the host when host_rgb) may still be NULL (colour_weight 0)
 template <typename Checks>
-int begin(sf_fuser* f, const sf_track_params* t, bool args_ok, Checks own_checks, Cam* cams, const uint16_t* host_depth) {
+int begin(sf_fuser* f, const sf_track_params* t, bool args_ok, Checks own_checks, Cam* cams, const uint16_t* host_depth, bool rgbd = false,
+          const void* rgb = nullptr, bool host_rgb = false) {
   int rc = check_track_params(t);
   if (rc != SF_OK) return rc;
+  if (rgbd && (rc = check_colour_args(t, rgb)) != SF_OK) return rc;
   if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
   if (!args_ok) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   if ((rc = own_checks()) != SF_OK) return rc;
+  if (rgb && f->pk.cW > 0 && !(std::isfinite(f->pk.cfx) && f->pk.cfx > 0.0f && std::isfinite(f->pk.cfy) && f->pk.cfy > 0.0f && std::isfinite(f->pk.cmx) &&
+                               std::isfinite(f->pk.cmy)))
+    return sf::fail(SF_ERR_INVALID_ARG, "tracking with colour: the fuser's colour intrinsics (cfx %g, cfy %g, cmx %g, cmy %g) cannot map a %d x %d picture", f->pk.cfx,
+                    f->pk.cfy, f->pk.cmx, f->pk.cmy, f->pk.cW, f->pk.cH);
   for (int l = 0; l < t->levels; l++)
     if (!level_cam(f->pk, l, &cams[l])) return sf::fail(SF_ERR_INVALID_ARG, "tracking level %d would be %d x %d (at least 8 x 8)", l, cams[l].W, cams[l].H);
   SF_HIP_CHECK(hipSetDevice(f->device));
   if ((rc = ensure_work(f, cams, t->levels)) != SF_OK) return rc;
+  if (rgb && (rc = sf_track_photo_reserve(f, cams, t->levels)) != SF_OK) return rc;
   if (host_depth) SF_HIP_CHECK(hipMemcpyAsync(f->track->d_in.p, host_depth, f->in_px * sizeof(uint16_t), hipMemcpyHostToDevice, f->stream));
+  if (rgb && host_rgb) SF_HIP_CHECK(hipMemcpyAsync(f->track->d_rgb.p, rgb, sf_track_picture_bytes(f), hipMemcpyHostToDevice, f->stream));
   return SF_OK;
 }
 
-// depth: a frame in HBM (on_device) or on the host
-int track(sf_fuser* f, const void* depth, bool on_device, const float* guess, const float* ref, const sf_track_params* t, float* pose_out, sf_track_result* res) {
+// depth (and, for sf_fuser_track_rgbd*, the picture rgb or NULL): a frame in HBM (on_device) or on the host
+int track(sf_fuser* f, const void* depth, bool on_device, const float* guess, const float* ref, const sf_track_params* t, float* pose_out, sf_track_result* res,
+          bool rgbd = false, const void* rgb = nullptr) {
   Cam cams[TK_MAX_LEVELS];
-  int rc = begin(f, t, depth && guess && pose_out, [] { return (int)SF_OK; }, cams, on_device ? nullptr : (const uint16_t*)depth);
+  int rc = begin(f, t, depth && guess && pose_out, [] { return (int)SF_OK; }, cams, on_device ? nullptr : (const uint16_t*)depth, rgbd, rgb, !on_device);
   if (rc != SF_OK) return rc;
+  const void* d_rgb = !rgb ? nullptr : (on_device ? rgb : f->track->d_rgb.p);
   sf_track_result r;
   std::memset(&r, 0, sizeof(r));
   for (int i = 0; i < 16; i++) pose_out[i] = -INFINITY;   // the "tracking lost" pose
@@ -270,16 +294,20 @@ int track(sf_fuser* f, const void* depth, bool on_device, const float* guess, co
     if (res) *res = r;
     return SF_OK;
   }
-  if ((rc = prepare(f, on_device ? depth : f->track->d_in.p, ref, t, cams)) != SF_OK) return rc;
+  if ((rc = prepare(f, on_device ? depth : f->track->d_in.p, ref, t, cams, d_rgb)) != SF_OK) return rc;
   double T[12], Tref[12], G[12];
   for (int i = 0; i < 12; i++) { T[i] = guess[i]; G[i] = guess[i]; Tref[i] = ref[i]; }
   const double* sys = f->track->h_sys.as<const double>();
   for (int l = t->levels - 1; l >= 0 && r.lost_reason == 0; l--) {
     for (int it = 0; it < t->max_iters[l]; it++) {
-      if ((rc = system_at(f, l, cams, T, Tref, t, false)) != SF_OK) return rc;
+      if ((rc = system_at(f, l, cams, T, Tref, t, false, rgbd, d_rgb != nullptr)) != SF_OK) return rc;
       if (l == 0) {
         r.correspondences = (int32_t)sys[28];
         r.rms_residual = sys[28] > 0.0 ? (float)std::sqrt(sys[27] / sys[28]) : 0.0f;
+        if (rgbd) {
+          r.colour_correspondences = (int32_t)sys[30];
+          r.colour_rms_residual = sys[30] > 0.0 ? (float)std::sqrt(sys[29] / sys[30]) : 0.0f;
+        }
         if (sys[28] < (double)t->min_correspondences) { r.lost_reason = 2; break; }
       }
       double xi[6];
@@ -327,6 +355,35 @@ SF_API int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, 
   for (int i = 0; i < 12; i++) { Td[i] = T[i]; Rd[i] = T_ref[i]; }
   if ((rc = system_at(f, level, cams, Td, Rd, t, mask != nullptr)) != SF_OK) return rc;
   for (int k = 0; k < TK_NSYS; k++) sys[k] = w->h_sys.as<const double>()[k];
+  if (mask) SF_HIP_CHECK(hipMemcpy(mask, w->d_mask.p, (size_t)cams[level].W * cams[level].H, hipMemcpyDeviceToHost));
+  return SF_OK;
+}
+
+SF_API int sf_fuser_track_rgbd_device(sf_fuser* f, const void* d_depth, const void* d_rgb, const float guess[16], const float ref[16], const sf_track_params* t,
+                                      float pose_out[16], sf_track_result* result) {
+  return track(f, d_depth, true, guess, ref, t, pose_out, result, true, d_rgb);
+}
+
+SF_API int sf_fuser_track_rgbd(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, const float guess[16], const float ref[16], const sf_track_params* t,
+                               float pose_out[16], sf_track_result* result) {
+  return track(f, depth, false, guess, ref, t, pose_out, result, true, rgb);
+}
+
+SF_API int sf_fuser_track_rgbd_system(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, int level, const float T[16], const float T_ref[16],
+                                      const sf_track_params* t, double sys[31], uint8_t* mask) {
+  Cam cams[TK_MAX_LEVELS];
+  int rc = begin(f, t, depth && T && T_ref && sys, [&] {
+    if (level < 0 || level >= t->levels) return sf::fail(SF_ERR_INVALID_ARG, "level %d of %d", level, t->levels);
+    if (!finite12(T) || !finite12(T_ref)) return sf::fail(SF_ERR_INVALID_ARG, "non-finite pose");
+    return (int)SF_OK;
+  }, cams, depth, true, rgb, true);
+  if (rc != SF_OK) return rc;
+  TrackWork* w = f->track;
+  if ((rc = prepare(f, w->d_in.p, T_ref, t, cams, rgb ? w->d_rgb.p : nullptr)) != SF_OK) return rc;
+  double Td[12], Rd[12];
+  for (int i = 0; i < 12; i++) { Td[i] = T[i]; Rd[i] = T_ref[i]; }
+  if ((rc = system_at(f, level, cams, Td, Rd, t, mask != nullptr, true, rgb != nullptr)) != SF_OK) return rc;
+  for (int k = 0; k < TK_NSYS_RGBD; k++) sys[k] = w->h_sys.as<const double>()[k];
   if (mask) SF_HIP_CHECK(hipMemcpy(mask, w->d_mask.p, (size_t)cams[level].W * cams[level].H, hipMemcpyDeviceToHost));
   return SF_OK;
 }

@@ -72,16 +72,18 @@ def load_raycast_params(path, base=None):
 class SfTrackParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("max_iters", C.c_int32 * 4), ("dist_thres", C.c_float * 4), ("normal_thres", C.c_float * 4),
                 ("early_out", C.c_float), ("min_correspondences", C.c_int32), ("max_translation", C.c_float), ("max_rotation", C.c_float),
-                ("raycast", SfRaycastParams), ("reserved", C.c_int32 * 8)]
+                ("raycast", SfRaycastParams), ("colour_weight", C.c_float), ("colour_thres", C.c_float), ("colour_gradient_min", C.c_float),
+                ("reserved", C.c_int32 * 5)]
 
 
 class SfTrackResult(C.Structure):
     _fields_ = [("tracked", C.c_int32), ("iterations", C.c_int32 * 4), ("correspondences", C.c_int32), ("rms_residual", C.c_float),
-                ("lost_reason", C.c_int32), ("reserved", C.c_int32 * 6)]
+                ("lost_reason", C.c_int32), ("colour_correspondences", C.c_int32), ("colour_rms_residual", C.c_float), ("reserved", C.c_int32 * 4)]
 
     def as_dict(self):
         return dict(tracked=bool(self.tracked), iterations=list(self.iterations), correspondences=int(self.correspondences),
-                    rms_residual=float(self.rms_residual), lost_reason=int(self.lost_reason))
+                    rms_residual=float(self.rms_residual), lost_reason=int(self.lost_reason), colour_correspondences=int(self.colour_correspondences),
+                    colour_rms_residual=float(self.colour_rms_residual))
 
 
 def default_track_params(**over):
@@ -274,10 +276,19 @@ def plan_reintegration(integrated, target, params=None, capacity=None):
     return out[:n.value].copy()
 
 
-def track_and_fuse(fuser, frames, first_pose, params=None):
+TRACK_COLOUR_WEIGHT = 0.1   # the working weight of the tracker's colour term (DESIGN.md 4g has the sweep); sf_track_params_default keeps 0, the term off
+
+
+def track_and_fuse(fuser, frames, first_pose, params=None, with_colour=False, colour_weight=None):
     """Frame-to-model tracking loop: frame 0 is fused at first_pose, every later frame is tracked against the volume so far, starting from the last
     tracked pose, and fused at the pose found; a lost frame is not fused.  frames: iterable of u16 depth [H,W] (or (depth, rgb) pairs).
+    with_colour: the frames are (depth, rgb) pairs and every track takes the frame's picture: sf_fuser_track_rgbd, the colour term of DESIGN.md 4g with
+    `colour_weight` (None: the parameters' own when positive, else TRACK_COLOUR_WEIGHT).
     -> list of poses (float32 [4,4]; all -inf where lost) and the list of result dicts (None for frame 0)."""
+    if with_colour:
+        t = params if params is not None else default_track_params()
+        params = SfTrackParams.from_buffer_copy(t)
+        params.colour_weight = float(colour_weight) if colour_weight is not None else (t.colour_weight if t.colour_weight > 0 else TRACK_COLOUR_WEIGHT)
     poses, results = [], []
     last = np.ascontiguousarray(first_pose, dtype=np.float32).reshape(4, 4)
     for k, fr in enumerate(frames):
@@ -285,7 +296,9 @@ def track_and_fuse(fuser, frames, first_pose, params=None):
         if k == 0:
             pose, res = last, None
         else:
-            pose, res = fuser.track(depth, last, params=params)
+            if with_colour and rgb is None:
+                raise ValueError("track_and_fuse(with_colour=True): frame %d has no picture" % k)
+            pose, res = fuser.track(depth, last, params=params, rgb=rgb if with_colour else None)
             res = res.as_dict()
         if pose is None:
             poses.append(np.full((4, 4), -np.inf, np.float32))
@@ -705,45 +718,67 @@ class Fuser:
                                            C.byref(a), _ptr(sys)))
         return sys
 
-    # -- camera tracking (DESIGN.md "Camera tracking") --------------------------------------------------
-    def track(self, depth, guess, ref=None, params=None):
+    # -- camera tracking (DESIGN.md "Camera tracking" and "The colour term of the tracker") ---------------
+    def _track_rgb(self, rgb):
+        """The frame's RGB8 picture at the size the fuser fuses colour at."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        w, h = (self.params.color_width, self.params.color_height) if self.params.color_width > 0 else (self.params.depth_width, self.params.depth_height)
+        if rgb.size != w * h * 3:
+            raise ValueError("picture has %d bytes, fuser expects %dx%dx3" % (rgb.size, w, h))
+        return rgb
+
+    def track(self, depth, guess, ref=None, params=None, rgb=None):
         """Track one u16 depth frame (host, the fuser's input size) against the volume, starting at camToWorld `guess`; the model is ray-cast at
-        `ref` (None: the guess).  -> (pose float32 [4,4] or None when lost, SfTrackResult)."""
+        `ref` (None: the guess).  rgb: the frame's RGB8 picture (color_width x color_height, else the depth frames' own size): sf_fuser_track_rgbd, the
+        colour term of DESIGN.md 4g with the parameters' colour_weight.  -> (pose float32 [4,4] or None when lost, SfTrackResult)."""
         t = params if params is not None else default_track_params()
         depth = np.ascontiguousarray(depth, dtype=np.uint16)
         if depth.size != self.params.depth_width * self.params.depth_height:
             raise ValueError("depth frame has %d pixels, fuser expects %dx%d" % (depth.size, self.params.depth_width, self.params.depth_height))
+        if rgb is not None:
+            return self._track(_abi.lib().sf_fuser_track_rgbd, _ptr(depth), guess, ref, t, (_ptr(self._track_rgb(rgb)),))
         return self._track(_abi.lib().sf_fuser_track, _ptr(depth), guess, ref, t)
 
-    def track_device(self, d_depth, guess, ref=None, params=None):
-        """track() for a u16 depth frame already in HBM (torch tensor or raw pointer), read on self.stream."""
+    def track_device(self, d_depth, guess, ref=None, params=None, d_rgb=None):
+        """track() for a u16 depth frame already in HBM (torch tensor or raw pointer), read on self.stream.  d_rgb: the frame's picture in HBM
+        (sf_fuser_track_rgbd_device)."""
         t = params if params is not None else default_track_params()
+        if d_rgb is not None:
+            return self._track(_abi.lib().sf_fuser_track_rgbd_device, _ptr(d_depth), guess, ref, t, (_ptr(d_rgb),))
         return self._track(_abi.lib().sf_fuser_track_device, _ptr(d_depth), guess, ref, t)
 
-    def _track(self, fn, depth_ptr, guess, ref, t):
+    def _track(self, fn, depth_ptr, guess, ref, t, rgb_ptr=()):
         guess = np.ascontiguousarray(guess, dtype=np.float32).reshape(16)
         ref = None if ref is None else np.ascontiguousarray(ref, dtype=np.float32).reshape(16)
         out = np.empty(16, np.float32)
         res = SfTrackResult()
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SfTrackParams), C.c_void_p, C.POINTER(SfTrackResult)]
-        check(fn(self._h, depth_ptr, _ptr(guess), _ptr(ref), C.byref(t), _ptr(out), C.byref(res)))
+        fn.argtypes = [C.c_void_p, C.c_void_p] + [C.c_void_p] * len(rgb_ptr) + [C.c_void_p, C.c_void_p, C.POINTER(SfTrackParams), C.c_void_p, C.POINTER(SfTrackResult)]
+        check(fn(self._h, depth_ptr, *rgb_ptr, _ptr(guess), _ptr(ref), C.byref(t), _ptr(out), C.byref(res)))
         return (out.reshape(4, 4) if res.tracked else None), res
 
-    def track_system(self, depth, level, T, T_ref, params=None, mask=False):
+    def track_system(self, depth, level, T, T_ref, params=None, mask=False, rgb=None, colour=False):
         """Test hook (scanfuse_internal.h sf_fuser_track_system): one level's 29-value system (float64) at estimate T with the model cast at
-        T_ref, and the level's correspondence mask (u8 [H_l, W_l]) when mask=True."""
+        T_ref, and the level's correspondence mask (u8 [H_l, W_l]) when mask=True.  rgb (or colour=True with rgb None, which needs colour_weight 0):
+        sf_fuser_track_rgbd_system, the 31 values with the colour term."""
         t = params if params is not None else default_track_params()
         depth = np.ascontiguousarray(depth, dtype=np.uint16)
         T = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
         T_ref = np.ascontiguousarray(T_ref, dtype=np.float32).reshape(16)
-        sys = np.zeros(29, np.float64)
+        colour = colour or rgb is not None
+        sys = np.zeros(31 if colour else 29, np.float64)
         m = None
         if mask:
             W, H = self.raycast_size()
             m = np.zeros((H >> level, W >> level), np.uint8)
         L = _abi.lib()
-        L.sf_fuser_track_system.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SfTrackParams), C.c_void_p, C.c_void_p]
-        check(L.sf_fuser_track_system(self._h, _ptr(depth), int(level), _ptr(T), _ptr(T_ref), C.byref(t), _ptr(sys), _ptr(m)))
+        if colour:
+            rgb = None if rgb is None else self._track_rgb(rgb)
+            L.sf_fuser_track_rgbd_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SfTrackParams), C.c_void_p,
+                                                     C.c_void_p]
+            check(L.sf_fuser_track_rgbd_system(self._h, _ptr(depth), _ptr(rgb), int(level), _ptr(T), _ptr(T_ref), C.byref(t), _ptr(sys), _ptr(m)))
+        else:
+            L.sf_fuser_track_system.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SfTrackParams), C.c_void_p, C.c_void_p]
+            check(L.sf_fuser_track_system(self._h, _ptr(depth), int(level), _ptr(T), _ptr(T_ref), C.byref(t), _ptr(sys), _ptr(m)))
         return (sys, m) if mask else sys
 
     def export_blocks(self):
