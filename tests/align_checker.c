@@ -1,28 +1,17 @@
 /*
- * tests/align_checker.c -- CPU restatement of the global alignment (DESIGN.md section 4e "Global alignment"; scannet_amd/csrc/align.hip is the GPU side).
+ * tests/align_checker.c -- CPU restatement of the global alignment, with the dense colour term optional (DESIGN.md sections 4e "Global alignment"
+ * and 4f "The colour term of the global alignment"; scannet_amd/csrc/align.hip and align_colour.hip are the GPU side).
  *
- * K keyframes (u16 depth, camera-to-world poses) and P directed pairs.  Each frame becomes a vertex and a normal map at one level; each pair gives
- * 29 numbers, reduced in the kernel's order (256-pixel workgroups, xor butterfly per 64-lane wave, (w0 + w1) + (w2 + w3), partials summed in index order
- * in double); the host loop drops thin pairs, keeps the frames connected to the fixed frame, assembles and solves by Cholesky, and updates the poses.
- * Every operation is written out as the specification states it; build with -ffp-contract=off (and -mfma, so that fmaf is one instruction).
+ * K keyframes (u16 depth, RGB8 colour or none, camera-to-world poses) and P directed pairs.  Each frame becomes a vertex map, a normal map and, with
+ * pictures, a map of {intensity, gx, gy} at one level; each pair gives 31 numbers, reduced in the kernel's order; the host loop drops thin pairs, keeps
+ * the frames connected to the fixed frame, assembles and solves by Cholesky on the first 29 values, and updates the poses.  The rules themselves are
+ * tests/solver_rules.h's; what is here is the alignment's own: its arguments, its maps and its host loop, sf_align_pairs and sf_align_spread.
+ * The pictures may be NULL: no colour rows are formed, values 29 and 30 are 0 and the first 29 are the depth term's, as they are at colour_weight 0.
  */
-#include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
+#include "solver_rules.h"
 
-#define AL_NSYS 29
-#define AL_DOWN_THRES 0.03f
-#define AL_PIVOT_REL 1e-5
 #define AL_MAX_FRAMES 256
 #define AL_MAX_PAIRS 4096
-
-typedef struct al_frame {
-  int32_t in_w, in_h;            /* input depth size                                  */
-  int32_t W, H;                  /* integration size                                  */
-  float fx, fy, mx, my;          /* integration intrinsics                            */
-  float depth_shift, depth_min, depth_max;
-} al_frame;
 
 /* sf_align_params */
 typedef struct al_params {
@@ -30,7 +19,8 @@ typedef struct al_params {
   float dist_thres, normal_thres, depth_min, depth_max, early_out;
   int32_t min_pair_correspondences, fixed_frame;
   float pair_max_dist, pair_max_angle, max_translation, max_rotation;
-  int32_t reserved[9];
+  float colour_weight, colour_thres, colour_gradient_min;
+  int32_t reserved[6];
 } al_params;
 
 /* sf_align_result */
@@ -38,42 +28,13 @@ typedef struct al_result {
   int32_t status, iterations, pairs_used, frames_unconnected, frames_rejected, reserved0;
   int64_t correspondences;
   float rms_first, rms_last;
-  int32_t reserved[6];
+  int64_t colour_correspondences;
+  float colour_rms_first, colour_rms_last;
+  int32_t reserved[2];
 } al_result;
 
-typedef struct { float x, y, z; } f3;
-typedef struct { int W, H; float fx, fy, mx, my; } cam_t;
-
-static f3 xf(const float* T, f3 v) {
-  f3 o = {fmaf(T[2], v.z, fmaf(T[1], v.y, fmaf(T[0], v.x, T[3]))), fmaf(T[6], v.z, fmaf(T[5], v.y, fmaf(T[4], v.x, T[7]))),
-          fmaf(T[10], v.z, fmaf(T[9], v.y, fmaf(T[8], v.x, T[11])))};
-  return o;
-}
-static f3 rot(const float* T, f3 n) {
-  f3 o = {fmaf(T[2], n.z, fmaf(T[1], n.y, T[0] * n.x)), fmaf(T[6], n.z, fmaf(T[5], n.y, T[4] * n.x)), fmaf(T[10], n.z, fmaf(T[9], n.y, T[8] * n.x))};
-  return o;
-}
-static float dot3(f3 a, f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-static f3 cross3(f3 a, f3 b) {
-  f3 o = {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-  return o;
-}
-static f3 sub3(f3 a, f3 b) {
-  f3 o = {a.x - b.x, a.y - b.y, a.z - b.z};
-  return o;
-}
-static f3 unproject(const cam_t* c, int x, int y, float d) {
-  f3 o = {((float)x - c->mx) / c->fx * d, ((float)y - c->my) / c->fy * d, d};
-  return o;
-}
-static int finite12(const float* T) {
-  for (int i = 0; i < 12; i++)
-    if (!isfinite(T[i])) return 0;
-  return 1;
-}
-
 /* the level the parameters choose on a W x H integration image and its camera; -1: none */
-static int pick_level(const al_frame* fr, const al_params* a, cam_t* c) {
+static int pick_level(const sr_frame* fr, const al_params* a, cam_t* c) {
   int l = a->level;
   if (l < 0 || l > 3) return -1;
   if ((a->down_width == 0) != (a->down_height == 0) || a->down_width < 0 || a->down_height < 0) return -1;
@@ -83,16 +44,10 @@ static int pick_level(const al_frame* fr, const al_params* a, cam_t* c) {
       if ((fr->W >> k) == a->down_width && (fr->H >> k) == a->down_height) l = k;
     if (l < 0) return -1;
   }
-  c->W = fr->W >> l;
-  c->H = fr->H >> l;
-  if (c->W < 8 || c->H < 8) return -1;
-  const float sx = (float)c->W / (float)fr->W, sy = (float)c->H / (float)fr->H;
-  c->fx = fr->fx * sx; c->mx = fr->mx * sx;
-  c->fy = fr->fy * sy; c->my = fr->my * sy;
-  return l;
+  return level_cam(fr, l, c) ? l : -1;
 }
 
-static int check_args(int64_t K, const int32_t* pairs, int64_t P, const al_params* a) {
+static int check_args(int64_t K, const int32_t* pairs, int64_t P, const al_params* a, const uint8_t* rgb) {
   if (a->max_iters < 1 || a->max_iters > 100) return -1;
   if (!isfinite(a->dist_thres) || !(a->dist_thres > 0.0f)) return -1;
   if (!(a->normal_thres >= -1.0f && a->normal_thres <= 1.0f)) return -1;
@@ -100,6 +55,7 @@ static int check_args(int64_t K, const int32_t* pairs, int64_t P, const al_param
   if (!isfinite(a->early_out) || !(a->early_out >= 0.0f)) return -1;
   if (a->min_pair_correspondences < 1) return -1;
   if (!isfinite(a->max_translation) || !(a->max_translation > 0.0f) || !isfinite(a->max_rotation) || !(a->max_rotation > 0.0f)) return -1;
+  if (!colour_args_ok(rgb != NULL, a->colour_weight, a->colour_thres, a->colour_gradient_min)) return -1;
   if (K < 2 || K > AL_MAX_FRAMES) return -1;
   if (a->fixed_frame < 0 || a->fixed_frame >= K) return -1;
   if (P < 1 || P > AL_MAX_PAIRS) return -1;
@@ -110,82 +66,40 @@ static int check_args(int64_t K, const int32_t* pairs, int64_t P, const al_param
   return 0;
 }
 
-/* one frame's vertex and normal map at level l (x = -inf: invalid) */
-static void frame_maps(const al_frame* fr, const uint16_t* depth, int l, const cam_t* c, float dmin, float dmax, f3* vmap, f3* nmap) {
-  int Wc = fr->W, Hc = fr->H;
-  float* d = (float*)malloc(sizeof(float) * Wc * Hc);
-  const int resample = fr->in_w != fr->W || fr->in_h != fr->H;
-  const float rsx = resample ? (float)(fr->in_w - 1) / (float)(fr->W - 1) : 1.0f, rsy = resample ? (float)(fr->in_h - 1) / (float)(fr->H - 1) : 1.0f;
-  for (int i = 0; i < Wc * Hc; i++) {   /* the pre-pass rule */
-    uint16_t u;
-    if (resample) {
-      const unsigned xi = (unsigned)((float)(i % fr->W) * rsx + 0.5f), yi = (unsigned)((float)(i / fr->W) * rsy + 0.5f);
-      u = (xi < (unsigned)fr->in_w && yi < (unsigned)fr->in_h) ? depth[(size_t)yi * fr->in_w + xi] : 0;
-    } else {
-      u = depth[i];
-    }
-    float v = (float)u / fr->depth_shift;
-    if (u == 0 || v < fr->depth_min || v > fr->depth_max) v = -INFINITY;
-    d[i] = v;
-  }
-  for (int k = 0; k < l; k++) {   /* l reductions */
-    const int Wd = Wc >> 1, Hd = Hc >> 1;
-    float* e = (float*)malloc(sizeof(float) * Wd * Hd);
-    for (int y = 0; y < Hd; y++)
-      for (int x = 0; x < Wd; x++) {
-        const float* p = d + (size_t)(2 * y) * Wc + 2 * x;
-        const float r = p[0];
-        float out = -INFINITY;
-        if (r > 0.0f) {
-          const float v[4] = {p[0], p[1], p[Wc], p[Wc + 1]};
-          float sum = 0.0f, cnt = 0.0f;
-          for (int q = 0; q < 4; q++)
-            if (v[q] > 0.0f && fabsf(v[q] - r) <= AL_DOWN_THRES) {
-              sum = sum + v[q];
-              cnt = cnt + 1.0f;
-            }
-          out = sum / cnt;
-        }
-        e[y * Wd + x] = out;
-      }
-    free(d);
-    d = e;
-    Wc = Wd;
-    Hc = Hd;
-  }
-  for (int i = 0; i < Wc * Hc; i++)   /* the solver's own gate */
-    if (!(d[i] >= dmin && d[i] <= dmax)) d[i] = -INFINITY;
-  for (int y = 0; y < c->H; y++)
-    for (int x = 0; x < c->W; x++) {
-      const int i = y * c->W + x;
-      const f3 inv = {-INFINITY, -INFINITY, -INFINITY};
-      f3 vo = inv, no = inv;
-      const float dz = d[i];
-      if (dz > 0.0f) {
-        const f3 v = unproject(c, x, y, dz);
-        vo = v;
-        if (x + 1 < c->W && y + 1 < c->H) {
-          const float dr = d[i + 1], dd = d[i + c->W];
-          if (dr > 0.0f && dd > 0.0f) {
-            const f3 n = cross3(sub3(unproject(c, x, y + 1, dd), v), sub3(unproject(c, x + 1, y, dr), v));
-            const float len = sqrtf(dot3(n, n));
-            if (len > 0.0f) { no.x = n.x / len; no.y = n.y / len; no.z = n.z / len; }
-          }
-        }
-      }
-      vmap[i] = vo;
-      nmap[i] = no;
-    }
-  free(d);
-}
-
 typedef struct {
   int K, npx;
   cam_t cam;
-  f3 *v, *n;   /* [K][npx] */
+  f3 *v, *n;   /* [K][npx]; x = -inf: invalid */
+  f3* ph;      /* [K][npx] {I, gx, gy}; NULL: no colour pictures */
 } maps_t;
 
-static int maps_build(maps_t* m, const al_frame* fr, const uint16_t* depth, int K, const al_params* a) {
+/* one frame's vertex and normal map at level l: the pre-pass rule, l reductions, the solver's own depth gate */
+static void frame_maps(const sr_frame* fr, const uint16_t* depth, int l, const cam_t* c, float dmin, float dmax, f3* vmap, f3* nmap) {
+  float* d = prepass_depth(fr, depth);
+  for (int k = 0; k < l; k++) {
+    float* e = down4(d, fr->W >> k, fr->H >> k);
+    free(d);
+    d = e;
+  }
+  for (int i = 0; i < c->W * c->H; i++)
+    if (!(d[i] >= dmin && d[i] <= dmax)) d[i] = -INFINITY;
+  vertex_normal_maps(c, d, vmap, nmap);
+  free(d);
+}
+
+/* one frame's {I, gx, gy} at level l from its RGB8 picture */
+static void frame_photo(const sr_frame* fr, const uint8_t* rgb, int l, const cam_t* c, f3* pmap) {
+  float* d = prepass_intensity(fr, rgb);
+  for (int k = 0; k < l; k++) {
+    float* e = photo_down(d, fr->W >> k, fr->H >> k);
+    free(d);
+    d = e;
+  }
+  photo_map(c, d, pmap);
+  free(d);
+}
+
+static int maps_build(maps_t* m, const sr_frame* fr, const uint16_t* depth, const uint8_t* rgb, int K, const al_params* a) {
   memset(m, 0, sizeof(*m));
   const int l = pick_level(fr, a, &m->cam);
   if (l < 0) return -1;
@@ -197,63 +111,47 @@ static int maps_build(maps_t* m, const al_frame* fr, const uint16_t* depth, int 
   m->n = (f3*)malloc(sizeof(f3) * (size_t)K * m->npx);
   for (int k = 0; k < K; k++)
     frame_maps(fr, depth + (size_t)k * fr->in_w * fr->in_h, l, &m->cam, dmin, dmax, m->v + (size_t)k * m->npx, m->n + (size_t)k * m->npx);
+  if (rgb) {
+    const size_t cpx = fr->color_w > 0 ? (size_t)fr->color_w * fr->color_h : (size_t)fr->W * fr->H;
+    m->ph = (f3*)malloc(sizeof(f3) * (size_t)K * m->npx);
+    for (int k = 0; k < K; k++) frame_photo(fr, rgb + 3 * cpx * k, l, &m->cam, m->ph + (size_t)k * m->npx);
+  }
   return 0;
 }
 static void maps_free(maps_t* m) {
   free(m->v);
   free(m->n);
+  free(m->ph);
 }
 
-/* T_j^-1 T_i: the inverse by cofactors over the determinant, the product and the translation in double, rounded to float once */
-static void compose_ref(const double* Tref, const double* T, float* M) {
-  const double a00 = Tref[0], a01 = Tref[1], a02 = Tref[2], a10 = Tref[4], a11 = Tref[5], a12 = Tref[6], a20 = Tref[8], a21 = Tref[9], a22 = Tref[10];
-  const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-  const double det = a00 * c00 + a01 * c01 + a02 * c02;
-  double inv[9];
-  inv[0] = c00 / det; inv[1] = (a02 * a21 - a01 * a22) / det; inv[2] = (a01 * a12 - a02 * a11) / det;
-  inv[3] = c01 / det; inv[4] = (a00 * a22 - a02 * a20) / det; inv[5] = (a02 * a10 - a00 * a12) / det;
-  inv[6] = c02 / det; inv[7] = (a01 * a20 - a00 * a21) / det; inv[8] = (a00 * a11 - a01 * a10) / det;
-  const double dt[3] = {T[3] - Tref[3], T[7] - Tref[7], T[11] - Tref[11]};
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) M[4 * r + c] = (float)((inv[3 * r] * T[c] + inv[3 * r + 1] * T[4 + c]) + inv[3 * r + 2] * T[8 + c]);
-    M[4 * r + 3] = (float)((inv[3 * r] * dt[0] + inv[3 * r + 1] * dt[1]) + inv[3 * r + 2] * dt[2]);
-  }
-}
-
-/* one source pixel's 29 values for the pair (i, j); 1 when it is a correspondence */
-static int pixel_row(const maps_t* m, int i, int j, int px, const float* Ti, const float* Tj, const float* M, float dthr, float nthr, float* acc) {
+/* one source pixel's 31 values for the pair (i, j); 1 when it is a (depth) correspondence.  rc, Jc (may be NULL): the colour row, when acc[30] is 1 */
+static int pixel_row(const maps_t* m, int i, int j, int px, const float* Ti, const float* Tj, const float* M, const al_params* a, float* acc, float* rc_out,
+                     float* Jc_out) {
   const cam_t* c = &m->cam;
   const f3 v = m->v[(size_t)i * m->npx + px], nc = m->n[(size_t)i * m->npx + px];
   if (!(v.z > 0.0f && nc.x > -INFINITY)) return 0;
   const f3 p = xf(Ti, v), n = rot(Ti, nc), pc = xf(M, v);
-  if (!(pc.z > 0.0f)) return 0;
-  const float ux = floorf(fmaf(pc.x / pc.z, c->fx, c->mx) + 0.5f), uy = floorf(fmaf(pc.y / pc.z, c->fy, c->my) + 0.5f);
-  if (!(ux >= 0.0f && ux < (float)c->W && uy >= 0.0f && uy < (float)c->H)) return 0;
-  const size_t t = (size_t)j * m->npx + (size_t)((int)uy * c->W + (int)ux);
+  int ux, uy;
+  if (!project_nearest(c, pc, &ux, &uy)) return 0;
+  const size_t t = (size_t)j * m->npx + (size_t)(uy * c->W + ux);
   const f3 vj = m->v[t], nj = m->n[t];
   if (!(vj.z > 0.0f && nj.x > -INFINITY)) return 0;
-  const f3 q = xf(Tj, vj), nm = rot(Tj, nj);
-  const f3 d = sub3(p, q);
-  if (!(sqrtf(dot3(d, d)) <= dthr && dot3(nm, n) >= nthr)) return 0;
-  const float r = dot3(nm, d);
-  const f3 cr = cross3(p, nm);
-  const float J[6] = {cr.x, cr.y, cr.z, nm.x, nm.y, nm.z};
-  int k = 0;
-  for (int a = 0; a < 6; a++)
-    for (int b = a; b < 6; b++) acc[k++] = J[a] * J[b];
-  for (int a = 0; a < 6; a++) acc[21 + a] = J[a] * r;
-  acc[27] = r * r;
-  acc[28] = 1.0f;
+  if (!plane_row(p, n, xf(Tj, vj), rot(Tj, nj), a->dist_thres, a->normal_thres, acc)) return 0;
+  float rc, Jc[6];
+  if (m->ph && colour_row(m->ph[(size_t)i * m->npx + px].x, m->ph + (size_t)j * m->npx, c, pc, p, Tj, a->colour_thres, a->colour_gradient_min, &rc, Jc)) {
+    add_colour_row(acc, a->colour_weight, rc, Jc);
+    if (rc_out) { *rc_out = rc; memcpy(Jc_out, Jc, sizeof(Jc)); }
+  }
   return 1;
 }
 
 /* the P systems at the poses T (K x 12 doubles) */
 static void systems_at(const maps_t* m, const double* T, const uint8_t* valid, const int32_t* pairs, int P, const al_params* a, double* sys) {
   const int nb = (m->npx + 255) / 256;
-  static float lane[256][AL_NSYS];
+  static float lane[256][SR_NSYS];
   for (int p = 0; p < P; p++) {
-    double* tot = sys + (size_t)p * AL_NSYS;
-    for (int k = 0; k < AL_NSYS; k++) tot[k] = 0.0;
+    double* tot = sys + (size_t)p * SR_NSYS;
+    for (int k = 0; k < SR_NSYS; k++) tot[k] = 0.0;
     const int i = pairs[2 * p], j = pairs[2 * p + 1];
     if (!valid[i] || !valid[j]) continue;
     float Ti[12], Tj[12], M[12];
@@ -263,42 +161,11 @@ static void systems_at(const maps_t* m, const double* T, const uint8_t* valid, c
       memset(lane, 0, sizeof(lane));
       for (int tid = 0; tid < 256; tid++) {
         const int px = b * 256 + tid;
-        if (px < m->npx) pixel_row(m, i, j, px, Ti, Tj, M, a->dist_thres, a->normal_thres, lane[tid]);
+        if (px < m->npx) pixel_row(m, i, j, px, Ti, Tj, M, a, lane[tid], NULL, NULL);
       }
-      float wsum[4][AL_NSYS];
-      for (int w = 0; w < 4; w++)
-        for (int k = 0; k < AL_NSYS; k++) {
-          float x[64];
-          for (int q = 0; q < 64; q++) x[q] = lane[64 * w + q][k];
-          for (int off = 32; off >= 1; off >>= 1)   /* the xor butterfly: lane 0 keeps x0 + x_off at every step */
-            for (int q = 0; q < off; q++) x[q] = x[q] + x[q + off];
-          wsum[w][k] = x[0];
-        }
-      for (int k = 0; k < AL_NSYS; k++) tot[k] += (double)((wsum[0][k] + wsum[1][k]) + (wsum[2][k] + wsum[3][k]));
+      reduce_block(lane, tot);
     }
   }
-}
-
-static void apply_update(const double* xi, double* T) {
-  const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
-  const double th = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-  double a = 1.0, b = 0.5;
-  if (th >= 1e-8) {
-    a = sin(th) / th;
-    b = (1.0 - cos(th)) / (th * th);
-  }
-  const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-  double R[3][3], out[12];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
-      R[i][j] = ((i == j ? 1.0 : 0.0) + a * K[i][j]) + b * k2;
-    }
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 4; j++) out[4 * i + j] = (R[i][0] * T[j] + R[i][1] * T[4 + j]) + R[i][2] * T[8 + j];
-    out[4 * i + 3] += xi[3 + i];
-  }
-  memcpy(T, out, sizeof(out));
 }
 
 static int uf_find(int* parent, int k) {
@@ -306,44 +173,13 @@ static int uf_find(int* parent, int k) {
   return k;
 }
 
-/* A x = -b, A symmetric N x N: Cholesky, sums in index order; 0 at a pivot <= AL_PIVOT_REL x its diagonal entry */
-static int solve_dense(const double* A, const double* b, int N, double* x) {
-  double* L = (double*)calloc((size_t)N * N, sizeof(double));
-  double* y = (double*)calloc((size_t)N, sizeof(double));
-  int ok = 1;
-  for (int j = 0; j < N && ok; j++) {
-    double s = A[(size_t)j * N + j];
-    for (int m = 0; m < j; m++) s -= L[(size_t)j * N + m] * L[(size_t)j * N + m];
-    if (!(s > AL_PIVOT_REL * A[(size_t)j * N + j])) { ok = 0; break; }
-    L[(size_t)j * N + j] = sqrt(s);
-    for (int i = j + 1; i < N; i++) {
-      double e = A[(size_t)i * N + j];
-      for (int m = 0; m < j; m++) e -= L[(size_t)i * N + m] * L[(size_t)j * N + m];
-      L[(size_t)i * N + j] = e / L[(size_t)j * N + j];
-    }
-  }
-  if (ok) {
-    for (int i = 0; i < N; i++) {
-      double e = -b[i];
-      for (int m = 0; m < i; m++) e -= L[(size_t)i * N + m] * y[m];
-      y[i] = e / L[(size_t)i * N + i];
-    }
-    for (int i = N - 1; i >= 0; i--) {
-      double e = y[i];
-      for (int m = i + 1; m < N; m++) e -= L[(size_t)m * N + i] * x[m];
-      x[i] = e / L[(size_t)i * N + i];
-    }
-  }
-  free(L);
-  free(y);
-  return ok;
-}
-
-/* The P per-pair systems at the given poses (the library's sf_fuser_align_system).  -1: an argument the library refuses. */
-int al_system(const al_frame* fr, const uint16_t* depth, int64_t K, const float* poses, const int32_t* pairs, int64_t P, const al_params* a, double* sys) {
-  if (check_args(K, pairs, P, a) != 0) return -1;
+/* The P per-pair systems at the given poses, 31 doubles each (the library's sf_fuser_align_system and sf_fuser_align_rgbd_system).  rgb: K pictures
+ * or NULL.  -1: an argument the library refuses. */
+int al_system(const sr_frame* fr, const uint16_t* depth, const uint8_t* rgb, int64_t K, const float* poses, const int32_t* pairs, int64_t P, const al_params* a,
+              double* sys) {
+  if (check_args(K, pairs, P, a, rgb) != 0) return -1;
   maps_t m;
-  if (maps_build(&m, fr, depth, (int)K, a) != 0) return -1;
+  if (maps_build(&m, fr, depth, rgb, (int)K, a) != 0) return -1;
   double* T = (double*)calloc((size_t)K * 12, sizeof(double));
   uint8_t* valid = (uint8_t*)calloc((size_t)K, 1);
   for (int k = 0; k < K; k++) {
@@ -357,18 +193,47 @@ int al_system(const al_frame* fr, const uint16_t* depth, int64_t K, const float*
   return 0;
 }
 
-/* The whole alignment (sf_fuser_align).  -1: an argument the library refuses. */
-int al_align(const al_frame* fr, const uint16_t* depth, int64_t K, const float* poses_in, const int32_t* pairs, int64_t P, const al_params* a, float* poses_out,
-             al_result* res) {
-  if (check_args(K, pairs, P, a) != 0) return -1;
+/* The maps of frame k at the solver's level for the tests: vmap npx x 3 floats, pmap npx x 3 floats {I, gx, gy}; cam_out: W, H as floats, fx, fy, mx, my */
+int al_maps(const sr_frame* fr, const uint16_t* depth, const uint8_t* rgb, int64_t K, int64_t k, const al_params* a, float* vmap, float* pmap, float* cam_out) {
   maps_t m;
-  if (maps_build(&m, fr, depth, (int)K, a) != 0) return -1;
+  if (!rgb || k < 0 || k >= K || maps_build(&m, fr, depth, rgb, (int)K, a) != 0) return -1;
+  memcpy(vmap, m.v + (size_t)k * m.npx, sizeof(f3) * m.npx);
+  memcpy(pmap, m.ph + (size_t)k * m.npx, sizeof(f3) * m.npx);
+  cam_out[0] = (float)m.cam.W; cam_out[1] = (float)m.cam.H; cam_out[2] = m.cam.fx; cam_out[3] = m.cam.fy; cam_out[4] = m.cam.mx; cam_out[5] = m.cam.my;
+  maps_free(&m);
+  return 0;
+}
+
+/* The colour rows of pair (i, j) at the given poses for the tests: rows npx x 8 floats {has a colour row, r_c, J_c[6]}, zeros elsewhere */
+int al_rows(const sr_frame* fr, const uint16_t* depth, const uint8_t* rgb, int64_t K, const float* poses, int32_t i, int32_t j, const al_params* a, float* rows) {
+  maps_t m;
+  if (!rgb || i < 0 || j < 0 || i >= K || j >= K || maps_build(&m, fr, depth, rgb, (int)K, a) != 0) return -1;
+  double Td[2][12];
+  float Ti[12], Tj[12], M[12];
+  for (int k = 0; k < 12; k++) { Td[0][k] = Ti[k] = poses[16 * i + k]; Td[1][k] = Tj[k] = poses[16 * j + k]; }
+  compose_ref(Td[1], Td[0], M);
+  memset(rows, 0, sizeof(float) * 8 * m.npx);
+  for (int px = 0; px < m.npx; px++) {
+    float acc[SR_NSYS] = {0};
+    float* o = rows + 8 * (size_t)px;
+    if (pixel_row(&m, i, j, px, Ti, Tj, M, a, acc, o + 1, o + 2)) o[0] = acc[30];
+  }
+  maps_free(&m);
+  return 0;
+}
+
+/* The whole alignment (sf_fuser_align and sf_fuser_align_rgbd).  -1: an argument the library refuses. */
+int al_align(const sr_frame* fr, const uint16_t* depth, const uint8_t* rgb, int64_t K, const float* poses_in, const int32_t* pairs, int64_t P, const al_params* a,
+             float* poses_out, al_result* res) {
+  if (check_args(K, pairs, P, a, rgb) != 0) return -1;
+  maps_t m;
+  if (maps_build(&m, fr, depth, rgb, (int)K, a) != 0) return -1;
   al_result r;
   memset(&r, 0, sizeof(r));
   memcpy(poses_out, poses_in, sizeof(float) * 16 * (size_t)K);
   double* T0 = (double*)calloc((size_t)K * 12, sizeof(double));
   double* T = (double*)calloc((size_t)K * 12, sizeof(double));
-  double* sys = (double*)calloc((size_t)P * AL_NSYS, sizeof(double));
+  double* sys = (double*)calloc((size_t)P * SR_NSYS, sizeof(double));
   uint8_t* valid = (uint8_t*)calloc((size_t)K, 1);
   uint8_t* kept = (uint8_t*)calloc((size_t)P, 1);
   uint8_t* conn = (uint8_t*)calloc((size_t)K, 1);
@@ -385,7 +250,7 @@ int al_align(const al_frame* fr, const uint16_t* depth, int64_t K, const float* 
     for (int k = 0; k < K; k++) parent[k] = k;
     for (int p = 0; p < P; p++) {
       const int i = pairs[2 * p], j = pairs[2 * p + 1];
-      kept[p] = valid[i] && valid[j] && sys[(size_t)p * AL_NSYS + 28] >= (double)a->min_pair_correspondences;
+      kept[p] = valid[i] && valid[j] && sys[(size_t)p * SR_NSYS + 28] >= (double)a->min_pair_correspondences;
       if (!kept[p]) continue;
       const int ra = uf_find(parent, i), rb = uf_find(parent, j);
       if (ra < rb) parent[rb] = ra;
@@ -407,15 +272,13 @@ int al_align(const al_frame* fr, const uint16_t* depth, int64_t K, const float* 
     double* b = (double*)calloc((size_t)N, sizeof(double));
     double* xi = (double*)calloc((size_t)N, sizeof(double));
     int used = 0;
-    double corr = 0.0, r2 = 0.0;
+    double corr = 0.0, r2 = 0.0, ccorr = 0.0, cr2 = 0.0;
     for (int p = 0; p < P; p++) {
       const int i = pairs[2 * p], j = pairs[2 * p + 1];
       if (!kept[p] || !conn[i]) continue;
-      const double* s = sys + (size_t)p * AL_NSYS;
+      const double* s = sys + (size_t)p * SR_NSYS;
       double H[6][6];
-      int k = 0;
-      for (int u = 0; u < 6; u++)
-        for (int v = u; v < 6; v++) H[u][v] = H[v][u] = s[k++];
+      unpack_sym6(s, H);
       const int si = slot[i], sj = slot[j];
       for (int u = 0; u < 6; u++) {
         for (int v = 0; v < 6; v++) {
@@ -432,18 +295,20 @@ int al_align(const al_frame* fr, const uint16_t* depth, int64_t K, const float* 
       used++;
       r2 += s[27];
       corr += s[28];
+      cr2 += s[29];
+      ccorr += s[30];
     }
     r.pairs_used = used;
     r.correspondences = (int64_t)corr;
-    r.rms_last = corr > 0.0 ? (float)sqrt(r2 / corr) : 0.0f;
-    if (it == 0) r.rms_first = r.rms_last;
-    const int ok = solve_dense(A, b, N, xi);
-    double mx = 0.0;
-    if (ok) {
+    r.rms_last = rms_of(r2, corr);
+    r.colour_correspondences = (int64_t)ccorr;
+    r.colour_rms_last = rms_of(cr2, ccorr);
+    if (it == 0) { r.rms_first = r.rms_last; r.colour_rms_first = r.colour_rms_last; }
+    const int ok = cholesky_solve(A, b, N, xi);
+    if (ok)
       for (int k = 0; k < K; k++)
         if (slot[k] >= 0) apply_update(xi + 6 * slot[k], T + 12 * k);
-      for (int k = 0; k < N; k++) mx = fmax(mx, fabs(xi[k]));
-    }
+    const double mx = ok ? max_abs(xi, N) : 0.0;
     free(A);
     free(b);
     free(xi);
@@ -455,20 +320,8 @@ int al_align(const al_frame* fr, const uint16_t* depth, int64_t K, const float* 
     if (!valid[k] || k == fixed) continue;
     if (!conn[k]) { r.frames_unconnected++; continue; }
     if (r.status != 0) continue;
-    const double* G = T0 + 12 * k;
-    const double* Tk = T + 12 * k;
-    const double dt[3] = {Tk[3] - G[3], Tk[7] - G[7], Tk[11] - G[11]};
-    const double dist = sqrt((dt[0] * dt[0] + dt[1] * dt[1]) + dt[2] * dt[2]);
-    double tr = 0.0;
-    for (int i = 0; i < 3; i++) tr += (G[i] * Tk[i] + G[4 + i] * Tk[4 + i]) + G[8 + i] * Tk[8 + i];
-    const double ang = acos(fmin(1.0, fmax(-1.0, (tr - 1.0) * 0.5)));
-    int fin = 1;
-    for (int i = 0; i < 12; i++) fin = fin && isfinite(Tk[i]);
-    if (!fin || !(dist <= (double)a->max_translation) || !(ang <= (double)a->max_rotation)) { r.frames_rejected++; continue; }
-    float* o = poses_out + 16 * k;
-    for (int i = 0; i < 12; i++) o[i] = (float)Tk[i];
-    o[12] = o[13] = o[14] = 0.0f;
-    o[15] = 1.0f;
+    if (!motion_ok(T0 + 12 * k, T + 12 * k, a->max_translation, a->max_rotation)) { r.frames_rejected++; continue; }
+    write_pose(T + 12 * k, poses_out + 16 * k);
   }
   *res = r;
   free(T0); free(T); free(sys); free(valid); free(kept); free(conn); free(parent); free(slot);
@@ -532,13 +385,9 @@ int al_spread(const float* poses, uint64_t n, const uint64_t* keyframes, uint64_
     if (k < 0 || !finite12(Tf)) { memmove(o, Tf, 16 * sizeof(float)); continue; }
     const float* To = poses + 16 * keyframes[k];
     const float* Tn = new_key_poses + 16 * k;
-    const double a00 = To[0], a01 = To[1], a02 = To[2], a10 = To[4], a11 = To[5], a12 = To[6], a20 = To[8], a21 = To[9], a22 = To[10];
-    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-    const double det = a00 * c00 + a01 * c01 + a02 * c02;
-    double inv[9], D[12];
-    inv[0] = c00 / det; inv[1] = (a02 * a21 - a01 * a22) / det; inv[2] = (a01 * a12 - a02 * a11) / det;
-    inv[3] = c01 / det; inv[4] = (a00 * a22 - a02 * a20) / det; inv[5] = (a02 * a10 - a00 * a12) / det;
-    inv[6] = c02 / det; inv[7] = (a01 * a20 - a00 * a21) / det; inv[8] = (a00 * a11 - a01 * a10) / det;
+    double Tod[12], inv[9], D[12];
+    for (int q = 0; q < 12; q++) Tod[q] = To[q];
+    inverse3(Tod, inv);
     for (int r = 0; r < 3; r++) {
       for (int c = 0; c < 3; c++) D[4 * r + c] = ((double)Tn[4 * r] * inv[c] + (double)Tn[4 * r + 1] * inv[3 + c]) + (double)Tn[4 * r + 2] * inv[6 + c];
       D[4 * r + 3] = (double)Tn[4 * r + 3] - ((D[4 * r] * (double)To[3] + D[4 * r + 1] * (double)To[7]) + D[4 * r + 2] * (double)To[11]);

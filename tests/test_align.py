@@ -8,8 +8,6 @@ BundleFusion's solver is not in the reference tree, so the rule is pinned the wa
     align_and_reintegrate, bin/depthsensing --track --align.
 """
 import ctypes as C
-import hashlib
-import importlib.util
 import os
 import shutil
 import subprocess
@@ -18,14 +16,14 @@ import numpy as np
 import pytest
 
 from scannet_amd import _abi, synth
+from tests import solver_scenes as ss
+from tests.solver_scenes import DRIFT_R, DRIFT_T, WALK_TOTAL, f32, perturb, pose_error, random_poses, worst_pose_error as worst
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "bin", "depthsensing")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "zParametersBundlingScanNet.txt")
 SF_ERR_INVALID_ARG = -1
 W, H = 320, 240
-WALK_TOTAL = 1200                              # the walk's 12 m perimeter in 1200 frames: 1 cm per frame
-DRIFT_T, DRIFT_R = 0.008, 0.004                # injected per keyframe: metres, radians
 # On noise-free planes the residual at the true poses is zero up to rounding and the 1 mm depth step: the truth is the solver's fixed point
 # (the bound test_track.py::test_checker_room_corner_converges uses on this scene)
 CORNER_T_BOUND, CORNER_R_BOUND = 1e-3, 1e-3    # metres, radians
@@ -33,131 +31,49 @@ CORNER_T_BOUND, CORNER_R_BOUND = 1e-3, 1e-3    # metres, radians
 ROOM_T_BOUND, ROOM_R_BOUND = 0.015, 0.005
 
 
-def _has_fma():
-    try:
-        return " fma " in open("/proc/cpuinfo").read().replace("\n", " ")
-    except OSError:
-        return False
-
-
-class AlFrame(C.Structure):
-    _fields_ = [("in_w", C.c_int32), ("in_h", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
-                ("fx", C.c_float), ("fy", C.c_float), ("mx", C.c_float), ("my", C.c_float),
-                ("depth_shift", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float)]
-
-
 @pytest.fixture(scope="module")
-def chk(tmp_path_factory):
-    """tests/align_checker.c, compiled as tests/test_track.py compiles its checker."""
-    if shutil.which("gcc") is None or not _has_fma():
+def chk():
+    """tests/align_checker.c is there to be compiled; the tests reach it through tests/solver_scenes.py."""
+    if not ss.checkers_available():
         pytest.skip("needs gcc and a CPU with fused multiply-add")
-    from scannet_amd import fusion
-    so = str(tmp_path_factory.mktemp("align_checker") / "libalign_checker.so")
-    subprocess.run(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "align_checker.c"), "-lm"],
-                   check=True)
-    al = C.CDLL(so)
-    PP, RP = C.POINTER(fusion.SfAlignParams), C.POINTER(fusion.SfAlignResult)
-    al.al_system.argtypes = [C.POINTER(AlFrame), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, PP, C.c_void_p]
-    al.al_align.argtypes = [C.POINTER(AlFrame), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, PP, C.c_void_p, RP]
-    al.al_pairs.argtypes = [C.c_void_p, C.c_int64, PP, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-    al.al_spread.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    return al
-
-
-def look_at(eye, target):
-    """camToWorld of a camera at eye looking at target, world z up, image y down."""
-    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
-    z = target - eye
-    z /= np.linalg.norm(z)
-    x = np.cross(z, [0.0, 0.0, 1.0])
-    x /= np.linalg.norm(x)
-    y = np.cross(z, x)
-    m = np.eye(4)
-    m[:3, 0], m[:3, 1], m[:3, 2], m[:3, 3] = x, y, z, eye
-    return m.astype(np.float32)
-
-
-def perturb(pose, dt, rad, axis=(0.3, -0.5, 0.8), tdir=(0.6, 0.64, -0.48)):
-    """pose moved dt metres along tdir and turned rad radians about axis (world frame, left increment)."""
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    R = np.eye(3) + np.sin(rad) * K + (1 - np.cos(rad)) * K @ K
-    out = np.eye(4)
-    out[:3, :3] = R @ pose[:3, :3].astype(np.float64)
-    out[:3, 3] = R @ pose[:3, 3].astype(np.float64) + dt * np.asarray(tdir, np.float64) / np.linalg.norm(tdir)
-    return out.astype(np.float32)
-
-
-def pose_error(a, b):
-    """(translation metres, rotation radians) between two camToWorld poses."""
-    a, b = np.asarray(a, np.float64).reshape(4, 4), np.asarray(b, np.float64).reshape(4, 4)
-    dt = float(np.linalg.norm(a[:3, 3] - b[:3, 3]))
-    c = (np.trace(a[:3, :3].T @ b[:3, :3]) - 1.0) / 2.0
-    return dt, float(np.arccos(np.clip(c, -1.0, 1.0)))
+    return ss.align_lib()
 
 
 def frame_of(W_=W, H_=H):
-    from scannet_amd import fusion
-    p = fusion.default_params(depth_width=W_, depth_height=H_)
-    fx, fy, mx, my = synth.intrinsics(W_, H_)
-    return AlFrame(W_, H_, W_, H_, fx, fy, mx, my, p.depth_shift, p.depth_min, p.depth_max)
+    return ss.align_frame(W_, H_)
 
 
 def fuser_params(voxel=0.008, W_=W, H_=H):
-    from scannet_amd import fusion
-    fx, fy, mx, my = synth.intrinsics(W_, H_)
-    return fusion.default_params(depth_width=W_, depth_height=H_, voxel_size=voxel, fx=fx, fy=fy, mx=mx, my=my, num_sdf_blocks=1 << 17)
+    return ss.fuser_params(W_, H_, ss.NO_COLOUR, voxel, num_sdf_blocks=1 << 17)
 
 
-def drifted(truth):
-    """Keyframe k starts k x (8 mm, 4 mrad) off the truth; keyframe 0 is true."""
-    return np.stack([perturb(t, DRIFT_T * k, DRIFT_R * k) if k else t for k, t in enumerate(truth)]).astype(np.float32)
-
-
-def cpu_align(chk, depth, poses, pairs, a, fr=None):
-    from scannet_amd import fusion
-    fr = fr or frame_of()
-    depth = np.ascontiguousarray(depth, np.uint16)
-    poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    out = np.empty_like(poses)
-    res = fusion.SfAlignResult()
-    rc = chk.al_align(C.byref(fr), depth.ctypes.data, len(poses), poses.ctypes.data, pairs.ctypes.data, len(pairs), C.byref(a), out.ctypes.data, C.byref(res))
+def cpu_align(depth, poses, pairs, a, fr=None):
+    """The depth-only alignment (no pictures): the colour term's result fields are 0."""
+    rc, out, res = ss.cpu_align(depth, poses, pairs, a, fr or frame_of())
+    assert rc != 0 or (res.colour_correspondences == 0 and res.colour_rms_first == 0.0 and res.colour_rms_last == 0.0)
     return rc, out, res
 
 
-def cpu_system(chk, depth, poses, pairs, a, fr=None):
-    fr = fr or frame_of()
-    depth = np.ascontiguousarray(depth, np.uint16)
-    poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    sys = np.zeros((len(pairs), 29), np.float64)
-    rc = chk.al_system(C.byref(fr), depth.ctypes.data, len(poses), poses.ctypes.data, pairs.ctypes.data, len(pairs), C.byref(a), sys.ctypes.data)
-    return rc, sys
+def cpu_system(depth, poses, pairs, a, fr=None):
+    """The depth-only systems (no pictures): 29 sums per pair, the colour term's two are 0."""
+    rc, sys = ss.cpu_align_system(depth, poses, pairs, a, fr or frame_of())
+    assert not sys[:, 29:].any()
+    return rc, np.ascontiguousarray(sys[:, :29])
 
 
 def res_tuple(r):
-    return (int(r.status), int(r.iterations), int(r.pairs_used), int(r.frames_unconnected), int(r.frames_rejected), int(r.correspondences),
-            np.float32(r.rms_first).tobytes(), np.float32(r.rms_last).tobytes())
+    """The depth term's fields of sf_align_result."""
+    return ss.align_res_tuple(r)[:8]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # Scenes (rendered once per module)
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-CORNER_EYE = (1.6, 1.3, 1.4)   # the room's corner at the origin: two walls and the floor, about 2.5 m away
-
-
 @pytest.fixture(scope="module")
 def corner():
-    """Test 1's input: 6 noise-free views of the room corner along a 50 cm arc about the vertical through it, all looking at the corner."""
-    r = float(np.hypot(CORNER_EYE[0], CORNER_EYE[1]))
-    az0 = float(np.arctan2(CORNER_EYE[1], CORNER_EYE[0]))
-    truth = []
-    for k in range(6):
-        az = az0 + (k - 2.5) * 0.1 / r   # 10 cm of arc per keyframe
-        truth.append(look_at((r * np.cos(az), r * np.sin(az), CORNER_EYE[2]), (0.0, 0.0, 0.0)))
-    depth = np.stack([synth.render_room_depth(p, W, H).reshape(-1) for p in truth])
-    return depth, np.stack(truth), drifted(truth)
+    """Test 1's input: 6 noise-free views of the room corner along a 50 cm arc about the vertical through it (10 cm of arc per keyframe), all looking
+    at the corner."""
+    return ss.corner_arc(6, W, H, metres=0.1)
 
 
 @pytest.fixture(scope="module")
@@ -166,7 +82,7 @@ def room():
     boxes = synth.clutter_boxes()
     truth = [synth.trajectory_pose(10 * k, WALK_TOTAL) for k in range(8)]
     depth = np.stack([synth.render_room_depth(p, W, H, noise_frame=10 * k, noise=2, boxes=boxes).reshape(-1) for k, p in enumerate(truth)])
-    return depth, np.stack(truth).astype(np.float32), drifted(truth)
+    return depth, np.stack(truth).astype(np.float32), ss.drifted(truth)
 
 
 @pytest.fixture(scope="module")
@@ -177,14 +93,9 @@ def corner_cpu(chk, corner):
     a = fusion.default_align_params()
     pairs, count = fusion.align_pairs(start, a)
     assert count == len(pairs)
-    rc, out, res = cpu_align(chk, depth, start, pairs, a)
+    rc, out, res = cpu_align(depth, start, pairs, a)
     assert rc == 0
     return pairs, out, res
-
-
-def worst(out, truth):
-    e = [pose_error(o.reshape(4, 4), t) for o, t in zip(out, truth)]
-    return max(x[0] for x in e), max(x[1] for x in e)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -212,7 +123,7 @@ def test_checker_furnished_scene_stays_within_the_trackers_bound(chk, room):
     a = fusion.default_align_params()
     pairs, count = fusion.align_pairs(start, a)
     assert count == len(pairs)
-    rc, out, res = cpu_align(chk, depth, start, pairs, a)
+    rc, out, res = cpu_align(depth, start, pairs, a)
     assert rc == 0
     et, er = worst(out, truth)
     print("room: worst %.3f mm / %.3f mrad, %s" % (et * 1e3, er * 1e3, res.as_dict()))
@@ -225,22 +136,7 @@ def test_checker_furnished_scene_stays_within_the_trackers_bound(chk, room):
 # CPU: structure
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 def structure_cases(corner):
-    """name -> (depth [K, H*W], poses [K,16], pairs).  thin: frame 2 keeps a 20 x 20 patch of its depth, 100 pixels at level 1, so both its pairs
-    fall below min_pair_correspondences = 500 and nothing connects it.  lost: frame 1 has the all -inf pose.  planes: two frames that each see one
-    single plane."""
-    depth, truth, start = corner
-    thin = depth[:3].copy().reshape(3, H, W)
-    keep = thin[2, 100:120, 150:170].copy()
-    thin[2] = 0
-    thin[2, 100:120, 150:170] = keep
-    lost = start[:3].copy().reshape(3, 16)
-    lost[1] = -np.inf
-    star = np.array([[0, 1], [1, 0], [0, 2], [2, 0]], np.int32)
-    plane = np.stack([synth.plane_frame(W, H).reshape(-1)] * 2)
-    pp = np.stack([np.eye(4, dtype=np.float32), perturb(np.eye(4, dtype=np.float32), 0.01, 0.01)]).reshape(2, 16)
-    return {"thin": (thin.reshape(3, -1), start[:3].reshape(3, 16), star),
-            "lost": (depth[:3], lost, star),
-            "planes": (plane, pp, np.array([[0, 1], [1, 0]], np.int32))}
+    return ss.structure_cases(corner, W, H)
 
 
 def check_structure(name, poses, out, res):
@@ -261,7 +157,7 @@ def check_structure(name, poses, out, res):
 def test_checker_structure(chk, corner, name):
     from scannet_amd import fusion
     depth, poses, pairs = structure_cases(corner)[name]
-    rc, out, res = cpu_align(chk, depth, poses, pairs, fusion.default_align_params())
+    rc, out, res = cpu_align(depth, poses, pairs, fusion.default_align_params())
     assert rc == 0
     check_structure(name, poses, out, res)
 
@@ -270,7 +166,7 @@ def test_nothing_connected_is_status_2(chk, corner):
     from scannet_amd import fusion
     depth, truth, start = corner
     a = fusion.default_align_params(min_pair_correspondences=W * H)   # more than a level-1 image holds
-    rc, out, res = cpu_align(chk, depth[:3], start[:3], np.array([[0, 1], [1, 2]], np.int32), a)
+    rc, out, res = cpu_align(depth[:3], start[:3], np.array([[0, 1], [1, 2]], np.int32), a)
     assert rc == 0 and res.status == 2 and res.frames_unconnected == 2 and res.pairs_used == 0
     assert out.tobytes() == start[:3].tobytes()
 
@@ -293,9 +189,9 @@ def test_refused_arguments(chk, corner, name, case):
     out = np.zeros_like(poses)
     res = fusion.SfAlignResult()
     fr = frame_of()
-    assert chk.al_align(C.byref(fr), d.ctypes.data, K, poses.ctypes.data, pairs.ctypes.data, P, C.byref(a), out.ctypes.data, C.byref(res)) == -1
-    sys = np.zeros((max(P, 1), 29))
-    assert chk.al_system(C.byref(fr), d.ctypes.data, K, poses.ctypes.data, pairs.ctypes.data, P, C.byref(a), sys.ctypes.data) == -1
+    assert chk.al_align(C.byref(fr), d.ctypes.data, None, K, poses.ctypes.data, pairs.ctypes.data, P, C.byref(a), out.ctypes.data, C.byref(res)) == -1
+    sys = np.zeros((max(P, 1), 31))
+    assert chk.al_system(C.byref(fr), d.ctypes.data, None, K, poses.ctypes.data, pairs.ctypes.data, P, C.byref(a), sys.ctypes.data) == -1
     L = _abi.lib()
     PP, RP = C.POINTER(fusion.SfAlignParams), C.POINTER(fusion.SfAlignResult)
     L.sf_fuser_align.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, PP, C.c_void_p, RP]
@@ -319,34 +215,18 @@ def test_checker_refuses_a_size_that_is_no_level(chk, corner):
     depth, truth, start = corner
     pairs = np.array([[0, 1], [1, 0]], np.int32)
     for dw, dh in ((100, 60), (80, 0), (20, 15)):
-        rc, _, _ = cpu_align(chk, depth[:2], start[:2], pairs, fusion.default_align_params(down_width=dw, down_height=dh))
+        rc, _, _ = cpu_align(depth[:2], start[:2], pairs, fusion.default_align_params(down_width=dw, down_height=dh))
         assert rc == -1, (dw, dh)
     # 80 x 60 is level 2 of 320 x 240, whatever `level` says
     a = fusion.default_align_params(down_width=80, down_height=60, level=0)
-    rc, s1 = cpu_system(chk, depth[:2], start[:2], pairs, a)
-    rc2, s2 = cpu_system(chk, depth[:2], start[:2], pairs, fusion.default_align_params(level=2))
+    rc, s1 = cpu_system(depth[:2], start[:2], pairs, a)
+    rc2, s2 = cpu_system(depth[:2], start[:2], pairs, fusion.default_align_params(level=2))
     assert rc == 0 and rc2 == 0 and s1.tobytes() == s2.tobytes() and s1[0, 28] > 1000
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # CPU: sf_align_pairs and sf_align_spread (host only)
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def random_poses(n, seed, spread=1.5, turn=0.7):
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        w = rng.normal(size=3)
-        w *= rng.uniform(0, turn) / np.linalg.norm(w)
-        th = np.linalg.norm(w)
-        Kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-        R = np.eye(3) + np.sin(th) / th * Kx + (1 - np.cos(th)) / th ** 2 * Kx @ Kx
-        m = np.eye(4)
-        m[:3, :3] = R
-        m[:3, 3] = rng.uniform(-spread, spread, 3)
-        out.append(m)
-    return np.stack(out).astype(np.float32)
-
-
 def numpy_pairs(poses, max_dist, max_angle):
     """The rule of sf_align_pairs in float64."""
     P = poses.astype(np.float64).reshape(-1, 4, 4)
@@ -397,7 +277,7 @@ def test_align_spread_equals_the_checker(chk):
     for lost in (0, 12, 13, 30, 23):                        # before the first keyframe, between keyframes, at a keyframe (23)
         poses[lost] = -np.inf
     assert 23 in keys
-    new = np.stack([perturb(poses[int(k)].reshape(4, 4), 0.004 * q, 0.002 * q) if np.isfinite(poses[int(k)]).all() else poses[int(k)].reshape(4, 4)
+    new = np.stack([perturb(poses[int(k)].reshape(4, 4), 0.004 * q, rad=0.002 * q) if np.isfinite(poses[int(k)]).all() else poses[int(k)].reshape(4, 4)
                     for q, k in enumerate(keys)]).astype(np.float32).reshape(-1, 16)
     new[5] = np.nan                                        # keyframe 37 came back without a pose: its frames follow keyframe 30
     got = fusion.align_spread(poses, keys, new)
@@ -423,10 +303,6 @@ def test_align_spread_equals_the_checker(chk):
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # CPU: parameters and layouts
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def f32(x):
-    return np.float32(x)
-
-
 def test_align_params_default_and_file(tmp_path):
     from scannet_amd import fusion
     a = fusion.default_align_params()
@@ -502,9 +378,7 @@ def test_depthsensing_refuses_align_without_track_and_with_ranks(tmp_path):
 def test_align_kernels_live_in_registers():
     if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("no llvm-readelf")
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
+    kr = ss.kernel_resources()
     rows = kr.kernels(os.path.join(ROOT, "scannet_amd", "libscanfuse.so"))
     mine = [(kr.short(n), r) for r, n in zip(rows, kr.demangle([r["name"] for r in rows])) if kr.short(n).startswith("k_align_")]
     assert {s.split("<")[0] for s, _ in mine} == {"k_align_prep", "k_align_assoc", "k_align_final"}
@@ -519,11 +393,6 @@ def test_align_kernels_live_in_registers():
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # GPU: the kernels against the checker, bit for bit
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def _volume_digest(f):
-    c, v = f.export_blocks()
-    return hashlib.sha256(c.tobytes() + v.tobytes()).hexdigest()
-
-
 @pytest.fixture(scope="module")
 def gpu_fuser(room):
     """A fuser holding 10 fused frames of the furnished room."""
@@ -553,7 +422,7 @@ def test_gpu_systems_bit_exact(chk, room, gpu_fuser, level):
     poses[3] = back
     pairs = np.array([[0, 1], [1, 0], [1, 2], [2, 1], [0, 2], [2, 0], [0, 3]], np.int32)
     a = fusion.default_align_params(level=level)
-    rc, want = cpu_system(chk, d, poses, pairs, a)
+    rc, want = cpu_system(d, poses, pairs, a)
     assert rc == 0
     got = gpu_fuser.align_system(d, poses, pairs, a)
     assert got.shape == (7, 29) and got.tobytes() == want.tobytes(), (level, np.abs(got - want).max())
@@ -572,7 +441,7 @@ def test_gpu_buffers_grow_on_demand_and_never_go_stale(chk, room):
            fusion.default_align_params(level=0))
     want = {}
     for name, (d, poses, pairs, a) in (("small", small), ("big", big)):
-        rc, want[name] = cpu_system(chk, d, poses, pairs, a)
+        rc, want[name] = cpu_system(d, poses, pairs, a)
         assert rc == 0 and (want[name][:2, 28] > 1000 >> (2 * a.level)).all(), want[name][:, 28]   # the comparison is not of empty systems
     with fusion.Fuser(fuser_params(), device=0) as f:
         for step, (name, (d, poses, pairs, a)) in enumerate((("small", small), ("big", big), ("small", small))):
@@ -599,7 +468,7 @@ def test_gpu_solve_bit_exact_and_leaves_the_volume_alone(corner, corner_cpu, gpu
     depth, truth, start = corner
     pairs, want, want_res = corner_cpu
     f = gpu_fuser
-    before, st0 = _volume_digest(f), f.stats()
+    before, st0 = ss.volume_digest(f), f.stats()
     a = fusion.default_align_params()
     out, res = f.align(depth, start, pairs, a)
     assert res_tuple(res) == res_tuple(want_res), (res.as_dict(), want_res.as_dict())
@@ -610,7 +479,7 @@ def test_gpu_solve_bit_exact_and_leaves_the_volume_alone(corner, corner_cpu, gpu
     torch.cuda.synchronize()
     out2, res2 = f.align_device(d, W * H * 2, start, pairs, a)
     assert out2.tobytes() == out.tobytes() and res_tuple(res2) == res_tuple(res)
-    assert _volume_digest(f) == before and f.stats() == st0
+    assert ss.volume_digest(f) == before and f.stats() == st0
 
 
 @pytest.mark.gpu
@@ -619,7 +488,7 @@ def test_gpu_structure_bit_exact(chk, corner, gpu_fuser, name):
     from scannet_amd import fusion
     depth, poses, pairs = structure_cases(corner)[name]
     a = fusion.default_align_params()
-    rc, want, want_res = cpu_align(chk, depth, poses, pairs, a)
+    rc, want, want_res = cpu_align(depth, poses, pairs, a)
     out, res = gpu_fuser.align(depth, poses, pairs, a)
     assert rc == 0 and res_tuple(res) == res_tuple(want_res) and out.tobytes() == want.tobytes()
     check_structure(name, poses, out, res)
@@ -642,7 +511,7 @@ def test_gpu_align_sees_queued_work_and_leaves_it_intact(corner, corner_cpu):
             assert b.integrate(d, pose)
             b.sync()
         assert a.stats()["frames_integrated"] == 3
-        assert _volume_digest(a) == _volume_digest(b)
+        assert ss.volume_digest(a) == ss.volume_digest(b)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -670,7 +539,7 @@ def test_gpu_align_and_reintegrate(tmp_path):
     """Test 2's drift scaled to 24 frames: frame i starts i / 23 x (56 mm, 28 mrad) off the truth."""
     from scannet_amd import fusion, sens
     truth = [synth.trajectory_pose(LOOP_STEP * i, WALK_TOTAL) for i in range(LOOP_N)]
-    start = np.stack([perturb(t, 7 * DRIFT_T * i / (LOOP_N - 1), 7 * DRIFT_R * i / (LOOP_N - 1)) if i else t for i, t in enumerate(truth)]).astype(np.float32)
+    start = np.stack([perturb(t, 7 * DRIFT_T * i / (LOOP_N - 1), rad=7 * DRIFT_R * i / (LOOP_N - 1)) if i else t for i, t in enumerate(truth)]).astype(np.float32)
     path, _ = _loop_scan(tmp_path, start)
     sd = sens.SensorData(path)
     clean = synth.render_room_depth(truth[-1], W, H, noise=0, boxes=synth.clutter_boxes()).astype(np.float32) / 1000.0

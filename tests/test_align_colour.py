@@ -1,15 +1,16 @@
 """The dense colour term of the global alignment (DESIGN.md "The colour term of the global alignment", 4f; scannet_amd/csrc/align_colour.hip).
 
-The rule is pinned as section 4e's is: tests/align_colour_checker.c restates it in C, this file renders its own scenes in numpy.
+The rule is pinned as section 4e's is: tests/align_checker.c restates it in C (one checker for the depth term and the colour term, over
+tests/solver_rules.h); the scenes are rendered in numpy by tests/solver_scenes.py.
   * without a GPU: a wall that depth alone cannot align (status 1) is aligned to sub-pixel accuracy with colour; the analytic row against a float64
-    finite difference; the furnished room with a painted texture stays within 4e's bound; colour_weight 0 equals tests/align_checker.c byte for
-    byte; parameters, struct layouts, the tool's refusals, the kernels' resources;
+    finite difference; the furnished room with a painted texture stays within 4e's bound; the checker against its recorded digests
+    (tests/golden/solver_checker.json), colour_weight 0 giving the depth term's bits; parameters, struct layouts, the tool's refusals, the kernels'
+    resources;
   * -m gpu: sf_fuser_align_rgbd_system and sf_fuser_align_rgbd against the checker bit for bit, the buffers' three states, the correction loop
     align_and_reintegrate(with_colour=True).
 """
 import ctypes as C
-import hashlib
-import importlib.util
+import json
 import os
 import shutil
 import subprocess
@@ -18,173 +19,41 @@ import numpy as np
 import pytest
 
 from scannet_amd import _abi, synth
+from tests import solver_scenes as ss
+from tests.solver_scenes import CFX, CFY, CH, CMX, CMY, CW, FOOT, FX, FY, H, MX, MY, SH, SW, W, WALL_Z, align_arrays as _arrays, texture, wall_scene
+from tests.solver_scenes import align_res_tuple as res_tuple, resampled_scene, small_scene, worst_in_plane_error as in_plane_error
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "bin", "depthsensing")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "zParametersBundlingScanNet.txt")
 SF_ERR_INVALID_ARG = -1
 ROOM_T_BOUND, ROOM_R_BOUND = 0.015, 0.005   # DESIGN.md 4e's bound on the furnished room
-
-# ---------------------------------------------------------------------------------------------------------------------------------------------
-# The wall: a textured plane z = WALL_Z in the world, cameras at z = 0 looking along +z.  Depth and colour come per pixel from the ray-plane
-# intersection; the colour camera has its own size and a narrower field, so the outer integration pixels have no colour.
-# ---------------------------------------------------------------------------------------------------------------------------------------------
-W, H = 160, 120
-LEVEL = 1
-WALL_Z = 2.0
-FX, FY, MX, MY = synth.intrinsics(W, H)
-FOOT = WALL_Z / (FX / (1 << LEVEL))          # metres of wall under one level pixel: 27.7 mm
-BOUND = 0.5 * FOOT                           # test 1's bound: half a level pixel's footprint
-CW, CH = 200, 150
-NARROW = 1.12
-CFX, CFY, CMX, CMY = FX * CW / W * NARROW, FY * CH / H * NARROW, (CW - 1) / 2.0, (CH - 1) / 2.0
-# sinusoids in plane coordinates: wavelength in level pixels (16 .. 64), direction (radians), phase; one amplitude row per channel
-WAVES = [(16.0, 0.3, 0.0), (24.0, 1.9, 1.0), (40.0, 2.6, 2.0), (64.0, 1.1, 4.0)]
-AMPS = {"r": (0.06, 0.10, 0.12, 0.12), "g": (0.05, 0.12, 0.10, 0.14), "b": (0.10, 0.06, 0.14, 0.08)}
-# in-plane start offsets in level pixels (at most 2) and turns about the wall's normal in radians, keyframes 1..; keyframe 0 is fixed at the truth
-OFFSETS = [(2.0, -1.5, 0.004), (-1.7, 2.0, -0.006), (1.2, 1.8, 0.005), (-2.0, -0.8, 0.003), (0.9, -2.0, -0.004), (1.6, 1.1, 0.006), (-1.1, 1.7, -0.003)]
+LEVEL = ss.ALIGN_LEVEL
+BOUND = 0.5 * FOOT                           # test 1's bound: half a level pixel's footprint (27.7 mm)
 
 
-def _has_fma():
-    try:
-        return " fma " in open("/proc/cpuinfo").read().replace("\n", " ")
-    except OSError:
-        return False
+def frame_of(w=W, h=H, intr=None, colour=ss.WALL_CAMERA):
+    return ss.align_frame(w, h, intr, colour)
 
 
-def texture(X, Y, scale=FOOT):
-    """RGB in [0, 1] at plane coordinates (metres): [..., 3]."""
-    out = []
-    for ch in "rgb":
-        v = np.full(np.shape(X), 0.5)
-        for (lam, th, ph), a in zip(WAVES, AMPS[ch]):
-            v = v + a * np.sin(2 * np.pi * (X * np.cos(th) + Y * np.sin(th)) / (lam * scale) + ph)
-        out.append(v)
-    return np.stack(out, -1)
-
-
-def wall_pose(x, y, rz=0.0):
-    """camToWorld of a camera at (x, y, 0) looking along +z, turned rz about z."""
-    m = np.eye(4)
-    m[:2, :2] = [[np.cos(rz), -np.sin(rz)], [np.sin(rz), np.cos(rz)]]
-    m[:3, 3] = (x, y, 0.0)
-    return m.astype(np.float32)
-
-
-def _hits(pose, w, h, fx, fy, mx, my):
-    """Ray-plane intersections of every pixel's ray with the wall: (range along the camera's z, world points)."""
-    yy, xx = np.mgrid[0:h, 0:w]
-    d = np.stack([(xx - mx) / fx, (yy - my) / fy, np.ones((h, w))], -1)
-    p = np.asarray(pose, np.float64)
-    dw = d @ p[:3, :3].T
-    s = (WALL_Z - p[2, 3]) / dw[..., 2]
-    return s, p[:3, 3] + s[..., None] * dw
-
-
-def render_wall(pose, w=W, h=H, intr=None, cw=CW, ch=CH, cintr=None):
-    """(u16 depth in mm [h*w], RGB8 [ch*cw*3]) of the wall from `pose`."""
-    fx, fy, mx, my = intr or (FX, FY, MX, MY)
-    cfx, cfy, cmx, cmy = cintr or (CFX, CFY, CMX, CMY)
-    s, _ = _hits(pose, w, h, fx, fy, mx, my)
-    _, pts = _hits(pose, cw, ch, cfx, cfy, cmx, cmy)
-    rgb = np.clip(np.rint(texture(pts[..., 0], pts[..., 1]) * 255.0), 0, 255).astype(np.uint8)
-    return np.rint(s * 1000.0).astype(np.uint16).reshape(-1), rgb.reshape(-1)
-
-
-def left_increment(pose, dx, dy, rz):
-    """[Rz(rz) | (dx, dy, 0)] pose."""
-    inc = wall_pose(dx, dy, rz).astype(np.float64)
-    return (inc @ np.asarray(pose, np.float64)).astype(np.float32)
-
-
-def wall_scene(K):
-    """K keyframes sliding along the wall 5 cm apart: (depth [K, H*W], rgb [K, CH*CW*3], truth [K,4,4], start [K,4,4])."""
-    truth = [wall_pose(0.05 * k, 0.012 * k) for k in range(K)]
-    start = [truth[0]] + [left_increment(t, o[0] * FOOT, o[1] * FOOT, o[2]) for t, o in zip(truth[1:], OFFSETS)]
-    frames = [render_wall(t) for t in truth]
-    return np.stack([f[0] for f in frames]), np.stack([f[1] for f in frames]), np.stack(truth), np.stack(start).astype(np.float32)
-
-
-def in_plane_error(out, truth):
-    """The largest distance in the wall's plane between a result and its truth, metres."""
-    return max(float(np.hypot(*(np.asarray(o, np.float64).reshape(4, 4)[:2, 3] - t[:2, 3]))) for o, t in zip(out, truth))
-
-
-class AlcFrame(C.Structure):
-    _fields_ = [("in_w", C.c_int32), ("in_h", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
-                ("fx", C.c_float), ("fy", C.c_float), ("mx", C.c_float), ("my", C.c_float),
-                ("depth_shift", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float),
-                ("color_w", C.c_int32), ("color_h", C.c_int32), ("cfx", C.c_float), ("cfy", C.c_float), ("cmx", C.c_float), ("cmy", C.c_float)]
-
-
-def frame_of(w=W, h=H, intr=None, colour=(CW, CH, CFX, CFY, CMX, CMY)):
-    from scannet_amd import fusion
-    p = fusion.default_params(depth_width=w, depth_height=h)
-    fx, fy, mx, my = intr or synth.intrinsics(w, h)
-    return AlcFrame(w, h, w, h, fx, fy, mx, my, p.depth_shift, p.depth_min, p.depth_max, *colour)
-
-
-def fuser_params(w=W, h=H, colour=(CW, CH, CFX, CFY, CMX, CMY), voxel=0.008):
-    from scannet_amd import fusion
-    fx, fy, mx, my = synth.intrinsics(w, h)
-    extra = dict(color_width=colour[0], color_height=colour[1], cfx=colour[2], cfy=colour[3], cmx=colour[4], cmy=colour[5]) if colour[0] else {}
-    return fusion.default_params(depth_width=w, depth_height=h, voxel_size=voxel, fx=fx, fy=fy, mx=mx, my=my, num_sdf_blocks=1 << 16, **extra)
-
-
-def _compile(tmp, name):
-    so = str(tmp / ("lib%s.so" % name))
-    subprocess.run(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", name + ".c"), "-lm"], check=True)
-    return C.CDLL(so)
+def fuser_params(w=W, h=H, colour=ss.WALL_CAMERA, voxel=0.008):
+    return ss.fuser_params(w, h, colour, voxel)
 
 
 @pytest.fixture(scope="module")
-def chk(tmp_path_factory):
-    """tests/align_colour_checker.c, compiled as tests/test_align.py compiles its checker."""
-    if shutil.which("gcc") is None or not _has_fma():
+def chk():
+    """tests/align_checker.c is there to be compiled; the tests reach it through tests/solver_scenes.py."""
+    if not ss.checkers_available():
         pytest.skip("needs gcc and a CPU with fused multiply-add")
-    from scannet_amd import fusion
-    al = _compile(tmp_path_factory.mktemp("align_colour_checker"), "align_colour_checker")
-    FP, PP, RP = C.POINTER(AlcFrame), C.POINTER(fusion.SfAlignParams), C.POINTER(fusion.SfAlignResult)
-    al.alc_system.argtypes = [FP, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, PP, C.c_void_p]
-    al.alc_align.argtypes = [FP, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, PP, C.c_void_p, RP]
-    al.alc_maps.argtypes = [FP, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, PP, C.c_void_p, C.c_void_p, C.c_void_p]
-    al.alc_rows.argtypes = [FP, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, PP, C.c_void_p]
-    return al
+    return ss.align_lib()
 
 
-def _arrays(depth, rgb, poses, pairs):
-    depth = np.ascontiguousarray(depth, np.uint16)
-    rgb = None if rgb is None else np.ascontiguousarray(rgb, np.uint8)
-    poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    return depth, rgb, poses, pairs
+def cpu_align(depth, rgb, poses, pairs, a, fr=None):
+    return ss.cpu_align(depth, poses, pairs, a, fr or frame_of(), rgb)
 
 
-def cpu_align(chk, depth, rgb, poses, pairs, a, fr=None):
-    from scannet_amd import fusion
-    fr = fr or frame_of()
-    depth, rgb, poses, pairs = _arrays(depth, rgb, poses, pairs)
-    out = np.empty_like(poses)
-    res = fusion.SfAlignResult()
-    rc = chk.alc_align(C.byref(fr), depth.ctypes.data, None if rgb is None else rgb.ctypes.data, len(poses), poses.ctypes.data, pairs.ctypes.data, len(pairs),
-                       C.byref(a), out.ctypes.data, C.byref(res))
-    return rc, out, res
-
-
-def cpu_system(chk, depth, rgb, poses, pairs, a, fr=None):
-    fr = fr or frame_of()
-    depth, rgb, poses, pairs = _arrays(depth, rgb, poses, pairs)
-    sys = np.zeros((len(pairs), 31), np.float64)
-    rc = chk.alc_system(C.byref(fr), depth.ctypes.data, None if rgb is None else rgb.ctypes.data, len(poses), poses.ctypes.data, pairs.ctypes.data, len(pairs),
-                        C.byref(a), sys.ctypes.data)
-    return rc, sys
-
-
-def res_tuple(r):
-    """Every field of sf_align_result."""
-    return (int(r.status), int(r.iterations), int(r.pairs_used), int(r.frames_unconnected), int(r.frames_rejected), int(r.correspondences),
-            np.float32(r.rms_first).tobytes(), np.float32(r.rms_last).tobytes(), int(r.colour_correspondences),
-            np.float32(r.colour_rms_first).tobytes(), np.float32(r.colour_rms_last).tobytes())
+def cpu_system(depth, rgb, poses, pairs, a, fr=None):
+    return ss.cpu_align_system(depth, poses, pairs, a, fr or frame_of(), rgb)
 
 
 def working_params(**over):
@@ -206,8 +75,8 @@ def wall_cpu(chk, wall):
     depth, rgb, truth, start = wall
     pairs, count = fusion.align_pairs(start, fusion.default_align_params())
     assert count == len(pairs) == 12
-    rc0, out0, res0 = cpu_align(chk, depth, rgb, start, pairs, working_params(colour_weight=0.0))
-    rc1, out1, res1 = cpu_align(chk, depth, rgb, start, pairs, working_params())
+    rc0, out0, res0 = cpu_align(depth, rgb, start, pairs, working_params(colour_weight=0.0))
+    rc1, out1, res1 = cpu_align(depth, rgb, start, pairs, working_params())
     assert rc0 == 0 and rc1 == 0
     return pairs, (out0, res0), (out1, res1)
 
@@ -232,22 +101,6 @@ def test_checker_wall_is_singular_without_colour_and_aligned_with_it(wall, wall_
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # CPU 2: the analytic row (p x a, a), +J for xi_i and -J for xi_j, against a float64 finite difference
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def _rodrigues(w):
-    th = np.linalg.norm(w)
-    Kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-    if th < 1e-12:
-        return np.eye(3) + Kx
-    return np.eye(3) + np.sin(th) / th * Kx + (1 - np.cos(th)) / th ** 2 * Kx @ Kx
-
-
-def _inc(xi, T):
-    out = np.eye(4)
-    R = _rodrigues(xi[:3])
-    out[:3, :3] = R @ T[:3, :3]
-    out[:3, 3] = R @ T[:3, 3] + xi[3:]
-    return out
-
-
 def test_colour_row_equals_a_finite_difference(chk, wall):
     """The bilinear interpolant's own derivative is a one-sided difference and is not what the term uses (it samples central differences), so the
     float64 residual here is the term's own linear intensity model about the sampled point, I_t + (gx, gy) . (u - u0, v - v0) - I_s with I_t, gx, gy
@@ -262,11 +115,11 @@ def test_colour_row_equals_a_finite_difference(chk, wall):
     i, j = 1, 0
     npx = (W >> LEVEL) * (H >> LEVEL)
     rows = np.zeros((npx, 8), np.float32)
-    assert chk.alc_rows(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), poses.ctypes.data, i, j, C.byref(a), rows.ctypes.data) == 0
+    assert chk.al_rows(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), poses.ctypes.data, i, j, C.byref(a), rows.ctypes.data) == 0
     vmap, pmap, cam = np.zeros((npx, 3), np.float32), np.zeros((npx, 3), np.float32), np.zeros(6, np.float32)
-    assert chk.alc_maps(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), i, C.byref(a), vmap.ctypes.data, pmap.ctypes.data, cam.ctypes.data) == 0
+    assert chk.al_maps(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), i, C.byref(a), vmap.ctypes.data, pmap.ctypes.data, cam.ctypes.data) == 0
     pj = np.zeros((npx, 3), np.float32)
-    assert chk.alc_maps(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), j, C.byref(a), vmap.copy().ctypes.data, pj.ctypes.data, cam.copy().ctypes.data) == 0
+    assert chk.al_maps(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), j, C.byref(a), vmap.copy().ctypes.data, pj.ctypes.data, cam.copy().ctypes.data) == 0
     wl, fx, fy, mx, my = int(cam[0]), float(cam[2]), float(cam[3]), float(cam[4]), float(cam[5])
     Ti, Tj = poses[i].reshape(4, 4).astype(np.float64), poses[j].reshape(4, 4).astype(np.float64)
     picked = np.flatnonzero(rows[:, 0] > 0)
@@ -292,7 +145,7 @@ def test_colour_row_equals_a_finite_difference(chk, wall):
         g = np.array([bil(1, u0), bil(2, u0)])
 
         def residual(xi_i, xi_j):
-            return float(g @ (project(_inc(xi_i, Ti), _inc(xi_j, Tj), v) - u0))   # the constant I_t - I_s drops out of every difference
+            return float(g @ (project(ss.increment(xi_i, Ti), ss.increment(xi_j, Tj), v) - u0))   # the constant I_t - I_s drops out of every difference
 
         J = rows[px, 2:8].astype(np.float64)
         scale = np.abs(J).max()
@@ -329,7 +182,7 @@ def test_sampled_gradient_is_the_derivative_of_the_intensity(chk, wall):
     depth_, rgb_, poses, _ = _arrays(depth, rgb, truth, [[1, 0]])
     wl, hl = W >> LEVEL, H >> LEVEL
     vmap, pmap, cam = np.zeros((wl * hl, 3), np.float32), np.zeros((wl * hl, 3), np.float32), np.zeros(6, np.float32)
-    assert chk.alc_maps(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), 0, C.byref(a), vmap.ctypes.data, pmap.ctypes.data, cam.ctypes.data) == 0
+    assert chk.al_maps(C.byref(fr), depth_.ctypes.data, rgb_.ctypes.data, len(poses), 0, C.byref(a), vmap.ctypes.data, pmap.ctypes.data, cam.ctypes.data) == 0
     I, gx, gy = (pmap[:, k].reshape(hl, wl).astype(np.float64) for k in range(3))
     ok = np.isfinite(gx)
     assert ok.sum() > 0.5 * wl * hl and not ok[0].any() and not ok[:, 0].any() and not ok[-1].any() and not ok[:, -1].any()
@@ -373,78 +226,45 @@ def test_picture_size_follows_the_fuser(wall):
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # CPU 3: the furnished room of 4e's test with the texture painted on by world position does not get worse
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-RW, RH = 320, 240
-
-
-def paint_room(depth, pose):
-    """RGB8 [RH*RW*3] at the depth camera's own pixels: the texture at each pixel's world position (two of its coordinates mixed, so that walls and
-    floor all carry it)."""
-    fx, fy, mx, my = synth.intrinsics(RW, RH)
-    yy, xx = np.mgrid[0:RH, 0:RW]
-    d = depth.reshape(RH, RW).astype(np.float64) / 1000.0
-    cam = np.stack([(xx - mx) / fx * d, (yy - my) / fy * d, d], -1)
-    p = np.asarray(pose, np.float64)
-    wp = cam @ p[:3, :3].T + p[:3, 3]
-    rgb = texture(wp[..., 0] + 0.7 * wp[..., 2], wp[..., 1] - 0.7 * wp[..., 2], scale=2.5 / (synth.intrinsics(RW, RH)[0] / 2))
-    return np.clip(np.rint(rgb * 255.0), 0, 255).astype(np.uint8).reshape(-1)
+RW, RH = ss.RW, ss.RH
 
 
 def test_checker_furnished_room_with_texture_stays_within_4e_bound(chk):
     from scannet_amd import fusion
-    ta = importlib.util.spec_from_file_location("test_align_scene", os.path.join(ROOT, "tests", "test_align.py"))
-    base = importlib.util.module_from_spec(ta)
-    ta.loader.exec_module(base)
     boxes = synth.clutter_boxes()
-    truth = [synth.trajectory_pose(10 * k, base.WALK_TOTAL) for k in range(8)]
+    truth = [synth.trajectory_pose(10 * k, ss.WALK_TOTAL) for k in range(8)]
     depth = np.stack([synth.render_room_depth(p, RW, RH, noise_frame=10 * k, noise=2, boxes=boxes).reshape(-1) for k, p in enumerate(truth)])
-    start = base.drifted(truth)
-    rgb = np.stack([paint_room(d, t) for d, t in zip(depth, truth)])
+    start = ss.drifted(truth)
+    rgb = np.stack([ss.paint_room(d, t) for d, t in zip(depth, truth)])
     fr = frame_of(RW, RH, colour=(0, 0, 0.0, 0.0, 0.0, 0.0))
     a = working_params()
     pairs, count = fusion.align_pairs(start, a)
-    rc, out, res = cpu_align(chk, depth, rgb, start, pairs, a, fr)
+    rc, out, res = cpu_align(depth, rgb, start, pairs, a, fr)
     assert rc == 0
-    et, er = base.worst(out, truth)
+    et, er = ss.worst_pose_error(out, truth)
     print("room with colour: worst %.3f mm / %.3f mrad, %s" % (et * 1e3, er * 1e3, res.as_dict()))
     assert res.status == 0 and res.frames_unconnected == 0 and res.frames_rejected == 0 and res.colour_correspondences > 0, res.as_dict()
     assert et < ROOM_T_BOUND and er < ROOM_R_BOUND, (et, er, res.as_dict())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# CPU 4: colour_weight 0 through the colour path is the depth-only checker, byte for byte
+# CPU 4: the checker says what it was recorded to say, and pictures at colour_weight 0 leave the depth term's bits alone
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def test_weight_zero_equals_the_depth_only_checker(chk, tmp_path):
-    from scannet_amd import fusion
-    old = _compile(tmp_path, "align_checker")
-    ta = importlib.util.spec_from_file_location("test_align_scene", os.path.join(ROOT, "tests", "test_align.py"))
-    base = importlib.util.module_from_spec(ta)
-    ta.loader.exec_module(base)
-    # a corner of the room (three planes: solvable by depth) seen by three keyframes, with pictures at the colour camera's own size
-    r, az0 = float(np.hypot(1.6, 1.3)), float(np.arctan2(1.3, 1.6))
-    truth = [base.look_at((r * np.cos(az0 + (k - 1) * 0.06), r * np.sin(az0 + (k - 1) * 0.06), 1.4), (0.0, 0.0, 0.0)) for k in range(3)]
-    depth = np.stack([synth.render_room_depth(p, W, H).reshape(-1) for p in truth])
-    start = base.drifted(truth)
-    rng = np.random.default_rng(5)
-    rgb = rng.integers(0, 256, (3, CH * CW * 3), dtype=np.uint8)
-    pairs, _ = fusion.align_pairs(start, fusion.default_align_params())
-    a = fusion.default_align_params()
-    assert a.colour_weight == 0.0
-    rc, out, res = cpu_align(chk, depth, rgb, start, pairs, a)
-    fr_old = base.AlFrame(W, H, W, H, FX, FY, MX, MY, frame_of().depth_shift, frame_of().depth_min, frame_of().depth_max)
-    want, want_res = np.empty((3, 16), np.float32), fusion.SfAlignResult()
-    old.al_align.argtypes = [C.POINTER(base.AlFrame), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(fusion.SfAlignParams), C.c_void_p,
-                             C.POINTER(fusion.SfAlignResult)]
-    d_, _, p_, q_ = _arrays(depth, None, start, pairs)
-    assert old.al_align(C.byref(fr_old), d_.ctypes.data, 3, p_.ctypes.data, q_.ctypes.data, len(q_), C.byref(a), want.ctypes.data, C.byref(want_res)) == 0
-    assert rc == 0 and res.status == 0 and res.iterations > 1
-    assert out.tobytes() == want.tobytes()
-    assert res_tuple(res)[:8] == res_tuple(want_res)[:8]
-    assert res.colour_correspondences > 0   # the rows were formed and weighed 0
-    _, sys31 = cpu_system(chk, depth, rgb, start, pairs, a)
-    sys29 = np.zeros((len(pairs), 29), np.float64)
-    old.al_system.argtypes = [C.POINTER(base.AlFrame), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(fusion.SfAlignParams), C.c_void_p]
-    assert old.al_system(C.byref(fr_old), d_.ctypes.data, 3, p_.ctypes.data, q_.ctypes.data, len(q_), C.byref(a), sys29.ctypes.data) == 0
-    assert sys31[:, :29].tobytes() == sys29.tobytes()
+ALIGN_CASES = [n for n in ss.CASE_NAMES if n.startswith("align-")]
+
+
+@pytest.mark.parametrize("name", ALIGN_CASES)
+def test_checker_reproduces_the_recorded_digests(chk, oracle, name):
+    """tests/golden/solver_checker.json holds what the checker said on each case when it was recorded (first by the separate depth-only and colour
+    checkers that tests/align_checker.c replaced).  A depth-only case is run without pictures and with random pictures at weight 0: both must give
+    the recorded first 29 sums, poses and depth fields of the result."""
+    want = json.load(open(ss.GOLDEN))["cases"][name]
+    got = ss.run_case(name, oracle)
+    assert got["inputs"] == want["inputs"], "%s: the case's INPUTS differ from the recorded ones (the scene, not the checker, changed)" % name
+    assert got["outputs"] == want["outputs"], name
+    if "-depth-" in name:
+        idle = ss.run_case(name, oracle, idle_picture=True)
+        assert idle["inputs"] == want["inputs"] and idle["outputs"] == want["outputs"], name
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -480,7 +300,7 @@ def test_refused_colour_arguments(chk, wall, name, over, with_rgb):
     depth, rgb, truth, start = wall
     pairs = np.array([[0, 1], [1, 0]], np.int32)
     a = working_params(**over)
-    rc, _, _ = cpu_align(chk, depth[:2], rgb[:2] if with_rgb else None, start[:2], pairs, a)
+    rc, _, _ = cpu_align(depth[:2], rgb[:2] if with_rgb else None, start[:2], pairs, a)
     assert rc == -1
     L = _abi.lib()
     d_, r_, p_, q_ = _arrays(depth[:2], rgb[:2] if with_rgb else None, start[:2], pairs)
@@ -527,19 +347,6 @@ int main(void) {
     assert got[0] == 96 and got[5] == 64   # the sizes before the colour term took its fields from `reserved`
 
 
-def _plain_sens(tmp_path, colour):
-    from scannet_amd import sens
-    w, h = 16, 12
-    K = synth.intrinsic_matrix(w, h)
-    sd = sens.SensorData.create(w if colour else 0, h if colour else 0, w, h, K, K, sensor_name="StructureSensor")
-    for i in range(2):
-        sd.add_frame(np.full(w * h, 1500, np.uint16), np.eye(4, dtype=np.float32), color=np.zeros(w * h * 3, np.uint8) if colour else None, timestamp_depth=i)
-    path = str(tmp_path / ("colour.sens" if colour else "grey.sens"))
-    sd.save(path)
-    sd.close()
-    return path
-
-
 def test_depthsensing_refuses_align_colour_without_align_and_without_colour_frames(tmp_path):
     if not os.path.exists(TOOL):
         pytest.skip("bin/depthsensing is built by build()")
@@ -553,16 +360,14 @@ def test_depthsensing_refuses_align_colour_without_align_and_without_colour_fram
         r = subprocess.run([TOOL] + base + [str(tmp_path / "none.sens"), "--track", "--align", bad], capture_output=True, text=True, timeout=120)
         assert r.returncode != 0
     # a file without colour frames is refused before the GPU is touched; the text names both flags
-    r = subprocess.run([TOOL] + base + [_plain_sens(tmp_path, False), "--track", "--align", "--align-colour"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([TOOL] + base + [ss.plain_sens(tmp_path, False), "--track", "--align", "--align-colour"], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--align-colour" in r.stderr and "--align" in r.stderr.replace("--align-colour", "") and "colour frames" in r.stderr, r.stderr
 
 
 def test_photo_kernels_live_in_registers():
     if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("no llvm-readelf")
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
+    kr = ss.kernel_resources()
     rows = kr.kernels(os.path.join(ROOT, "scannet_amd", "libscanfuse.so"))
     mine = [(kr.short(n), r) for r, n in zip(rows, kr.demangle([r["name"] for r in rows])) if kr.short(n).startswith("k_photo_")]
     assert {s.split("<")[0] for s, _ in mine} == {"k_photo_prep", "k_photo_assoc", "k_photo_final"}
@@ -577,39 +382,9 @@ def test_photo_kernels_live_in_registers():
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-SW, SH, SCW, SCH = 72, 56, 90, 70   # test 6's sizes: level 0 is 4 032 pixels (a full last workgroup), level 1 36 x 28 = 1 008 (a partial one), level 2 18 x 14
-
-
-def small_scene():
-    """5 frames of the wall at 72 x 56 with 90 x 70 pictures and 12 pairs: both directions of neighbours; a pair whose projections reach the last row and
-    column (frame 3 is up and left of frame 0, so frame 0's lower right pixels project onto frame 3's border taps); frame 4 has an all -inf pose;
-    frames 0 and 2b (frame 2 turned to look away) share nothing."""
-    intr = synth.intrinsics(SW, SH)
-    cintr = (intr[0] * SCW / SW * NARROW * 0.93, intr[1] * SCH / SH * NARROW * 0.93, (SCW - 1) / 2.0, (SCH - 1) / 2.0)
-    foot = WALL_Z / intr[0]
-    truth = [wall_pose(0.0, 0.0), wall_pose(3.3 * foot, -1.2 * foot, 0.01), wall_pose(-2.4 * foot, 2.1 * foot, -0.02), wall_pose(-6.5 * foot, -5.5 * foot, 0.0),
-             wall_pose(1.0 * foot, 1.0 * foot)]
-    frames = [render_wall(t, SW, SH, intr, SCW, SCH, cintr) for t in truth]
-    poses = np.stack(truth).astype(np.float32)
-    poses[4] = -np.inf
-    away = poses[2].copy()
-    away[:3, 0] *= -1.0
-    away[:3, 2] *= -1.0
-    poses = np.concatenate([poses, away[None]])
-    depth = np.stack([f[0] for f in frames] + [frames[2][0]])
-    rgb = np.stack([f[1] for f in frames] + [frames[2][1]])
-    pairs = np.array([[0, 1], [1, 0], [1, 2], [2, 1], [0, 2], [2, 0], [0, 3], [3, 0], [1, 3], [0, 4], [4, 1], [0, 5]], np.int32)
-    return depth, rgb, poses, pairs, (SCW, SCH) + cintr
-
-
 @pytest.fixture(scope="module")
 def small():
     return small_scene()
-
-
-def _volume_digest(f):
-    c, v = f.export_blocks()
-    return hashlib.sha256(c.tobytes() + v.tobytes()).hexdigest()
 
 
 @pytest.mark.gpu
@@ -618,7 +393,7 @@ def test_gpu_rgbd_systems_bit_exact(chk, small, level):
     from scannet_amd import fusion
     depth, rgb, poses, pairs, colour = small
     a = working_params(level=level, min_pair_correspondences=1)
-    rc, want = cpu_system(chk, depth, rgb, poses, pairs, a, frame_of(SW, SH, colour=colour))
+    rc, want = cpu_system(depth, rgb, poses, pairs, a, frame_of(SW, SH, colour=colour))
     assert rc == 0
     with fusion.Fuser(fuser_params(SW, SH, colour), device=0) as f:
         got = f.align_rgbd_system(depth, rgb, poses, pairs, a)
@@ -631,27 +406,9 @@ def test_gpu_rgbd_systems_bit_exact(chk, small, level):
     assert none[:, :29].tobytes() == plain.tobytes() and not none[:, 29:].any()   # without pictures: the depth term's bits
 
 
-def resampled_scene():
-    """Depth frames of 144 x 112 resampled by the fuser to 72 x 56, color_width 0: the pictures are 144 x 112, seen through the depth frames' camera."""
-    iw, ih, w, h = 144, 112, 72, 56
-    intr = synth.intrinsics(iw, ih)
-    foot = WALL_Z / intr[0]
-    truth = [wall_pose(0.0, 0.0), wall_pose(4.2 * foot, -2.6 * foot, 0.01), wall_pose(-3.4 * foot, 3.1 * foot, -0.015)]
-    frames = [render_wall(t, iw, ih, intr, iw, ih, intr) for t in truth]
-    f32 = np.float32
-    fx, fy = f32(intr[0]) * (f32(w) / f32(iw)), f32(intr[1]) * (f32(h) / f32(ih))          # fuser.hip's integration camera, in float
-    mx, my = f32(intr[2]) * (f32(w - 1) / f32(iw - 1)), f32(intr[3]) * (f32(h - 1) / f32(ih - 1))
-    from scannet_amd import fusion
-    p = fusion.default_params(depth_width=iw, depth_height=ih, voxel_size=0.008, fx=intr[0], fy=intr[1], mx=intr[2], my=intr[3], num_sdf_blocks=1 << 16,
-                              integration_width=w, integration_height=h)
-    fr = AlcFrame(iw, ih, w, h, fx, fy, mx, my, p.depth_shift, p.depth_min, p.depth_max, iw, ih, intr[0], intr[1], intr[2], intr[3])
-    pairs = np.array([[0, 1], [1, 0], [0, 2], [2, 1]], np.int32)
-    return np.stack([f[0] for f in frames]), np.stack([f[1] for f in frames]), np.stack(truth).astype(np.float32), pairs, p, fr
-
-
 def test_checker_resampled_depth_reads_pictures_at_the_depth_size(chk):
     depth, rgb, poses, pairs, p, fr = resampled_scene()
-    rc, want = cpu_system(chk, depth, rgb, poses, pairs, working_params(level=0, min_pair_correspondences=1), fr)
+    rc, want = cpu_system(depth, rgb, poses, pairs, working_params(level=0, min_pair_correspondences=1), fr)
     assert rc == 0 and (want[:, 30] > 1000).all() and (want[:, 30] <= want[:, 28]).all(), want[:, 28:]
     assert np.sqrt(want[:, 29] / want[:, 30]).max() < 0.02   # at the true poses the pictures agree: the look-up hits the right pixels
 
@@ -663,7 +420,7 @@ def test_gpu_rgbd_systems_bit_exact_with_resampled_depth(chk):
     with fusion.Fuser(p, device=0) as f:
         for level in (0, 1):
             a = working_params(level=level, min_pair_correspondences=1)
-            rc, want = cpu_system(chk, depth, rgb, poses, pairs, a, fr)
+            rc, want = cpu_system(depth, rgb, poses, pairs, a, fr)
             got = f.align_rgbd_system(depth, rgb, poses, pairs, a)
             assert rc == 0 and (want[:, 30] > 0).all() and got.tobytes() == want.tobytes(), (level, np.abs(got - want).max())
 
@@ -678,7 +435,7 @@ def test_gpu_rgbd_solve_bit_exact_and_leaves_the_volume_alone(wall, wall_cpu):
         for k in range(2):
             assert f.integrate(depth[k], truth[k], rgb=rgb[k])
         f.sync()
-        before, st0 = _volume_digest(f), f.stats()
+        before, st0 = ss.volume_digest(f), f.stats()
         out, res = f.align(depth, start, pairs, working_params(), rgb=rgb)
         assert res_tuple(res) == res_tuple(res1), (res.as_dict(), res1.as_dict())
         assert out.tobytes() == out1.tobytes()
@@ -697,23 +454,15 @@ def test_gpu_rgbd_solve_bit_exact_and_leaves_the_volume_alone(wall, wall_cpu):
         o_dd, r_dd = f.align_device(d, W * H * 2, start, pairs, a0)   # sf_fuser_align_device
         o_d0, r_d0 = f.align_device(d, W * H * 2, start, pairs, a0, d_rgb=c, rgb_stride_bytes=CW * CH * 3)
         assert o_d0.tobytes() == o_dd.tobytes() and res_tuple(r_d0)[:8] == res_tuple(r_dd)[:8] and r_d0.colour_correspondences > 0
-        assert _volume_digest(f) == before and f.stats() == st0
+        assert ss.volume_digest(f) == before and f.stats() == st0
 
 
 @pytest.mark.gpu
 def test_gpu_rgbd_solvable_scene_with_weight_zero_equals_the_depth_only_call(chk):
     """On a scene depth can solve, the colour path at weight 0 returns sf_fuser_align_device's poses and every old field of its result."""
     from scannet_amd import fusion
-    ta = importlib.util.spec_from_file_location("test_align_scene", os.path.join(ROOT, "tests", "test_align.py"))
-    base = importlib.util.module_from_spec(ta)
-    ta.loader.exec_module(base)
-    r, az0 = float(np.hypot(1.6, 1.3)), float(np.arctan2(1.3, 1.6))
-    truth = [base.look_at((r * np.cos(az0 + (k - 1) * 0.06), r * np.sin(az0 + (k - 1) * 0.06), 1.4), (0.0, 0.0, 0.0)) for k in range(3)]
-    depth = np.stack([synth.render_room_depth(p, W, H).reshape(-1) for p in truth])
-    start = base.drifted(truth)
-    rgb = np.random.default_rng(5).integers(0, 256, (3, CH * CW * 3), dtype=np.uint8)
+    depth, rgb, start, pairs = ss.coloured_arc()   # three keyframes of the room's corner, random pictures at the colour camera's own size
     a = fusion.default_align_params()
-    pairs, _ = fusion.align_pairs(start, a)
     with fusion.Fuser(fuser_params(), device=0) as f:
         o_d, r_d = f.align(depth, start, pairs, a)
         o_c, r_c = f.align(depth, start, pairs, a, rgb=rgb)
@@ -732,7 +481,7 @@ def test_gpu_rgbd_buffers_grow_and_never_go_stale(chk, small):
     big = (depth, rgb, poses, pairs, working_params(level=0, min_pair_correspondences=1))
     want = {}
     for name, (d, c, p, q, a) in (("little", little), ("big", big)):
-        rc, want[name] = cpu_system(chk, d, c, p, q, a, fr)
+        rc, want[name] = cpu_system(d, c, p, q, a, fr)
         assert rc == 0 and (want[name][:2, 30] > 0).all()
     with fusion.Fuser(fuser_params(SW, SH, colour), device=0) as f:
         for step, name in enumerate(("little", "big", "little")):
@@ -762,14 +511,14 @@ def test_gpu_align_and_reintegrate_with_colour(tmp_path):
             assert f.integrate(depth[k], start[k], rgb=rgb[k])
         integrated = np.ascontiguousarray(start.reshape(8, 16))
         held = integrated.copy()
-        before = _volume_digest(f)
+        before = ss.volume_digest(f)
         target, res, stats = fusion.align_and_reintegrate(f, sd, integrated, every=1, params=fusion.default_align_params(level=LEVEL), colour=True)
-        assert res.status == 1 and target.tobytes() == held.tobytes() and stats["frames_moved"] == 0 and _volume_digest(f) == before, (res.as_dict(), stats)
+        assert res.status == 1 and target.tobytes() == held.tobytes() and stats["frames_moved"] == 0 and ss.volume_digest(f) == before, (res.as_dict(), stats)
         target, res, stats = fusion.align_and_reintegrate(f, sd, integrated, every=1, params=fusion.default_align_params(level=LEVEL), colour=True,
                                                           with_colour=True)
         e = in_plane_error(target, truth)
         print("loop: in-plane error %.2f mm -> %.2f mm, %s, %s" % (in_plane_error(start, truth) * 1e3, e * 1e3, res.as_dict(), stats))
         assert res.status == 0 and res.frames_rejected == 0 and res.frames_unconnected == 0, res.as_dict()
         assert e < BOUND, (e, BOUND)
-        assert integrated.tobytes() == target.tobytes() and stats["frames_moved"] == 7 and _volume_digest(f) != before
+        assert integrated.tobytes() == target.tobytes() and stats["frames_moved"] == 7 and ss.volume_digest(f) != before
     sd.close()

@@ -1,17 +1,16 @@
 """The dense colour term of the camera tracker (DESIGN.md "The colour term of the tracker", 4g; scannet_amd/csrc/track_colour.hip).
 
-The rule is pinned as section 4c's is: tests/track_colour_checker.c restates it in C (the depth term with it), the oracle fuses, tests/raycast_checker.c
-renders the model's depth, normals and colour.
+The rule is pinned as section 4c's is: tests/track_checker.c restates it in C (one checker for the depth term and the colour term, over
+tests/solver_rules.h), the oracle fuses, tests/raycast_checker.c renders the model's depth, normals and colour.
   * without a GPU: a frame sliding along one textured wall, which depth alone loses (lost_reason 3), is tracked to sub-pixel accuracy with colour; the
     analytic row against a float64 finite difference; the furnished room's loop with a painted texture stays within 4c's bound and is no worse than
-    its depth-only run; colour_weight 0 equals tests/track_checker.c byte for byte; a model miss gives no colour row; parameters, struct layouts, the
-    tool's refusals, the kernels' resources;
+    its depth-only run; the checker against its recorded digests (tests/golden/solver_checker.json), colour_weight 0 giving the depth term's bits; a
+    model miss gives no colour row; parameters, struct layouts, the tool's refusals, the kernels' resources;
   * -m gpu: sf_fuser_track_rgbd_system and sf_fuser_track_rgbd against the checker bit for bit, the device entry point, the work set's states,
     track_and_fuse(with_colour=True), bin/depthsensing --track --track-colour.
 """
 import ctypes as C
-import hashlib
-import importlib.util
+import json
 import os
 import re
 import shutil
@@ -21,62 +20,22 @@ import numpy as np
 import pytest
 
 from scannet_amd import _abi, synth
+from tests import solver_scenes as ss
+from tests.solver_scenes import CAMERAS, FOOT0, H, W, cpu_model, cpu_system, cpu_track, in_plane_error, ptr as _p, walk_pose
+from tests.solver_scenes import TrackWall as Wall, render_walk as render, track_res_tuple as res_tuple, under_the_depth_rays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "bin", "depthsensing")
 SF_ERR_INVALID_ARG = -1
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name + "_scene", os.path.join(ROOT, "tests", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-tt = _load("test_track")          # the CPU chain's helpers, the furnished room's loop, 4c's bounds
-ac = _load("test_align_colour")   # the textured wall, its colour camera, the room's paint
-
-W, H = ac.W, ac.H                 # 160 x 120
-VOXEL = 0.008
-FOOT0 = ac.WALL_Z / ac.FX         # metres of wall under one level-0 pixel: 13.8 mm
-BOUND = 0.5 * FOOT0               # test 1's bound: half a level-0 pixel's footprint, the sampling limit
-STEP = (0.03, 0.008)              # the walk along the wall, metres per frame
-FUSED = 4                         # frames fused before the tracked one
-TURN = 0.004                      # the tracked frame's turn about the wall's normal, radians
-CAMERAS = {"narrow": (ac.CW, ac.CH, ac.CFX, ac.CFY, ac.CMX, ac.CMY), "same": (0, 0, 0.0, 0.0, 0.0, 0.0)}
-
-
-def walk_pose(k, rz=0.0):
-    return ac.wall_pose(STEP[0] * k, STEP[1] * k, rz)
-
-
-def render(pose, colour):
-    """(u16 depth [H*W], RGB8 picture at the colour camera's size, or at the depth camera's own when the fuser has no colour camera)."""
-    if colour[0]:
-        return ac.render_wall(pose, W, H, None, colour[0], colour[1], colour[2:])
-    return ac.render_wall(pose, W, H, None, W, H, (ac.FX, ac.FY, ac.MX, ac.MY))
-
-
-def under_the_depth_rays(rgb, colour):
-    """What the fuser's pre-pass looks up for a picture of a colour camera (nearest pixel under the depth pixel's ray, black outside), for the oracle,
-    which takes colour at the depth size: tests/test_gpu_tsdf.py::test_colour_at_its_own_resolution."""
-    if not colour[0]:
-        return rgb
-    cw, ch, cfx, cfy, cmx, cmy = colour
-    f32 = np.float32
-    xs, ys = np.meshgrid(np.arange(W, dtype=f32), np.arange(H, dtype=f32))
-    u = (((xs - f32(ac.MX)) / f32(ac.FX)).astype(np.float64) * np.float64(f32(cfx)) + np.float64(f32(cmx))).astype(f32) + f32(0.5)
-    v = (((ys - f32(ac.MY)) / f32(ac.FY)).astype(np.float64) * np.float64(f32(cfy)) + np.float64(f32(cmy))).astype(f32) + f32(0.5)
-    ok = (u >= 0) & (u < cw) & (v >= 0) & (v < ch)
-    iu, iv = np.where(ok, u, 0).astype(np.int64), np.where(ok, v, 0).astype(np.int64)
-    return np.where(ok[..., None], rgb.reshape(ch, cw, 3)[iv, iu], 0).astype(np.uint8).reshape(-1)
+VOXEL = ss.TRACK_VOXEL
+BOUND = 0.5 * FOOT0               # test 1's bound: half a level-0 pixel's footprint (13.8 mm), the sampling limit
+# 4c's furnished room: its size, its loop and its bounds (tests/test_track.py)
+ROOM_W, ROOM_H = 320, 240
+LOOP_T_BOUND, LOOP_R_BOUND = 0.015, 0.005
 
 
 def oracle_params(oracle, w=W, h=H, voxel=VOXEL):
-    op = oracle.default_params(w, h, voxel)
-    op.fx, op.fy, op.mx, op.my = synth.intrinsics(w, h)
-    return op
+    return ss.oracle_params(oracle, w, h, voxel)
 
 
 def working_params(**over):
@@ -86,109 +45,16 @@ def working_params(**over):
 
 
 @pytest.fixture(scope="module")
-def chk(tmp_path_factory):
-    """(ray-cast checker, colour track checker)."""
-    if shutil.which("gcc") is None or not tt._has_fma():
+def chk():
+    """tests/raycast_checker.c and tests/track_checker.c are there to be compiled."""
+    if not ss.checkers_available():
         pytest.skip("needs gcc and a CPU with fused multiply-add")
-    from scannet_amd import fusion
-    rc = tt._compile(tmp_path_factory, "raycast_checker")
-    rc.rc_raycast.restype = C.c_int64
-    rc.rc_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(tt.RcArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    tk = tt._compile(tmp_path_factory, "track_colour_checker")
-    FP, PP, RP, vp = C.POINTER(ac.AlcFrame), C.POINTER(fusion.SfTrackParams), C.POINTER(fusion.SfTrackResult), C.c_void_p
-    tk.tkc_system.argtypes = [FP, vp, vp, vp, vp, vp, PP, C.c_int, vp, vp, vp, vp]
-    tk.tkc_track.argtypes = [FP, vp, vp, vp, vp, vp, PP, vp, vp, vp, RP]
-    tk.tkc_maps.argtypes = [FP, vp, vp, vp, vp, vp, PP, C.c_int, vp, vp, vp, vp]
-    tk.tkc_rows.argtypes = [FP, vp, vp, vp, vp, vp, PP, C.c_int, vp, vp, vp]
-    return rc, tk
-
-
-def frame_of(op, colour):
-    return ac.AlcFrame(op.width, op.height, op.width, op.height, op.fx, op.fy, op.mx, op.my, op.depth_shift, op.depth_min, op.depth_max, *colour)
-
-
-def cpu_model(rc, blocks, op, pose, t):
-    """The model the tracker casts at `pose`: raycast_checker.c at the integration size, depth, normals and colour."""
-    r = t.raycast
-    a = tt.RcArgs(op.width, op.height, op.fx, op.fy, op.mx, op.my, r.depth_min, r.depth_max, r.ray_increment_factor, r.thres_sample_dist_factor,
-                  r.thres_dist_factor, r.refine_iters, op.voxel_size, op.trunc_base)
-    depth = np.empty((op.height, op.width), np.float32)
-    nrm = np.empty((op.height, op.width, 3), np.float32)
-    rgb = np.empty((op.height, op.width, 3), np.uint8)
-    coords, vox = np.ascontiguousarray(blocks[0], np.int32), np.ascontiguousarray(blocks[1])
-    p = np.ascontiguousarray(pose, np.float32).reshape(16)
-    rc.rc_raycast(coords.ctypes.data, vox.ctypes.data, len(coords), C.byref(a), p.ctypes.data, depth.ctypes.data, nrm.ctypes.data, rgb.ctypes.data)
-    return depth, nrm, rgb
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
-
-
-def cpu_track(chk, blocks, op, colour, depth, rgb, guess, t, ref=None):
-    """The whole tracker with the colour term on the CPU over exported blocks -> (rc, pose [4,4] f32, SfTrackResult)."""
-    from scannet_amd import fusion
-    rc, tk = chk
-    md, mn, mrgb = cpu_model(rc, blocks, op, guess if ref is None else ref, t)
-    d = np.ascontiguousarray(depth, np.uint16)
-    c = None if rgb is None else np.ascontiguousarray(rgb, np.uint8)
-    g = np.ascontiguousarray(guess, np.float32).reshape(16)
-    rf = None if ref is None else np.ascontiguousarray(ref, np.float32).reshape(16)
-    out = np.empty(16, np.float32)
-    res = fusion.SfTrackResult()
-    code = tk.tkc_track(C.byref(frame_of(op, colour)), _p(d), _p(c), _p(md), _p(mn), None if c is None else _p(mrgb), C.byref(t), _p(g), _p(rf), _p(out),
-                        C.byref(res))
-    return code, out.reshape(4, 4), res
-
-
-def cpu_system(chk, blocks, op, colour, depth, rgb, level, T, Tref, t, model=None):
-    rc, tk = chk
-    md, mn, mrgb = model or cpu_model(rc, blocks, op, Tref, t)
-    d = np.ascontiguousarray(depth, np.uint16)
-    c = None if rgb is None else np.ascontiguousarray(rgb, np.uint8)
-    sys = np.zeros(31, np.float64)
-    mask = np.zeros((op.height >> level, op.width >> level), np.uint8)
-    T = np.ascontiguousarray(T, np.float32).reshape(16)
-    Tref = np.ascontiguousarray(Tref, np.float32).reshape(16)
-    code = tk.tkc_system(C.byref(frame_of(op, colour)), _p(d), _p(c), _p(md), _p(mn), None if c is None else _p(mrgb), C.byref(t), level, _p(T), _p(Tref),
-                         _p(sys), _p(mask))
-    return code, sys, mask
-
-
-def res_tuple(r):
-    """Every field of sf_track_result."""
-    return (int(r.tracked), tuple(r.iterations), int(r.correspondences), np.float32(r.rms_residual).tobytes(), int(r.lost_reason),
-            int(r.colour_correspondences), np.float32(r.colour_rms_residual).tobytes())
-
-
-def in_plane_error(pose, truth):
-    return float(np.hypot(*(np.asarray(pose, np.float64)[:2, 3] - np.asarray(truth, np.float64)[:2, 3])))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# The wall: FUSED frames sliding along it are fused with colour; the next frame lies one step (3 cm) further and is turned TURN about the normal
+# The wall (tests/solver_scenes.py TrackWall): FUSED frames sliding along it are fused with colour; the next frame lies one step (3 cm) further and is
+# turned TURN about the normal
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-class Wall:
-    def __init__(self, oracle, camera, hole=False):
-        self.colour = CAMERAS[camera]
-        self.op = oracle_params(oracle)
-        self.fused = []
-        vol = oracle.Volume(self.op, threads=8)
-        for k in range(FUSED):
-            d, c = render(walk_pose(k), self.colour)
-            if hole:   # a patch the sensor did not see: the model misses there
-                d = d.reshape(H, W).copy()
-                d[40:70, 60:100] = 0
-                d = d.reshape(-1)
-            self.fused.append((d, c, walk_pose(k)))
-            vol.integrate(d, walk_pose(k), rgb=under_the_depth_rays(c, self.colour))
-        self.blocks = vol.export()
-        vol.close()
-        self.truth = walk_pose(FUSED, TURN)
-        self.guess = walk_pose(FUSED - 1)
-        self.depth, self.rgb = render(self.truth, self.colour)
-
-
 @pytest.fixture(scope="module", params=sorted(CAMERAS))
 def wall(request, oracle):
     return Wall(oracle, request.param)
@@ -197,8 +63,8 @@ def wall(request, oracle):
 @pytest.fixture(scope="module")
 def wall_cpu(chk, wall):
     """The checker's answers on the wall, without and with colour (shared with the GPU tests)."""
-    a0 = cpu_track(chk, wall.blocks, wall.op, wall.colour, wall.depth, wall.rgb, wall.guess, working_params(colour_weight=0.0))
-    a1 = cpu_track(chk, wall.blocks, wall.op, wall.colour, wall.depth, wall.rgb, wall.guess, working_params())
+    a0 = cpu_track(wall.blocks, wall.op, wall.depth, wall.guess, working_params(colour_weight=0.0), colour=wall.colour, rgb=wall.rgb)
+    a1 = cpu_track(wall.blocks, wall.op, wall.depth, wall.guess, working_params(), colour=wall.colour, rgb=wall.rgb)
     assert a0[0] == 0 and a1[0] == 0
     return a0[1:], a1[1:]
 
@@ -213,7 +79,7 @@ def test_checker_wall_is_lost_without_colour_and_tracked_with_it(wall, wall_cpu)
     assert res0.tracked == 0 and res0.lost_reason == 3 and np.isneginf(pose0).all(), res0.as_dict()
     assert res1.tracked == 1 and res1.lost_reason == 0, res1.as_dict()
     e = in_plane_error(pose1, wall.truth)
-    et, er = tt.pose_error(pose1, wall.truth)
+    et, er = ss.pose_error(pose1, wall.truth)
     print("wall: in-plane error %.2f mm -> %.2f mm (bound %.2f mm), whole pose %.2f mm / %.2f mrad, %s" % (e_start * 1e3, e * 1e3, BOUND * 1e3, et * 1e3, er * 1e3,
                                                                                                        res1.as_dict()))
     assert res1.colour_correspondences > 0.3 * res1.correspondences and res1.correspondences > 0.8 * W * H, res1.as_dict()
@@ -228,20 +94,16 @@ def test_colour_row_equals_a_finite_difference(chk, wall):
     I_t + (gx, gy) . (u - u0, v - v0) - I_s with gx, gy as the checker sampled them, so the difference tests what the row states: the projection, the
     rigid motion of T and its sign (the model does not move).  Bound: 10 x the larger of the difference quotient's own error (steps h and h / 2) and
     float32's 6e-7 relative error of an entry, relative to the row's largest entry."""
-    rc, tk = chk
     t = working_params()
     level = 1
-    fr = frame_of(wall.op, wall.colour)
-    md, mn, mrgb = cpu_model(rc, wall.blocks, wall.op, wall.guess, t)
-    T = ac.left_increment(wall.guess, 0.7 * FOOT0, -0.4 * FOOT0, 0.002)
+    model = cpu_model(wall.blocks, wall.op, wall.guess, t)
+    T = ss.left_increment(wall.guess, 0.7 * FOOT0, -0.4 * FOOT0, 0.002)
     T32, R32 = np.ascontiguousarray(T, np.float32).reshape(16), np.ascontiguousarray(wall.guess, np.float32).reshape(16)
-    wl, hl = W >> level, H >> level
-    npx = wl * hl
-    rows = np.zeros((npx, 8), np.float32)
-    d, c = np.ascontiguousarray(wall.depth, np.uint16), np.ascontiguousarray(wall.rgb, np.uint8)
-    assert tk.tkc_rows(C.byref(fr), _p(d), _p(c), _p(md), _p(mn), _p(mrgb), C.byref(t), level, _p(T32), _p(R32), _p(rows)) == 0
-    vmap, pm, cam = np.zeros((npx, 3), np.float32), np.zeros((npx, 3), np.float32), np.zeros(6, np.float32)
-    assert tk.tkc_maps(C.byref(fr), _p(d), _p(c), _p(md), _p(mn), _p(mrgb), C.byref(t), level, _p(R32), _p(vmap), _p(pm), _p(cam)) == 0
+    wl = W >> level
+    code, rows = ss.cpu_track_rows(wall.op, wall.depth, wall.rgb, model, level, T32, R32, t, wall.colour)
+    assert code == 0
+    code, vmap, pm, cam = ss.cpu_track_maps(wall.op, wall.depth, wall.rgb, model, level, R32, t, wall.colour)
+    assert code == 0
     fx, fy, mx, my = (float(x) for x in cam[2:])
     Td, Rd = T32.reshape(4, 4).astype(np.float64), R32.reshape(4, 4).astype(np.float64)
     picked = np.flatnonzero(rows[:, 0] > 0)
@@ -273,7 +135,7 @@ def test_colour_row_equals_a_finite_difference(chk, wall):
             for k in range(6):
                 e = np.zeros(6)
                 e[k] = h
-                dd[k] = (float(g @ (project(ac._inc(e, Td), v) - u0)) - float(g @ (project(ac._inc(-e, Td), v) - u0))) / (2 * h)
+                dd[k] = (float(g @ (project(ss.increment(e, Td), v) - u0)) - float(g @ (project(ss.increment(-e, Td), v) - u0))) / (2 * h)
             fd[h] = dd
         worst_fd = max(worst_fd, np.abs(fd[1e-4] - fd[5e-5]).max() / scale)
         worst = max(worst, np.abs(fd[5e-5] - J).max() / scale)
@@ -285,20 +147,20 @@ def test_colour_row_equals_a_finite_difference(chk, wall):
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # CPU 3: the furnished room's loop of 4c with the texture painted on by world position: within 4c's bound, and no worse than depth alone
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def room_loop(chk, oracle, t, n=tt.LOOP_FRAMES):
+def room_loop(oracle, t, n=ss.LOOP_FRAMES):
     """4c's track-and-fuse loop (tests/test_track.py cpu_loop) with every frame's painted picture fused and handed to the tracker."""
-    op = oracle_params(oracle, tt.W, tt.H, 0.004)
+    op = oracle_params(oracle, ROOM_W, ROOM_H, 0.004)
     none = CAMERAS["same"]
     vol = oracle.Volume(op, threads=8)
-    frames = tt.loop_frames()[:n]
+    frames = ss.loop_frames(ROOM_W, ROOM_H)[:n]
     poses, results = [], []
     last = frames[0][1]
     for k, (d, truth) in enumerate(frames):
-        rgb = ac.paint_room(d.reshape(-1), truth)
+        rgb = ss.paint_room(d.reshape(-1), truth)
         if k == 0:
             pose, res = truth, None
         else:
-            code, pose, res = cpu_track(chk, vol.export(), op, none, d, rgb, last, t)
+            code, pose, res = cpu_track(vol.export(), op, d, last, t, colour=none, rgb=rgb)
             assert code == 0
         poses.append(pose)
         results.append(res)
@@ -311,82 +173,53 @@ def room_loop(chk, oracle, t, n=tt.LOOP_FRAMES):
 
 
 def _worst(frames, poses):
-    errs = [tt.pose_error(p, truth) for p, (_, truth) in zip(poses[1:], frames[1:])]
+    errs = [ss.pose_error(p, truth) for p, (_, truth) in zip(poses[1:], frames[1:])]
     return max(e[0] for e in errs), max(e[1] for e in errs)
 
 
 def test_checker_furnished_room_loop_with_colour(chk, oracle):
-    frames, p0, r0, _ = room_loop(chk, oracle, working_params(colour_weight=0.0))
-    frames, p1, r1, _ = room_loop(chk, oracle, working_params())
+    frames, p0, r0, _ = room_loop(oracle, working_params(colour_weight=0.0))
+    frames, p1, r1, _ = room_loop(oracle, working_params())
     assert all(r.tracked for r in r0[1:]) and all(r.tracked for r in r1[1:]), [res_tuple(r) for r in r1[1:] if not r.tracked]
     (t0, a0), (t1, a1) = _worst(frames, p0), _worst(frames, p1)
     print("room loop: depth only worst %.2f mm / %.2f mrad, with colour %.2f mm / %.2f mrad (bound %.0f mm / %.0f mrad)" % (
-        t0 * 1e3, a0 * 1e3, t1 * 1e3, a1 * 1e3, tt.LOOP_T_BOUND * 1e3, tt.LOOP_R_BOUND * 1e3))
+        t0 * 1e3, a0 * 1e3, t1 * 1e3, a1 * 1e3, LOOP_T_BOUND * 1e3, LOOP_R_BOUND * 1e3))
     assert min(r.colour_correspondences for r in r1[1:]) > 1000
-    assert t1 < tt.LOOP_T_BOUND and a1 < tt.LOOP_R_BOUND, (t1, a1)
+    assert t1 < LOOP_T_BOUND and a1 < LOOP_R_BOUND, (t1, a1)
     assert t1 <= t0 and a1 <= a0, ((t0, a0), (t1, a1))   # colour does not make the loop worse than depth alone
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# CPU 4: colour_weight 0 through the colour path is tests/track_checker.c byte for byte; a model miss gives no colour row
+# CPU 4: the checker says what it was recorded to say, a picture at colour_weight 0 leaves the depth term's bits alone; a model miss gives no colour row
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def test_weight_zero_equals_the_depth_only_checker(chk, oracle, tmp_path_factory):
-    from scannet_amd import fusion
-    old = tt._compile(tmp_path_factory, "track_checker")
-    old.tk_system.argtypes = [C.POINTER(tt.TkFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fusion.SfTrackParams), C.c_int, C.c_void_p, C.c_void_p,
-                              C.c_void_p, C.c_void_p]
-    old.tk_track.argtypes = [C.POINTER(tt.TkFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fusion.SfTrackParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                             C.POINTER(tt.TkResult)]
-    # the room's corner (three planes: solvable by depth) at 160 x 120 with a random picture at the colour camera's own size
-    op = oracle_params(oracle, W, H, VOXEL)
-    vol = oracle.Volume(op, threads=8)
-    poses = [tt.corner_truth(), tt.look_at((1.7, 1.2, 1.45), (0.05, 0.0, 0.0)), tt.look_at((1.5, 1.4, 1.35), (0.0, 0.05, 0.05))]
-    rng = np.random.default_rng(5)
-    for p in poses:
-        vol.integrate(synth.render_room_depth(p, W, H), p, rgb=rng.integers(0, 256, W * H * 3, dtype=np.uint8))
-    blocks = vol.export()
-    vol.close()
-    depth = synth.render_room_depth(poses[0], W, H)
-    rgb = rng.integers(0, 256, ac.CH * ac.CW * 3, dtype=np.uint8)
-    colour = CAMERAS["narrow"]
-    t = fusion.default_track_params()
-    assert t.colour_weight == 0.0
-    guess = tt.perturb(poses[0], 0.02, 2.0)
-    code, pose, res = cpu_track(chk, blocks, op, colour, depth, rgb, guess, t, ref=poses[0])
-    md, mn, _ = cpu_model(chk[0], blocks, op, poses[0], t)
-    fr_old = tt.TkFrame(W, H, W, H, op.fx, op.fy, op.mx, op.my, op.depth_shift, op.depth_min, op.depth_max)
-    d, g, rf = np.ascontiguousarray(depth, np.uint16), guess.reshape(16).copy(), poses[0].reshape(16).copy()
-    want, want_res = np.empty(16, np.float32), tt.TkResult()
-    assert old.tk_track(C.byref(fr_old), _p(d), _p(md), _p(mn), C.byref(t), _p(g), _p(rf), _p(want), C.byref(want_res)) == 0
-    assert code == 0 and res.tracked == 1 and sum(res.iterations) > 3
-    assert pose.tobytes() == want.tobytes()
-    assert res_tuple(res)[:5] == tt.res_tuple(want_res)
-    assert res.colour_correspondences > 0   # the rows were formed and weighed 0
-    for level in range(t.levels):
-        code, sys31, mask31 = cpu_system(chk, blocks, op, colour, depth, rgb, level, guess, poses[0], t)
-        sys29, mask29 = np.zeros(29, np.float64), np.zeros_like(mask31)
-        assert old.tk_system(C.byref(fr_old), _p(d), _p(md), _p(mn), C.byref(t), level, _p(g), _p(rf), _p(sys29), _p(mask29)) == 0
-        assert code == 0 and sys31[:29].tobytes() == sys29.tobytes() and np.array_equal(mask31, mask29) and sys31[30] > 0, level
-        # without a picture no colour row is formed
-        code, sysn, _ = cpu_system(chk, blocks, op, colour, depth, None, level, guess, poses[0], t)
-        assert code == 0 and sysn[:29].tobytes() == sys29.tobytes() and sysn[29] == 0.0 and sysn[30] == 0.0
+TRACK_CASES = [n for n in ss.CASE_NAMES if n.startswith("track-")]
+
+
+@pytest.mark.parametrize("name", TRACK_CASES)
+def test_checker_reproduces_the_recorded_digests(chk, oracle, name):
+    """tests/golden/solver_checker.json holds what the checker said on each case when it was recorded (first by the separate depth-only and colour
+    checkers that tests/track_checker.c replaced).  A depth-only case is run without a picture and with a random picture at weight 0: both must give
+    the recorded first 29 sums, masks, poses and depth fields of the result."""
+    want = json.load(open(ss.GOLDEN))["cases"][name]
+    got = ss.run_case(name, oracle)
+    assert got["inputs"] == want["inputs"], "%s: the case's INPUTS differ from the recorded ones (the scene, not the checker, changed)" % name
+    assert got["outputs"] == want["outputs"], name
+    if "-depth-" in name:
+        idle = ss.run_case(name, oracle, idle_picture=True)
+        assert idle["inputs"] == want["inputs"] and idle["outputs"] == want["outputs"], name
 
 
 def test_a_model_miss_gives_no_colour_row(chk, oracle):
     """A patch of the wall that no fused frame saw renders as a miss (colour 0, 0, 0): depth correspondences whose taps touch it get no colour row, so
     the black of a miss never enters a residual."""
-    rc, tk = chk
     w = Wall(oracle, "same", hole=True)
     t = working_params()
-    md, mn, mrgb = cpu_model(rc, w.blocks, w.op, w.guess, t)
+    md, mn, mrgb = cpu_model(w.blocks, w.op, w.guess, t)
     miss = ~((md > 0) & (mn[..., 0] > -np.inf))   # k_track_model's validity
     assert miss[45:65, 70:90].all() and (mrgb[~(md > 0)] == 0).all() and not miss[5:30, 5:150].any()
-    fr = frame_of(w.op, w.colour)
-    rows = np.zeros((W * H, 8), np.float32)
-    d, c = np.ascontiguousarray(w.depth, np.uint16), np.ascontiguousarray(w.rgb, np.uint8)
-    g = np.ascontiguousarray(w.guess, np.float32).reshape(16)
-    assert tk.tkc_rows(C.byref(fr), _p(d), _p(c), _p(md), _p(mn), _p(mrgb), C.byref(t), 0, _p(g), _p(g), _p(rows)) == 0
-    code, sys, mask = cpu_system(chk, w.blocks, w.op, w.colour, w.depth, w.rgb, 0, w.guess, w.guess, t, model=(md, mn, mrgb))
+    code, rows = ss.cpu_track_rows(w.op, w.depth, w.rgb, (md, mn, mrgb), 0, w.guess, w.guess, t, w.colour)
+    assert code == 0
+    code, sys, mask = cpu_system(w.blocks, w.op, w.depth, 0, w.guess, w.guess, t, colour=w.colour, rgb=w.rgb, model=(md, mn, mrgb))
     assert code == 0 and sys[30] == (rows[:, 0] > 0).sum() > 1000
     has = (rows[:, 0] > 0).reshape(H, W)
     # the estimate is the reference pose, so every pixel projects onto itself and its taps are itself and its right, lower and lower-right neighbours
@@ -504,16 +337,14 @@ def test_depthsensing_refuses_track_colour_without_track_and_without_colour_fram
         r = subprocess.run([TOOL] + base + [str(tmp_path / "none.sens"), "--track", bad], capture_output=True, text=True, timeout=120)
         assert r.returncode != 0 and "--track-colour" in r.stdout, (bad, r.stdout)   # the usage line names the flag
     # a file without colour frames is refused before the GPU is touched; the text names both flags
-    r = subprocess.run([TOOL] + base + [ac._plain_sens(tmp_path, False), "--track", "--track-colour"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([TOOL] + base + [ss.plain_sens(tmp_path, False), "--track", "--track-colour"], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--track-colour" in r.stderr and "--track" in r.stderr.replace("--track-colour", "") and "colour frames" in r.stderr, r.stderr
 
 
 def test_track_photo_kernels_live_in_registers():
     if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("no llvm-readelf")
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
+    kr = ss.kernel_resources()
     rows = kr.kernels(os.path.join(ROOT, "scannet_amd", "libscanfuse.so"))
     mine = {kr.short(n): r for r, n in zip(rows, kr.demangle([r["name"] for r in rows])) if kr.short(n).startswith("k_track_photo_")}
     assert set(mine) == {"k_track_photo_in0", "k_track_photo_model0", "k_track_photo_down", "k_track_photo_grad", "k_track_photo_assoc", "k_track_photo_final"}
@@ -526,15 +357,10 @@ def test_track_photo_kernels_live_in_registers():
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def _volume_digest(f):
-    c, v = f.export_blocks()
-    return hashlib.sha256(c.tobytes() + v.tobytes()).hexdigest()
-
-
 def fused_wall(wall):
     """A fuser holding the wall's fused frames; the checker reads its exported blocks."""
     from scannet_amd import fusion
-    f = fusion.Fuser(ac.fuser_params(W, H, wall.colour, VOXEL), device=0)
+    f = fusion.Fuser(ss.fuser_params(W, H, wall.colour, VOXEL), device=0)
     for d, c, p in wall.fused:
         assert f.integrate(d, p, rgb=c)
     f.sync()
@@ -561,11 +387,11 @@ def test_gpu_rgbd_system_bit_exact_every_level(chk, wall, gpu_wall):
     onto its last row and column: the float range test of the taps."""
     f, blocks = gpu_wall
     t = working_params(levels=4)
-    estimates = [("near", ac.left_increment(wall.guess, 0.6 * FOOT0, -0.3 * FOOT0, 0.001)), ("outside", ac.left_increment(wall.guess, 9.0 * FOOT0, -7.5 * FOOT0, 0.03))]
-    model = cpu_model(chk[0], blocks, wall.op, wall.guess, t)
+    estimates = [("near", ss.left_increment(wall.guess, 0.6 * FOOT0, -0.3 * FOOT0, 0.001)), ("outside", ss.left_increment(wall.guess, 9.0 * FOOT0, -7.5 * FOOT0, 0.03))]
+    model = cpu_model(blocks, wall.op, wall.guess, t)
     for name, T in estimates:
         for level in range(t.levels):
-            code, want, wmask = cpu_system(chk, blocks, wall.op, wall.colour, wall.depth, wall.rgb, level, T, wall.guess, t, model=model)
+            code, want, wmask = cpu_system(blocks, wall.op, wall.depth, level, T, wall.guess, t, colour=wall.colour, rgb=wall.rgb, model=model)
             got, gmask = f.track_system(wall.depth, level, T, wall.guess, t, mask=True, rgb=wall.rgb)
             assert code == 0 and np.array_equal(gmask, wmask), (name, level, int((gmask != wmask).sum()))
             assert got.tobytes() == want.tobytes(), (name, level, got, want)
@@ -578,14 +404,14 @@ def test_gpu_rgbd_system_bit_exact_every_level(chk, wall, gpu_wall):
 def test_gpu_rgbd_track_bit_exact_and_leaves_the_volume_alone(wall, wall_cpu, gpu_wall):
     f, blocks = gpu_wall
     (pose0, res0), (pose1, res1) = wall_cpu
-    before, st0 = _volume_digest(f), f.stats()
+    before, st0 = ss.volume_digest(f), f.stats()
     pose, res = f.track(wall.depth, wall.guess, params=working_params(), rgb=wall.rgb)
     assert res_tuple(res) == res_tuple(res1), (res_tuple(res), res_tuple(res1))
     assert res.tracked == 1 and pose.tobytes() == pose1.tobytes()
     assert in_plane_error(pose, wall.truth) <= BOUND
     lost, res = f.track(wall.depth, wall.guess, params=working_params(colour_weight=0.0), rgb=wall.rgb)
     assert lost is None and res_tuple(res) == res_tuple(res0) and res.lost_reason == 3
-    assert _volume_digest(f) == before and f.stats() == st0
+    assert ss.volume_digest(f) == before and f.stats() == st0
 
 
 @pytest.mark.gpu
@@ -601,17 +427,17 @@ def test_gpu_rgbd_device_equals_host_and_weight_zero_equals_the_depth_only_call(
     p0, r0 = f.track(wall.depth, wall.guess, params=t, rgb=wall.rgb)
     assert r0.tracked == 1 and p1.tobytes() == p0.tobytes() and res_tuple(r1) == res_tuple(r0)
     # weight 0 on a scene depth can solve: the room's corner, with and without a picture, against sf_fuser_track
-    op, gp = tt.params_pair(oracle)
+    gp = ss.fuser_params(ROOM_W, ROOM_H, ss.NO_COLOUR, 0.004, num_sdf_blocks=1 << 18)   # 4c's fuser (tests/test_track.py params_pair)
     with fusion.Fuser(gp, device=0) as g:
-        frames = tt.corner_frames()
+        frames = ss.corner_frames(ROOM_W, ROOM_H)
         rng = np.random.default_rng(3)
         for dd, p in frames:   # fused with colour: a model without colour renders black, which has no gradient and so no colour row
-            assert g.integrate(dd, p, rgb=rng.integers(0, 256, tt.W * tt.H * 3, dtype=np.uint8))
+            assert g.integrate(dd, p, rgb=rng.integers(0, 256, ROOM_W * ROOM_H * 3, dtype=np.uint8))
         depth, truth = frames[0]
-        guess = tt.perturb(truth, 0.02, 2.0)
+        guess = ss.perturb(truth, 0.02, deg=2.0)
         off = fusion.default_track_params()
         want, wres = g.track(depth, guess, ref=truth, params=off)
-        rgb = rng.integers(0, 256, tt.W * tt.H * 3, dtype=np.uint8)
+        rgb = rng.integers(0, 256, ROOM_W * ROOM_H * 3, dtype=np.uint8)
         for picture in (rgb, None):
             if picture is None:
                 L = _abi.lib()
@@ -636,7 +462,7 @@ def test_gpu_rgbd_device_equals_host_and_weight_zero_equals_the_depth_only_call(
 def test_gpu_work_set_states(chk, wall):
     """One fuser's tracking buffers through their states, each answer equal to a fresh fuser's: a colour call after a depth-only call, then a colour
     call with more levels (the set is made again), then a depth-only call."""
-    T = ac.left_increment(wall.guess, 0.6 * FOOT0, -0.3 * FOOT0, 0.001)
+    T = ss.left_increment(wall.guess, 0.6 * FOOT0, -0.3 * FOOT0, 0.001)
     steps = [(2, 1, False), (2, 1, True), (4, 3, True), (2, 0, False), (3, 2, True)]
     f = fused_wall(wall)
     try:
@@ -671,14 +497,14 @@ def test_gpu_track_and_fuse_with_colour_reproduces_the_cpu_chain(chk, oracle):
         if k == 0:
             pose = truth[0]
         else:
-            code, pose, res = cpu_track(chk, vol.export(), op, colour, d, c, last, t)
+            code, pose, res = cpu_track(vol.export(), op, d, last, t, colour=colour, rgb=c)
             assert code == 0 and res.tracked == 1, (k, res.as_dict())
         vol.integrate(d, pose, rgb=under_the_depth_rays(c, colour))
         cpu.append(pose)
         last = pose
     coords, vox = vol.export()
     vol.close()
-    with fusion.Fuser(ac.fuser_params(W, H, colour, VOXEL), device=0) as f:
+    with fusion.Fuser(ss.fuser_params(W, H, colour, VOXEL), device=0) as f:
         poses, results = fusion.track_and_fuse(f, frames, truth[0], with_colour=True)
         f.sync()
         for k in range(1, WALK):
@@ -686,7 +512,7 @@ def test_gpu_track_and_fuse_with_colour_reproduces_the_cpu_chain(chk, oracle):
             assert poses[k].tobytes() == np.asarray(cpu[k], np.float32).tobytes(), k
         gc, gv = f.export_blocks()
         assert np.array_equal(gc, coords) and gv.tobytes() == vox.tobytes()
-    with fusion.Fuser(ac.fuser_params(W, H, colour, VOXEL), device=0) as f:   # the same walk without colour loses every frame after the first
+    with fusion.Fuser(ss.fuser_params(W, H, colour, VOXEL), device=0) as f:   # the same walk without colour loses every frame after the first
         poses, results = fusion.track_and_fuse(f, frames, truth[0])
         assert [r["lost_reason"] for r in results[1:]] == [3] * (WALK - 1)
 
