@@ -327,7 +327,8 @@ int sf_fuser_track_rgbd_device(sf_fuser* f, const void* d_depth, const void* d_r
  * pose one in frames_integrated -- except total_pass_tiles, which counts what the passes really read.  d_rgb may be NULL (geometry only).  Up to
  * sf_fuser_batch_frames() operations share a pass, the two of a frame always do.  Revised poses come from sf_fuser_align below (a dense-depth solver
  * over keyframes, with BundleFusion's dense colour term through sf_fuser_align_rgbd) or from the caller (sf_sens_apply_transform on part of a scan, a
- * second tracking sweep, a solver of its own): BundleFusion's SIFT matching, loop detection and local / global hierarchy are not in this library. */
+ * second tracking sweep, a solver of its own): BundleFusion's SIFT matching and loop detection are not in this library; of its local / global hierarchy
+ * the dense part is (sf_fuser_align_scan below). */
 int sf_fuser_reintegrate_batch_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes,
                                       const float* old_poses, const float* new_poses, uint64_t n);
 /* one frame from host buffers (as sf_fuser_integrate takes them); SF_ERR_SKIPPED when both poses are all -inf */
@@ -367,9 +368,9 @@ int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float* integ
  * Server/tools/recons/zParametersBundlingScanNet.txt:22-44; the code that reads them is not in the reference tree).  The semantics, per pixel, per pair
  * and per Gauss-Newton iteration, are DESIGN.md section 4e "Global alignment".  sf_fuser_align_rgbd* add BundleFusion's dense colour term to every
  * depth correspondence (s_denseColorThresh, s_denseColorGradientMin, :24-25): it pins the motion inside a plane, which depth
- * alone leaves free.  SIFT matching, loop detection, the bilateral depth filter, the Gaussian pre-filter of the colour frames (s_colorDownSigma), the
- * local / global hierarchy of BundleFusion are not built.  An alignment changes nothing in the volume, its counters
- * or frame numbering. */
+ * alone leaves free.  SIFT matching, loop detection, the bilateral depth filter and the Gaussian pre-filter of the colour frames (s_colorDownSigma)
+ * are not built; scans of more than 256 keyframes go through sf_fuser_align_scan* below, the dense part of BundleFusion's local / global hierarchy.
+ * An alignment changes nothing in the volume, its counters or frame numbering. */
 typedef struct sf_align_params {
   int32_t level;                    /* the one image size the solver works at, (W >> level) x (H >> level), 0..3: 1                 */
   int32_t down_width, down_height;  /* s_downsampledWidth / Height (:44-45); both 0: `level` decides, else the level of that size   */
@@ -434,6 +435,62 @@ int sf_fuser_align_rgbd_device(sf_fuser* f, const void* d_depth, uint64_t frame_
 /* The same from host frames (K x input-size u16 and K x colour-size RGB8, one after the other). */
 int sf_fuser_align_rgbd(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
                         const sf_align_params* a, float* poses_out, sf_align_result* result);
+
+
+/* Scans of any length: groups of consecutive keyframes under the global solve.  BundleFusion solves chunks of s_submapSize
+ * consecutive frames locally, each with its own gauge, and the chunks' first frames globally (Server/tools/recons/zParametersBundlingScanNet.txt:31,
+ * s_submapSize = 10; the code that reads the key is not in the reference tree).  What is built here is that hierarchy for the DENSE terms above: every
+ * group is sf_fuser_align*'s own problem with its first member fixed, all groups of all levels are solved at once, their first frames one level up, and
+ * the top by sf_fuser_align* itself.  What is not BundleFusion's: its local level matches SIFT features and its global level uses the chunks' merged
+ * features; neither is built, so a loop closure between frames of different groups acts only at the level where both frames are represented. */
+typedef struct sf_align_scan_params {
+  int32_t group_size;               /* frames of a group (the last of a level may have fewer), 2..16: 16                            */
+  int32_t top_frames;               /* most frames of the top level, which sf_fuser_align* solves, 2..256: 256                      */
+  int32_t reserved[6];
+} sf_align_scan_params;
+void sf_align_scan_params_default(sf_align_scan_params* s);
+typedef struct sf_align_scan_result {
+  int32_t levels;                   /* grouping levels below the top; 0: the call was one sf_fuser_align*                           */
+  int32_t groups;                   /* groups of all levels                                                                         */
+  int32_t groups_status[3];         /* how many of them ended with status 0 / 1 / 2                                                 */
+  int32_t max_iterations;           /* the largest iteration count of a group or of the top                                         */
+  int32_t frames_unconnected;       /* summed over the groups and the top                                                           */
+  int32_t frames_rejected;          /* summed over the groups and the top                                                           */
+  int64_t correspondences;          /* of the last systems, summed over the groups and the top                                      */
+  sf_align_result top;              /* the top level's own result                                                                   */
+  int32_t reserved[4];
+} sf_align_scan_result;
+/* The plan (host only, double, no GPU).  L starts as the frames whose poses are finite in rows 0..2, ascending.  While L has more than top_frames
+ * frames, or sf_align_pairs on the poses of L yields more than 4096 pairs: L is split into consecutive runs of group_size (the last may be shorter,
+ * down to one frame), each run is a group of this level, and L becomes the first frame of every run.  What is left of L is the top.  Groups come in
+ * level order and within a level in frame order: group g has the frames members[group_first[g] .. group_first[g + 1] - 1] and the level
+ * group_level[g]; its fixed frame is its first member.  group_first has room for groups_capacity + 1 values.  Writing stops at each capacity, the
+ * counts are the full ones (as sf_align_pairs).  Any output array may be NULL when its capacity is 0. */
+int sf_align_scan_plan(const float* poses, uint64_t K, const sf_align_params* a, const sf_align_scan_params* s, int32_t* members, uint64_t members_capacity,
+                       int32_t* group_first, int32_t* group_level, uint64_t groups_capacity, int32_t* top, uint64_t top_capacity, uint64_t* n_members,
+                       uint64_t* n_groups, uint64_t* n_top, int32_t* levels);
+/* G groups of the K keyframes in HBM solved at once: group g has the frames members[group_first[g] .. group_first[g + 1] - 1] (1..16 of them, indices
+ * into the K frames; a frame may be a member of several groups), G <= 4096, M = group_first[G] <= 8192, 1 <= K <= 4096.  poses_in / poses_out: M x 16
+ * floats, one pose per member SLOT; results: one per group.  d_rgb NULL: the depth term only.  a->fixed_frame must be 0.  For a group of n >= 2
+ * members, poses_out and every field of its result are bit for bit what sf_fuser_align_device (with pictures: sf_fuser_align_rgbd_device) returns for
+ * that group alone: frames 0 .. n - 1, fixed_frame 0, the sf_align_pairs list of the group's own poses_in, the same parameters.  A group of one
+ * member, or whose pair list is empty, has status 2, every other field 0 and its poses as given.  Per Gauss-Newton iteration all groups still
+ * running share one pair table, one run of sf_fuser_align*'s kernels (in launches of at most 4096 pairs), the group solve on the device (one
+ * workgroup per group) and ONE read-back; the pose update stays on the host. */
+int sf_fuser_align_groups_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K,
+                                 const int32_t* members, const int32_t* group_first, uint64_t G, const float* poses_in, const sf_align_params* a,
+                                 float* poses_out, sf_align_result* results);
+/* 2 <= K <= 4096 keyframes in HBM: sf_align_scan_plan; ALL groups of ALL levels in one sf_fuser_align_groups_device call, every group from the input
+ * poses (a first frame never moves in its own group, so the levels are independent); the top by sf_fuser_align_device (with pictures:
+ * sf_fuser_align_rgbd_device) over the sf_align_pairs list of the top's poses; then the corrections carried down level by level: a group whose first
+ * member now has the pose T' becomes sf_align_spread(the group's solved poses, keyframes {0}, {T'}).  A frame whose pose is not finite is returned
+ * as it came.  With no grouping level, poses_out and result->top are sf_fuser_align[_rgbd]_device's bits for the frames with finite poses.
+ * a->fixed_frame must be 0: the first frame with a finite pose keeps its pose. */
+int sf_fuser_align_scan_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K,
+                               const float* poses_in, const sf_align_params* a, const sf_align_scan_params* s, float* poses_out, sf_align_scan_result* result);
+/* The same from host frames (K x input-size u16 and, unless rgb is NULL, K x colour-size RGB8, one after the other). */
+int sf_fuser_align_scan(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses_in, const sf_align_params* a,
+                        const sf_align_scan_params* s, float* poses_out, sf_align_scan_result* result);
 
 /* Host <-> device helpers so that callers without a HIP binding can stage inputs in HBM. */
 int sf_device_malloc(int device, uint64_t bytes, void** out);

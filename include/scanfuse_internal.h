@@ -135,6 +135,15 @@ int sf_fuser_align_system(sf_fuser* f, const uint16_t* depth, uint64_t K, const 
 int sf_fuser_align_rgbd_system(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses, const int32_t* pairs, uint64_t P,
                                const sf_align_params* a, double* sys);
 
+/* Stage hook of the batched group solve (tests/test_align_scan.py; scannet_amd/csrc/align_scan.hip): k_group_solve ALONE on GPU `device`, on
+ * caller-supplied per-pair systems.  Group g has n = group_first[g + 1] - group_first[g] members (1..16) and the pairs pair_first[g] ..
+ * pair_first[g + 1] - 1 (at most 240) of local_pairs (2 x P int32: source, target as member indices 0..n-1); valid_masks[g] bit k: member k takes part;
+ * sys: P x nsys doubles (nsys 29 or 31).  Out, per group: xi (6 doubles per member slot, M x 6 in all), status, pairs used, the connected flags (bit k)
+ * and the four sums {counts, r^2, colour counts, colour r^2}. */
+int sf_align_group_solve_stage(int device, uint64_t G, const int32_t* group_first, const int32_t* pair_first, const int32_t* local_pairs,
+                               const uint32_t* valid_masks, const double* sys, int nsys, int min_pair_correspondences, double* xi_out, int32_t* status_out,
+                               int32_t* used_out, uint32_t* conn_out, double* sums_out);
+
 /* Stage hooks of the 2-D annotation filter (tests/test_filter2d_stages.py; scannet_amd/csrc/filter2d.hip): each call runs ONE kernel of the filter on host
  * arrays on GPU `device`, through the launcher sf_filter2d_frame uses for it (same grid, same workgroup, same dynamic LDS), and returns the output to the
  * host.  Images are row-major, w x h.  Sides are 1 .. 16384 (2 .. 16384 for the resamples, whose scale divides by side - 1).

@@ -5,7 +5,8 @@
 // rules, track_math.h).  Per Gauss-Newton iteration: the host writes the pair table (indices, T_i, T_j, T_j^-1 T_i) and copies it over; k_align_assoc
 // pairs every source pixel of every pair with the target pixel it projects to and reduces the pair's 29 values per 256-pixel workgroup (no atomics);
 // k_align_final sums a pair's partials in index order in double; one read-back.  The host drops thin pairs, finds the frames connected to the fixed
-// frame, assembles the sparse-by-blocks normal equations densely and solves them by Cholesky in double.  Every step is deterministic and
+// frame, assembles the sparse-by-blocks normal equations densely and solves them by Cholesky in double (align_solve.h states each entry's arithmetic
+// once, for this loop and for align_scan.hip's group solve on the device).  Every step is deterministic and
 // tests/align_checker.c restates it bit for bit.  sf_fuser_align_rgbd* run the same host loop over align_colour.hip's kernels, which add the dense
 // colour term's row to every correspondence and two sums to the pair's values (tests/align_colour_checker.c).
 #include <hip/hip_runtime.h>
@@ -109,7 +110,7 @@ void sf_align_release(sf_fuser* f) {
 namespace {
 
 // what can be checked without a fuser
-int check_align_args(uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a) {
+int check_params(const sf_align_params* a) {
   if (!a) return sf::fail(SF_ERR_INVALID_ARG, "NULL alignment parameters");
   if (a->level < 0 || a->level >= TK_MAX_LEVELS) return sf::fail(SF_ERR_INVALID_ARG, "alignment level %d (0..3)", a->level);
   if (a->down_width < 0 || a->down_height < 0 || (a->down_width == 0) != (a->down_height == 0))
@@ -123,6 +124,11 @@ int check_align_args(uint64_t K, const float* poses, const int32_t* pairs, uint6
   if (a->min_pair_correspondences < 1) return sf::fail(SF_ERR_INVALID_ARG, "min_pair_correspondences %d (>= 1)", a->min_pair_correspondences);
   if (!std::isfinite(a->max_translation) || !(a->max_translation > 0.0f) || !std::isfinite(a->max_rotation) || !(a->max_rotation > 0.0f))
     return sf::fail(SF_ERR_INVALID_ARG, "alignment motion bound %g m, %g rad: not positive finite numbers", a->max_translation, a->max_rotation);
+  return SF_OK;
+}
+
+int check_align_args(uint64_t K, const float* poses, const int32_t* pairs, uint64_t P, const sf_align_params* a) {
+  if (const int rc = check_params(a)) return rc;
   if (K < 2 || K > (uint64_t)AL_MAX_FRAMES) return sf::fail(SF_ERR_INVALID_ARG, "alignment of %llu frames (2..%d)", (unsigned long long)K, AL_MAX_FRAMES);
   if (a->fixed_frame < 0 || (uint64_t)a->fixed_frame >= K) return sf::fail(SF_ERR_INVALID_ARG, "fixed_frame %d of %llu frames", a->fixed_frame, (unsigned long long)K);
   if (P < 1 || P > (uint64_t)AL_MAX_PAIRS) return sf::fail(SF_ERR_INVALID_ARG, "alignment over %llu pairs (1..%d)", (unsigned long long)P, AL_MAX_PAIRS);
@@ -154,7 +160,8 @@ int resolve_level(const sf_fuser* f, const sf_align_params* a, int* level, Cam* 
 uint64_t picture_bytes(const sf_fuser* f) { return (f->pk.cW ? (uint64_t)f->pk.cW * f->pk.cH : (uint64_t)f->pk.W * f->pk.H) * 3; }
 
 // nsys: 29, or 31 with the colour term's sums; host_rgb / photo: the pictures come from the host / there are pictures at all
-int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames, int nsys = TK_NSYS, bool host_rgb = false, bool photo = false) {
+// P: rows of the pair table and of the systems; chunk: the most pairs one launch takes (0: P)
+int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames, int nsys = TK_NSYS, bool host_rgb = false, bool photo = false, uint64_t chunk = 0) {
   if (!f->align) f->align = new AlignWork();
   AlignWork* w = f->align;
   const size_t map_bytes = (size_t)K * npx * sizeof(float4);
@@ -163,7 +170,7 @@ int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames, 
   if (e == hipSuccess) e = w->photo.reserve(photo ? map_bytes : 0);
   if (e == hipSuccess) e = w->vmap.reserve(map_bytes);
   if (e == hipSuccess) e = w->nmap.reserve(map_bytes);
-  if (e == hipSuccess) e = w->partials.reserve((size_t)P * ((npx + 255) / 256) * TK_PSTRIDE * sizeof(float));
+  if (e == hipSuccess) e = w->partials.reserve((size_t)(chunk ? chunk : P) * ((npx + 255) / 256) * TK_PSTRIDE * sizeof(float));
   if (e == hipSuccess) e = w->d_table.reserve(P * sizeof(PairEntry));
   if (e == hipSuccess) e = w->h_table.reserve(P * sizeof(PairEntry));
   if (e == hipSuccess) e = w->d_sys.reserve(P * nsys * sizeof(double));
@@ -172,21 +179,12 @@ int ensure_work(sf_fuser* f, uint64_t K, uint64_t P, int npx, bool host_frames, 
   return SF_OK;
 }
 
-struct Job {
-  const void* d_depth;   // the K frames in HBM, stride bytes apart
-  uint64_t stride;
-  uint64_t K, P;
-  const int32_t* pairs;
-  int level;
-  Cam cam;
-  float dmin, dmax;
-  int nsys = TK_NSYS;            // values per pair: 29, or 31 through sf_fuser_align_rgbd* (align_colour.hip's kernels)
-  const void* d_rgb = nullptr;   // the K colour pictures in HBM, rgb_stride bytes apart; nullptr: none
-  uint64_t rgb_stride = 0;
-};
+using Job = AlignJob;
+
+}  // namespace
 
 // the maps of all K frames, queued on f->stream behind everything queued on the handle so far
-int prepare(sf_fuser* f, const Job& j) {
+int sf_align_prepare(sf_fuser* f, const AlignJob& j) {
   AlignWork* w = f->align;
   // the maps read no volume, so nothing queued later on the front streams has to wait for them
   if (const int oc = sf_order_behind_fronts(f)) return oc;
@@ -206,31 +204,43 @@ int prepare(sf_fuser* f, const Job& j) {
   return j.d_rgb ? sf_photo_prepare(f, j.d_rgb, j.rgb_stride, j.K, j.level, j.cam) : SF_OK;
 }
 
+// rows first .. first + count - 1 of w->d_table into the same rows of w->d_sys, queued on f->stream; count <= AL_MAX_PAIRS
+int sf_align_systems(sf_fuser* f, const AlignJob& j, const sf_align_params* a, uint64_t first, uint64_t count) {
+  AlignWork* w = f->align;
+  if (j.nsys == AL_NSYS_RGBD) return sf_photo_systems(f, count, j.cam, a, j.d_rgb != nullptr, first);
+  const int npx = j.cam.W * j.cam.H, nb = (npx + 255) / 256;
+  hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)count), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
+                     w->d_table.as<const PairEntry>() + first, j.cam, a->dist_thres, a->normal_thres, w->partials.as<float>());
+  SF_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_align_final, dim3((unsigned)count), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>() + first * TK_NSYS);
+  SF_HIP_CHECK(hipGetLastError());
+  return SF_OK;
+}
+
+// one row of the pair table: frames fi -> fj of the maps at the poses Ti, Tj (12 doubles each); active: both frames take part
+void sf_align_pair_row(AlignPair* e, int32_t fi, int32_t fj, bool active, const double* Ti, const double* Tj) {
+  std::memset(e, 0, sizeof(*e));
+  e->i = fi;
+  e->j = fj;
+  e->active = active;
+  if (!active) return;
+  for (int k = 0; k < 12; k++) { e->Ti.T[k] = (float)Ti[k]; e->Tj.T[k] = (float)Tj[k]; }
+  compose_ref(Tj, Ti, e->M.T);
+}
+
+namespace {
+
+int prepare(sf_fuser* f, const Job& j) { return j.maps_ready ? SF_OK : sf_align_prepare(f, j); }
+
 // the P systems at the poses T (K x 12 doubles; valid[k]: the frame takes part) into w->h_sys
 int systems_at(sf_fuser* f, const Job& j, const double* T, const uint8_t* valid, const sf_align_params* a) {
   AlignWork* w = f->align;
   for (uint64_t p = 0; p < j.P; p++) {
-    PairEntry& e = w->h_table.as<PairEntry>()[p];
-    std::memset(&e, 0, sizeof(e));
-    e.i = j.pairs[2 * p];
-    e.j = j.pairs[2 * p + 1];
-    e.active = valid[e.i] && valid[e.j];
-    if (!e.active) continue;
-    const double *Ti = T + 12 * e.i, *Tj = T + 12 * e.j;
-    for (int k = 0; k < 12; k++) { e.Ti.T[k] = (float)Ti[k]; e.Tj.T[k] = (float)Tj[k]; }
-    compose_ref(Tj, Ti, e.M.T);
+    const int32_t pi = j.pairs[2 * p], pj = j.pairs[2 * p + 1];
+    sf_align_pair_row(&w->h_table.as<PairEntry>()[p], j.remap ? j.remap[pi] : pi, j.remap ? j.remap[pj] : pj, valid[pi] && valid[pj], T + 12 * pi, T + 12 * pj);
   }
   SF_HIP_CHECK(hipMemcpyAsync(w->d_table.p, w->h_table.p, j.P * sizeof(PairEntry), hipMemcpyHostToDevice, f->stream));
-  if (j.nsys == AL_NSYS_RGBD) {
-    if (const int rc = sf_photo_systems(f, j.P, j.cam, a, j.d_rgb != nullptr)) return rc;
-  } else {
-    const int npx = j.cam.W * j.cam.H, nb = (npx + 255) / 256;
-    hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)j.P), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
-                       w->d_table.as<const PairEntry>(), j.cam, a->dist_thres, a->normal_thres, w->partials.as<float>());
-    SF_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_align_final, dim3((unsigned)j.P), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
-    SF_HIP_CHECK(hipGetLastError());
-  }
+  if (const int rc = sf_align_systems(f, j, a, 0, j.P)) return rc;
   SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, j.P * j.nsys * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   SF_HIP_CHECK(hipStreamSynchronize(f->stream));
   return SF_OK;
@@ -241,7 +251,10 @@ int find_root(std::vector<int>& parent, int k) {
   return k;
 }
 
-int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_params* a, float* poses_out, sf_align_result* res) {
+}  // namespace
+
+// sf_fuser_align*'s Gauss-Newton loop over the job's pair list (align_scan.hip runs it for the top of a scan)
+int sf_align_solve(sf_fuser* f, const AlignJob& j, const float* poses_in, const sf_align_params* a, float* poses_out, sf_align_result* res) {
   int rc;
   const uint64_t K = j.K;
   sf_align_result r;
@@ -260,7 +273,7 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
   const size_t ns = (size_t)j.nsys;   // the loop reads a pair's first 29 values; the colour term's two only for the result
   std::vector<uint8_t> kept(j.P), conn(K, 0);
   std::vector<int> parent(K), slot(K);
-  std::vector<double> A, b, xi;
+  std::vector<double> A, b, y, xi;
   for (int it = 0; it < a->max_iters; it++) {
     if ((rc = systems_at(f, j, T.data(), valid.data(), a)) != SF_OK) return rc;
     for (uint64_t k = 0; k < K; k++) parent[k] = (int)k;
@@ -280,7 +293,7 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
     }
     if (!valid[fixed] || nconn < 2) { r.status = 2; break; }
     const int N = 6 * n;
-    A.assign((size_t)N * N, 0.0);
+    A.assign(als::tri(N, 0), 0.0);   // the lower triangle, packed (align_solve.h)
     b.assign(N, 0.0);
     int used = 0;
     double corr = 0.0, r2 = 0.0, ccorr = 0.0, cr2 = 0.0;
@@ -288,22 +301,13 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
       const int pi = j.pairs[2 * p], pj = j.pairs[2 * p + 1];
       if (!kept[p] || !conn[pi]) continue;
       const double* s = sys + p * ns;
-      double Hm[6][6];
-      int k = 0;
-      for (int u = 0; u < 6; u++)
-        for (int v = u; v < 6; v++) Hm[u][v] = Hm[v][u] = s[k++];
       const int si = slot[pi], sj = slot[pj];
       for (int u = 0; u < 6; u++) {
         for (int v = 0; v < 6; v++) {
-          if (si >= 0) A[(size_t)(6 * si + u) * N + 6 * si + v] += Hm[u][v];
-          if (sj >= 0) A[(size_t)(6 * sj + u) * N + 6 * sj + v] += Hm[u][v];
-          if (si >= 0 && sj >= 0) {
-            A[(size_t)(6 * si + u) * N + 6 * sj + v] -= Hm[u][v];
-            A[(size_t)(6 * sj + u) * N + 6 * si + v] -= Hm[u][v];
-          }
+          als::assemble_diag(A.data(), si, sj, u, v, s[als::sym21(u, v)]);
+          als::assemble_off(A.data(), si, sj, u, v, s[als::sym21(u, v)]);
         }
-        if (si >= 0) b[6 * si + u] += s[21 + u];
-        if (sj >= 0) b[6 * sj + u] -= s[21 + u];
+        als::assemble_rhs(b.data(), si, sj, u, s[21 + u]);
       }
       used++;
       r2 += s[27];
@@ -318,7 +322,8 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
     r.colour_rms_last = ccorr > 0.0 ? (float)std::sqrt(cr2 / ccorr) : 0.0f;
     if (it == 0) r.colour_rms_first = r.colour_rms_last;
     xi.resize(N);
-    if (!solve_spd(A.data(), b.data(), N, xi.data())) { r.status = 1; break; }
+    y.resize(N);
+    if (!als::solve_packed(A.data(), b.data(), N, y.data(), xi.data())) { r.status = 1; break; }
     double mx = 0.0;
     for (uint64_t k = 0; k < K; k++)
       if (slot[k] >= 0) apply_update(&xi[6 * slot[k]], &T[12 * k]);
@@ -338,6 +343,8 @@ int align(sf_fuser* f, const Job& j, const float* poses_in, const sf_align_param
   return SF_OK;
 }
 
+namespace {
+
 // the colour term's three parameters, which only the rgbd entry points read
 int check_colour_args(const sf_align_params* a, const void* rgb) {
   if (!std::isfinite(a->colour_weight) || !(a->colour_weight >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "alignment colour_weight %g: not a finite number >= 0", a->colour_weight);
@@ -354,6 +361,19 @@ int begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool 
           const sf_align_params* a, Job* j, bool rgbd = false, const void* rgb = nullptr, uint64_t rgb_stride = 0) {
   int rc = check_align_args(K, poses, pairs, P, a);
   if (rc != SF_OK) return rc;
+  j->pairs = pairs;
+  return sf_align_begin(f, depth, on_device, stride, out_ok, K, P, 0, a, j, rgbd, rgb, rgb_stride);
+}
+
+}  // namespace
+
+int sf_align_check_params(const sf_align_params* a) { return check_params(a); }
+
+// what follows the checks of the pair list: the colour arguments, the handle, the strides, the level, the device, the buffers (P table rows, `chunk`
+// pairs per launch, 0: P) and, for frames on the host, their copy into w->d_in (and w->d_rgb)
+int sf_align_begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool out_ok, uint64_t K, uint64_t P, uint64_t chunk, const sf_align_params* a,
+                   AlignJob* j, bool rgbd, const void* rgb, uint64_t rgb_stride) {
+  int rc;
   if (rgbd && (rc = check_colour_args(a, rgb)) != SF_OK) return rc;
   if (!f) return sf::fail(SF_ERR_INVALID_ARG, "NULL fuser");
   if (!depth || !out_ok) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
@@ -362,14 +382,14 @@ int begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool 
   const uint64_t frame_bytes = f->in_px * sizeof(uint16_t);
   if (on_device && (stride < frame_bytes || stride % sizeof(uint16_t)))
     return sf::fail(SF_ERR_INVALID_ARG, "frame stride %llu bytes for frames of %llu", (unsigned long long)stride, (unsigned long long)frame_bytes);
-  j->K = K; j->P = P; j->pairs = pairs;
+  j->K = K; j->P = P;
   if ((rc = resolve_level(f, a, &j->level, &j->cam)) != SF_OK) return rc;
   const bool own = a->depth_min == 0.0f && a->depth_max == 0.0f;
   j->dmin = own ? f->pk.dmin : a->depth_min;
   j->dmax = own ? f->pk.dmax : a->depth_max;
   SF_HIP_CHECK(hipSetDevice(f->device));
   j->nsys = rgbd ? AL_NSYS_RGBD : TK_NSYS;
-  if ((rc = ensure_work(f, K, P, j->cam.W * j->cam.H, !on_device, j->nsys, rgb && !on_device, rgb != nullptr)) != SF_OK) return rc;
+  if ((rc = ensure_work(f, K, P, j->cam.W * j->cam.H, !on_device, j->nsys, rgb && !on_device, rgb != nullptr, chunk)) != SF_OK) return rc;
   j->d_depth = depth;
   j->stride = stride;
   j->d_rgb = rgb;
@@ -387,34 +407,32 @@ int begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool 
   return SF_OK;
 }
 
-}  // namespace
-
 SF_API int sf_fuser_align_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
                                  const sf_align_params* a, float* poses_out, sf_align_result* result) {
   Job j;
   const int rc = begin(f, d_depth, true, frame_stride_bytes, poses_out != nullptr, K, poses_in, pairs, P, a, &j);
-  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
+  return rc != SF_OK ? rc : sf_align_solve(f, j, poses_in, a, poses_out, result);
 }
 
 SF_API int sf_fuser_align(sf_fuser* f, const uint16_t* depth, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a,
                           float* poses_out, sf_align_result* result) {
   Job j;
   const int rc = begin(f, depth, false, 0, poses_out != nullptr, K, poses_in, pairs, P, a, &j);
-  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
+  return rc != SF_OK ? rc : sf_align_solve(f, j, poses_in, a, poses_out, result);
 }
 
 SF_API int sf_fuser_align_rgbd_device(sf_fuser* f, const void* d_depth, uint64_t frame_stride_bytes, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K,
                                       const float* poses_in, const int32_t* pairs, uint64_t P, const sf_align_params* a, float* poses_out, sf_align_result* result) {
   Job j;
   const int rc = begin(f, d_depth, true, frame_stride_bytes, poses_out != nullptr, K, poses_in, pairs, P, a, &j, true, d_rgb, rgb_stride_bytes);
-  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
+  return rc != SF_OK ? rc : sf_align_solve(f, j, poses_in, a, poses_out, result);
 }
 
 SF_API int sf_fuser_align_rgbd(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, uint64_t K, const float* poses_in, const int32_t* pairs, uint64_t P,
                                const sf_align_params* a, float* poses_out, sf_align_result* result) {
   Job j;
   const int rc = begin(f, depth, false, 0, poses_out != nullptr, K, poses_in, pairs, P, a, &j, true, rgb, 0);
-  return rc != SF_OK ? rc : align(f, j, poses_in, a, poses_out, result);
+  return rc != SF_OK ? rc : sf_align_solve(f, j, poses_in, a, poses_out, result);
 }
 
 namespace {

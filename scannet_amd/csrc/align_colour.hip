@@ -100,14 +100,14 @@ int sf_photo_prepare(sf_fuser* f, const void* d_rgb, uint64_t rgb_stride_bytes, 
   return SF_OK;
 }
 
-int sf_photo_systems(sf_fuser* f, uint64_t P, const Cam& cam, const sf_align_params* a, bool with_photo) {
+int sf_photo_systems(sf_fuser* f, uint64_t P, const Cam& cam, const sf_align_params* a, bool with_photo, uint64_t first) {
   AlignWork* w = f->align;
   const int npx = cam.W * cam.H, nb = (npx + 255) / 256;
   hipLaunchKernelGGL(k_photo_assoc, dim3(nb, (unsigned)P), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
-                     with_photo ? w->photo.as<const float4>() : nullptr, w->d_table.as<const AlignPair>(), cam, a->dist_thres, a->normal_thres,
+                     with_photo ? w->photo.as<const float4>() : nullptr, w->d_table.as<const AlignPair>() + first, cam, a->dist_thres, a->normal_thres,
                      a->colour_weight, a->colour_thres, a->colour_gradient_min, w->partials.as<float>());
   SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_photo_final, dim3((unsigned)P), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
+  hipLaunchKernelGGL(k_photo_final, dim3((unsigned)P), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>() + first * AL_NSYS_RGBD);
   SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }

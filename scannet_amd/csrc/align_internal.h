@@ -4,6 +4,7 @@
 #include "fuser_internal.h"
 #include "hip_util.h"
 #include "scanfuse.h"
+#include "align_solve.h"
 #include "track_math.h"
 
 constexpr int AL_NSYS_RGBD = 31;   // the 29 values of track_math.h, then the colour term's sum r_c^2 and count
@@ -23,9 +24,40 @@ struct AlignWork {   // every buffer grows on demand and never shrinks
   sf::HostBuf h_table;         // page-locked
   sf::DevBuf d_sys;            // double [P][29 or 31]
   sf::HostBuf h_sys;           // page-locked read-back
+  // sf_fuser_align_groups_device (align_scan.hip)
+  sf::DevBuf d_group;          // the groups' descriptions, local pair lists and running list
+  sf::HostBuf h_group;
+  sf::DevBuf d_record;         // als::GroupOut per running group
+  sf::HostBuf h_record;
 };
+
+struct AlignJob {   // one call's frames, level and pair list
+  const void* d_depth;   // the K frames in HBM, stride bytes apart
+  uint64_t stride;
+  uint64_t K, P;
+  const int32_t* pairs = nullptr;
+  int level;
+  tk::Cam cam;
+  float dmin, dmax;
+  int nsys = tk::TK_NSYS;        // values per pair: 29, or 31 through sf_fuser_align_rgbd* (align_colour.hip's kernels)
+  const void* d_rgb = nullptr;   // the K colour pictures in HBM, rgb_stride bytes apart; nullptr: none
+  uint64_t rgb_stride = 0;
+  const int32_t* remap = nullptr;   // frame k of the call is frame remap[k] of the maps (align_scan.hip: the top of a scan); nullptr: k itself
+  bool maps_ready = false;          // the maps are in w->vmap / nmap / photo already
+};
+
+// align.hip, for align_scan.hip: the parameter checks, the set-up behind them, the maps, one row of the pair table, the kernels over a range of its
+// rows, and the whole solve of the job's pair list (sf_fuser_align*'s own loop)
+int sf_align_check_params(const sf_align_params* a);
+int sf_align_begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stride, bool out_ok, uint64_t K, uint64_t P, uint64_t chunk, const sf_align_params* a,
+                   AlignJob* j, bool rgbd, const void* rgb, uint64_t rgb_stride);
+int sf_align_prepare(sf_fuser* f, const AlignJob& j);
+void sf_align_pair_row(AlignPair* e, int32_t fi, int32_t fj, bool active, const double* Ti, const double* Tj);
+int sf_align_systems(sf_fuser* f, const AlignJob& j, const sf_align_params* a, uint64_t first, uint64_t count);
+int sf_align_solve(sf_fuser* f, const AlignJob& j, const float* poses_in, const sf_align_params* a, float* poses_out, sf_align_result* res);
 
 // align_colour.hip, both queued on f->stream.  The intensity and gradient maps of K pictures at `level` into w->photo:
 int sf_photo_prepare(sf_fuser* f, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K, int level, const tk::Cam& cam);
-// the P pairs' 31-value systems from the maps and w->d_table into w->d_sys; with_photo false: no colour rows (the depth term's bits, the colour sums 0)
-int sf_photo_systems(sf_fuser* f, uint64_t P, const tk::Cam& cam, const sf_align_params* a, bool with_photo);
+// the 31-value systems of rows first .. first + P - 1 of w->d_table, from the maps, into the same rows of w->d_sys; with_photo false: no colour rows
+// (the depth term's bits, the colour sums 0)
+int sf_photo_systems(sf_fuser* f, uint64_t P, const tk::Cam& cam, const sf_align_params* a, bool with_photo, uint64_t first = 0);

@@ -54,6 +54,8 @@ extern char** environ;
 #pragma weak sf_fuser_align_rgbd
 #pragma weak sf_align_pairs
 #pragma weak sf_align_spread
+#pragma weak sf_fuser_align_scan
+#pragma weak sf_align_scan_params_default
 #pragma weak sf_fuse_update_trajectory
 
 namespace {
@@ -93,6 +95,8 @@ struct Args {
   const char* write_sens = nullptr;   // --write-sens=<out.sens>: the input with the tracked (and, with --align, corrected) trajectory
   int align = -1;                     // --align[=N]: keyframes every N-th tracked frame are aligned jointly (see align_scan below); 0: N from the parameter file
   const char* align_params = nullptr; // --align-params=<file>: zParametersBundlingScanNet.txt
+  int align_group = 0;                // --align-group=G: frames of a group of the scan call, 2..16 (0: the library's default, 16)
+  int align_top = 0;                  // --align-top=T: most keyframes of the top level, 2..256 (0: the library's default, 256)
   float align_colour = -1.0f;         // --align-colour[=w]: --align's solver with the dense colour term at weight w; < 0: depth only
   float track_colour = -1.0f;         // --track-colour[=w]: --track's tracker with the dense colour term at weight w; < 0: depth only
   const char* pos[8];
@@ -239,6 +243,8 @@ int render_depth(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_in
 // or 10); the keyframes are aligned jointly over the default pair list (sf_align_pairs, sf_fuser_align), the correction is carried to the frames between
 // them (sf_align_spread) and the volume is moved to the corrected trajectory (sf_fuse_update_trajectory).  traj: n x 16, in: what the volume holds, out: the same.
 // --align-colour[=w]: the keyframes' colour frames go with their depth and the solver adds the dense colour term at weight w (sf_fuser_align_rgbd).
+// With more than T keyframes (--align-top=T, default 256) or more than 4096 pairs the keyframes go through sf_fuser_align_scan instead: groups of G
+// consecutive keyframes (--align-group=G, default 16) under the global solve; up to 4096 keyframes.
 constexpr float ALIGN_COLOUR_WEIGHT = 0.1f;   // --align-colour without a value: the working weight (DESIGN.md 4f has the sweep)
 constexpr float TRACK_COLOUR_WEIGHT = 0.1f;   // --track-colour without a value: the working weight (DESIGN.md 4g has the sweep)
 int submap_size(const char* path) {
@@ -284,7 +290,9 @@ int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
   }
   const uint64_t K = keys.size();
   if (K < 2) { say("Aligned nothing: %llu keyframes\n", (unsigned long long)K); return 0; }
-  if (K > 256) return die_msg("--align=%d gives %llu keyframes, the solver takes 256: choose a larger stride", every, (unsigned long long)K);
+  // the one bound left: the scan call's 4096 keyframes (the solver's own 256 keyframes and 4096 pairs no longer stop the tool)
+  if (K > 4096) return die_msg("--align=%d gives %llu keyframes, the scan call takes 4096: choose a larger stride", every, (unsigned long long)K);
+  const uint64_t top = a.align_top ? (uint64_t)a.align_top : 256;
   const size_t px = (size_t)info.depth_width * info.depth_height;
   const size_t cpx = (size_t)info.color_width * info.color_height * 3;
   std::vector<uint16_t> depth(K * px);
@@ -298,20 +306,40 @@ int align_scan(const Args& a, sf_fuser* fuser, sf_sens* sens, const sf_sens_info
   std::vector<int32_t> pairs(2 * 4096);
   uint64_t P = 0;
   if (sf_align_pairs(kp.data(), K, &ap, pairs.data(), 4096, &P) != SF_OK) return die("pairs");
-  if (P > 4096) return die_msg("--align: %llu pairs, the solver takes 4096: choose a larger stride", (unsigned long long)P);
-  sf_align_result res;
-  const auto t0 = std::chrono::steady_clock::now();
-  if ((photo ? sf_fuser_align_rgbd(fuser, depth.data(), rgb.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res)
-             : sf_fuser_align(fuser, depth.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res)) != SF_OK)
-    return die("alignment");
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  say("Aligned %llu keyframes (every %d) over %llu pairs in %.1f ms: status %d, %d iterations, %d pairs and %lld correspondences in the last system, rms %.4f -> %.4f m, "
-      "%d unconnected, %d rejected\n", (unsigned long long)K, every, (unsigned long long)P, ms, res.status, res.iterations, res.pairs_used, (long long)res.correspondences,
-      res.rms_first, res.rms_last, res.frames_unconnected, res.frames_rejected);
-  if (photo)
-    say("Colour term at weight %g: %lld colour correspondences in the last system, rms %.4f -> %.4f of the intensity range\n", ap.colour_weight,
-        (long long)res.colour_correspondences, res.colour_rms_first, res.colour_rms_last);
-  if (res.status != 0) return 0;   // the poses came back as they went in
+  if (K > top || P > 4096) {   // beyond the solver's limits: groups under the global solve; its result is spread whatever the top's status
+    if (!sf_fuser_align_scan || !sf_align_scan_params_default) return die_msg("--align: %llu keyframes, %llu pairs: this libscanfuse has no scan call", (unsigned long long)K, (unsigned long long)P);
+    sf_align_scan_params sp;
+    sf_align_scan_params_default(&sp);
+    if (a.align_group) sp.group_size = a.align_group;
+    if (a.align_top) sp.top_frames = a.align_top;
+    sf_align_scan_result sr;
+    const auto s0 = std::chrono::steady_clock::now();
+    if (sf_fuser_align_scan(fuser, depth.data(), photo ? rgb.data() : nullptr, K, kp.data(), &ap, &sp, knew.data(), &sr) != SF_OK) return die("alignment");
+    const double sms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
+    say("Aligned %llu keyframes (every %d) in %d levels of groups of %d under a top of at most %d in %.1f ms: %d groups, %d solved, %d singular, %d unconnected; "
+        "at most %d iterations, %lld correspondences in the last systems, %d frames unconnected, %d rejected\n", (unsigned long long)K, every, sr.levels, sp.group_size,
+        sp.top_frames, sms, sr.groups, sr.groups_status[0], sr.groups_status[1], sr.groups_status[2], sr.max_iterations, (long long)sr.correspondences,
+        sr.frames_unconnected, sr.frames_rejected);
+    say("Top level: status %d, %d iterations, %d pairs and %lld correspondences in the last system, rms %.4f -> %.4f m, %d unconnected, %d rejected\n", sr.top.status,
+        sr.top.iterations, sr.top.pairs_used, (long long)sr.top.correspondences, sr.top.rms_first, sr.top.rms_last, sr.top.frames_unconnected, sr.top.frames_rejected);
+    if (photo)
+      say("Colour term at weight %g: %lld colour correspondences in the top's last system, rms %.4f -> %.4f of the intensity range\n", ap.colour_weight,
+          (long long)sr.top.colour_correspondences, sr.top.colour_rms_first, sr.top.colour_rms_last);
+  } else {
+    sf_align_result res;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((photo ? sf_fuser_align_rgbd(fuser, depth.data(), rgb.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res)
+               : sf_fuser_align(fuser, depth.data(), K, kp.data(), pairs.data(), P, &ap, knew.data(), &res)) != SF_OK)
+      return die("alignment");
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    say("Aligned %llu keyframes (every %d) over %llu pairs in %.1f ms: status %d, %d iterations, %d pairs and %lld correspondences in the last system, rms %.4f -> %.4f m, "
+        "%d unconnected, %d rejected\n", (unsigned long long)K, every, (unsigned long long)P, ms, res.status, res.iterations, res.pairs_used, (long long)res.correspondences,
+        res.rms_first, res.rms_last, res.frames_unconnected, res.frames_rejected);
+    if (photo)
+      say("Colour term at weight %g: %lld colour correspondences in the last system, rms %.4f -> %.4f of the intensity range\n", ap.colour_weight,
+          (long long)res.colour_correspondences, res.colour_rms_first, res.colour_rms_last);
+    if (res.status != 0) return 0;   // the poses came back as they went in
+  }
   std::vector<float> target(n * 16);
   if (sf_align_spread(traj.data(), n, keys.data(), K, knew.data(), target.data()) != SF_OK) return die("spread");
   sf_reint_params rp;
@@ -671,6 +699,8 @@ int main(int argc, const char** argv_in) {
     else if (!std::strcmp(s, "--align")) a.align = 0;
     else if (!std::strncmp(s, "--align=", 8)) { a.align = std::atoi(s + 8); if (a.align < 1) bad = true; }
     else if (!std::strncmp(s, "--align-params=", 15) && s[15]) a.align_params = s + 15;
+    else if (!std::strncmp(s, "--align-group=", 14)) { a.align_group = std::atoi(s + 14); if (a.align_group < 2 || a.align_group > 16) bad = true; }
+    else if (!std::strncmp(s, "--align-top=", 12)) { a.align_top = std::atoi(s + 12); if (a.align_top < 2 || a.align_top > 256) bad = true; }
     else if (!std::strcmp(s, "--align-colour")) a.align_colour = ALIGN_COLOUR_WEIGHT;
     else if (!std::strncmp(s, "--align-colour=", 15) && s[15]) {
       char* end = nullptr;
@@ -687,11 +717,13 @@ int main(int argc, const char** argv_in) {
     else if (a.n_pos < 8) a.pos[a.n_pos++] = s;
   }
   if (a.n_pos < 4 || bad || a.ranks < 1 || a.ranks > 64 || (a.rank >= 0 && (a.rank >= a.ranks || a.ipc.empty()))) {
-    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--track-colour[=w]] [--align[=N] [--align-colour[=w]]] [--align-params=<zParametersBundling.txt>] [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
+    std::printf("Usage: depthsensing [--upstream[=voxelhashing|bundlefusion]] [--ranks N [--share-gpu]] [--track [--track-colour[=w]] [--align[=N] [--align-group=G] [--align-top=T] [--align-colour[=w]]] [--align-params=<zParametersBundling.txt>] [--write-sens=<out.sens>]] <zParameters.txt> <zParametersTracking.txt> <scan.sens> [out.ply]\n");
     return 255;
   }
   if (a.render_dir && a.ranks > 1)
     return die_msg("--render-depth ray-casts one volume on one GPU; a partitioned run (--ranks %d) has no such volume: run without --ranks to render", a.ranks);
+  if ((a.align_group || a.align_top) && a.align < 0)
+    return die_msg("--align-group and --align-top shape --align's scan call: they need --track --align");
   if (a.align_colour >= 0.0f && a.align < 0)
     return die_msg("--align-colour adds the dense colour term to --align's solver: it needs --track --align");
   if (a.track_colour >= 0.0f && !a.track)

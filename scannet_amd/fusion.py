@@ -221,6 +221,58 @@ def align_spread(poses, keyframes, new_key_poses):
     return out
 
 
+class SfAlignScanParams(C.Structure):
+    _fields_ = [("group_size", C.c_int32), ("top_frames", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class SfAlignScanResult(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("groups", C.c_int32), ("groups_status", C.c_int32 * 3), ("max_iterations", C.c_int32),
+                ("frames_unconnected", C.c_int32), ("frames_rejected", C.c_int32), ("correspondences", C.c_int64), ("top", SfAlignResult),
+                ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        return dict(levels=int(self.levels), groups=int(self.groups), groups_status=[int(x) for x in self.groups_status],
+                    max_iterations=int(self.max_iterations), frames_unconnected=int(self.frames_unconnected),
+                    frames_rejected=int(self.frames_rejected), correspondences=int(self.correspondences), top=self.top.as_dict())
+
+
+def default_align_scan_params(**over):
+    """sf_align_scan_params_default: group_size 16, top_frames 256; keyword overrides."""
+    s = SfAlignScanParams()
+    L = _abi.lib()
+    L.sf_align_scan_params_default.argtypes = [C.POINTER(SfAlignScanParams)]
+    L.sf_align_scan_params_default.restype = None
+    L.sf_align_scan_params_default(C.byref(s))
+    for k, v in over.items():
+        if k not in ("group_size", "top_frames"):
+            raise AttributeError("sf_align_scan_params has no field %r" % k)
+        setattr(s, k, int(v))
+    return s
+
+
+def align_scan_plan(poses, params=None, scan=None, members_capacity=None, groups_capacity=None, top_capacity=None):
+    """sf_align_scan_plan (host only): the groups and the top of K keyframe poses -> dict(members int32 [M], group_first int32 [G + 1], group_level
+    int32 [G], top int32 [T], levels, counts (M, G, T) as the rule gives them; the arrays stop at the capacities, which default to what the rule can give)."""
+    a = params if params is not None else default_align_params()
+    sp = scan if scan is not None else default_align_scan_params()
+    poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+    K = len(poses)
+    mc = 2 * K + 16 if members_capacity is None else int(members_capacity)
+    gc = K + 1 if groups_capacity is None else int(groups_capacity)
+    tc = K if top_capacity is None else int(top_capacity)
+    members, first, level, top = np.zeros(max(mc, 1), np.int32), np.zeros(gc + 1, np.int32), np.zeros(max(gc, 1), np.int32), np.zeros(max(tc, 1), np.int32)
+    nm, ng, nt, levels = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int32(0)
+    L = _abi.lib()
+    L.sf_align_scan_plan.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(SfAlignParams), C.POINTER(SfAlignScanParams), C.c_void_p, C.c_uint64, C.c_void_p,
+                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_int32)]
+    check(L.sf_align_scan_plan(_ptr(poses), K, C.byref(a), C.byref(sp), _ptr(members), mc, _ptr(first), _ptr(level), gc, _ptr(top), tc, C.byref(nm), C.byref(ng),
+                               C.byref(nt), C.byref(levels)))
+    g = min(ng.value, gc)
+    return dict(members=members[:min(nm.value, mc)].copy(), group_first=first[:g + 1].copy(), group_level=level[:g].copy(), top=top[:min(nt.value, tc)].copy(),
+                levels=int(levels.value), counts=(int(nm.value), int(ng.value), int(nt.value)))
+
+
 def align_keyframes(poses, every):
     """Every `every`-th of the frames with a finite pose (rows 0..2), in frame order, starting with the first -> uint64 frame indices."""
     poses = np.asarray(poses, dtype=np.float32).reshape(-1, 16)
@@ -231,12 +283,15 @@ def align_keyframes(poses, every):
 ALIGN_COLOUR_WEIGHT = 0.1   # the working weight of the colour term (DESIGN.md 4f has the sweep); sf_align_params_default keeps 0, the term off
 
 
-def align_and_reintegrate(fuser, sensor_data, integrated, every=10, params=None, reint_params=None, colour=False, with_colour=False, colour_weight=None):
+def align_and_reintegrate(fuser, sensor_data, integrated, every=10, params=None, reint_params=None, colour=False, with_colour=False, colour_weight=None,
+                          group=None, top=None):
     """The correction loop: keyframes are every `every`-th frame with a finite integrated pose; their depth is decoded, the default pairs built, the
     keyframes aligned (Fuser.align), the correction spread over the trajectory, and the volume moved there (Fuser.update_trajectory, which updates a
     float32 C-contiguous `integrated` in place).  with_colour: the keyframes' colour pictures are decoded too and the aligner runs its colour term
      with `colour_weight` (None: the parameters' own when positive, else ALIGN_COLOUR_WEIGHT).  `colour` is the re-integration's:
-    the file's colour frames go back into the volume with the depth.  -> (target poses float32 [n,16], SfAlignResult, re-integration statistics)."""
+    the file's colour frames go back into the volume with the depth.  -> (target poses float32 [n,16], SfAlignResult, re-integration statistics).
+    group / top: sf_align_scan_params' group_size / top_frames.  With more keyframes than the top takes (256 unless `top` says otherwise), or when
+    either is given, the keyframes go through Fuser.align_scan and the second value is its SfAlignScanResult."""
     a = params if params is not None else default_align_params()
     if with_colour:
         b = SfAlignParams.from_buffer_copy(a)
@@ -247,13 +302,15 @@ def align_and_reintegrate(fuser, sensor_data, integrated, every=10, params=None,
     if len(keys) < 2:
         raise ValueError("alignment needs two keyframes, the trajectory has %d" % len(keys))
     depth = np.stack([np.ascontiguousarray(sensor_data.frames[int(k)].decompress_depth(), dtype=np.uint16).reshape(-1) for k in keys])
-    pairs, count = align_pairs(cur[keys.astype(np.int64)], a)
-    if count > len(pairs):
-        raise ValueError("the pair rule gives %d pairs, the solver takes %d" % (count, len(pairs)))
     rgb = None
     if with_colour:
         rgb = np.stack([np.ascontiguousarray(sensor_data.frames[int(k)].decompress_color(), dtype=np.uint8).reshape(-1) for k in keys])
-    new, res = fuser.align(depth, cur[keys.astype(np.int64)], pairs, a, rgb=rgb)
+    scan = default_align_scan_params(**{k: v for k, v in (("group_size", group), ("top_frames", top)) if v is not None})
+    pairs, count = align_pairs(cur[keys.astype(np.int64)], a)
+    if group is not None or top is not None or len(keys) > scan.top_frames or count > len(pairs):
+        new, res = fuser.align_scan(depth, cur[keys.astype(np.int64)], a, scan, rgb=rgb)
+    else:
+        new, res = fuser.align(depth, cur[keys.astype(np.int64)], pairs, a, rgb=rgb)
     target = align_spread(cur, keys, new)
     _, stats = fuser.update_trajectory(sensor_data, integrated, target, params=reint_params, colour=colour)
     return target, res, stats
@@ -692,6 +749,100 @@ class Fuser:
         check(L.sf_fuser_align_device(self._h, _ptr(d_depth), int(frame_stride_bytes), len(poses), _ptr(poses), _ptr(pairs), len(pairs), C.byref(a),
                                       _ptr(out), C.byref(res)))
         return out, res
+
+    def _staged(self, host):
+        """A host array's copy in HBM (sf_device_malloc / sf_device_upload) -> the device pointer; the caller frees it with sf_device_free."""
+        L = _abi.lib()
+        d = C.c_void_p()
+        check(L.sf_device_malloc(int(self.device), host.nbytes, C.byref(d)))
+        rc = L.sf_device_upload(d, _ptr(host), host.nbytes)
+        if rc != 0:
+            L.sf_device_free(d)
+            check(rc)
+        return d
+
+    def align_groups(self, depth, members, group_first, poses, params=None, rgb=None):
+        """sf_fuser_align_groups_device on host arrays (staged through sf_device_upload): K u16 keyframes [K, H*W], the groups' frames `members` [M] with
+        group_first [G + 1], one pose per member slot [M,16]; rgb: the K pictures (the colour term) -> (poses float32 [M,16], [SfAlignResult] * G)."""
+        a = params if params is not None else default_align_params()
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        px = self.params.depth_width * self.params.depth_height
+        if depth.size % px or depth.size == 0:
+            raise ValueError("depth holds %d pixels, frames of %dx%d expected" % (depth.size, self.params.depth_width, self.params.depth_height))
+        K = depth.size // px
+        members = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        group_first = np.ascontiguousarray(group_first, dtype=np.int32).reshape(-1)
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+        G = len(group_first) - 1
+        if G < 1 or group_first[G] != len(members) or len(poses) != len(members):
+            raise ValueError("group_first must end at the %d member slots, which have one pose each (%d given)" % (len(members), len(poses)))
+        out = np.empty_like(poses)
+        res = (SfAlignResult * G)()
+        L = _abi.lib()
+        L.sf_fuser_align_groups_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                   C.c_void_p, C.POINTER(SfAlignParams), C.c_void_p, C.c_void_p]
+        d_depth, d_rgb, rgb_stride = self._staged(depth), None, 0
+        try:
+            if rgb is not None:
+                rgb = self._align_rgb(rgb, K)
+                rgb_stride = rgb.size // K
+                d_rgb = self._staged(rgb)
+            check(L.sf_fuser_align_groups_device(self._h, d_depth, px * 2, d_rgb, rgb_stride, K, _ptr(members), _ptr(group_first), G, _ptr(poses), C.byref(a),
+                                                 _ptr(out), C.cast(res, C.c_void_p)))
+        finally:
+            L.sf_device_free(d_depth)
+            if d_rgb is not None:
+                L.sf_device_free(d_rgb)
+        return out, list(res)
+
+    def align_scan(self, depth, poses, params=None, scan=None, rgb=None):
+        """sf_fuser_align_scan: K u16 keyframes (host, [K, H*W]) of any number up to 4096 with camToWorld poses [K,16]: groups of consecutive keyframes
+        under the global solve.  rgb: the keyframes' pictures (the colour term) -> (poses float32 [K,16], SfAlignScanResult)."""
+        a = params if params is not None else default_align_params()
+        sp = scan if scan is not None else default_align_scan_params()
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if depth.size != len(poses) * self.params.depth_width * self.params.depth_height:
+            raise ValueError("depth holds %d pixels, %d frames of %dx%d expected" % (depth.size, len(poses), self.params.depth_width, self.params.depth_height))
+        if rgb is not None:
+            rgb = self._align_rgb(rgb, len(poses))
+        out = np.empty_like(poses)
+        res = SfAlignScanResult()
+        L = _abi.lib()
+        L.sf_fuser_align_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(SfAlignParams), C.POINTER(SfAlignScanParams),
+                                          C.c_void_p, C.POINTER(SfAlignScanResult)]
+        check(L.sf_fuser_align_scan(self._h, _ptr(depth), _ptr(rgb), len(poses), _ptr(poses), C.byref(a), C.byref(sp), _ptr(out), C.byref(res)))
+        return out, res
+
+    def align_scan_device(self, d_depth, frame_stride_bytes, poses, params=None, scan=None, d_rgb=None, rgb_stride_bytes=0):
+        """align_scan() for keyframes already in HBM, `frame_stride_bytes` apart (sf_fuser_align_scan_device)."""
+        a = params if params is not None else default_align_params()
+        sp = scan if scan is not None else default_align_scan_params()
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+        out = np.empty_like(poses)
+        res = SfAlignScanResult()
+        L = _abi.lib()
+        L.sf_fuser_align_scan_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(SfAlignParams),
+                                                 C.POINTER(SfAlignScanParams), C.c_void_p, C.POINTER(SfAlignScanResult)]
+        check(L.sf_fuser_align_scan_device(self._h, _ptr(d_depth), int(frame_stride_bytes), _ptr(d_rgb), int(rgb_stride_bytes), len(poses), _ptr(poses),
+                                           C.byref(a), C.byref(sp), _ptr(out), C.byref(res)))
+        return out, res
+
+    def align_groups_device(self, d_depth, frame_stride_bytes, K, members, group_first, poses, params=None, d_rgb=None, rgb_stride_bytes=0):
+        """align_groups() for keyframes already in HBM."""
+        a = params if params is not None else default_align_params()
+        members = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+        group_first = np.ascontiguousarray(group_first, dtype=np.int32).reshape(-1)
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+        G = len(group_first) - 1
+        out = np.empty_like(poses)
+        res = (SfAlignResult * max(G, 1))()
+        L = _abi.lib()
+        L.sf_fuser_align_groups_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                   C.c_void_p, C.POINTER(SfAlignParams), C.c_void_p, C.c_void_p]
+        check(L.sf_fuser_align_groups_device(self._h, _ptr(d_depth), int(frame_stride_bytes), _ptr(d_rgb), int(rgb_stride_bytes), int(K), _ptr(members),
+                                             _ptr(group_first), G, _ptr(poses), C.byref(a), _ptr(out), C.cast(res, C.c_void_p)))
+        return out, list(res)
 
     def align_system(self, depth, poses, pairs, params=None):
         """Test hook (scanfuse_internal.h sf_fuser_align_system): the P per-pair 29-value systems (float64 [P,29]) at the given poses."""
