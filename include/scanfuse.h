@@ -895,6 +895,65 @@ int sf_segment_file_ex(const char* mesh_path, float kThresh, int segMinVerts, co
 int sf_segment_file_gpu(const char* mesh_path, float kThresh, int segMinVerts, const char* out_json, uint64_t* num_segments,
                         uint64_t* counts4, char* out_path, uint64_t out_path_cap, int* obj_multi, int device);
 
+/* ------------------------------------------------------------------------------------------------
+ * Axis alignment: the `alignment.exe <scan dir>` call of the `clean` stage (Server/scan_processor.py:132-135).  Replaces
+ * Alignment::alignScan (Alignment/src/alignment.h:154-308) with upVectorFromViews :23-35, hasGravity :71-80, upVectorFromGravity :82-107,
+ * removeInvalidIMUFrames :128-152, and PlaneExtract (Alignment/src/planeExtract.h:75-154) with Cluster :13-71: up vector, floor plane, walls onto
+ * x and y, the scan into the positive octant with the floor at z = 0 -- one rigid transform applied to every .ply of the folder and to every pose
+ * of the .sens.  mLib and CGAL are not in the reference tree, so the arithmetic is this library's statement: DESIGN.md section 4i, operation by
+ * operation, with tests/axis_align_checker.c as its executable form.  alignScanFromAlnFile (:322-362) is unreachable from the reference's main and
+ * is not built.  scannet_amd/csrc/axis_align.cpp (the rule on the host, device = -1) and axis_align.hip (the same bits on HIP device >= 0).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sf_axis_align_params {
+  float merge_distance;             /* alignment.h:211 mergeCloseVertices: 0.0005                                           */
+  uint32_t min_piece_faces;         /* :212 removeIsolatedPieces, counted in FACES as sf_mesh_clean counts a piece: 5000     */
+  uint32_t gravity_min_records;     /* :71 hasGravity numThresh: gravity is used when MORE records than this carry it: 10   */
+  float cluster_normal_thresh;      /* planeExtract.h:88 normalThresh: 0.90                                                 */
+  float cluster_dist_thresh;        /* :88 distThresh: 0.05                                                                 */
+  uint32_t min_cluster_points;      /* :122 removeSmallClusters minSize: 500                                                */
+  float behind_dist;                /* alignment.h:238 removeNonBoundingClusters distThresh: 0.1                            */
+  uint32_t behind_max;              /* :238 numthresh: a cluster with MORE vertices behind it than this goes: 100           */
+  float floor_normal_z;             /* :245 a floor's representative normal has z above this: 0.8                           */
+  float floor_inlier_dist;          /* planeExtract.h:41 reComputeNormalAlignment: 0.05                                     */
+  int32_t reserved[6];
+} sf_axis_align_params;
+void sf_axis_align_params_default(sf_axis_align_params* p);
+typedef struct sf_axis_align_stats {
+  uint64_t vertices, faces;         /* the working mesh, after cleaning                                                     */
+  uint64_t clusters_founded;        /* planeExtract.h:88-104                                                                */
+  uint64_t clusters_after_small;    /* left by removeSmallClusters :122-131                                                 */
+  uint64_t clusters_kept;           /* left by removeNonBoundingClusters :134-143                                           */
+  uint64_t floor_points;            /* members of the floor cluster                                                         */
+  uint64_t floor_inliers;           /* of them within floor_inlier_dist of its plane                                        */
+  uint64_t frames_without_gravity;  /* frames whose closest IMU record carried no gravity (alignment.h:91-94)               */
+  uint64_t imu_records_dropped;     /* records with time stamp 0 (:128-152)                                                 */
+  int32_t up_source;                /* 0: the views, 1: gravity                                                             */
+  int32_t floor_found;              /* 0: "could not find a horizontal plane" (:255), the floor rotation is the identity    */
+  /* the device path's counters (0 on the host path): speculation batches, representatives of clusters changed earlier in a batch that were
+   * evaluated again, vertices for which the commit scanned the whole table again */
+  uint64_t gpu_batches, gpu_dirty_evaluations, gpu_fallback_rescans;
+  /* sf_axis_align_scan: 0 aligned; skipped: 1 no processed.txt, 2 valid = false, 3 aligned already (no force), 4 frame 0's pose is -inf */
+  int32_t outcome;
+  int32_t reverted;                 /* 1: frame 0's pose was not the identity and the previous alignment was undone first (:189-208) */
+  float transform[16];              /* the result, row-major                                                                 */
+  double seconds[6];                /* wall time: cleaning, normals, clustering, behind counts, covariance, everything else  */
+  double gpu_seconds_match, gpu_seconds_commit;   /* the clustering's two kernels summed over the batches (HIP events), only under sf_axis_align_tune("profile", 1) */
+} sf_axis_align_stats;
+/* The transform of a scan from its surface and its trajectory (neither is changed): `mesh` is the scan's `<base>.ply` as read; the working mesh
+ * (sf_mesh_clean with merge_distance / min_piece_faces; sf_mesh_clean_gpu on the device path) serves the estimate only.  params NULL: the defaults.
+ * device -1: the host path; >= 0: that HIP device (SF_ERR_DEVICE without one), the same 16 floats.  SF_ERR_INVALID_ARG for a .sens without
+ * frames or a parameter that is negative or not finite. */
+int sf_axis_align_estimate(const sf_mesh* mesh, const struct sf_sens* sens, const sf_axis_align_params* params, int device, float transform[16],
+                           sf_axis_align_stats* stats /*nullable*/);
+/* MeshDataf::applyTransform as alignment.h:205,298 uses it: every position <- the affine part of the row-major 4x4 (the
+ * host loop: what the tool and sf_axis_align_scan use for the folder's files). */
+int sf_mesh_apply_transform(sf_mesh* mesh, const float transform[16]);
+/* Alignment::alignScan(path, forceRealign) (:154-308) on the folder <dir> with base = its last path component: the gates on processed.txt
+ * (:156-170), the revert (:189-208), the estimate from <dir>/<base>.ply and <dir>/<base>.sens, then the transform applied to every *.ply of the
+ * folder (names ascending) and to the .sens, which is rewritten in place without its IMU records of time stamp 0, and processed.txt saved in
+ * ProcessedFile::saveToFile's five-line format (Alignment/src/processedFile.h:57-63) with aligned = true.  A skipped folder is SF_OK with
+ * stats->outcome set and nothing written.  Prints nothing: bin/alignment prints the reference's messages from *stats. */
+int sf_axis_align_scan(const char* dir, int force, const sf_axis_align_params* params /*nullable*/, int device, sf_axis_align_stats* stats /*nullable*/);
 
 
 #ifdef __cplusplus

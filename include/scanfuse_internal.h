@@ -170,6 +170,31 @@ int sf_filter2d_stage_to_label(int device, const uint8_t* instance, const uint16
  * the quotient scheme is not defined for an infinite dividend. */
 int sf_filter2d_selftest_gauss(int device, float sigma, const float* dist, const int32_t* dx, const int32_t* dy, uint64_t n, float* out_r, float* out_d);
 
+/* Stage hooks of the axis alignment (tests/test_alignment.py, tests/test_alignment_gpu.py): each call runs ONE stage of
+ * sf_axis_align_estimate on host arrays -- on the host for device = -1, else the stage's kernels alone on that GPU (scannet_amd/csrc/axis_align.hip) --
+ * and returns its output to the host.  xyz / normals: 3 floats per vertex; tris: 3 u32 per face, every index below num_vertices.
+ *   normals    vertex normals (k_aa_normals)
+ *   planes     the clustering (k_aa_match + k_aa_commit per batch), the stable sort by size and removeSmallClusters: index_out[v] = the cluster of vertex
+ *              v in creation order; *n_founded clusters in all; the *n_sorted <= capacity clusters of at least p->min_cluster_points points, largest
+ *              first: ids (creation order), table (10 floats each: representative normal, d, sumNormal, sumPoint), counts, and behind[] = the vertices
+ *              further than p->behind_dist behind each (k_aa_behind); counters = {batches, dirty re-evaluations, fallback rescans} (0 on the host)
+ *   behind     k_aa_behind alone on K representative planes (4 floats each)
+ *   cov        the blocked double sums of the members of `cluster` within inlier_dist of the plane rep4 (k_aa_cov): {n, x, y, z, xx, xy, xz, yy, yz, zz}
+ *   transform  positions through a row-major 4x4 with the bounding box {min x y z, max x y z} of the result (k_aa_transform); xyz_out may be NULL
+ *   tune       "batch": vertices per speculation batch, 64..1024 in steps of 64 (default 1024), for the calls of this process that follow;
+ *              "profile" 0 / 1: the device clustering brackets every launch with HIP events and fills gpu_seconds_match / _commit (default 0) */
+/*   up         the up vector of a trajectory (host only): up3, *source (0 views, 1 gravity), *no_gravity = frames whose closest record had none */
+int sf_axis_align_stage_up(const struct sf_sens* sens, uint32_t gravity_min_records, float up3[3], int32_t* source, uint64_t* no_gravity);
+int sf_axis_align_stage_normals(const float* xyz, uint64_t num_vertices, const uint32_t* tris, uint64_t num_faces, int device, float* normals_out);
+int sf_axis_align_stage_planes(const float* xyz, const float* normals, uint64_t num_vertices, const sf_axis_align_params* p, int device, uint32_t* index_out,
+                               uint64_t* n_founded, uint32_t* ids, float* table10, uint32_t* counts, uint32_t* behind, uint64_t capacity, uint64_t* n_sorted,
+                               uint64_t counters[3]);
+int sf_axis_align_stage_behind(const float* xyz, uint64_t num_vertices, const float* reps4, uint64_t K, float behind_dist, int device, uint32_t* counts_out);
+int sf_axis_align_stage_cov(const float* xyz, const uint32_t* index, uint64_t num_vertices, uint32_t cluster, const float rep4[4], float inlier_dist, int device,
+                            double sums10[10]);
+int sf_axis_align_stage_transform(const float* xyz, uint64_t num_vertices, const float m[16], int device, float* xyz_out, float bbox6[6]);
+int sf_axis_align_tune(const char* key, int value);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

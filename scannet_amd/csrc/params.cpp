@@ -126,6 +126,11 @@ int read_param_file(const char* path, std::map<std::string, std::vector<std::str
 
 }  // namespace
 
+namespace sf {
+// the reader for the other units that take an mLib ParameterFile (axis_align.cpp: processed.txt)
+int param_file_read(const char* path, std::map<std::string, std::vector<std::string>>& kv) { return read_param_file(path, kv); }
+}  // namespace sf
+
 SF_API int sf_params_load_file(const char* path, sf_params* p) {
   if (!path || !p) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   std::map<std::string, std::vector<std::string>> kv;
