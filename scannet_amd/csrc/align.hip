@@ -7,8 +7,8 @@
 // k_align_final sums a pair's partials in index order in double; one read-back.  The host drops thin pairs, finds the frames connected to the fixed
 // frame, assembles the sparse-by-blocks normal equations densely and solves them by Cholesky in double (align_solve.h states each entry's arithmetic
 // once, for this loop and for align_scan.hip's group solve on the device).  Every step is deterministic and
-// tests/align_checker.c restates it bit for bit.  sf_fuser_align_rgbd* run the same host loop over align_colour.hip's kernels, which add the dense
-// colour term's row to every correspondence and two sums to the pair's values (tests/align_colour_checker.c).
+// tests/align_checker.c restates it bit for bit.  sf_fuser_align_rgbd* run the same host loop over the kernels' colour instantiation, which adds the
+// dense colour term's row to every correspondence and two sums to the pair's values (align_colour.hip makes the intensity maps).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -17,6 +17,7 @@
 
 #include "align_internal.h"
 #include "common.h"
+#include "photo_math.h"
 #include "scanfuse_internal.h"
 
 namespace {
@@ -68,20 +69,25 @@ __global__ void __launch_bounds__(256) k_align_prep(const uint8_t* __restrict__ 
 }
 
 // one pair per blockIdx.y: association of the source frame's pixels with the target frame's maps and the pair's point-to-plane rows, reduced to one
-// 29-float partial per 256-pixel workgroup; partials[P][nb][32]
-__global__ void __launch_bounds__(256) k_align_assoc(const float4* __restrict__ vmap, const float4* __restrict__ nmap, const PairEntry* __restrict__ table,
-                                                     const Cam c, float dist_thres, float normal_thres, float* __restrict__ partials) {
-  __shared__ float red[4][TK_NSYS];
+// 29-float partial per 256-pixel workgroup; partials[P][nb][32].  COLOUR: 31 floats, with the colour row of the correspondence in the same lane;
+// photo == nullptr: no colour rows
+template <bool COLOUR>
+__global__ void __launch_bounds__(256) k_align_assoc(const float4* __restrict__ vmap, const float4* __restrict__ nmap, const float4* __restrict__ photo,
+                                                     const PairEntry* __restrict__ table, const Cam c, float dist_thres, float normal_thres, float weight,
+                                                     float colour_thres, float gradient_min, float* __restrict__ partials) {
+  constexpr int N = nsys_of<COLOUR>;
+  __shared__ float red[4][N];
   const PairEntry& e = table[blockIdx.y];
   const int i = blockIdx.x * 256 + threadIdx.x;
   const int npx = c.W * c.H;
-  float acc[TK_NSYS];
+  float acc[N];
 #pragma unroll
-  for (int k = 0; k < TK_NSYS; k++) acc[k] = 0.0f;
+  for (int k = 0; k < N; k++) acc[k] = 0.0f;
   if (e.active && i < npx) {
     const size_t so = (size_t)e.i * npx, to = (size_t)e.j * npx;
+    const float4 v4 = vmap[so + i];
     // the target is frame j's maps at the same level, moved to the world by T_j
-    correspond(c, e.Ti, e.M, vmap[so + i], nmap[so + i], dist_thres, normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
+    const bool hit = correspond(c, e.Ti, e.M, v4, nmap[so + i], dist_thres, normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
       const size_t t = to + (size_t)(uy * c.W + ux);
       const float4 w4 = vmap[t], m4 = nmap[t];
       if (!(w4.z > 0.0f && m4.x > -INFINITY)) return false;
@@ -89,14 +95,23 @@ __global__ void __launch_bounds__(256) k_align_assoc(const float4* __restrict__ 
       *nm = rot(e.Tj, make_float3(m4.x, m4.y, m4.z));
       return true;
     }, acc);
+    if constexpr (COLOUR) {
+      if (hit && photo) {
+        const float Is = photo[so + i].x;
+        const float3 v = make_float3(v4.x, v4.y, v4.z);
+        colour_row(photo + to, c, e.Tj, Is, xf(e.Ti, v), xf(e.M, v), weight, colour_thres, gradient_min, acc);
+      }
+    }
   }
   reduce256(acc, red, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TK_PSTRIDE);
 }
 
-// one wave per pair: lane k sums value k of the pair's partials in index order, in double; out[P][29]
+// one wave per pair: lane k sums value k of the pair's partials in index order, in double; out[P][29 or 31]
+template <bool COLOUR>
 __global__ void __launch_bounds__(64) k_align_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
+  constexpr int N = nsys_of<COLOUR>;
   const int k = threadIdx.x;
-  if (k < TK_NSYS) out[(size_t)blockIdx.x * TK_NSYS + k] = sum_partials(partials + (size_t)blockIdx.x * nb * TK_PSTRIDE, nb, k);
+  if (k < N) out[(size_t)blockIdx.x * N + k] = sum_partials(partials + (size_t)blockIdx.x * nb * TK_PSTRIDE, nb, k);
 }
 
 }  // namespace
@@ -205,14 +220,17 @@ int sf_align_prepare(sf_fuser* f, const AlignJob& j) {
 }
 
 // rows first .. first + count - 1 of w->d_table into the same rows of w->d_sys, queued on f->stream; count <= AL_MAX_PAIRS
+// j.nsys 31: the kernels' colour instantiation, with colour rows when the job has pictures (without: the depth term's bits, the colour sums 0)
 int sf_align_systems(sf_fuser* f, const AlignJob& j, const sf_align_params* a, uint64_t first, uint64_t count) {
   AlignWork* w = f->align;
-  if (j.nsys == AL_NSYS_RGBD) return sf_photo_systems(f, count, j.cam, a, j.d_rgb != nullptr, first);
+  const bool rgbd = j.nsys == TK_NSYS_RGBD;
   const int npx = j.cam.W * j.cam.H, nb = (npx + 255) / 256;
-  hipLaunchKernelGGL(k_align_assoc, dim3(nb, (unsigned)count), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
-                     w->d_table.as<const PairEntry>() + first, j.cam, a->dist_thres, a->normal_thres, w->partials.as<float>());
+  hipLaunchKernelGGL(rgbd ? k_align_assoc<true> : k_align_assoc<false>, dim3(nb, (unsigned)count), dim3(256), 0, f->stream, w->vmap.as<const float4>(),
+                     w->nmap.as<const float4>(), j.d_rgb ? w->photo.as<const float4>() : nullptr, w->d_table.as<const PairEntry>() + first, j.cam, a->dist_thres,
+                     a->normal_thres, a->colour_weight, a->colour_thres, a->colour_gradient_min, w->partials.as<float>());
   SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_align_final, dim3((unsigned)count), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>() + first * TK_NSYS);
+  hipLaunchKernelGGL(rgbd ? k_align_final<true> : k_align_final<false>, dim3((unsigned)count), dim3(64), 0, f->stream, w->partials.as<const float>(), nb,
+                     w->d_sys.as<double>() + first * j.nsys);
   SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }
@@ -312,7 +330,7 @@ int sf_align_solve(sf_fuser* f, const AlignJob& j, const float* poses_in, const 
       used++;
       r2 += s[27];
       corr += s[28];
-      if (j.nsys == AL_NSYS_RGBD) { cr2 += s[29]; ccorr += s[30]; }
+      if (j.nsys == TK_NSYS_RGBD) { cr2 += s[29]; ccorr += s[30]; }
     }
     r.pairs_used = used;
     r.correspondences = (int64_t)corr;
@@ -388,7 +406,7 @@ int sf_align_begin(sf_fuser* f, const void* depth, bool on_device, uint64_t stri
   j->dmin = own ? f->pk.dmin : a->depth_min;
   j->dmax = own ? f->pk.dmax : a->depth_max;
   SF_HIP_CHECK(hipSetDevice(f->device));
-  j->nsys = rgbd ? AL_NSYS_RGBD : TK_NSYS;
+  j->nsys = rgbd ? TK_NSYS_RGBD : TK_NSYS;
   if ((rc = ensure_work(f, K, P, j->cam.W * j->cam.H, !on_device, j->nsys, rgb && !on_device, rgb != nullptr, chunk)) != SF_OK) return rc;
   j->d_depth = depth;
   j->stride = stride;
@@ -527,13 +545,8 @@ SF_API int sf_align_spread(const float* poses, uint64_t n, const uint64_t* keyfr
     if (!finite12(To) || !finite12(Tn)) continue;
     usable[k] = 1;
     if (first < 0) first = (int64_t)k;
-    const double a00 = To[0], a01 = To[1], a02 = To[2], a10 = To[4], a11 = To[5], a12 = To[6], a20 = To[8], a21 = To[9], a22 = To[10];
-    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-    const double det = a00 * c00 + a01 * c01 + a02 * c02;
     double inv[9];
-    inv[0] = c00 / det; inv[1] = (a02 * a21 - a01 * a22) / det; inv[2] = (a01 * a12 - a02 * a11) / det;
-    inv[3] = c01 / det; inv[4] = (a00 * a22 - a02 * a20) / det; inv[5] = (a02 * a10 - a00 * a12) / det;
-    inv[6] = c02 / det; inv[7] = (a01 * a20 - a00 * a21) / det; inv[8] = (a00 * a11 - a01 * a10) / det;
+    inverse3(To, inv);
     double* d = &D[12 * k];
     for (int r = 0; r < 3; r++) {
       for (int c = 0; c < 3; c++) d[4 * r + c] = ((double)Tn[4 * r] * inv[c] + (double)Tn[4 * r + 1] * inv[3 + c]) + (double)Tn[4 * r + 2] * inv[6 + c];

@@ -2,10 +2,10 @@
 // s_denseColorThresh / s_denseColorGradientMin, zParametersBundlingScanNet.txt:24-25).
 //
 // Once per call: k_photo_prep turns every keyframe's RGB8 picture into one float4 {intensity, gx, gy, 0} per pixel of the solver's level, so that a
-// bilinear tap is one 16-byte load.  Per Gauss-Newton iteration k_photo_assoc is k_align_assoc with a second row: every depth correspondence
-// (tk::correspond, unchanged) whose source has an intensity and whose four target taps have an intensity and a gradient adds colour_weight x the
-// photometric row (p x a, a) to the pair's 27 sums, and its r_c^2 and 1 behind the depth term's two; k_photo_final sums the 31 values of a pair's
-// partials in index order in double.  The host loop is align.hip's.  tests/align_colour_checker.c restates every operation bit for bit.
+// bilinear tap is one 16-byte load.  Per Gauss-Newton iteration align.hip's k_align_assoc<true> is its depth kernel with a second row: every depth
+// correspondence (tk::correspond, unchanged) whose source has an intensity and whose four target taps have an intensity and a gradient adds
+// colour_weight x the photometric row (p x a, a) to the pair's 27 sums, and its r_c^2 and 1 behind the depth term's two; k_align_final<true> sums the
+// 31 values of a pair's partials in index order in double.  The host loop is align.hip's.  tests/align_checker.c restates every operation bit for bit.
 #include <hip/hip_runtime.h>
 
 #include "align_internal.h"
@@ -43,44 +43,6 @@ __global__ void __launch_bounds__(256) k_photo_prep(const uint8_t* __restrict__ 
   photo[(size_t)blockIdx.y * npx + i] = photo_texel(I, inner, xl, xr, yu, yd);
 }
 
-// one pair per blockIdx.y: k_align_assoc's association and depth row, and in the same lane the colour row of the correspondence; one 31-float partial
-// per 256-pixel workgroup, partials[P][nb][32].  photo == nullptr: no colour rows
-__global__ void __launch_bounds__(256) k_photo_assoc(const float4* __restrict__ vmap, const float4* __restrict__ nmap, const float4* __restrict__ photo,
-                                                     const AlignPair* __restrict__ table, const Cam c, float dist_thres, float normal_thres, float weight,
-                                                     float colour_thres, float gradient_min, float* __restrict__ partials) {
-  __shared__ float red[4][AL_NSYS_RGBD];
-  const AlignPair& e = table[blockIdx.y];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int npx = c.W * c.H;
-  float acc[AL_NSYS_RGBD];
-#pragma unroll
-  for (int k = 0; k < AL_NSYS_RGBD; k++) acc[k] = 0.0f;
-  if (e.active && i < npx) {
-    const size_t so = (size_t)e.i * npx, to = (size_t)e.j * npx;
-    const float4 v4 = vmap[so + i];
-    const bool hit = correspond(c, e.Ti, e.M, v4, nmap[so + i], dist_thres, normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
-      const size_t t = to + (size_t)(uy * c.W + ux);
-      const float4 w4 = vmap[t], m4 = nmap[t];
-      if (!(w4.z > 0.0f && m4.x > -INFINITY)) return false;
-      *q = xf(e.Tj, make_float3(w4.x, w4.y, w4.z));
-      *nm = rot(e.Tj, make_float3(m4.x, m4.y, m4.z));
-      return true;
-    }, acc);
-    if (hit && photo) {
-      const float Is = photo[so + i].x;
-      const float3 v = make_float3(v4.x, v4.y, v4.z);
-      colour_row(photo + to, c, e.Tj, Is, xf(e.Ti, v), xf(e.M, v), weight, colour_thres, gradient_min, acc);
-    }
-  }
-  reduce256(acc, red, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * TK_PSTRIDE);
-}
-
-// one wave per pair: lane k sums value k of the pair's partials in index order, in double; out[P][31]
-__global__ void __launch_bounds__(64) k_photo_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
-  const int k = threadIdx.x;
-  if (k < AL_NSYS_RGBD) out[(size_t)blockIdx.x * AL_NSYS_RGBD + k] = sum_partials(partials + (size_t)blockIdx.x * nb * TK_PSTRIDE, nb, k);
-}
-
 }  // namespace
 
 int sf_photo_prepare(sf_fuser* f, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K, int level, const Cam& cam) {
@@ -96,18 +58,6 @@ int sf_photo_prepare(sf_fuser* f, const void* d_rgb, uint64_t rgb_stride_bytes, 
     default: PH_PREP(3); break;
   }
 #undef PH_PREP
-  SF_HIP_CHECK(hipGetLastError());
-  return SF_OK;
-}
-
-int sf_photo_systems(sf_fuser* f, uint64_t P, const Cam& cam, const sf_align_params* a, bool with_photo, uint64_t first) {
-  AlignWork* w = f->align;
-  const int npx = cam.W * cam.H, nb = (npx + 255) / 256;
-  hipLaunchKernelGGL(k_photo_assoc, dim3(nb, (unsigned)P), dim3(256), 0, f->stream, w->vmap.as<const float4>(), w->nmap.as<const float4>(),
-                     with_photo ? w->photo.as<const float4>() : nullptr, w->d_table.as<const AlignPair>() + first, cam, a->dist_thres, a->normal_thres,
-                     a->colour_weight, a->colour_thres, a->colour_gradient_min, w->partials.as<float>());
-  SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_photo_final, dim3((unsigned)P), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>() + first * AL_NSYS_RGBD);
   SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }

@@ -1,13 +1,11 @@
 // align_internal.h -- what the two files of the global alignment share: align.hip (the depth term's kernels and the host's Gauss-Newton loop) and
-// align_colour.hip (the colour term's kernels): the pair table's row, the fuser's alignment work set and the colour side's two launchers
+// align_colour.hip (the colour term's kernels): the pair table's row, the fuser's alignment work set and the colour side's launcher
 #pragma once
 #include "fuser_internal.h"
 #include "hip_util.h"
 #include "scanfuse.h"
 #include "align_solve.h"
 #include "track_math.h"
-
-constexpr int AL_NSYS_RGBD = 31;   // the 29 values of track_math.h, then the colour term's sum r_c^2 and count
 
 struct AlignPair {   // one row of the device table; read through the scalar unit (the index is blockIdx.y)
   int32_t i, j, active, pad;
@@ -56,8 +54,5 @@ void sf_align_pair_row(AlignPair* e, int32_t fi, int32_t fj, bool active, const 
 int sf_align_systems(sf_fuser* f, const AlignJob& j, const sf_align_params* a, uint64_t first, uint64_t count);
 int sf_align_solve(sf_fuser* f, const AlignJob& j, const float* poses_in, const sf_align_params* a, float* poses_out, sf_align_result* res);
 
-// align_colour.hip, both queued on f->stream.  The intensity and gradient maps of K pictures at `level` into w->photo:
+// align_colour.hip, queued on f->stream: the intensity and gradient maps of K pictures at `level` into w->photo
 int sf_photo_prepare(sf_fuser* f, const void* d_rgb, uint64_t rgb_stride_bytes, uint64_t K, int level, const tk::Cam& cam);
-// the 31-value systems of rows first .. first + P - 1 of w->d_table, from the maps, into the same rows of w->d_sys; with_photo false: no colour rows
-// (the depth term's bits, the colour sums 0)
-int sf_photo_systems(sf_fuser* f, uint64_t P, const tk::Cam& cam, const sf_align_params* a, bool with_photo, uint64_t first = 0);

@@ -402,7 +402,7 @@ SF_API int sf_align_group_solve_stage(int device, uint64_t G, const int32_t* gro
                                       int32_t* used_out, uint32_t* conn_out, double* sums_out) {
   if (!group_first || !pair_first || !valid_masks || !xi_out || !status_out || !used_out || !conn_out || !sums_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   if (G < 1 || G > AS_MAX_GROUPS) return sf::fail(SF_ERR_INVALID_ARG, "%llu groups (1..%llu)", (unsigned long long)G, (unsigned long long)AS_MAX_GROUPS);
-  if (nsys != TK_NSYS && nsys != AL_NSYS_RGBD) return sf::fail(SF_ERR_INVALID_ARG, "%d values per pair (29 or 31)", nsys);
+  if (nsys != TK_NSYS && nsys != TK_NSYS_RGBD) return sf::fail(SF_ERR_INVALID_ARG, "%d values per pair (29 or 31)", nsys);
   if (group_first[0] != 0 || pair_first[0] != 0) return sf::fail(SF_ERR_INVALID_ARG, "group_first[0] and pair_first[0] must be 0");
   for (uint64_t g = 0; g < G; g++) {
     const int64_t n = (int64_t)group_first[g + 1] - group_first[g], np = (int64_t)pair_first[g + 1] - pair_first[g];

@@ -12,8 +12,6 @@
 
 namespace tk {
 
-constexpr int TK_NSYS_RGBD = 31;   // the 29 values of track_math.h, then the colour term's sum r_c^2 and count
-
 // intensity in [0, 1] of an RGB8 pixel
 __device__ inline float intensity_rgb8(const uint8_t* __restrict__ q) {
   return ((0.299f * (float)q[0] + 0.587f * (float)q[1]) + 0.114f * (float)q[2]) / 255.0f;

@@ -6,8 +6,8 @@
 // Per iteration: k_track_assoc pairs every input pixel with the model pixel it projects to, builds its point-to-plane row and reduces the 29 values
 // of the normal equations of its 256-pixel workgroup (xor butterfly in the wave, (w0 + w1) + (w2 + w3) across waves: no atomics); k_track_final
 // sums the partials in index order in double.  The host solves the 6x6 system in double and updates the pose.  Every step is deterministic and
-// tests/track_checker.c restates it bit for bit.  sf_fuser_track_rgbd* run the same host loop over track_colour.hip's kernels, which add the dense
-// colour term's row to every correspondence and two sums to the system's values (tests/track_colour_checker.c).
+// tests/track_checker.c restates it bit for bit.  sf_fuser_track_rgbd* run the same host loop over the kernels' colour instantiation, which adds the
+// dense colour term's row to every correspondence and two sums to the system's values (track_colour.hip makes the intensity maps).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,9 +27,10 @@ using namespace tk;   // track_math.h: the rules shared with align.hip
 
 struct AssocArgs {
   Cam c;
-  int W0, shift;   // the model image (level 0) and the level's subsampling of it
-  Rows T, M;       // the estimate (world), the estimate in the reference camera (T_ref^-1 T)
+  int W0, shift;     // the model image (level 0) and the level's subsampling of it (the depth target)
+  Rows T, M, Rref;   // the estimate (world), the estimate in the reference camera (T_ref^-1 T), the reference pose
   float dist_thres, normal_thres;
+  float weight, colour_thres, gradient_min;   // the colour term's
 };
 
 // u16 frame at the input size -> metres at the integration size: k_prepass's rule (nearest resample, then the depth range)
@@ -78,18 +79,23 @@ __global__ void __launch_bounds__(256) k_track_model(const float* __restrict__ m
   mnorm[i] = n;
 }
 
-// one level's association and point-to-plane rows, reduced to one 29-float partial per 256-pixel workgroup
+// one level's association and point-to-plane rows, reduced to one 29-float partial per 256-pixel workgroup.  COLOUR: 31 floats, with the colour row of
+// the correspondence against the model's map of the level in the same lane; photo_in == nullptr: no colour rows
+template <bool COLOUR>
 __global__ void __launch_bounds__(256) k_track_assoc(const float4* __restrict__ vmap, const float4* __restrict__ nmap, const float4* __restrict__ mq,
-                                                     const float4* __restrict__ mnorm, const AssocArgs A, float* __restrict__ partials,
+                                                     const float4* __restrict__ mnorm, const float4* __restrict__ photo_in,
+                                                     const float4* __restrict__ photo_model, const AssocArgs A, float* __restrict__ partials,
                                                      uint8_t* __restrict__ mask) {
-  __shared__ float red[4][TK_NSYS];
+  constexpr int N = nsys_of<COLOUR>;
+  __shared__ float red[4][N];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  float acc[TK_NSYS];
+  float acc[N];
 #pragma unroll
-  for (int k = 0; k < TK_NSYS; k++) acc[k] = 0.0f;
+  for (int k = 0; k < N; k++) acc[k] = 0.0f;
   if (i < A.c.W * A.c.H) {
-    // the target is the model image (level 0) subsampled; its normal is read only where its vertex is valid
-    const bool ok = correspond(A.c, A.T, A.M, vmap[i], nmap[i], A.dist_thres, A.normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
+    const float4 v4 = vmap[i];
+    // the depth target is the model image (level 0) subsampled; its normal is read only where its vertex is valid
+    const bool ok = correspond(A.c, A.T, A.M, v4, nmap[i], A.dist_thres, A.normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
       const size_t j = (size_t)(uy << A.shift) * A.W0 + (ux << A.shift);
       const float4 q4 = mq[j];
       if (!(q4.x > -INFINITY)) return false;
@@ -98,15 +104,23 @@ __global__ void __launch_bounds__(256) k_track_assoc(const float4* __restrict__ 
       *nm = make_float3(m4.x, m4.y, m4.z);
       return true;
     }, acc);
+    if constexpr (COLOUR) {
+      if (ok && photo_in) {
+        const float Is = photo_in[i].x;
+        const float3 v = make_float3(v4.x, v4.y, v4.z);
+        colour_row(photo_model, A.c, A.Rref, Is, xf(A.T, v), xf(A.M, v), A.weight, A.colour_thres, A.gradient_min, acc);
+      }
+    }
     if (mask) mask[i] = ok ? 1 : 0;
   }
   reduce256(acc, red, partials + (size_t)blockIdx.x * TK_PSTRIDE);
 }
 
 // the workgroups' partials summed in index order, in double: lane k sums value k
+template <bool COLOUR>
 __global__ void __launch_bounds__(64) k_track_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
   const int k = threadIdx.x;
-  if (k < TK_NSYS) out[k] = sum_partials(partials, nb, k);
+  if (k < nsys_of<COLOUR>) out[k] = sum_partials(partials, nb, k);
 }
 
 }  // namespace
@@ -210,35 +224,29 @@ int prepare(sf_fuser* f, const void* d_depth, const float* Tref, const sf_track_
 }
 
 // one level's system at the estimate T (double, rows 0..2 used), summed into w->h_sys; the mask optionally into w->d_mask
-// rgbd: the 31 values of track_colour.hip's kernels, with colour rows when photo
+// rgbd: the 31 values of the kernels' colour instantiation, with colour rows when photo
 int system_at(sf_fuser* f, int l, const Cam* cams, const double* T, const double* Tref, const sf_track_params* t, bool want_mask, bool rgbd = false,
               bool photo = false) {
   TrackWork* w = f->track;
-  if (rgbd) {
-    Rows Tf, M, Rf;
-    for (int i = 0; i < 12; i++) { Tf.T[i] = (float)T[i]; Rf.T[i] = (float)Tref[i]; }
-    compose_ref(Tref, T, M.T);
-    const int rc = sf_track_photo_system(f, l, cams, Tf, M, Rf, t, photo, want_mask ? w->d_mask.as<uint8_t>() : nullptr);
-    if (rc != SF_OK) return rc;
-    SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, TK_NSYS_RGBD * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    SF_HIP_CHECK(hipStreamSynchronize(f->stream));
-    return SF_OK;
-  }
   AssocArgs A;
   A.c = cams[l];
   A.W0 = cams[0].W;
   A.shift = l;
-  for (int i = 0; i < 12; i++) A.T.T[i] = (float)T[i];
+  for (int i = 0; i < 12; i++) { A.T.T[i] = (float)T[i]; A.Rref.T[i] = (float)Tref[i]; }
   compose_ref(Tref, T, A.M.T);
   A.dist_thres = t->dist_thres[l];
   A.normal_thres = t->normal_thres[l];
+  A.weight = t->colour_weight;
+  A.colour_thres = t->colour_thres;
+  A.gradient_min = t->colour_gradient_min;
   const int n = cams[l].W * cams[l].H, nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_track_assoc, dim3(nb), dim3(256), 0, f->stream, w->vmap[l].as<const float4>(), w->nmap[l].as<const float4>(), w->mq.as<const float4>(),
-                     w->mn.as<const float4>(), A, w->partials.as<float>(), want_mask ? w->d_mask.as<uint8_t>() : nullptr);
+  hipLaunchKernelGGL(rgbd ? k_track_assoc<true> : k_track_assoc<false>, dim3(nb), dim3(256), 0, f->stream, w->vmap[l].as<const float4>(),
+                     w->nmap[l].as<const float4>(), w->mq.as<const float4>(), w->mn.as<const float4>(), photo ? w->photo[0][l].as<const float4>() : nullptr,
+                     photo ? w->photo[1][l].as<const float4>() : nullptr, A, w->partials.as<float>(), want_mask ? w->d_mask.as<uint8_t>() : nullptr);
   SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_track_final, dim3(1), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
+  hipLaunchKernelGGL(rgbd ? k_track_final<true> : k_track_final<false>, dim3(1), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
   SF_HIP_CHECK(hipGetLastError());
-  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, TK_NSYS * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(w->h_sys.p, w->d_sys.p, (rgbd ? TK_NSYS_RGBD : TK_NSYS) * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   SF_HIP_CHECK(hipStreamSynchronize(f->stream));
   return SF_OK;
 }
@@ -340,23 +348,33 @@ SF_API int sf_fuser_track(sf_fuser* f, const uint16_t* depth, const float guess[
   return track(f, depth, false, guess, ref, t, pose_out, result);
 }
 
-SF_API int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, const float T[16], const float T_ref[16], const sf_track_params* t,
-                                 double sys[29], uint8_t* mask) {
+namespace {
+
+// sf_fuser_track_system and sf_fuser_track_rgbd_system (rgbd; its picture rgb may be NULL): one level's 29 or 31 values and optionally its mask
+int system_export(sf_fuser* f, const uint16_t* depth, bool rgbd, const uint8_t* rgb, int level, const float* T, const float* T_ref, const sf_track_params* t,
+                  double* sys, uint8_t* mask) {
   Cam cams[TK_MAX_LEVELS];
   int rc = begin(f, t, depth && T && T_ref && sys, [&] {
     if (level < 0 || level >= t->levels) return sf::fail(SF_ERR_INVALID_ARG, "level %d of %d", level, t->levels);
     if (!finite12(T) || !finite12(T_ref)) return sf::fail(SF_ERR_INVALID_ARG, "non-finite pose");
     return (int)SF_OK;
-  }, cams, depth);
+  }, cams, depth, rgbd, rgb, true);
   if (rc != SF_OK) return rc;
   TrackWork* w = f->track;
-  if ((rc = prepare(f, w->d_in.p, T_ref, t, cams)) != SF_OK) return rc;
+  if ((rc = prepare(f, w->d_in.p, T_ref, t, cams, rgb ? w->d_rgb.p : nullptr)) != SF_OK) return rc;
   double Td[12], Rd[12];
   for (int i = 0; i < 12; i++) { Td[i] = T[i]; Rd[i] = T_ref[i]; }
-  if ((rc = system_at(f, level, cams, Td, Rd, t, mask != nullptr)) != SF_OK) return rc;
-  for (int k = 0; k < TK_NSYS; k++) sys[k] = w->h_sys.as<const double>()[k];
+  if ((rc = system_at(f, level, cams, Td, Rd, t, mask != nullptr, rgbd, rgb != nullptr)) != SF_OK) return rc;
+  for (int k = 0; k < (rgbd ? TK_NSYS_RGBD : TK_NSYS); k++) sys[k] = w->h_sys.as<const double>()[k];
   if (mask) SF_HIP_CHECK(hipMemcpy(mask, w->d_mask.p, (size_t)cams[level].W * cams[level].H, hipMemcpyDeviceToHost));
   return SF_OK;
+}
+
+}  // namespace
+
+SF_API int sf_fuser_track_system(sf_fuser* f, const uint16_t* depth, int level, const float T[16], const float T_ref[16], const sf_track_params* t,
+                                 double sys[29], uint8_t* mask) {
+  return system_export(f, depth, false, nullptr, level, T, T_ref, t, sys, mask);
 }
 
 SF_API int sf_fuser_track_rgbd_device(sf_fuser* f, const void* d_depth, const void* d_rgb, const float guess[16], const float ref[16], const sf_track_params* t,
@@ -371,19 +389,5 @@ SF_API int sf_fuser_track_rgbd(sf_fuser* f, const uint16_t* depth, const uint8_t
 
 SF_API int sf_fuser_track_rgbd_system(sf_fuser* f, const uint16_t* depth, const uint8_t* rgb, int level, const float T[16], const float T_ref[16],
                                       const sf_track_params* t, double sys[31], uint8_t* mask) {
-  Cam cams[TK_MAX_LEVELS];
-  int rc = begin(f, t, depth && T && T_ref && sys, [&] {
-    if (level < 0 || level >= t->levels) return sf::fail(SF_ERR_INVALID_ARG, "level %d of %d", level, t->levels);
-    if (!finite12(T) || !finite12(T_ref)) return sf::fail(SF_ERR_INVALID_ARG, "non-finite pose");
-    return (int)SF_OK;
-  }, cams, depth, true, rgb, true);
-  if (rc != SF_OK) return rc;
-  TrackWork* w = f->track;
-  if ((rc = prepare(f, w->d_in.p, T_ref, t, cams, rgb ? w->d_rgb.p : nullptr)) != SF_OK) return rc;
-  double Td[12], Rd[12];
-  for (int i = 0; i < 12; i++) { Td[i] = T[i]; Rd[i] = T_ref[i]; }
-  if ((rc = system_at(f, level, cams, Td, Rd, t, mask != nullptr, true, rgb != nullptr)) != SF_OK) return rc;
-  for (int k = 0; k < TK_NSYS_RGBD; k++) sys[k] = w->h_sys.as<const double>()[k];
-  if (mask) SF_HIP_CHECK(hipMemcpy(mask, w->d_mask.p, (size_t)cams[level].W * cams[level].H, hipMemcpyDeviceToHost));
-  return SF_OK;
+  return system_export(f, depth, true, rgb, level, T, T_ref, t, sys, mask);
 }

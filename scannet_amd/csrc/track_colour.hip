@@ -4,10 +4,10 @@
 // Once per frame, level by level: the frame's RGB8 picture and the model's rendered colour become an intensity image (k_track_photo_in0,
 // k_track_photo_model0: the model has no intensity where it has no depth or no normal), every coarser level is the 2x2 mean of the one below
 // (k_track_photo_down), and each level gets one float4 {intensity, gx, gy, 0} per pixel (k_track_photo_grad), so that a bilinear tap is one 16-byte
-// load.  Per iteration k_track_photo_assoc is k_track_assoc with a second row: every depth correspondence (tk::correspond, unchanged; its target stays
-// the subsampled level-0 model) whose pixel has an intensity and whose four taps in the model's map of the level have an intensity and a gradient adds
-// colour_weight x the row (p x a, a) to the 27 sums, and its r_c^2 and 1 behind the depth term's two; k_track_photo_final sums the 31 values of the
-// partials in index order in double.  The host loop is track.hip's.  tests/track_colour_checker.c restates every operation bit for bit.
+// load.  Per iteration track.hip's k_track_assoc<true> is its depth kernel with a second row: every depth correspondence (tk::correspond, unchanged; its
+// target stays the subsampled level-0 model) whose pixel has an intensity and whose four taps in the model's map of the level have an intensity and a
+// gradient adds colour_weight x the row (p x a, a) to the 27 sums, and its r_c^2 and 1 behind the depth term's two; k_track_final<true> sums the 31
+// values of the partials in index order in double.  The host loop is track.hip's.  tests/track_checker.c restates every operation bit for bit.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -17,14 +17,6 @@
 namespace {
 
 using namespace tk;
-
-struct PhotoArgs {
-  Cam c;
-  int W0, shift;       // the model image (level 0) and the level's subsampling of it (the depth target)
-  Rows T, M, Rref;     // the estimate (world), the estimate in the reference camera (T_ref^-1 T), the reference pose
-  float dist_thres, normal_thres;
-  float weight, colour_thres, gradient_min;
-};
 
 // level 0 of the frame: the intensity of the colour pixel under every integration pixel's ray (photo_math.h intensity0_at)
 __global__ void __launch_bounds__(256) k_track_photo_in0(const uint8_t* __restrict__ rgb, const ParamsK P, float* __restrict__ I0) {
@@ -74,45 +66,6 @@ __global__ void __launch_bounds__(256) k_track_photo_grad(const float* __restric
   out[i] = photo_texel(I[i], inner, xl, xr, yu, yd);
 }
 
-// k_track_assoc's association and depth row, and in the same lane the colour row of the correspondence against the model's map of the level; one
-// 31-float partial per 256-pixel workgroup.  photo_in == nullptr: no colour rows
-__global__ void __launch_bounds__(256) k_track_photo_assoc(const float4* __restrict__ vmap, const float4* __restrict__ nmap, const float4* __restrict__ mq,
-                                                           const float4* __restrict__ mnorm, const float4* __restrict__ photo_in,
-                                                           const float4* __restrict__ photo_model, const PhotoArgs A, float* __restrict__ partials,
-                                                           uint8_t* __restrict__ mask) {
-  __shared__ float red[4][TK_NSYS_RGBD];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  float acc[TK_NSYS_RGBD];
-#pragma unroll
-  for (int k = 0; k < TK_NSYS_RGBD; k++) acc[k] = 0.0f;
-  if (i < A.c.W * A.c.H) {
-    const float4 v4 = vmap[i];
-    // the depth target is the model image (level 0) subsampled; its normal is read only where its vertex is valid
-    const bool ok = correspond(A.c, A.T, A.M, v4, nmap[i], A.dist_thres, A.normal_thres, [&](int ux, int uy, float3* q, float3* nm) {
-      const size_t j = (size_t)(uy << A.shift) * A.W0 + (ux << A.shift);
-      const float4 q4 = mq[j];
-      if (!(q4.x > -INFINITY)) return false;
-      const float4 m4 = mnorm[j];
-      *q = make_float3(q4.x, q4.y, q4.z);
-      *nm = make_float3(m4.x, m4.y, m4.z);
-      return true;
-    }, acc);
-    if (ok && photo_in) {
-      const float Is = photo_in[i].x;
-      const float3 v = make_float3(v4.x, v4.y, v4.z);
-      colour_row(photo_model, A.c, A.Rref, Is, xf(A.T, v), xf(A.M, v), A.weight, A.colour_thres, A.gradient_min, acc);
-    }
-    if (mask) mask[i] = ok ? 1 : 0;
-  }
-  reduce256(acc, red, partials + (size_t)blockIdx.x * TK_PSTRIDE);
-}
-
-// the workgroups' partials summed in index order, in double: lane k sums value k
-__global__ void __launch_bounds__(64) k_track_photo_final(const float* __restrict__ partials, int nb, double* __restrict__ out) {
-  const int k = threadIdx.x;
-  if (k < TK_NSYS_RGBD) out[k] = sum_partials(partials, nb, k);
-}
-
 }  // namespace
 
 int sf_track_photo_reserve(sf_fuser* f, const Cam* cams, int levels) {
@@ -152,30 +105,5 @@ int sf_track_photo_prepare(sf_fuser* f, const void* d_rgb, const Cam* cams, int 
                        cams[l].W, cams[l].H, w->photo[0][l].as<float4>(), w->photo[1][l].as<float4>());
     SF_HIP_CHECK(hipGetLastError());
   }
-  return SF_OK;
-}
-
-int sf_track_photo_system(sf_fuser* f, int l, const Cam* cams, const Rows& T, const Rows& M, const Rows& Tref, const sf_track_params* t, bool with_photo,
-                          uint8_t* d_mask) {
-  TrackWork* w = f->track;
-  PhotoArgs A;
-  A.c = cams[l];
-  A.W0 = cams[0].W;
-  A.shift = l;
-  A.T = T;
-  A.M = M;
-  A.Rref = Tref;
-  A.dist_thres = t->dist_thres[l];
-  A.normal_thres = t->normal_thres[l];
-  A.weight = t->colour_weight;
-  A.colour_thres = t->colour_thres;
-  A.gradient_min = t->colour_gradient_min;
-  const int n = cams[l].W * cams[l].H, nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_track_photo_assoc, dim3(nb), dim3(256), 0, f->stream, w->vmap[l].as<const float4>(), w->nmap[l].as<const float4>(), w->mq.as<const float4>(),
-                     w->mn.as<const float4>(), with_photo ? w->photo[0][l].as<const float4>() : nullptr, with_photo ? w->photo[1][l].as<const float4>() : nullptr, A,
-                     w->partials.as<float>(), d_mask);
-  SF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_track_photo_final, dim3(1), dim3(64), 0, f->stream, w->partials.as<const float>(), nb, w->d_sys.as<double>());
-  SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }

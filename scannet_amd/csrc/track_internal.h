@@ -33,6 +33,3 @@ int sf_track_photo_reserve(sf_fuser* f, const tk::Cam* cams, int levels);
 // queued on f->stream behind the model's ray cast (depth, normals and colour in f->track): the {I, gx, gy, 0} maps of every level of the picture
 // d_rgb and of the model
 int sf_track_photo_prepare(sf_fuser* f, const void* d_rgb, const tk::Cam* cams, int levels);
-// one level's 31-value system into f->track->d_sys, queued on f->stream; with_photo false: no colour rows (the depth term's bits, the colour sums 0)
-int sf_track_photo_system(sf_fuser* f, int l, const tk::Cam* cams, const tk::Rows& T, const tk::Rows& M, const tk::Rows& Tref, const sf_track_params* t,
-                          bool with_photo, uint8_t* d_mask);

@@ -16,6 +16,9 @@ namespace tk {
 
 constexpr int TK_MAX_LEVELS = 4;
 constexpr int TK_NSYS = 29;         // 21 of J^T J, 6 of J^T r, sum r^2, count
+constexpr int TK_NSYS_RGBD = 31;    // the 29, then the colour term's sum r_c^2 and count (photo_math.h)
+template <bool COLOUR>
+constexpr int nsys_of = COLOUR ? TK_NSYS_RGBD : TK_NSYS;   // the values of a solver kernel's instantiation
 constexpr int TK_PSTRIDE = 32;      // floats per workgroup partial
 constexpr float TK_DOWN_THRES = 0.03f;   // 2x2 reduction: depths within this many metres of the reference pixel's are averaged
 constexpr double TK_PIVOT_REL = 1e-5;     // a Cholesky pivot at or below this share of its diagonal entry counts as non-positive
@@ -204,15 +207,21 @@ inline bool solve_spd(const double* A, const double* b, int N, double* x) {
   return true;
 }
 
-// T_ref^-1 (cofactors over the determinant, as the oracle's frame set-up) composed with T, in double: rounded to float once
-inline void compose_ref(const double* Tref, const double* T, float* M) {
-  const double a00 = Tref[0], a01 = Tref[1], a02 = Tref[2], a10 = Tref[4], a11 = Tref[5], a12 = Tref[6], a20 = Tref[8], a21 = Tref[9], a22 = Tref[10];
+// the inverse of the 3x3 block of a pose's rows (doubles or floats, four to a row): cofactors over the determinant, as the oracle's frame set-up
+template <typename F>
+inline void inverse3(const F* A, double* inv) {
+  const double a00 = A[0], a01 = A[1], a02 = A[2], a10 = A[4], a11 = A[5], a12 = A[6], a20 = A[8], a21 = A[9], a22 = A[10];
   const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
   const double det = a00 * c00 + a01 * c01 + a02 * c02;
-  double inv[9];
   inv[0] = c00 / det; inv[1] = (a02 * a21 - a01 * a22) / det; inv[2] = (a01 * a12 - a02 * a11) / det;
   inv[3] = c01 / det; inv[4] = (a00 * a22 - a02 * a20) / det; inv[5] = (a02 * a10 - a00 * a12) / det;
   inv[6] = c02 / det; inv[7] = (a01 * a20 - a00 * a21) / det; inv[8] = (a00 * a11 - a01 * a10) / det;
+}
+
+// T_ref^-1 (inverse3) composed with T, in double: rounded to float once
+inline void compose_ref(const double* Tref, const double* T, float* M) {
+  double inv[9];
+  inverse3(Tref, inv);
   const double dt[3] = {T[3] - Tref[3], T[7] - Tref[7], T[11] - Tref[11]};
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) M[4 * r + c] = (float)((inv[3 * r] * T[c] + inv[3 * r + 1] * T[4 + c]) + inv[3 * r + 2] * T[8 + c]);

@@ -380,13 +380,17 @@ def test_align_kernels_live_in_registers():
         pytest.skip("no llvm-readelf")
     kr = ss.kernel_resources()
     rows = kr.kernels(os.path.join(ROOT, "scannet_amd", "libscanfuse.so"))
-    mine = [(kr.short(n), r) for r, n in zip(rows, kr.demangle([r["name"] for r in rows])) if kr.short(n).startswith("k_align_")]
+    every = [(kr.short(n), r) for r, n in zip(rows, kr.demangle([r["name"] for r in rows]))]
+    mine = [(s, r) for s, r in every if s.startswith("k_align_")]
     assert {s.split("<")[0] for s, _ in mine} == {"k_align_prep", "k_align_assoc", "k_align_final"}
     assert len([s for s, _ in mine if s.startswith("k_align_prep<")]) == 4   # one per level
+    # one association body per solver, instantiated without and with the colour row; nothing else associates
+    assert sorted(s for s, _ in every if "assoc" in s) == ["k_align_assoc<false>", "k_align_assoc<true>", "k_track_assoc<false>", "k_track_assoc<true>"]
+    assert sorted(s for s, _ in mine if "final" in s) == ["k_align_final<false>", "k_align_final<true>"]
     for s, r in mine:
-        assert r["scratch"] == 0 and r["vspill"] == 0, (s, r["scratch"], r["vspill"])
+        assert r["scratch"] == 0 and r["vspill"] == 0 and r["sspill"] == 0, (s, r)
         assert r["lds"] <= 160 * 1024, (s, r["lds"])
-    assoc = [r for s, r in mine if s == "k_align_assoc"][0]
+    assoc = [r for s, r in mine if s == "k_align_assoc<false>"][0]
     assert assoc["lds"] == 464
 
 

@@ -369,13 +369,16 @@ def test_photo_kernels_live_in_registers():
         pytest.skip("no llvm-readelf")
     kr = ss.kernel_resources()
     rows = kr.kernels(os.path.join(ROOT, "scannet_amd", "libscanfuse.so"))
-    mine = [(kr.short(n), r) for r, n in zip(rows, kr.demangle([r["name"] for r in rows])) if kr.short(n).startswith("k_photo_")]
-    assert {s.split("<")[0] for s, _ in mine} == {"k_photo_prep", "k_photo_assoc", "k_photo_final"}
-    assert len([s for s, _ in mine if s.startswith("k_photo_prep<")]) == 4   # one per level
+    every = [(kr.short(n), r) for r, n in zip(rows, kr.demangle([r["name"] for r in rows]))]
+    # the colour term's own kernel, and the colour instantiation of the aligner's two (align.hip)
+    mine = [(s, r) for s, r in every if s.startswith("k_photo_") or s in ("k_align_assoc<true>", "k_align_final<true>")]
+    assert {s.split("<")[0] for s, _ in mine} == {"k_photo_prep", "k_align_assoc", "k_align_final"}
+    assert len(mine) == 6 and len([s for s, _ in mine if s.startswith("k_photo_prep<")]) == 4   # one per level
+    assert [s for s, _ in every if "assoc" in s and "align" in s and s != "k_align_assoc<true>"] == ["k_align_assoc<false>"]
     for s, r in mine:
         assert r["scratch"] == 0 and r["vspill"] == 0 and r["sspill"] == 0, (s, r)
         assert r["lds"] <= 160 * 1024, (s, r["lds"])
-    assoc = [r for s, r in mine if s == "k_photo_assoc"][0]
+    assoc = [r for s, r in mine if s == "k_align_assoc<true>"][0]
     assert assoc["lds"] == 4 * 31 * 4   # the cross-wave step of 31 sums
 
 

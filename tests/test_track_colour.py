@@ -346,12 +346,17 @@ def test_track_photo_kernels_live_in_registers():
         pytest.skip("no llvm-readelf")
     kr = ss.kernel_resources()
     rows = kr.kernels(os.path.join(ROOT, "scannet_amd", "libscanfuse.so"))
-    mine = {kr.short(n): r for r, n in zip(rows, kr.demangle([r["name"] for r in rows])) if kr.short(n).startswith("k_track_photo_")}
-    assert set(mine) == {"k_track_photo_in0", "k_track_photo_model0", "k_track_photo_down", "k_track_photo_grad", "k_track_photo_assoc", "k_track_photo_final"}
+    every = {kr.short(n): r for r, n in zip(rows, kr.demangle([r["name"] for r in rows]))}
+    # the colour term's own kernels, and both instantiations of the tracker's two (track.hip: <false> the depth term alone, <true> with the colour row)
+    mine = {s: r for s, r in every.items() if s.startswith("k_track_photo_") or s.split("<")[0] in ("k_track_assoc", "k_track_final")}
+    assert set(mine) == {"k_track_photo_in0", "k_track_photo_model0", "k_track_photo_down", "k_track_photo_grad", "k_track_assoc<false>", "k_track_assoc<true>",
+                         "k_track_final<false>", "k_track_final<true>"}
+    assert sorted(s for s in every if "assoc" in s and "track" in s) == ["k_track_assoc<false>", "k_track_assoc<true>"]
     for s, r in mine.items():
         assert r["scratch"] == 0 and r["vspill"] == 0 and r["sspill"] == 0, (s, r)
         assert r["lds"] <= 160 * 1024, (s, r["lds"])
-    assert mine["k_track_photo_assoc"]["lds"] == 4 * 31 * 4   # the cross-wave step of 31 sums
+    assert mine["k_track_assoc<false>"]["lds"] == 464           # the cross-wave step of 29 sums
+    assert mine["k_track_assoc<true>"]["lds"] == 4 * 31 * 4     # and of 31
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
