@@ -195,6 +195,20 @@ int sf_axis_align_stage_cov(const float* xyz, const uint32_t* index, uint64_t nu
 int sf_axis_align_stage_transform(const float* xyz, uint64_t num_vertices, const float m[16], int device, float* xyz_out, float bbox6[6]);
 int sf_axis_align_tune(const char* key, int value);
 
+/* Stage hooks of the annotation projector (tests/test_project_stages.py; scannet_amd/csrc/project.hip): each call runs ONE launch group of
+ * sf_projector_run on an existing projector -- through the helper sf_projector_run itself launches it with (same kernels, same grids, same stream) --
+ * on host arrays, and returns the output to the host.  n = 1 .. sf_projector_max_batch() frames; images are row-major, color_w x color_h per frame.
+ *   raster    k_pa_vertex + k_pa_raster + k_pa_raster_big for n poses (cam2world as for sf_projector_run): keys_out = the raw depth buffer,
+ *             {z_ndc bits << 32 | triangle index} per pixel, all-ones where nothing was drawn (and everywhere in a frame without a valid pose);
+ *             late_counts_out[n] = how many (triangle, half) entries k_pa_raster queued for k_pa_raster_big in each frame
+ *   resolve   k_pa_resolve alone on the caller's keys (every index below the mesh's triangle count, else SF_ERR_INVALID_ARG and no launch);
+ *             orig_depth n x depth_w*depth_h or NULL (no depth-consistency filter); outputs = the images BEFORE the vote; zcam_out may be NULL
+ *   vote      k_pa_vote alone (needs no mesh) */
+int sf_projector_stage_raster(sf_projector* p, int n, const float* cam2world, uint64_t* keys_out, uint32_t* late_counts_out);
+int sf_projector_stage_resolve(sf_projector* p, int n, const uint64_t* keys_in, const uint16_t* orig_depth, uint8_t* instance_out, uint16_t* label_out,
+                               float* zcam_out);
+int sf_projector_stage_vote(sf_projector* p, int n, const uint8_t* instance_in, const uint16_t* label_in, uint8_t* instance_out, uint16_t* label_out);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

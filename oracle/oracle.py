@@ -387,6 +387,56 @@ def project_frame(params, xyz, tris, vinst, vlabel, cam2world, orig_depth=None, 
     return (io, lo, z) if want_depth else (io, lo)
 
 
+def _or_project_params(params):
+    return OrProjectParams(*[getattr(params, f) for f, _ in OrProjectParams._fields_])
+
+
+def project_raster(params, xyz, tris, cam2world):
+    """Stage 1 of project_frame: the raw depth buffer u64 [h, w], {z_ndc bits << 32 | triangle index}, all-ones where nothing was drawn."""
+    L = lib()
+    vp = C.c_void_p
+    L.or_project_raster.argtypes = [C.POINTER(OrProjectParams), vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+    P = _or_project_params(params)
+    x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    c = np.ascontiguousarray(cam2world, np.float32).reshape(16)
+    keys = np.empty((P.color_height, P.color_width), np.uint64)
+    assert L.or_project_raster(C.byref(P), x.ctypes.data, len(x), t.ctypes.data, len(t), c.ctypes.data, keys.ctypes.data) == 0
+    return keys
+
+
+def project_resolve(params, tris, vinst, vlabel, keys, orig_depth=None):
+    """Stage 2: keys [h, w] (+ sensor depth [dh, dw] u16) -> (instance, label, rendered depth in metres) before the vote."""
+    L = lib()
+    vp = C.c_void_p
+    L.or_project_resolve.argtypes = [C.POINTER(OrProjectParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    P = _or_project_params(params)
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    vi, vl = np.ascontiguousarray(vinst, np.uint8), np.ascontiguousarray(vlabel, np.uint16)
+    k = np.ascontiguousarray(keys, np.uint64).reshape(P.color_height, P.color_width)
+    assert np.all((k == np.uint64(2 ** 64 - 1)) | ((k & np.uint64(0xFFFFFFFF)) < len(t)))
+    d = None if orig_depth is None else np.ascontiguousarray(orig_depth, np.uint16).reshape(P.depth_height, P.depth_width)
+    io = np.empty(k.shape, np.uint8)
+    lo = np.empty(k.shape, np.uint16)
+    z = np.empty(k.shape, np.float32)
+    assert L.or_project_resolve(C.byref(P), t.ctypes.data, vi.ctypes.data, vl.ctypes.data, k.ctypes.data, d.ctypes.data if d is not None else None,
+                                io.ctypes.data, lo.ctypes.data, z.ctypes.data) == 0
+    return io, lo, z
+
+
+def project_vote(inst, label):
+    """Stage 3: the 5x5 vote on (instance u8, label u16) images [h, w] -> (instance, label)."""
+    L = lib()
+    vp = C.c_void_p
+    L.or_project_vote.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
+    L.or_project_vote.restype = None
+    i, l = np.ascontiguousarray(inst, np.uint8), np.ascontiguousarray(label, np.uint16)
+    assert i.ndim == 2 and i.shape == l.shape
+    io, lo = np.empty_like(i), np.empty_like(l)
+    L.or_project_vote(i.shape[1], i.shape[0], i.ctypes.data, l.ctypes.data, io.ctypes.data, lo.ctypes.data)
+    return io, lo
+
+
 def project_matrix(cam2world, fx, fy, W, H, n, f):
     L = lib()
     L.or_project_matrix.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_void_p]

@@ -145,22 +145,18 @@ static float camera_z(float d, float n, float f) {
   return (z >= n && z <= f) ? z : 0.0f;
 }
 
-// One frame.  zcam_out (nullable): the camera-space depth image at colour resolution (Visualizer.cpp:127-141).
-int or_project_frame(const or_project_params* P, const float* xyz, uint64_t V, const uint32_t* tris, uint64_t F, const uint8_t* vinst,
-                     const uint16_t* vlabel, const float* cam2world, const uint16_t* orig_depth, uint8_t* inst_out, uint16_t* label_out,
-                     float* zcam_out) {
-  const int w = (int)P->color_width, h = (int)P->color_height, dw = (int)P->depth_width, dh = (int)P->depth_height;
+// The three stages of a frame, exported one by one for tests/test_project_stages.py (the device's stage hooks are compared with them bit for bit);
+// or_project_frame below is their composition.
+// Stage 1: the raw depth buffer, {z_ndc bits << 32 | triangle index} per pixel, all-ones where nothing was drawn (everywhere without a valid pose).
+int or_project_raster(const or_project_params* P, const float* xyz, uint64_t V, const uint32_t* tris, uint64_t F, const float* cam2world, uint64_t* zbuf) {
+  const int w = (int)P->color_width, h = (int)P->color_height;
   const size_t n = (size_t)w * h;
-  memset(inst_out, 0, n);
-  memset(label_out, 0, 2 * n);
-  if (zcam_out) memset(zcam_out, 0, 4 * n);
+  memset(zbuf, 0xff, 8 * n);
   if (cam2world[0] == -INFINITY) return 0;  // Visualizer.cpp:63,187-192
   float M[16];
   or_project_matrix(cam2world, P->fx, P->fy, P->color_width, P->color_height, P->depth_min, P->depth_max, M);
-  uint64_t* zbuf = (uint64_t*)malloc(8 * n);
   clipv* cv = (clipv*)malloc(sizeof(clipv) * (V ? V : 1));
-  if (!zbuf || !cv) { free(zbuf); free(cv); return -1; }
-  memset(zbuf, 0xff, 8 * n);
+  if (!cv) return -1;
   for (uint64_t i = 0; i < V; i++) {
     const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
     cv[i].x = M[0] * x + M[1] * y + M[2] * z + M[3];
@@ -192,10 +188,20 @@ int or_project_frame(const or_project_params* P, const float* xyz, uint64_t V, c
     raster_tri(zbuf, w, h, s[0], s[1], s[2], (uint32_t)t);
     if (np == 4) raster_tri(zbuf, w, h, s[0], s[2], s[3], (uint32_t)t);
   }
-  // colour buffer -> ids (:104-114), depth buffer -> camera z (:123-141)
-  uint8_t* inst1 = (uint8_t*)calloc(n, 1);
-  uint16_t* lab1 = (uint16_t*)calloc(n, 2);
+  free(cv);
+  return 0;
+}
+
+// Stage 2: colour buffer -> ids (:104-114), depth buffer -> camera z (:123-141), depth consistency (:144-164; orig_depth NULL = skipped).
+// Outputs are the images before the vote; zcam_out is nullable.
+int or_project_resolve(const or_project_params* P, const uint32_t* tris, const uint8_t* vinst, const uint16_t* vlabel, const uint64_t* zbuf,
+                       const uint16_t* orig_depth, uint8_t* inst1, uint16_t* lab1, float* zcam_out) {
+  const int w = (int)P->color_width, h = (int)P->color_height, dw = (int)P->depth_width, dh = (int)P->depth_height;
+  const size_t n = (size_t)w * h;
   float* zc = (float*)calloc(n, 4);
+  if (!zc) return -1;
+  memset(inst1, 0, n);
+  memset(lab1, 0, 2 * n);
   for (size_t i = 0; i < n; i++) {
     const uint64_t key = zbuf[i];
     if (key == UINT64_MAX) continue;
@@ -208,7 +214,6 @@ int or_project_frame(const or_project_params* P, const float* xyz, uint64_t V, c
     zc[i] = camera_z(d, P->depth_min, P->depth_max);
   }
   if (zcam_out) memcpy(zcam_out, zc, 4 * n);
-  // depth consistency (:144-164)
   if (orig_depth) {
     const float sw = (float)(dw - 1) / (float)(w - 1), sh = (float)(dh - 1) / (float)(h - 1);
     const float rw = (float)(w - 1) / (float)(dw - 1), rh = (float)(h - 1) / (float)(dh - 1);
@@ -229,7 +234,15 @@ int or_project_frame(const or_project_params* P, const float* xyz, uint64_t V, c
         }
       }
   }
-  // 5x5 vote (:166-186), reading the pre-vote labels
+  free(zc);
+  return 0;
+}
+
+// Stage 3: 5x5 vote (:166-186), reading the pre-vote labels
+void or_project_vote(int w, int h, const uint8_t* inst1, const uint16_t* lab1, uint8_t* inst_out, uint16_t* label_out) {
+  const size_t n = (size_t)w * h;
+  memset(inst_out, 0, n);
+  memset(label_out, 0, 2 * n);
   const int radius = 2;
   for (int y = 0; y < h; y++)
     for (int x = 0; x < w; x++) {
@@ -247,6 +260,24 @@ int or_project_frame(const or_project_params* P, const float* xyz, uint64_t V, c
       label_out[i] = v;
       inst_out[i] = inst1[i];
     }
-  free(zbuf); free(cv); free(inst1); free(lab1); free(zc);
-  return 0;
+}
+
+// One frame.  zcam_out (nullable): the camera-space depth image at colour resolution (Visualizer.cpp:127-141).
+int or_project_frame(const or_project_params* P, const float* xyz, uint64_t V, const uint32_t* tris, uint64_t F, const uint8_t* vinst,
+                     const uint16_t* vlabel, const float* cam2world, const uint16_t* orig_depth, uint8_t* inst_out, uint16_t* label_out,
+                     float* zcam_out) {
+  const size_t n = (size_t)P->color_width * P->color_height;
+  memset(inst_out, 0, n);
+  memset(label_out, 0, 2 * n);
+  if (zcam_out) memset(zcam_out, 0, 4 * n);
+  if (cam2world[0] == -INFINITY) return 0;  // Visualizer.cpp:63,187-192
+  uint64_t* zbuf = (uint64_t*)malloc(8 * n);
+  uint8_t* inst1 = (uint8_t*)malloc(n);
+  uint16_t* lab1 = (uint16_t*)malloc(2 * n);
+  int rc = (zbuf && inst1 && lab1) ? 0 : -1;
+  if (rc == 0) rc = or_project_raster(P, xyz, V, tris, F, cam2world, zbuf);
+  if (rc == 0) rc = or_project_resolve(P, tris, vinst, vlabel, zbuf, orig_depth, inst1, lab1, zcam_out);
+  if (rc == 0) or_project_vote((int)P->color_width, (int)P->color_height, inst1, lab1, inst_out, label_out);
+  free(zbuf); free(inst1); free(lab1);
+  return rc;
 }

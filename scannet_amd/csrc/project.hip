@@ -481,6 +481,44 @@ struct sf_projector {
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
+// The launches of sf_projector_run in three groups, shared with the stage hooks at the end of this file: same kernels, same grids, same stream.
+static PaBatch pa_batch(const sf_projector* p, int n, const float* cam2world) {
+  PaBatch b;
+  std::memset(&b, 0, sizeof(b));
+  for (int i = 0; i < n; i++) {
+    const float* c = cam2world + 16 * (size_t)i;
+    b.valid[i] = c[0] != -INFINITY;
+    if (b.valid[i]) world_view_proj(c, p->p.fx, p->p.fy, p->p.color_width, p->p.color_height, p->k.zn, p->k.zf, b.M[i]);
+  }
+  return b;
+}
+
+// depth buffers of n frames to all-ones, the queue counters to 0
+static hipError_t pa_clear(sf_projector* p, int n) {
+  const hipError_t e = hipMemsetAsync(p->zbuf, 0xFF, (size_t)n * p->k.w * p->k.h * 8, p->stream);
+  return e != hipSuccess ? e : hipMemsetAsync(p->late_count, 0, PA_MAX_BATCH * 4, p->stream);
+}
+
+static void pa_launch_raster(sf_projector* p, int n, const PaBatch& b) {
+  const PaK& k = p->k;
+  const unsigned cluster_blocks = (unsigned)(((k.F + PA_CLUSTER - 1) / PA_CLUSTER + 3) / 4);
+  hipLaunchKernelGGL(k_pa_vertex, dim3((k.V + 255) / 256, n), dim3(256), 0, p->stream, k, b, p->xyz, p->clip);
+  hipLaunchKernelGGL(k_pa_raster, dim3(cluster_blocks, n), dim3(256), 0, p->stream, k, b, p->tris, p->clip, p->bounds, p->zbuf, p->late, p->late_count);
+  hipLaunchKernelGGL(k_pa_raster_big, dim3(512, n), dim3(256), 0, p->stream, k, b, p->tris, p->clip, p->zbuf, p->late, p->late_count);
+}
+
+static void pa_launch_resolve(sf_projector* p, int n, const PaBatch& b, bool want_zcam) {
+  const PaK& k = p->k;
+  const size_t np = (size_t)k.w * k.h;
+  hipLaunchKernelGGL(k_pa_resolve, dim3((unsigned)((np + 255) / 256), n), dim3(256), 0, p->stream, k, b, p->tris, p->vinst, p->vlabel, p->zbuf, p->depth,
+                     p->inst1, p->label1, want_zcam ? p->zcam : nullptr);
+}
+
+static void pa_launch_vote(sf_projector* p, int n) {
+  const PaK& k = p->k;
+  hipLaunchKernelGGL(k_pa_vote, dim3((unsigned)(((k.w + 63) / 64) * ((k.h + 7) / 8)), n), dim3(256), 0, p->stream, k, p->inst1, p->label1, p->inst2, p->label2);
+}
+
 SF_API int sf_projector_max_batch(void) { return PA_MAX_BATCH; }
 
 // page-locked host memory for the images handed to / returned by sf_projector_run: the copies then run at PCIe speed instead of
@@ -594,25 +632,14 @@ SF_API int sf_projector_run(sf_projector* p, int n, const float* cam2world, cons
   SF_HIP_CHECK(hipSetDevice(p->device));
   const PaK& k = p->k;
   const size_t np = (size_t)k.w * k.h, dn = (size_t)k.dw * k.dh;
-  PaBatch b;
-  std::memset(&b, 0, sizeof(b));
-  for (int i = 0; i < n; i++) {
-    const float* c = cam2world + 16 * (size_t)i;
-    b.valid[i] = c[0] != -INFINITY;
-    if (b.valid[i]) world_view_proj(c, p->p.fx, p->p.fy, p->p.color_width, p->p.color_height, k.zn, k.zf, b.M[i]);
-  }
+  PaBatch b = pa_batch(p, n, cam2world);
   b.has_depth = orig_depth != nullptr;
-  SF_HIP_CHECK(hipMemsetAsync(p->zbuf, 0xFF, (size_t)n * np * 8, p->stream));
-  SF_HIP_CHECK(hipMemsetAsync(p->late_count, 0, PA_MAX_BATCH * 4, p->stream));
+  SF_HIP_CHECK(pa_clear(p, n));
   if (orig_depth) SF_HIP_CHECK(hipMemcpyAsync(p->depth, orig_depth, (size_t)n * dn * 2, hipMemcpyHostToDevice, p->stream));
   if (kernel_us) SF_HIP_CHECK(hipEventRecord(p->e0, p->stream));
-  const unsigned cluster_blocks = (unsigned)(((k.F + PA_CLUSTER - 1) / PA_CLUSTER + 3) / 4);
-  hipLaunchKernelGGL(k_pa_vertex, dim3((k.V + 255) / 256, n), dim3(256), 0, p->stream, k, b, p->xyz, p->clip);
-  hipLaunchKernelGGL(k_pa_raster, dim3(cluster_blocks, n), dim3(256), 0, p->stream, k, b, p->tris, p->clip, p->bounds, p->zbuf, p->late, p->late_count);
-  hipLaunchKernelGGL(k_pa_raster_big, dim3(512, n), dim3(256), 0, p->stream, k, b, p->tris, p->clip, p->zbuf, p->late, p->late_count);
-  hipLaunchKernelGGL(k_pa_resolve, dim3((unsigned)((np + 255) / 256), n), dim3(256), 0, p->stream, k, b, p->tris, p->vinst, p->vlabel, p->zbuf, p->depth,
-                     p->inst1, p->label1, zcam_out ? p->zcam : nullptr);
-  hipLaunchKernelGGL(k_pa_vote, dim3((unsigned)(((k.w + 63) / 64) * ((k.h + 7) / 8)), n), dim3(256), 0, p->stream, k, p->inst1, p->label1, p->inst2, p->label2);
+  pa_launch_raster(p, n, b);
+  pa_launch_resolve(p, n, b, zcam_out != nullptr);
+  pa_launch_vote(p, n);
   SF_HIP_CHECK(hipGetLastError());
   if (kernel_us) SF_HIP_CHECK(hipEventRecord(p->e1, p->stream));
   SF_HIP_CHECK(hipMemcpyAsync(instance_out, p->inst2, (size_t)n * np, hipMemcpyDeviceToHost, p->stream));
@@ -624,5 +651,68 @@ SF_API int sf_projector_run(sf_projector* p, int n, const float* cam2world, cons
     SF_HIP_CHECK(hipEventElapsedTime(&ms, p->e0, p->e1));
     *kernel_us = 1000.0f * ms;
   }
+  return SF_OK;
+}
+
+// ---- stage hooks (include/scanfuse_internal.h): one launch group of sf_projector_run per call, host arrays in and out -- for tests/test_project_stages.py ----
+static int pa_stage_args(const sf_projector* p, int n, bool need_mesh) {
+  if (!p) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (n < 1 || n > PA_MAX_BATCH) return sf::fail(SF_ERR_INVALID_ARG, "batch of %d frames (1..%d)", n, PA_MAX_BATCH);
+  if (need_mesh && p->k.V == 0) return sf::fail(SF_ERR_INVALID_ARG, "no mesh set (sf_projector_set_mesh)");
+  return SF_OK;
+}
+
+SF_API int sf_projector_stage_raster(sf_projector* p, int n, const float* cam2world, uint64_t* keys_out, uint32_t* late_counts_out) {
+  if (const int rc = pa_stage_args(p, n, true)) return rc;
+  if (!cam2world || !keys_out || !late_counts_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(p->device));
+  const size_t np = (size_t)p->k.w * p->k.h;
+  const PaBatch b = pa_batch(p, n, cam2world);
+  SF_HIP_CHECK(pa_clear(p, n));
+  pa_launch_raster(p, n, b);
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(keys_out, p->zbuf, (size_t)n * np * 8, hipMemcpyDeviceToHost, p->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(late_counts_out, p->late_count, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(p->stream));
+  return SF_OK;
+}
+
+SF_API int sf_projector_stage_resolve(sf_projector* p, int n, const uint64_t* keys_in, const uint16_t* orig_depth, uint8_t* instance_out, uint16_t* label_out,
+                                      float* zcam_out) {
+  if (const int rc = pa_stage_args(p, n, true)) return rc;
+  if (!keys_in || !instance_out || !label_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  const size_t np = (size_t)p->k.w * p->k.h, dn = (size_t)p->k.dw * p->k.dh;
+  // k_pa_resolve reads the first vertex of the triangle a key names: the product path only ever stores indices below F
+  for (size_t i = 0; i < (size_t)n * np; i++)
+    if (keys_in[i] != ~0ull && (uint32_t)keys_in[i] >= p->k.F)
+      return sf::fail(SF_ERR_INVALID_ARG, "key %llu names triangle %u of %u", (unsigned long long)i, (uint32_t)keys_in[i], p->k.F);
+  SF_HIP_CHECK(hipSetDevice(p->device));
+  PaBatch b;
+  std::memset(&b, 0, sizeof(b));
+  for (int i = 0; i < n; i++) b.valid[i] = 1;
+  b.has_depth = orig_depth != nullptr;
+  SF_HIP_CHECK(hipMemcpyAsync(p->zbuf, keys_in, (size_t)n * np * 8, hipMemcpyHostToDevice, p->stream));
+  if (orig_depth) SF_HIP_CHECK(hipMemcpyAsync(p->depth, orig_depth, (size_t)n * dn * 2, hipMemcpyHostToDevice, p->stream));
+  pa_launch_resolve(p, n, b, zcam_out != nullptr);
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(instance_out, p->inst1, (size_t)n * np, hipMemcpyDeviceToHost, p->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(label_out, p->label1, (size_t)n * np * 2, hipMemcpyDeviceToHost, p->stream));
+  if (zcam_out) SF_HIP_CHECK(hipMemcpyAsync(zcam_out, p->zcam, (size_t)n * np * 4, hipMemcpyDeviceToHost, p->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(p->stream));
+  return SF_OK;
+}
+
+SF_API int sf_projector_stage_vote(sf_projector* p, int n, const uint8_t* instance_in, const uint16_t* label_in, uint8_t* instance_out, uint16_t* label_out) {
+  if (const int rc = pa_stage_args(p, n, false)) return rc;
+  if (!instance_in || !label_in || !instance_out || !label_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(p->device));
+  const size_t np = (size_t)p->k.w * p->k.h;
+  SF_HIP_CHECK(hipMemcpyAsync(p->inst1, instance_in, (size_t)n * np, hipMemcpyHostToDevice, p->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(p->label1, label_in, (size_t)n * np * 2, hipMemcpyHostToDevice, p->stream));
+  pa_launch_vote(p, n);
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(instance_out, p->inst2, (size_t)n * np, hipMemcpyDeviceToHost, p->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(label_out, p->label2, (size_t)n * np * 2, hipMemcpyDeviceToHost, p->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(p->stream));
   return SF_OK;
 }

@@ -34,6 +34,9 @@ def _lib():
     L.sf_projector_max_batch.argtypes = []
     L.sf_projector_set_mesh.argtypes = [vp, vp, u64, vp, u64, vp, vp]
     L.sf_projector_run.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+    L.sf_projector_stage_raster.argtypes = [vp, C.c_int, vp, vp, vp]   # stage hooks: include/scanfuse_internal.h
+    L.sf_projector_stage_resolve.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.sf_projector_stage_vote.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.sf_host_alloc.argtypes = [u64, C.POINTER(vp)]
     L.sf_host_free.argtypes = [vp]
     L.sf_host_free.restype = None
@@ -126,3 +129,35 @@ class Projector:
         check(_lib().sf_projector_run(self._h, n, c.ctypes.data, d.ctypes.data if d is not None else None, inst.ctypes.data, label.ctypes.data,
                                       z.ctypes.data if z is not None else None, C.byref(us)))
         return (inst, label, z, us.value) if want_depth else (inst, label, us.value)
+
+    # ---- stage hooks (include/scanfuse_internal.h): one launch group of run() per call, host arrays in and out -- for tests/test_project_stages.py ----
+    def stage_raster(self, cam2world):
+        """k_pa_vertex + k_pa_raster + k_pa_raster_big: cam2world (n, 4, 4) -> (keys u64 (n, ch, cw): z_ndc bits << 32 | triangle index, all-ones where
+        nothing was drawn; late_counts u32 (n,): what k_pa_raster queued for k_pa_raster_big per frame)."""
+        p = self.params
+        c = np.ascontiguousarray(cam2world, np.float32).reshape(-1, 16)
+        keys = np.empty((len(c), p.color_height, p.color_width), np.uint64)
+        late = np.empty(len(c), np.uint32)
+        check(_lib().sf_projector_stage_raster(self._h, len(c), c.ctypes.data, keys.ctypes.data, late.ctypes.data))
+        return keys, late
+
+    def stage_resolve(self, keys, orig_depth=None, want_depth=True):
+        """k_pa_resolve alone: keys (n, ch, cw) u64, orig_depth (n, dh, dw) u16 or None -> (instance, label, rendered depth or None) before the vote."""
+        p = self.params
+        k = np.ascontiguousarray(keys, np.uint64).reshape(-1, p.color_height, p.color_width)
+        n = len(k)
+        d = None if orig_depth is None else np.ascontiguousarray(orig_depth, np.uint16).reshape(n, p.depth_height, p.depth_width)
+        inst, label = np.empty(k.shape, np.uint8), np.empty(k.shape, np.uint16)
+        z = np.empty(k.shape, np.float32) if want_depth else None
+        check(_lib().sf_projector_stage_resolve(self._h, n, k.ctypes.data, d.ctypes.data if d is not None else None, inst.ctypes.data, label.ctypes.data,
+                                                z.ctypes.data if z is not None else None))
+        return inst, label, z
+
+    def stage_vote(self, inst, label):
+        """k_pa_vote alone: (instance u8, label u16) (n, ch, cw) -> (instance, label)."""
+        p = self.params
+        i = np.ascontiguousarray(inst, np.uint8).reshape(-1, p.color_height, p.color_width)
+        l = np.ascontiguousarray(label, np.uint16).reshape(i.shape)
+        io, lo = np.empty_like(i), np.empty_like(l)
+        check(_lib().sf_projector_stage_vote(self._h, len(i), i.ctypes.data, l.ctypes.data, io.ctypes.data, lo.ctypes.data))
+        return io, lo

@@ -113,14 +113,28 @@ def _sha(*arrays):
     return h.hexdigest()
 
 
-# ---------------------------------------------------------------------------------------------------------------- checker, closed forms
-def test_pixel_alignment_and_fill_rule():
+# ---------------------------------------------------------------------------------------------------------------- closed forms
+BACKENDS = ["checker", pytest.param("device", marks=pytest.mark.gpu)]
+
+
+def _frame(backend, P, xyz, tris, vinst, vlabel, T, orig_depth=None, want_depth=False):
+    """one frame through the checker or through the device's product path (sf_projector_run), same return values"""
+    if backend == "checker":
+        return orc.project_frame(P, xyz, tris, vinst, vlabel, T, orig_depth, want_depth=want_depth)
+    with project.Projector(P) as pr:
+        pr.set_mesh(xyz, tris, vinst, vlabel)
+        out = pr.run(np.asarray(T, np.float32)[None], None if orig_depth is None else np.asarray(orig_depth)[None], want_depth=want_depth)
+    return tuple(o[0] for o in out[:-1])
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_pixel_alignment_and_fill_rule(backend):
     """a fronto-parallel square whose edges project exactly onto pixel boundaries covers exactly those pixels"""
     P = _params(cw=64, ch=48, dw=32, dh=24, fx=64.0, fy=64.0)
     z = 2.0
     x0, x1, y0, y1 = [(px - 32) * z / 64.0 for px in (10, 20)] + [(py - 24) * z / 64.0 for py in (5, 9)]
     v, t = _quad([x0, y0, z], [x1, y0, z], [x1, y1, z], [x0, y1, z])
-    inst, label, zc = orc.project_frame(P, v, t, [3] * 4, [700] * 4, np.eye(4), None, want_depth=True)
+    inst, label, zc = _frame(backend, P, v, t, [3] * 4, [700] * 4, np.eye(4), None, want_depth=True)
     want = np.zeros((48, 64), bool)
     want[5:9, 10:20] = True
     # the 5x5 vote cannot remove anything here: every pixel of a 10 x 4 block sees >= 20 % of its own label
@@ -128,18 +142,20 @@ def test_pixel_alignment_and_fill_rule():
     assert np.allclose(zc[want], z, atol=2e-4) and np.all(zc[~want] == 0)
 
 
-def test_flat_colour_comes_from_the_first_vertex():
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_flat_colour_comes_from_the_first_vertex(backend):
     P = _params(cw=64, ch=48, dw=32, dh=24, fx=64.0, fy=64.0)
     v = [[-2, -2, 2.0], [2, -2, 2.0], [2, 2, 2.0], [-2, 2, 2.0]]
     t = [[1, 2, 0], [3, 0, 2]]                      # first vertices: 1 and 3
-    inst, label = orc.project_frame(P, v, t, [1, 2, 3, 4], [10, 20, 30, 40], np.eye(4))
+    inst, label = _frame(backend, P, v, t, [1, 2, 3, 4], [10, 20, 30, 40], np.eye(4))
     assert set(np.unique(label)) == {20, 40} and set(np.unique(inst)) == {2, 4}
     yy, xx = np.mgrid[0:48, 0:64]
     upper = (xx + 0.5 - 32) / 64 - (yy + 0.5 - 24) / 64 > 0.05    # well on the (1, 2, 0) side of the diagonal x = y
     assert np.all(label[upper] == 20) and np.all(label[~upper & ((xx + 0.5 - 32) / 64 - (yy + 0.5 - 24) / 64 < -0.05)] == 40)
 
 
-def test_depth_test_and_draw_order():
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_depth_test_and_draw_order(backend):
     P = _params(cw=64, ch=48, dw=32, dh=24, fx=64.0, fy=64.0)
     far, _ = _quad([-3, -3, 3.0], [3, -3, 3.0], [3, 3, 3.0], [-3, 3, 3.0])
     near, _ = _quad([-0.5, -0.5, 1.5], [0.5, -0.5, 1.5], [0.5, 0.5, 1.5], [-0.5, 0.5, 1.5])
@@ -147,17 +163,18 @@ def test_depth_test_and_draw_order():
     v = np.array(far + near + same)
     t = np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6], [4, 6, 7], [8, 9, 10], [8, 10, 11]])
     vi = [1] * 4 + [2] * 4 + [3] * 4
-    inst, label, zc = orc.project_frame(P, v, t, vi, [x * 10 for x in vi], np.eye(4), None, want_depth=True)
+    inst, label, zc = _frame(backend, P, v, t, vi, [x * 10 for x in vi], np.eye(4), None, want_depth=True)
     assert set(np.unique(inst)) == {1, 2}
     assert np.all(inst[24 - 10:24 + 10, 32 - 10:32 + 10] == 2) and np.allclose(zc[24, 32], 1.5, atol=1e-4) and np.allclose(zc[2, 2], 3.0, atol=1e-3)
 
 
-def test_near_plane_clip_against_ray_plane_hits():
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_near_plane_clip_against_ray_plane_hits(backend):
     """a huge floor passing under and behind the camera: every pixel whose ray meets it between depth_min and depth_max is labelled"""
     P = _params()
     T = _pose([0.0, 0.0, 0.12], 0.4, -0.05)
     v, t = _quad([-60, -60, 0], [60, -60, 0], [60, 60, 0], [-60, 60, 0])
-    inst, label, zc = orc.project_frame(P, v, t, [9] * 4, [99] * 4, T, None, want_depth=True)
+    inst, label, zc = _frame(backend, P, v, t, [9] * 4, [99] * 4, T, None, want_depth=True)
     yy, xx = np.mgrid[0:CH, 0:CW]
     ray = np.stack([(xx + 0.5 - CW / 2) / FX, (yy + 0.5 - CH / 2) / FY, np.ones_like(xx, float)], -1) @ T[:3, :3].T.astype(float)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -203,11 +220,25 @@ def test_depth_consistency_and_vote_filters():
     assert lv[10, 10] == 0 and np.all(lv[30:33, 40:43] == 30) and lv[20, 20] == 10
 
 
-def test_invalid_pose_gives_empty_images():
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_vote_removes_a_speck_and_keeps_a_patch(backend):
+    """the vote case of test_depth_consistency_and_vote_filters, on either backend"""
+    Pv = _params(cw=64, ch=48, dw=32, dh=24, fx=64.0, fy=64.0)
+    wall, wt = _quad([-3, -3, 3.0], [3, -3, 3.0], [3, 3, 3.0], [-3, 3, 3.0])
+    px = lambda a, b, c, e, zz: _quad(*[[(x - 32) * zz / 64, (y - 24) * zz / 64, zz] for x, y in ((a, c), (b, c), (b, e), (a, e))])[0]
+    v = np.array(wall + px(10, 11, 10, 11, 2.0) + px(40, 43, 30, 33, 2.0))
+    t = np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6], [4, 6, 7], [8, 9, 10], [8, 10, 11]])
+    vi = [1] * 4 + [2] * 4 + [3] * 4
+    iv, lv = _frame(backend, Pv, v, t, vi, [x * 10 for x in vi], np.eye(4))
+    assert lv[10, 10] == 0 and np.all(lv[30:33, 40:43] == 30) and lv[20, 20] == 10
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_invalid_pose_gives_empty_images(backend):
     P = _params()
     xyz, tris, inst, label = room_scene(4)
     T = np.full((4, 4), -np.inf, np.float32)
-    i, l = orc.project_frame(P, xyz, tris, inst, label, T)
+    i, l = _frame(backend, P, xyz, tris, inst, label, T)
     assert not i.any() and not l.any()
 
 
