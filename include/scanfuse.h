@@ -730,8 +730,9 @@ int sf_filter2d_frame(sf_filter2d* f, const uint16_t* depth, const uint8_t* rgb,
  * write.  *data is malloc'ed (sf_free); 16-bit samples are in host byte order. */
 int sf_png_read(const char* path, uint32_t* width, uint32_t* height, int* channels, int* bits, void** data);
 int sf_png_write_gray(const char* path, const void* data, uint32_t width, uint32_t height, int bits);
-/* grey (channels = 1) or RGB (channels = 3), 8 or 16 bits: the 16-bit depth PNGs of SensReader/python/SensorData.py:78-91 (pypng there) and the
- * colour PNG that SensorData::saveToImages makes of a TYPE_RAW colour frame (sensorData.h:1432-1440) */
+/* grey (channels = 1), RGB (channels = 3) or RGBA (channels = 4: the `render` stage's pictures, below), 8 or 16 bits: the 16-bit depth PNGs of
+ * SensReader/python/SensorData.py:78-91 (pypng there) and the colour PNG that SensorData::saveToImages makes of a TYPE_RAW colour frame
+ * (sensorData.h:1432-1440) */
 int sf_png_write(const char* path, const void* data, uint32_t width, uint32_t height, int channels, int bits);
 void sf_free(void* p);
 
@@ -955,6 +956,64 @@ int sf_mesh_apply_transform(sf_mesh* mesh, const float transform[16]);
  * stats->outcome set and nothing written.  Prints nothing: bin/alignment prints the reference's messages from *stats. */
 int sf_axis_align_scan(const char* dir, int force, const sf_axis_align_params* params /*nullable*/, int device, sf_axis_align_stats* stats /*nullable*/);
 
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh render and thumbnail: the `render` and `thumbnail` stages (Server/scan_processor.py:159-165 with :42-45; Server/mts_render.py,
+ * Server/thumbnail.sh).  Replaces the Mitsuba preview of the vertex-coloured decimated mesh under a constant sky (mts_render.py:33-66: `diffuse`
+ * with `vertexcolors`, a `constant` emitter, a 45-degree `perspective` sensor, `ldrfilm` RGBA) and its camera (:69-99: the bounding sphere of the
+ * mesh's AABB, bsphere_mult radii out along camera_offset + world_up, turned by theta about world_up).  Mitsuba is not in the reference tree and
+ * its sampler is not specified bit for bit, so the picture is this library's statement of that scene: DESIGN.md section 4j, operation by
+ * operation, with tests/render_checker.c as its executable form (brute force, no tree).  scannet_amd/csrc/render_walk.h is the one statement
+ * of the walk; render.hip runs it on HIP device >= 0, render_host.cpp on host threads (device = -1): the same float bits.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SF_RENDER_PATH = 0, SF_RENDER_AO = 1 };   /* mts_render.py:134-135 --integrator; `mlt` and `vpl` are refused by bin/render */
+#define SF_RENDER_MAX_SAMPLES 4096
+#define SF_RENDER_MAX_DEPTH 16
+#define SF_RENDER_MAX_SIDE 8192
+#define SF_RENDER_MAX_BATCH 32
+typedef struct sf_render_params {
+  int32_t width, height;   /* mts_render.py:140-145: 640 x 480; 1 .. SF_RENDER_MAX_SIDE                                              */
+  int32_t samples;         /* :137-139 samples per pixel: 16; 1 .. SF_RENDER_MAX_SAMPLES                                             */
+  int32_t max_depth;       /* bounces a path may take before a further hit ends it with radiance 0: 8; 1 .. SF_RENDER_MAX_DEPTH      */
+  int32_t integrator;      /* SF_RENDER_PATH, or SF_RENDER_AO: reflectance 1 and one bounce                                          */
+  float fov;               /* :50 degrees across the image WIDTH (Mitsuba's default fovAxis): 45; in (0, 180)                        */
+  float exposure;          /* :152-154 the film scales radiance by 2^exposure: 1.0 (sf_render_film takes it as an argument)          */
+  int32_t pixel_centre;    /* 0: the sub-pixel position of a sample comes from the hash; 1: it is (0.5, 0.5)                         */
+  int32_t reserved[8];
+} sf_render_params;
+void sf_render_params_default(sf_render_params* p);
+typedef struct sf_camera {   /* a view as the walk takes it: right-handed, `forward` into the scene, pixel (0, 0) top left */
+  float origin[3], right[3], up[3], forward[3];
+  float tan_half_fov;      /* tan(fov / 2)                                                                                           */
+  float aspect;            /* width / height                                                                                         */
+  float reserved[2];
+} sf_camera;
+/* mts_render.py:69-99.  The box is the mesh's AABB, or aabb6 = {min x y z, max x y z} when mesh is NULL.  Centre (min + max) / 2, radius the
+ * distance from it to max; origin = centre + bsphere_mult * radius * normalize(camera_offset + world_up), then the origin (about the centre) and
+ * camera_up turned by theta_deg about world_up; forward = towards the centre, right = normalize(forward x camera_up), up = right x forward.
+ * Computed in double, returned as floats.  world_up / camera_up / camera_offset NULL: (0,0,1) / (0,1,0) / (0,0,0).  SF_ERR_INVALID_ARG for a
+ * non-finite input, a zero world_up or camera_offset + world_up, a camera_up parallel to the view direction, an empty box, bad params. */
+int sf_render_camera(const sf_mesh* mesh, const float* aabb6, const sf_render_params* params, const float* world_up, const float* camera_up,
+                     const float* camera_offset, float bsphere_mult, float theta_deg, sf_camera* out);
+typedef struct sf_renderer sf_renderer;
+/* device -1: the host path (threads over rows); >= 0: that HIP device, SF_ERR_DEVICE without one -- never a silent fallback.  params NULL: the defaults. */
+int sf_renderer_create(const sf_render_params* params, int device, sf_renderer** out);
+/* Builds the tree over the mesh (deterministic, on the host) and, on a device, uploads it; may be called again with another mesh.  A mesh without
+ * colours renders with every byte 128.  SF_ERR_INVALID_ARG for an empty mesh, an index >= the vertex count, a non-finite vertex, 2^28 or more triangles. */
+int sf_renderer_set_mesh(sf_renderer* r, const sf_mesh* mesh);
+/* n >= 1 views -> rgba: n x height x width x 4 floats, the mean radiance and alpha of every pixel (before the film).  On a device the views go
+ * SF_RENDER_MAX_BATCH per launch.  kernel_us (nullable): the launches' time by HIP events (device) or the wall time of the rows (host), microseconds. */
+int sf_renderer_run(sf_renderer* r, int n, const sf_camera* cameras, float* rgba, float* kernel_us);
+void sf_renderer_destroy(sf_renderer* r);
+/* The film (Mitsuba's ldrfilm, gamma -1), in double, per pixel: rgb x 2^exposure, the sRGB curve (12.92 v up to 0.0031308, else
+ * 1.055 v^(1/2.4) - 0.055), clamped to [0, 1], (int)(255 v + 0.5); alpha: clamped, (int)(255 a + 0.5).  NaN gives 0. */
+int sf_render_film(const float* rgba, uint64_t num_pixels, float exposure, uint8_t* rgba8);
+/* Server/thumbnail.sh's `convert -resize WxH` (128 x 128 there): the picture fitted into box_w x box_h keeping its aspect ratio -- the side that
+ * fills the box takes the box's size, the other (int)(side * scale + 0.5), at least 1, so 640 x 480 gives 128 x 96 -- by an area average in integer
+ * arithmetic on the 8-bit values of every channel; ImageMagick's filter, pngquant and optipng are not reproduced.  channels 1..4.
+ * out holds box_w x box_h x channels bytes at most; the size comes back in out_w / out_h. */
+int sf_image_thumbnail(const uint8_t* in, uint32_t width, uint32_t height, int channels, uint32_t box_w, uint32_t box_h, uint8_t* out,
+                       uint32_t* out_w, uint32_t* out_h);
 
 #ifdef __cplusplus
 }

@@ -209,6 +209,19 @@ int sf_projector_stage_resolve(sf_projector* p, int n, const uint64_t* keys_in, 
                                float* zcam_out);
 int sf_projector_stage_vote(sf_projector* p, int n, const uint8_t* instance_in, const uint16_t* label_in, uint8_t* instance_out, uint16_t* label_out);
 
+/* Stage hooks of the mesh render (tests/test_render.py, tests/test_render_gpu.py).
+ *   nodes      the tree of the renderer's mesh as the traversal reads it: boxes6 = {min x y z, max x y z} per node (padded as stored), links2 =
+ *              {skip, info} per node (info & 15: the leaf's triangle count, 0 for an inner node); either may be NULL; *n_nodes always comes back,
+ *              SF_ERR_BOUNDS when capacity (in nodes) is smaller
+ *   rays       closest hit of n rays {origin x y z, direction x y z} (finite; the direction as given, not normalised) on the renderer's device
+ *              (k_render_rays) or on the host: tri_out = the mesh index of the triangle or 0xFFFFFFFF, tuv_out = {t, u, v} (0 on a miss)
+ *   sample     the bounce direction about unit normal n3 for (pixel, sample, bounce) (host)
+ *   tune       "leaf": the most triangles the builder leaves in a leaf, 1..15 (default 4), for the sf_renderer_set_mesh calls that follow */
+int sf_render_stage_nodes(const sf_renderer* r, float* boxes6, uint32_t* links2, uint64_t capacity, uint64_t* n_nodes);
+int sf_render_stage_rays(sf_renderer* r, uint64_t n, const float* rays6, uint32_t* tri_out, float* tuv_out);
+int sf_render_stage_sample(const float n3[3], uint32_t pixel, uint32_t sample, uint32_t bounce, float dir3[3]);
+int sf_render_tune(const char* key, int value);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

@@ -235,10 +235,10 @@ SF_API int sf_png_read(const char* path, uint32_t* width, uint32_t* height, int*
 
 SF_API void sf_free(void* p) { std::free(p); }
 
-// Writes a grey (channels = 1) or RGB (channels = 3) image; bits = 8: uint8 samples, bits = 16: uint16 samples in host byte order.
+// Writes a grey (channels = 1), RGB (channels = 3) or RGBA (channels = 4) image; bits = 8: uint8 samples, bits = 16: uint16 samples in host byte order.
 SF_API int sf_png_write(const char* path, const void* data, uint32_t width, uint32_t height, int channels, int bits) {
-  if (!path || !data || width == 0 || height == 0 || (bits != 8 && bits != 16) || (channels != 1 && channels != 3))
-    return sf::fail(SF_ERR_INVALID_ARG, "sf_png_write: bad argument (grey or RGB, 8 or 16 bits)");
+  if (!path || !data || width == 0 || height == 0 || (bits != 8 && bits != 16) || (channels != 1 && channels != 3 && channels != 4))
+    return sf::fail(SF_ERR_INVALID_ARG, "sf_png_write: bad argument (grey, RGB or RGBA, 8 or 16 bits)");
   const size_t bpp = bits / 8, stride = (size_t)width * bpp * channels;
   std::vector<uint8_t> raw((stride + 1) * height);
   const uint8_t* src = (const uint8_t*)data;
@@ -267,7 +267,7 @@ SF_API int sf_png_write(const char* path, const void* data, uint32_t width, uint
   };
   std::vector<uint8_t> ihdr;
   put32(ihdr, width); put32(ihdr, height);
-  ihdr.push_back((uint8_t)bits); ihdr.push_back(channels == 3 ? 2 : 0); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);
+  ihdr.push_back((uint8_t)bits); ihdr.push_back(channels == 4 ? 6 : channels == 3 ? 2 : 0); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);
   chunk("IHDR", ihdr.data(), ihdr.size());
   chunk("IDAT", z.data(), (size_t)zn);
   chunk("IEND", nullptr, 0);
