@@ -26,7 +26,8 @@ typedef enum sf_status {
   SF_ERR_DEVICE = -5,      /* HIP error, no GPU */
   SF_ERR_CAPACITY = -6,    /* SDF block heap or hash table exhausted */
   SF_ERR_BOUNDS = -7,
-  SF_ERR_SKIPPED = -8      /* frame skipped: camToWorld is all -inf (tracking lost, sensorData.h:382) */
+  SF_ERR_SKIPPED = -8,     /* frame skipped: camToWorld is all -inf (tracking lost, sensorData.h:382) */
+  SF_ERR_PARAM = -9        /* a parameter beyond what a kernel can serve (sf_lut_estimator_create: n_slices); nothing was launched */
 } sf_status;
 
 const char* sf_last_error(void);
@@ -1014,6 +1015,69 @@ int sf_render_film(const float* rgba, uint64_t num_pixels, float exposure, uint8
  * out holds box_w x box_h x channels bytes at most; the size comes back in out_w / out_h. */
 int sf_image_thumbnail(const uint8_t* in, uint32_t width, uint32_t height, int channels, uint32_t box_w, uint32_t box_h, uint8_t* out,
                        uint32_t* out_w, uint32_t* out_h);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth-distortion table: estimate and apply (scannet_amd/csrc/depth_lut.hip, depth_lut.cpp).  Replaces the two batch modes
+ * of CameraParameterEstimation/apps/calibrate_depth/src/calibrate_depth.cpp -- EstimateDistortion (:647-836, `-e`) and ApplyUndistortion
+ * (:565-644, `-a`) -- with the table and its file of src/grid3d.h (GetValue :177-209, WriteFile :464-494) and the angle / intersect / normalize of
+ * basics/linalg/geometry.h:58-73 and vector.h:1140-1157.  The OpenGL viewer, calibration_explorer and the Matlab scripts are not provided.
+ * device -1: the host path (the same bits); >= 0: that HIP device, SF_ERR_DEVICE without one -- never a silent fallback.
+ * ---------------------------------------------------------------------------------------------- */
+int sf_lut_save(const char* path, const sf_lut* t);                  /* Grid3D::WriteFile, grid3d.h:464-494: what sf_lut_load reads */
+typedef struct sf_lut_estimator sf_lut_estimator;
+/* Images are width x height u16, both even, width >= 10; the table is (width / 2) x (height / 2) x n_slices (:771-776 hard-codes 640 x 480).
+ * n_slices above what a workgroup's LDS holds (128): SF_ERR_PARAM on either path, nothing is launched.  bitshift: :623 (the default of the tool). */
+int sf_lut_estimator_create(int width, int height, float fx, float fy, float mx, float my, int n_slices, float max_depth, int bitshift, int device,
+                            sf_lut_estimator** out);
+/* n >= 1 host images and their n plane poses (n x 16 floats, row-major, in the depth camera's frame: :680-688), in sequence order; calls chain.
+ * An image whose plane is tilted more than 25 degrees contributes nothing (:691-697).  Synchronous. */
+int sf_lut_estimator_add(sf_lut_estimator* e, int n, const uint16_t* const* images, const float* plane_poses);
+/* the same on device images (4-byte aligned), sf_lut_estimator_max_batch() per launch; kernel_us != NULL: synchronous, the launches' duration in
+ * microseconds; NULL: the last launch is left running on the estimator's stream (sums / finish / destroy order behind it) */
+int sf_lut_estimator_add_device(sf_lut_estimator* e, int n, const void* const* d_images, const float* plane_poses, float* kernel_us);
+int sf_lut_estimator_max_batch(void);   /* images per launch: 64 */
+/* :809-833: divide, side stripe, unknowns -> 1.  out->data is owned by the caller (sf_lut_free); the estimator may go on taking images. */
+int sf_lut_estimator_finish(sf_lut_estimator* e, sf_lut* out);
+void sf_lut_estimator_destroy(sf_lut_estimator* e);
+/* :618-636 on n images of width x height: out = in corrected through the table (which must not be finer than the image).  A result of 65 536 mm
+ * or more, undefined in the reference, is 65 535; where the table's resolution does not divide the image, the last cell serves the remainder. */
+int sf_lut_apply(const sf_lut* lut, int n, const uint16_t* const* in, uint16_t* const* out, int width, int height, int bitshift, int device);
+int sf_lut_apply_device(const sf_lut* lut, int n, const void* const* d_in, void* const* d_out, int width, int height, int bitshift, int device,
+                        float* kernel_us /*nullable*/);
+/* The configuration file (:296-362: `parameters <file>`, `n_images <N>`, `plane_poses <file>`, `scan <depth> <colour> <16 numbers>`, # comments), the
+ * parameter file behind it (sf_calib_params_load; :112-181 reads fx_depth fy_depth mx_depth my_depth depthToColorExtrinsics) and the plane poses
+ * (:184-223): N row-major matrices, each returned as inverse(F D2C F) pose, F = diag(1, -1, -1, 1), the inverse in double.  File names are
+ * relative to root (NULL: the current directory).  plane_poses before parameters and n_images, n_images above the scan lines, a truncated poses
+ * file: SF_ERR_FORMAT (the reference goes on with defaults or uninitialised poses). */
+typedef struct sf_depth_calib {
+  float fx, fy, mx, my;
+  float depth_to_color[16];
+  int32_t n_images, n_scans;   /* the n_images line; the scan lines read (>= n_images) */
+  float* plane_poses;          /* n_images x 16, row-major, converted                */
+  char** image_names;          /* n_scans depth image names                          */
+} sf_depth_calib;
+int sf_depth_calib_load(const char* config_path, const char* root /*nullable*/, sf_depth_calib* out);
+void sf_depth_calib_free(sf_depth_calib* c);
+typedef struct sf_calibrate_depth_options {   /* struct Options, :96-107, defaults :1150-1156 */
+  float max_depth;        /* -d: 5.0 */
+  int32_t n_slices;       /* -s: 15  */
+  int32_t bitshift;       /* -b: 1   */
+  int32_t verbose;        /* -v: the bin table of ReportBinCounts (:516-563) and the skipped images, on stdout */
+  int32_t save_slices;    /* -l: slice_%03d.png under root, the colour ramp of :845-891 */
+  const char* root;       /* depth_raw/, depth/ and the files the configuration names live here; NULL: the current directory */
+  int32_t reserved[8];
+} sf_calibrate_depth_options;
+void sf_calibrate_depth_options_default(sf_calibrate_depth_options* o);
+typedef struct sf_calibrate_depth_stats {
+  uint64_t images, images_used, images_skipped, images_applied;
+  double seconds_read, seconds_estimate, seconds_apply, seconds_write, seconds_total;
+  uint32_t threads;
+} sf_calibrate_depth_stats;
+/* The tool's body: estimate_path != NULL writes the table estimated from depth_raw/<name> (-e); apply_path != NULL then reads that table and
+ * writes depth/<name minus 4 characters>.png from depth_raw/<the same>.png (-a).  Both NULL: SF_ERR_INVALID_ARG (the reference opens its viewer).
+ * PNG decode and encode run on `threads` host threads (<= 0: the CPUs this process may use). */
+int sf_calibrate_depth(const char* config, const char* estimate_path /*nullable*/, const char* apply_path /*nullable*/,
+                       const sf_calibrate_depth_options* options /*nullable*/, int device, int threads, sf_calibrate_depth_stats* stats /*nullable*/);
 
 #ifdef __cplusplus
 }

@@ -222,6 +222,10 @@ int sf_render_stage_rays(sf_renderer* r, uint64_t n, const float* rays6, uint32_
 int sf_render_stage_sample(const float n3[3], uint32_t pixel, uint32_t sample, uint32_t bounce, float dir3[3]);
 int sf_render_tune(const char* key, int value);
 
+/* The raw sums of a depth-distortion table estimator (tests/test_depth_lut.py, tests/test_depth_lut_gpu.py): acc and div,
+ * (width / 2) x (height / 2) x n_slices floats each, before the division; images / used (nullable) = how many were added / passed the angle filter. */
+int sf_lut_estimator_sums(sf_lut_estimator* e, float* acc, float* div, uint64_t* images, uint64_t* used);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

@@ -33,6 +33,7 @@
 #include "codecs_internal.h"
 #include "common.h"
 #include "jpeg_idct.h"
+#include "lut_value.h"
 
 namespace {
 
@@ -105,27 +106,6 @@ __global__ __launch_bounds__(256) void k_undistort_rgb(CalibBatch B, CalibK P) {
   } else {
     for (int k = 0; k < 12 && 3 * i0 + k < 3 * n; k++) dst[3 * i0 + k] = px[k];
   }
-}
-
-// grid3d.cpp:119-151
-__device__ inline float lut_value(const float* __restrict__ t, int xr, int yr, int zr, float x, float y, float z) {
-  const int x1 = (int)x, y1 = (int)y, z1 = (int)z;
-  int x2 = x1 + 1, y2 = y1 + 1, z2 = z1 + 1;
-  if (x2 >= xr) x2 = x1;
-  if (y2 >= yr) y2 = y1;
-  if (z2 >= zr) z2 = z1;
-  const float dx = x - (float)x1, dy = y - (float)y1, dz = z - (float)z1;
-  auto G = [&](int a, int b, int c) { return t[((size_t)c * yr + b) * xr + a]; };
-  float v = 0.0f;
-  v += G(x1, y1, z1) * (1.0f - dx) * (1.0f - dy) * (1.0f - dz);
-  v += G(x1, y1, z2) * (1.0f - dx) * (1.0f - dy) * dz;
-  v += G(x1, y2, z1) * (1.0f - dx) * dy * (1.0f - dz);
-  v += G(x1, y2, z2) * (1.0f - dx) * dy * dz;
-  v += G(x2, y1, z1) * dx * (1.0f - dy) * (1.0f - dz);
-  v += G(x2, y1, z2) * dx * (1.0f - dy) * dz;
-  v += G(x2, y2, z1) * dx * dy * (1.0f - dz);
-  v += G(x2, y2, z2) * dx * dy * dz;
-  return v;
 }
 
 struct Vert { float px, py, z; bool ok; };
