@@ -209,6 +209,22 @@ int sf_projector_stage_resolve(sf_projector* p, int n, const uint64_t* keys_in, 
                                float* zcam_out);
 int sf_projector_stage_vote(sf_projector* p, int n, const uint8_t* instance_in, const uint16_t* label_in, uint8_t* instance_out, uint16_t* label_out);
 
+/* Stage hooks of the calibrate stage (tests/test_calibrate_stages.py; scannet_amd/csrc/calibrate.hip): each call runs ONE of the four launches of
+ * sf_calibrator_run_device on an existing calibrator -- through the helper sf_calibrator_run_device itself launches it with (same kernel, grid, workgroup
+ * and stream) -- on host arrays of n = 1 .. sf_calibrator_max_batch() contiguous frames, and returns the output to the host.  The sizes must be the
+ * calibrator's (w x h depth, cw x ch colour); anything else, or n out of range, is SF_ERR_INVALID_ARG and no launch.
+ *   undistort_rgb  k_undistort_rgb; the frames sit in the staging buffers of sf_calibrator_run, frame j at j * cw*ch*3 bytes
+ *   prepare        k_depth_prepare on raw u16 frames: und_out = the undistorted, table-corrected depth in metres; vert_out = 4 floats per pixel, the
+ *                  mesh vertex {target x, target y, projected z, valid (1 / 0)}; zbuf_out = the cleared depth buffer (the bits of 1.0f)
+ *   raster         k_raster_quads on the caller's depth in metres, vertex records and INITIAL depth buffer; zbuf_out = the buffer as raw 32-bit words.
+ *                  The depth test orders bit patterns: the initial buffer must lie in [0, 1] and a valid vertex must not carry a negative z (what
+ *                  k_depth_prepare guarantees), else SF_ERR_INVALID_ARG
+ *   finalize       k_finalize on the caller's depth buffer and undistorted colour frames (rgb NULL: nothing is invalidated; cw, ch are then ignored) */
+int sf_calibrator_stage_undistort_rgb(sf_calibrator* c, int n, int cw, int ch, const uint8_t* rgb_in, uint8_t* rgb_out);
+int sf_calibrator_stage_prepare(sf_calibrator* c, int n, int w, int h, const uint16_t* depth_in, float* und_out, float* vert_out, uint32_t* zbuf_out);
+int sf_calibrator_stage_raster(sf_calibrator* c, int n, int w, int h, const float* und, const float* vert, const uint32_t* zbuf_in, uint32_t* zbuf_out);
+int sf_calibrator_stage_finalize(sf_calibrator* c, int n, int w, int h, int cw, int ch, const uint32_t* zbuf, const uint8_t* rgb, uint16_t* depth_out);
+
 /* Stage hooks of the mesh render (tests/test_render.py, tests/test_render_gpu.py).
  *   nodes      the tree of the renderer's mesh as the traversal reads it: boxes6 = {min x y z, max x y z} per node (padded as stored), links2 =
  *              {skip, info} per node (info & 15: the leaf's triangle count, 0 for an inner node); either may be NULL; *n_nodes always comes back,

@@ -13,6 +13,10 @@
  *   - the draw call as a software rasteriser with the Direct3D 11 rules: viewport = target size, pixel centres at +0.5,
  *     vertex positions snapped to 1/256 pixel, top-left fill rule, no culling, LESS depth test on a float depth buffer
  *     cleared to 1.0, z interpolated affinely (w = 1) from the three vertices' projected z.
+ *   - the table cell coordinate of a pixel is i / bin and, where it reaches the table's resolution (a resolution that does not divide the image: the
+ *     reference's GetValue asserts there), the last cell's, the rule calibrate_depth's apply mode states;
+ *   - the draw's depth test writes a strictly smaller z; the stages (or_calib_stage_prepare / _raster / _finalize, or_calib_undistort_rgb) are the
+ *     four launches of the HIP path, and or_calib_frame / or_calib_depth_to_color are their composition.
  * The HIP path (scannet_amd/csrc/calibrate.hip) implements the same statements; tests compare them bit for bit and
  * cross-check the rasterised result against the reference's point-splat variant. */
 #include <math.h>
@@ -91,13 +95,19 @@ static float lut_value(const or_lut* t, float x, float y, float z) {
   return v;
 }
 
+/* the table cell coordinate of pixel i: i / bin, the last cell's where it reaches res (a resolution that does not divide the image) */
+static float lut_cell(int i, float bin, int res) {
+  const float x = (float)i / bin;
+  return x >= (float)res ? (float)res - 1.0f : x;
+}
+
 /* calibration.h:226-250, one pixel: u16 in, u16 out (truncating conversion) */
 static uint16_t undistort_distance_px(uint16_t raw, int i, int j, int w, int h, const or_lut* t, float shift) {
   const float xbin = (float)(w / t->xres), ybin = (float)(h / t->yres);
   const float zbin = (float)t->zres / t->max_dist;
   const float depth = (float)raw / shift;
   const float zidx = fminf(depth * zbin, (float)t->zres - 1.0f);
-  const float multiplier = 1.0f / lut_value(t, (float)i / xbin, (float)j / ybin, zidx);
+  const float multiplier = 1.0f / lut_value(t, lut_cell(i, xbin, t->xres), lut_cell(j, ybin, t->yres), zidx);
   const float nd = depth * multiplier * shift;
   if (!(nd >= 0.0f)) return 0;            /* NaN / negative: the reference's cast is undefined there */
   return nd >= 65535.0f ? 65535 : (uint16_t)nd;
@@ -127,10 +137,8 @@ typedef struct { float px, py, z; int ok; } vert_t;
 #define DEPTH_WORLD_MAX 10.0f
 
 /* aligner.hlsl:52-103 ComputeQuadVertex + the viewport transform: target pixel coordinates and projected z */
-static vert_t quad_vertex(const float* depth, int w, int h, const float* Kinv, const float* E, const float* Kc, unsigned wnew, unsigned hnew,
-                          int x, int y) {
+static vert_t quad_vertex(float d, int w, int h, const float* Kinv, const float* E, const float* Kc, unsigned wnew, unsigned hnew, int x, int y) {
   vert_t v;
-  const float d = depth[(size_t)y * w + x];
   const float ax = (float)x * d, ay = (float)y * d;
   /* posCam = Kinv * (x d, y d, d, d), w forced to 1 (:55-56) */
   const float cx = Kinv[0] * ax + Kinv[1] * ay + Kinv[2] * d + Kinv[3] * d;
@@ -219,13 +227,10 @@ static void raster_tri(float* zbuf, int w, int h, const vert_t* a, const vert_t*
     }
 }
 
-/* aligner.h:21-87: result in metres, `invalid` where nothing was drawn */
-void or_calib_depth_to_color(const float* depth, float* out, int w, int h, const or_calib* cb, float invalid) {
-  float Kinv[16];
-  invert_intrinsic(cb->depth_intrinsic, Kinv);
+/* The draw on caller-given data: und = the depth image in metres (the quad tests read it), vert = 4 floats per pixel {target x, target y, projected z,
+ * valid}, zbuf = the depth buffer, initial contents in, result out.  aligner.hlsl:131-173 */
+void or_calib_stage_raster(int w, int h, const float* depth, const float* vert, float* zbuf) {
   const float thresh_lin = 0.05f, thresh_off = 0.01f; /* aligner.h:31-32 */
-  float* zbuf = (float*)malloc((size_t)w * h * sizeof(float));
-  for (size_t i = 0; i < (size_t)w * h; i++) zbuf[i] = 1.0f;
   for (int y = 0; y < h - 1; y++)      /* aligner.hlsl:139-140 */
     for (int x = 0; x < w - 1; x++) {
       const float d0 = depth[(size_t)y * w + x], d1 = depth[(size_t)(y + 1) * w + x], d2 = depth[(size_t)y * w + x + 1], d3 = depth[(size_t)(y + 1) * w + x + 1];
@@ -234,17 +239,40 @@ void or_calib_depth_to_color(const float* depth, float* out, int w, int h, const
       const float dmax = fmaxf(fmaxf(d0, d1), fmaxf(d2, d3)), dmin = fminf(fminf(d0, d1), fminf(d2, d3));
       const float dm = 0.5f * (dmax + dmin);
       if (dmax - dmin > thresh_off + thresh_lin * dm) continue;                                                      /* :154 */
-      const vert_t v0 = quad_vertex(depth, w, h, Kinv, cb->depth_extrinsic, cb->color_intrinsic, cb->color_width, cb->color_height, x, y + 1);
-      const vert_t v1 = quad_vertex(depth, w, h, Kinv, cb->depth_extrinsic, cb->color_intrinsic, cb->color_width, cb->color_height, x, y);
-      const vert_t v2 = quad_vertex(depth, w, h, Kinv, cb->depth_extrinsic, cb->color_intrinsic, cb->color_width, cb->color_height, x + 1, y + 1);
-      const vert_t v3 = quad_vertex(depth, w, h, Kinv, cb->depth_extrinsic, cb->color_intrinsic, cb->color_width, cb->color_height, x + 1, y);
-      if (!(v0.ok && v1.ok && v2.ok && v3.ok)) continue;                                                             /* :162 */
-      raster_tri(zbuf, w, h, &v0, &v1, &v2); /* triangle strip v0 v1 v2 v3 */
-      raster_tri(zbuf, w, h, &v1, &v2, &v3);
+      vert_t v[4];
+      const int at[4][2] = {{x, y + 1}, {x, y}, {x + 1, y + 1}, {x + 1, y}};
+      for (int k = 0; k < 4; k++) {
+        const float* q = vert + 4 * ((size_t)at[k][1] * w + at[k][0]);
+        v[k].px = q[0]; v[k].py = q[1]; v[k].z = q[2]; v[k].ok = q[3] != 0.0f;
+      }
+      if (!(v[0].ok && v[1].ok && v[2].ok && v[3].ok)) continue;                                                     /* :162 */
+      raster_tri(zbuf, w, h, &v[0], &v[1], &v[2]); /* triangle strip v0 v1 v2 v3 */
+      raster_tri(zbuf, w, h, &v[1], &v[2], &v[3]);
     }
+}
+
+/* the mesh vertex of every pixel of a depth image in metres (aligner.hlsl:66-103), 4 floats per pixel */
+static void mesh_vertices(const float* depth, float* vert, int w, int h, const or_calib* cb) {
+  float Kinv[16];
+  invert_intrinsic(cb->depth_intrinsic, Kinv);
+  for (int y = 0; y < h; y++)
+    for (int x = 0; x < w; x++) {
+      const vert_t v = quad_vertex(depth[(size_t)y * w + x], w, h, Kinv, cb->depth_extrinsic, cb->color_intrinsic, cb->color_width, cb->color_height, x, y);
+      float* q = vert + 4 * ((size_t)y * w + x);
+      q[0] = v.px; q[1] = v.py; q[2] = v.z; q[3] = v.ok ? 1.0f : 0.0f;
+    }
+}
+
+/* aligner.h:21-87: result in metres, `invalid` where nothing was drawn */
+void or_calib_depth_to_color(const float* depth, float* out, int w, int h, const or_calib* cb, float invalid) {
+  float* zbuf = (float*)malloc((size_t)w * h * sizeof(float));
+  float* vert = (float*)malloc((size_t)w * h * 4 * sizeof(float));
+  for (size_t i = 0; i < (size_t)w * h; i++) zbuf[i] = 1.0f;
+  mesh_vertices(depth, vert, w, h, cb);
+  or_calib_stage_raster(w, h, depth, vert, zbuf);
   for (size_t i = 0; i < (size_t)w * h; i++)  /* aligner.h:78-81 */
     out[i] = zbuf[i] == 1.0f ? invalid : DEPTH_WORLD_MIN + zbuf[i] * (DEPTH_WORLD_MAX - DEPTH_WORLD_MIN);
-  free(zbuf);
+  free(zbuf); free(vert);
 }
 
 /* aligner.h:90-117 / calibration.h:153-183: the reference's CPU variant (forward point splat, last writer wins in scan order) */
@@ -270,32 +298,55 @@ void or_calib_depth_to_color_splat(const float* depth, float* out, int w, int h,
     }
 }
 
-/* calibration.h:262-304: one frame.  rgb_in / rgb_out may be NULL (no colour: nothing is invalidated by black pixels). */
-void or_calib_frame(const or_calib* cb, const or_lut* lut, float shift, const uint8_t* rgb_in, uint8_t* rgb_out, const uint16_t* depth_in, uint16_t* depth_out) {
+/* calibration.h:272-281 + the vertices and the clear of the draw: raw u16 -> the table-corrected (on the source pixel), undistorted depth in metres,
+ * the mesh vertex of every pixel and the cleared depth buffer.  lut may be NULL. */
+void or_calib_stage_prepare(const or_calib* cb, const or_lut* lut, float shift, const uint16_t* depth_in, float* und, float* vert, float* zbuf) {
+  const int w = (int)cb->depth_width, h = (int)cb->depth_height;
+  for (int y = 0; y < h; y++)
+    for (int x = 0; x < w; x++) {
+      int sx, sy;
+      sample_loc(cb->depth_intrinsic, cb->depth_dist, (unsigned)x, (unsigned)y, &sx, &sy);
+      float v = 0.0f; /* invalid value of the depth image, calibration.h:276 */
+      if (sx >= 0 && sx < w && sy >= 0 && sy < h) {
+        uint16_t u = depth_in[(size_t)sy * w + sx];
+        if (lut) u = undistort_distance_px(u, sx, sy, w, h, lut, shift);                                              /* :272 */
+        v = (float)u / shift;                                                                                          /* :275-278 */
+      }
+      und[(size_t)y * w + x] = v;
+      zbuf[(size_t)y * w + x] = 1.0f;
+    }
+  mesh_vertices(und, vert, w, h, cb);
+}
+
+/* aligner.h:78-81 + calibration.h:286-301: depth buffer -> metres -> "invalidate depth where we have no color" -> u16.  rgb (undistorted) may be NULL. */
+void or_calib_stage_finalize(const or_calib* cb, float shift, const float* zbuf, const uint8_t* rgb, uint16_t* depth_out) {
   const int w = (int)cb->depth_width, h = (int)cb->depth_height, cw = (int)cb->color_width, ch = (int)cb->color_height;
-  if (rgb_in && rgb_out) or_calib_undistort_rgb(rgb_in, rgb_out, cw, ch, cb->color_intrinsic, cb->color_dist);      /* :264-268 */
-  uint16_t* u = (uint16_t*)malloc((size_t)w * h * 2);
-  memcpy(u, depth_in, (size_t)w * h * 2);
-  if (lut) or_calib_undistort_distance(u, w, h, lut, shift);                                                          /* :272 */
-  float* d = (float*)malloc((size_t)w * h * 4);
-  float* e = (float*)malloc((size_t)w * h * 4);
-  for (size_t i = 0; i < (size_t)w * h; i++) d[i] = (float)u[i] / shift;                                               /* :275-278 */
-  or_calib_undistort_f32(d, e, w, h, cb->depth_intrinsic, cb->depth_dist, 0.0f);                                       /* :281 */
-  or_calib_depth_to_color(e, d, w, h, cb, 0.0f);                                                                       /* :283 */
-  if (rgb_out) {                                                                                                       /* :286-295 */
-    const float sw = (float)(w - 1) / (float)(cw - 1), sh = (float)(h - 1) / (float)(ch - 1);
-    for (int y = 0; y < h; y++)
-      for (int x = 0; x < w; x++) {
+  const float sw = (float)(w - 1) / (float)(cw - 1), sh = (float)(h - 1) / (float)(ch - 1);
+  for (int y = 0; y < h; y++)
+    for (int x = 0; x < w; x++) {
+      const float zb = zbuf[(size_t)y * w + x];
+      float d = zb == 1.0f ? 0.0f : DEPTH_WORLD_MIN + zb * (DEPTH_WORLD_MAX - DEPTH_WORLD_MIN);
+      if (rgb) {                                                                                                       /* :286-295 */
         int cx = round_i((float)x / sw), cy = round_i((float)y / sh);
         if (cx > cw - 1) cx = cw - 1;  /* c(x, y) of an out-of-range coordinate is undefined in the reference; clamped */
         if (cy > ch - 1) cy = ch - 1;
-        const uint8_t* p = rgb_out + 3 * ((size_t)cy * cw + cx);
-        if (p[0] == 0 && p[1] == 0 && p[2] == 0) d[(size_t)y * w + x] = 0.0f;
+        const uint8_t* p = rgb + 3 * ((size_t)cy * cw + cx);
+        if (p[0] == 0 && p[1] == 0 && p[2] == 0) d = 0.0f;
       }
-  }
-  for (size_t i = 0; i < (size_t)w * h; i++) {                                                                         /* :298-301 */
-    const int r = round_i(d[i] * shift);
-    depth_out[i] = (uint16_t)(r < 0 ? 0 : (r > 65535 ? 65535 : r));
-  }
-  free(u); free(d); free(e);
+      const int r = round_i(d * shift);                                                                                /* :298-301 */
+      depth_out[(size_t)y * w + x] = (uint16_t)(r < 0 ? 0 : (r > 65535 ? 65535 : r));
+    }
+}
+
+/* calibration.h:262-304: one frame, the composition of the stages.  rgb_in / rgb_out may be NULL (no colour: nothing is invalidated by black pixels). */
+void or_calib_frame(const or_calib* cb, const or_lut* lut, float shift, const uint8_t* rgb_in, uint8_t* rgb_out, const uint16_t* depth_in, uint16_t* depth_out) {
+  const int w = (int)cb->depth_width, h = (int)cb->depth_height, cw = (int)cb->color_width, ch = (int)cb->color_height;
+  if (rgb_in && rgb_out) or_calib_undistort_rgb(rgb_in, rgb_out, cw, ch, cb->color_intrinsic, cb->color_dist);      /* :264-268 */
+  float* und = (float*)malloc((size_t)w * h * 4);
+  float* zbuf = (float*)malloc((size_t)w * h * 4);
+  float* vert = (float*)malloc((size_t)w * h * 16);
+  or_calib_stage_prepare(cb, lut, shift, depth_in, und, vert, zbuf);                                                   /* :272-281 */
+  or_calib_stage_raster(w, h, und, vert, zbuf);                                                                        /* :283 */
+  or_calib_stage_finalize(cb, shift, zbuf, rgb_out, depth_out);                                                        /* :286-301 */
+  free(und); free(zbuf); free(vert);
 }

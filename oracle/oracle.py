@@ -291,6 +291,9 @@ def calib_lib():
     L.or_calib_depth_to_color.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(OrCalib), C.c_float]
     L.or_calib_depth_to_color_splat.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(OrCalib), C.c_float]
     L.or_calib_frame.argtypes = [C.POINTER(OrCalib), C.POINTER(OrLut), C.c_float, vp, vp, vp, vp]
+    L.or_calib_stage_prepare.argtypes = [C.POINTER(OrCalib), C.POINTER(OrLut), C.c_float, vp, vp, vp, vp]
+    L.or_calib_stage_raster.argtypes = [C.c_int, C.c_int, vp, vp, vp]
+    L.or_calib_stage_finalize.argtypes = [C.POINTER(OrCalib), C.c_float, vp, vp, vp]
     return L
 
 
@@ -323,6 +326,50 @@ def calib_frame(cb, depth, rgb=None, lut_grid=None, lut_max_dist=0.0, shift=1000
     L.or_calib_frame(C.byref(cb), C.byref(lut) if lut is not None else None, float(shift), rin.ctypes.data if rin is not None else None,
                      rout.ctypes.data if rout is not None else None, d.ctypes.data, dout.ctypes.data)
     return dout, rout
+
+
+def calib_undistort_rgb(cb, rgb):
+    """One colour frame [Hc, Wc, 3] through Calibration::undistort."""
+    r = np.ascontiguousarray(rgb, np.uint8)
+    out = np.empty_like(r)
+    K = np.array(cb.color_intrinsic, np.float32)
+    k = np.array(cb.color_dist, np.float32)
+    calib_lib().or_calib_undistort_rgb(r.ctypes.data, out.ctypes.data, r.shape[1], r.shape[0], K.ctypes.data, k.ctypes.data)
+    return out
+
+
+def calib_stage_prepare(cb, depth, lut_grid=None, lut_max_dist=0.0, shift=1000.0):
+    """One raw frame [H, W] uint16 -> (depth in metres, vertex records [H, W, 4], cleared depth buffer as uint32 words)."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    h, w = d.shape
+    lut = None
+    if lut_grid is not None:
+        g = np.ascontiguousarray(lut_grid, np.float32)
+        lut = OrLut(g.shape[2], g.shape[1], g.shape[0], float(lut_max_dist), g.ctypes.data)
+    und, vert, zbuf = np.empty((h, w), np.float32), np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
+    calib_lib().or_calib_stage_prepare(C.byref(cb), C.byref(lut) if lut is not None else None, float(shift), d.ctypes.data, und.ctypes.data, vert.ctypes.data,
+                                       zbuf.ctypes.data)
+    return und, vert, zbuf.view(np.uint32)
+
+
+def calib_stage_raster(und, vert, zbuf):
+    """The draw of one frame on caller-given depth [H, W], vertex records [H, W, 4] and initial depth buffer (uint32 words) -> the depth buffer."""
+    u = np.ascontiguousarray(und, np.float32)
+    v = np.ascontiguousarray(vert, np.float32)
+    z = np.array(zbuf, np.uint32).view(np.float32)      # a copy: the stage works in place
+    h, w = u.shape
+    assert v.shape == (h, w, 4) and z.shape == (h, w)
+    calib_lib().or_calib_stage_raster(w, h, u.ctypes.data, v.ctypes.data, z.ctypes.data)
+    return z.view(np.uint32)
+
+
+def calib_stage_finalize(cb, zbuf, rgb=None, shift=1000.0):
+    """Depth buffer (uint32 words) [H, W] and the undistorted colour frame or None -> uint16 [H, W]."""
+    z = np.ascontiguousarray(zbuf, np.uint32)
+    r = None if rgb is None else np.ascontiguousarray(rgb, np.uint8)
+    out = np.empty(z.shape, np.uint16)
+    calib_lib().or_calib_stage_finalize(C.byref(cb), float(shift), z.ctypes.data, r.ctypes.data if r is not None else None, out.ctypes.data)
+    return out
 
 
 # ---------------------------------------------------------------- 2-D annotation filter (oracle/filter2d_oracle.c)

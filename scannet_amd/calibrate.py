@@ -31,6 +31,11 @@ def _lib():
     L.sf_calibrator_destroy.restype = None
     L.sf_calibrator_run.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.sf_calibrator_run_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_float)]
+    L.sf_calibrator_max_batch.argtypes = []
+    L.sf_calibrator_stage_undistort_rgb.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.sf_calibrator_stage_prepare.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.sf_calibrator_stage_raster.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.sf_calibrator_stage_finalize.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.sf_calibrate_sens.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(SfCalibrateStats)]
     L.sf_jpeg_encode.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     return L
@@ -173,3 +178,47 @@ class Calibrator:
             ro = arr([rout[i].ctypes.data for i in range(n)])
         check(_lib().sf_calibrator_run(self._h, n, ri, ro, di, do))
         return dout, rout
+
+    # ---- stage hooks (include/scanfuse_internal.h): one launch of run() each, on host arrays of n frames
+    def stage_undistort_rgb(self, rgb_frames):
+        """[n, Hc, Wc, 3] uint8 -> the undistorted frames (k_undistort_rgb, in the staging layout of run())."""
+        r = np.ascontiguousarray(rgb_frames, np.uint8)
+        out = np.empty_like(r)
+        check(_lib().sf_calibrator_stage_undistort_rgb(self._h, r.shape[0], r.shape[2], r.shape[1], r.ctypes.data, out.ctypes.data))
+        return out
+
+    def stage_prepare(self, depth_frames):
+        """[n, H, W] uint16 -> (depth in metres [n, H, W] float32, vertex records {px, py, z, ok} [n, H, W, 4] float32, the cleared depth buffer
+        [n, H, W] uint32) (k_depth_prepare)."""
+        d = np.ascontiguousarray(depth_frames, np.uint16)
+        n, h, w = d.shape
+        und, vert, zbuf = np.empty((n, h, w), np.float32), np.empty((n, h, w, 4), np.float32), np.empty((n, h, w), np.uint32)
+        check(_lib().sf_calibrator_stage_prepare(self._h, n, w, h, d.ctypes.data, und.ctypes.data, vert.ctypes.data, zbuf.ctypes.data))
+        return und, vert, zbuf
+
+    def stage_raster(self, und, vert, zbuf):
+        """The draw on the caller's depth in metres [n, H, W], vertex records [n, H, W, 4] and initial depth buffer [n, H, W] uint32 (the bits of floats
+        in [0, 1]) -> the depth buffer as raw words (k_raster_quads)."""
+        u = np.ascontiguousarray(und, np.float32)
+        v = np.ascontiguousarray(vert, np.float32)
+        z = np.ascontiguousarray(zbuf, np.uint32)
+        n, h, w = u.shape
+        if v.shape != (n, h, w, 4) or z.shape != (n, h, w):
+            raise ValueError("stage_raster: vertex records %r and depth buffer %r for depth %r" % (v.shape, z.shape, u.shape))
+        out = np.empty_like(z)
+        check(_lib().sf_calibrator_stage_raster(self._h, n, w, h, u.ctypes.data, v.ctypes.data, z.ctypes.data, out.ctypes.data))
+        return out
+
+    def stage_finalize(self, zbuf, rgb_frames=None):
+        """Depth buffer [n, H, W] uint32 and the undistorted colour frames [n, Hc, Wc, 3] or None -> [n, H, W] uint16 (k_finalize)."""
+        z = np.ascontiguousarray(zbuf, np.uint32)
+        n, h, w = z.shape
+        r, cw, ch = None, 0, 0
+        if rgb_frames is not None:
+            r = np.ascontiguousarray(rgb_frames, np.uint8)
+            if r.shape[0] != n:
+                raise ValueError("stage_finalize: %d colour frames for %d depth buffers" % (r.shape[0], n))
+            ch, cw = r.shape[1:3]
+        out = np.empty((n, h, w), np.uint16)
+        check(_lib().sf_calibrator_stage_finalize(self._h, n, w, h, cw, ch, z.ctypes.data, r.ctypes.data if r is not None else None, out.ctypes.data))
+        return out

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void k_depth_prepare(CalibBatch B, CalibK P, c
       const float zbin = (float)P.lz / P.lmax;
       const float depth = (float)u / P.shift;
       const float zidx = fminf(depth * zbin, (float)P.lz - 1.0f);
-      const float multiplier = 1.0f / lut_value(lut, P.lx, P.ly, P.lz, (float)sx / xbin, (float)sy / ybin, zidx);
+      const float multiplier = 1.0f / lut_value(lut, P.lx, P.ly, P.lz, lut_cell(sx, xbin, P.lx), lut_cell(sy, ybin, P.ly), zidx);
       const float nd = depth * multiplier * P.shift;
       u = !(nd >= 0.0f) ? (uint16_t)0 : (nd >= 65535.0f ? (uint16_t)65535 : (uint16_t)nd);
     }
@@ -373,6 +373,9 @@ SF_API int sf_calibrator_create(const sf_calib_params* p, const sf_lut* lut, flo
   if (!p->depth_width || !p->depth_height || p->color_width < 2 || p->color_height < 2 || !(depth_shift > 0.0f) || !(p->depth_intrinsic[0] != 0.0f) ||
       !(p->depth_intrinsic[5] != 0.0f) || !(p->color_intrinsic[0] != 0.0f) || !(p->color_intrinsic[5] != 0.0f))
     return sf::fail(SF_ERR_INVALID_ARG, "invalid calibration parameters");
+  // sf_lut_load checks a file's header; a table handed over in memory is checked here: max_dist divides the slice index
+  if (lut && lut->data && (lut->xres <= 0 || lut->yres <= 0 || lut->zres <= 0 || !(lut->max_dist > 0.0f) || !std::isfinite(lut->max_dist)))
+    return sf::fail(SF_ERR_INVALID_ARG, "implausible look-up table %d x %d x %d, max distance %g", lut->xres, lut->yres, lut->zres, (double)lut->max_dist);
   if (lut && lut->data && (lut->xres > (int)p->depth_width || lut->yres > (int)p->depth_height))
     return sf::fail(SF_ERR_INVALID_ARG, "look-up table is finer than the depth image");
   int ndev = 0;
@@ -431,6 +434,24 @@ SF_API int sf_calibrator_create(const sf_calib_params* p, const sf_lut* lut, flo
 
 SF_API int sf_calibrator_max_batch(void) { return CALIB_MAX_BATCH; }
 
+// The four launches of a batch of n frames on the calibrator's stream: sf_calibrator_run_device and the stage hooks below go through these.
+static void cal_launch_undistort_rgb(const sf_calibrator* c, int n, const CalibBatch& b) {
+  const size_t cn = (size_t)c->k.cw * c->k.ch;
+  hipLaunchKernelGGL(k_undistort_rgb, dim3((unsigned)((cn / 4 + 1 + 255) / 256), 1, n), dim3(256), 0, c->stream, b, c->k);
+}
+static void cal_launch_prepare(const sf_calibrator* c, int n, const CalibBatch& b) {
+  const int np = c->k.w * c->k.h;
+  hipLaunchKernelGGL(k_depth_prepare, dim3((np + 255) / 256, 1, n), dim3(256), 0, c->stream, b, c->k, c->lut, c->und, c->zbuf, c->vert);
+}
+static void cal_launch_raster(const sf_calibrator* c, int n) {
+  const int np = c->k.w * c->k.h;
+  hipLaunchKernelGGL(k_raster_quads, dim3((np + 255) / 256, 1, n), dim3(256), 0, c->stream, c->k, c->und, c->vert, c->zbuf);
+}
+static void cal_launch_finalize(const sf_calibrator* c, int n, const CalibBatch& b) {
+  const int np = c->k.w * c->k.h;
+  hipLaunchKernelGGL(k_finalize, dim3((np + 255) / 256, 1, n), dim3(256), 0, c->stream, b, c->k, c->zbuf);
+}
+
 // n <= 16 frames, device pointers.  rgb_in / rgb_out NULL (all frames): depth only, nothing invalidated by black pixels.
 // Asynchronous on the calibrator's stream; kernel_us (nullable) makes it synchronous and returns the four launches' duration.
 SF_API int sf_calibrator_run_device(sf_calibrator* c, int n, const void* const* d_rgb_in, void* const* d_rgb_out, const void* const* d_depth_in,
@@ -448,14 +469,11 @@ SF_API int sf_calibrator_run_device(sf_calibrator* c, int n, const void* const* 
     b.depth_out[j] = (uint16_t*)d_depth_out[j];
     if (!b.depth_in[j] || !b.depth_out[j] || (rgb && (!b.rgb_in[j] || !b.rgb_out[j]))) return sf::fail(SF_ERR_INVALID_ARG, "NULL frame pointer in batch");
   }
-  const CalibK& k = c->k;
-  const int np = k.w * k.h;
-  const size_t cn = (size_t)k.cw * k.ch;
   if (kernel_us) SF_HIP_CHECK(hipEventRecord(c->e0, c->stream));
-  if (rgb) hipLaunchKernelGGL(k_undistort_rgb, dim3((unsigned)((cn / 4 + 1 + 255) / 256), 1, n), dim3(256), 0, c->stream, b, k);
-  hipLaunchKernelGGL(k_depth_prepare, dim3((np + 255) / 256, 1, n), dim3(256), 0, c->stream, b, k, c->lut, c->und, c->zbuf, c->vert);
-  hipLaunchKernelGGL(k_raster_quads, dim3((np + 255) / 256, 1, n), dim3(256), 0, c->stream, k, c->und, c->vert, c->zbuf);
-  hipLaunchKernelGGL(k_finalize, dim3((np + 255) / 256, 1, n), dim3(256), 0, c->stream, b, k, c->zbuf);
+  if (rgb) cal_launch_undistort_rgb(c, n, b);
+  cal_launch_prepare(c, n, b);
+  cal_launch_raster(c, n);
+  cal_launch_finalize(c, n, b);
   SF_HIP_CHECK(hipGetLastError());
   if (kernel_us) {
     SF_HIP_CHECK(hipEventRecord(c->e1, c->stream));
@@ -495,6 +513,92 @@ SF_API int sf_calibrator_run(sf_calibrator* c, int n, const uint8_t* const* rgb_
     SF_HIP_CHECK(hipMemcpyAsync(depth_out[j], dout[j], nb, hipMemcpyDeviceToHost, c->stream));
     if (rgb) SF_HIP_CHECK(hipMemcpyAsync(rgb_out[j], ro[j], cb, hipMemcpyDeviceToHost, c->stream));
   }
+  SF_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return SF_OK;
+}
+
+// ---- stage hooks (include/scanfuse_internal.h) -------------------------------------------------------------------------------------------------
+// One launch of sf_calibrator_run_device each, on host arrays of n contiguous frames, in the staging layout of sf_calibrator_run.
+static int cal_stage_args(const sf_calibrator* c, int n, bool depth, int w, int h, bool colour, int cw, int ch) {
+  if (!c) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (n < 1 || n > CALIB_MAX_BATCH) return sf::fail(SF_ERR_INVALID_ARG, "batch of %d frames (limit %d)", n, CALIB_MAX_BATCH);
+  if ((depth && (w != c->k.w || h != c->k.h)) || (colour && (cw != c->k.cw || ch != c->k.ch)))
+    return sf::fail(SF_ERR_INVALID_ARG, "frames of %d x %d / %d x %d for a calibrator of %d x %d / %d x %d", w, h, cw, ch, c->k.w, c->k.h, c->k.cw, c->k.ch);
+  return SF_OK;
+}
+
+static CalibBatch cal_stage_batch(const sf_calibrator* c, int n, bool rgb) {
+  const size_t nb = (size_t)c->k.w * c->k.h * 2, cb = (size_t)c->k.cw * c->k.ch * 3;
+  CalibBatch b;
+  std::memset(&b, 0, sizeof(b));
+  for (int j = 0; j < n; j++) {
+    b.rgb_in[j] = rgb ? c->d_rgb_in + j * cb : nullptr;
+    b.rgb_out[j] = rgb ? c->d_rgb_out + j * cb : nullptr;
+    b.depth_in[j] = (const uint16_t*)((uint8_t*)c->d_depth_in + j * nb);
+    b.depth_out[j] = (uint16_t*)((uint8_t*)c->d_depth_out + j * nb);
+  }
+  return b;
+}
+
+SF_API int sf_calibrator_stage_undistort_rgb(sf_calibrator* c, int n, int cw, int ch, const uint8_t* rgb_in, uint8_t* rgb_out) {
+  if (const int rc = cal_stage_args(c, n, false, 0, 0, true, cw, ch)) return rc;
+  if (!rgb_in || !rgb_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(c->device));
+  const size_t cb = (size_t)c->k.cw * c->k.ch * 3;
+  SF_HIP_CHECK(hipMemcpyAsync(c->d_rgb_in, rgb_in, n * cb, hipMemcpyHostToDevice, c->stream));
+  cal_launch_undistort_rgb(c, n, cal_stage_batch(c, n, true));
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(rgb_out, c->d_rgb_out, n * cb, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return SF_OK;
+}
+
+SF_API int sf_calibrator_stage_prepare(sf_calibrator* c, int n, int w, int h, const uint16_t* depth_in, float* und_out, float* vert_out, uint32_t* zbuf_out) {
+  if (const int rc = cal_stage_args(c, n, true, w, h, false, 0, 0)) return rc;
+  if (!depth_in || !und_out || !vert_out || !zbuf_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(c->device));
+  const size_t np = (size_t)n * c->k.w * c->k.h;
+  SF_HIP_CHECK(hipMemcpyAsync(c->d_depth_in, depth_in, np * 2, hipMemcpyHostToDevice, c->stream));
+  cal_launch_prepare(c, n, cal_stage_batch(c, n, false));
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(und_out, c->und, np * 4, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(vert_out, c->vert, np * 16, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(zbuf_out, c->zbuf, np * 4, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return SF_OK;
+}
+
+SF_API int sf_calibrator_stage_raster(sf_calibrator* c, int n, int w, int h, const float* und, const float* vert, const uint32_t* zbuf_in, uint32_t* zbuf_out) {
+  if (const int rc = cal_stage_args(c, n, true, w, h, false, 0, 0)) return rc;
+  if (!und || !vert || !zbuf_in || !zbuf_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  const size_t np = (size_t)n * c->k.w * c->k.h;
+  // the depth test is a 32-bit atomicMin on the bits: it orders what k_depth_prepare produces, a buffer in [0, 1] and valid vertices without a sign
+  for (size_t i = 0; i < np; i++) {
+    if (zbuf_in[i] > 0x3f800000u) return sf::fail(SF_ERR_INVALID_ARG, "depth buffer word %llu is outside [0, 1]", (unsigned long long)i);
+    const float z = vert[4 * i + 2];
+    if (vert[4 * i + 3] != 0.0f && std::signbit(z) && !std::isnan(z)) return sf::fail(SF_ERR_INVALID_ARG, "valid vertex %llu has a negative z", (unsigned long long)i);
+  }
+  SF_HIP_CHECK(hipSetDevice(c->device));
+  SF_HIP_CHECK(hipMemcpyAsync(c->und, und, np * 4, hipMemcpyHostToDevice, c->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(c->vert, vert, np * 16, hipMemcpyHostToDevice, c->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(c->zbuf, zbuf_in, np * 4, hipMemcpyHostToDevice, c->stream));
+  cal_launch_raster(c, n);
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(zbuf_out, c->zbuf, np * 4, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return SF_OK;
+}
+
+SF_API int sf_calibrator_stage_finalize(sf_calibrator* c, int n, int w, int h, int cw, int ch, const uint32_t* zbuf, const uint8_t* rgb, uint16_t* depth_out) {
+  if (const int rc = cal_stage_args(c, n, true, w, h, rgb != nullptr, cw, ch)) return rc;
+  if (!zbuf || !depth_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(c->device));
+  const size_t np = (size_t)n * c->k.w * c->k.h, cb = (size_t)c->k.cw * c->k.ch * 3;
+  SF_HIP_CHECK(hipMemcpyAsync(c->zbuf, zbuf, np * 4, hipMemcpyHostToDevice, c->stream));
+  if (rgb) SF_HIP_CHECK(hipMemcpyAsync(c->d_rgb_out, rgb, n * cb, hipMemcpyHostToDevice, c->stream));
+  cal_launch_finalize(c, n, cal_stage_batch(c, n, rgb != nullptr));
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(depth_out, c->d_depth_out, np * 2, hipMemcpyDeviceToHost, c->stream));
   SF_HIP_CHECK(hipStreamSynchronize(c->stream));
   return SF_OK;
 }

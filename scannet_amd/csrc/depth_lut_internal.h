@@ -62,14 +62,12 @@ struct LutApplyK {
 };
 
 // :622-634.  Where the table's resolution does not divide the image, i / xbin can reach xres: the reference's GetValue asserts there; the
-// coordinate is then the last cell's.  A product of 65 536 or more (undefined in the reference) is 65 535; a negative or NaN one is 0.
+// coordinate is then the last cell's (lut_cell, lut_value.h).  A product of 65 536 or more (undefined in the reference) is 65 535; a negative or NaN one is 0.
 __host__ __device__ inline uint16_t lut_apply_pixel(const LutApplyK& k, const float* __restrict__ t, int i, int j, uint16_t raw) {
   const uint16_t d = k.bitshift ? lut_unshift(raw) : raw;
   const float depth = (float)d * 0.001f;
   const float zi = fminf(depth * k.zbin, (float)k.zr - 1.0f);
-  float x = (float)i / k.xbin, y = (float)j / k.ybin;
-  if (x >= (float)k.xr) x = (float)k.xr - 1.0f;
-  if (y >= (float)k.yr) y = (float)k.yr - 1.0f;
+  const float x = lut_cell(i, k.xbin, k.xr), y = lut_cell(j, k.ybin, k.yr);
   const float mult = 1.0f / lut_value(t, k.xr, k.yr, k.zr, x, y, zi);
   const float v = 1000.0f * (depth * mult);
   uint16_t nd = !(v >= 0.0f) ? (uint16_t)0 : (v >= 65535.0f ? (uint16_t)65535 : (uint16_t)v);

@@ -4,7 +4,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// grid3d.cpp:119-151
+// The table cell coordinate of pixel i along an axis of `res` cells, bin = (float)(size / res) pixels per cell (calibration.h:241, calibrate_depth.cpp:626).
+// Where res does not divide the image size, i / bin reaches res (the reference's GetValue asserts there): the coordinate is then the last cell's.
+__host__ __device__ inline float lut_cell(int i, float bin, int res) {
+  const float x = (float)i / bin;
+  return x >= (float)res ? (float)res - 1.0f : x;
+}
+
+// grid3d.cpp:119-151.  x in [0, xr), y in [0, yr), z in [0, zr): only the upper neighbour is clamped.
 __host__ __device__ inline float lut_value(const float* __restrict__ t, int xr, int yr, int zr, float x, float y, float z) {
   const int x1 = (int)x, y1 = (int)y, z1 = (int)z;
   int x2 = x1 + 1, y2 = y1 + 1, z2 = z1 + 1;

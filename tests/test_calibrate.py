@@ -235,6 +235,18 @@ def test_gpu_edge_cases():
         dout, rout = cal.run(d[None], rgb[None])
         do, ro = orc.calib_frame(cb, d, rgb)
         assert np.array_equal(rout[0], ro) and np.array_equal(dout[0], do)
+    # the same sizes with the 18 x 14 x 2 table calibrate_depth writes for a 37 x 29 image (the bin of 2 does not divide 37 or 29: the last column
+    # and row read the table's last cell), three frames: the colour frames of a batch start at every alignment (53 * 41 * 3 bytes is odd)
+    grid = (1.0 + 0.05 * rng.standard_normal((2, 14, 18))).astype(np.float32)
+    d3 = np.stack([d, d[::-1], (d.astype(np.int64) * 3 // 2).astype(np.uint16)])
+    rgb3 = rng.integers(0, 256, (3, ch, cw, 3), dtype=np.uint8)
+    with calibrate.Calibrator(p, grid, 4.0) as cal:
+        dout, rout = cal.run(d3, rgb3)
+        for i in range(3):
+            do, ro = orc.calib_frame(cb, d3[i], rgb3[i], grid, 4.0)
+            assert np.array_equal(rout[i], ro), "colour frame %d" % i
+            assert np.array_equal(dout[i], do), "depth frame %d: %d pixels differ" % (i, (dout[i] != do).sum())
+        assert (dout > 0).mean() > 0.5
 
 
 @pytest.mark.gpu
