@@ -100,6 +100,24 @@ struct sf_mesh;
 int sf_simplify_probe_edge(const struct sf_mesh* in, const sf_simplify_params* p, uint32_t v0, uint32_t v1, double quadric10[10], float position[3],
                            float* priority, double* scale_factor);
 
+/* Stage hooks of the GPU decimation (tests/test_simplify_stages.py; scannet_amd/csrc/simplify_gpu.hip): each call runs ONE part of a round of
+ * sf_mesh_simplify_gpu on host arrays -- V vertices, F faces, `alive` one byte per face -- through the helpers its round loop itself calls (same
+ * kernels, grids, workgroups, sorts), and returns the result to the host.  Edges are numbered in key order (v0 << 32 | v1, v0 < v1) over the live faces.
+ *   edges     k_emit, the sorts, k_vertex_ranges, k_fix_counts, the run-length encode, k_init_quadrics (Q_in == NULL; otherwise Q_in, V x 10 doubles
+ *             {a00 a01 a02 a11 a12 a22, b0 b1 b2, c}, is used), k_priority and the quantile.  scale <= 0: ScaleFactor of pos' bounding box.  Arrays
+ *             sized for 3 F edges; tau is the clamped threshold of a round that still needs `needed` collapses (`stalled` != 0: no threshold).
+ *   winners   the three passes of k_lock / k_winners on priorities of the CALLER's (E_in must be the mesh's edge count): pass_out[e] = the pass in
+ *             which edge e won (1..3, 0 = none), taken_out[V] after the third pass, counters = {winners, faces removed, top priority bits}.
+ *   collapse  k_collapse on the n edges named (they must be independent, as one round's winners are), x = 3 floats per edge; pos, tri, alive and Q
+ *             are updated in place, vdel_out[V] marks the deleted vertices. */
+int sf_simplify_stage_edges(int device, uint32_t V, uint32_t F, const float* pos, const uint32_t* tri, const uint8_t* alive, const double* Q_in /*nullable*/,
+                            const sf_simplify_params* p, double scale, uint64_t needed, int stalled, uint32_t* E_out, uint64_t* ukey, uint32_t* ucnt,
+                            double* Q_out, float* pri, float* x, float* tau_out, double* scale_out /*nullable*/);
+int sf_simplify_stage_winners(int device, uint32_t V, uint32_t F, const uint32_t* tri, const uint8_t* alive, uint32_t E_in, const float* pri, float tau,
+                              uint32_t round, uint8_t* pass_out, uint8_t* taken_out, uint32_t counters[3]);
+int sf_simplify_stage_collapse(int device, uint32_t V, uint32_t F, float* pos, uint32_t* tri, uint8_t* alive, double* Q, uint32_t n, const uint32_t* edges,
+                               uint32_t E_in, const float* x, uint8_t* vdel_out);
+
 /* Device self-test: the hand-expanded correctly rounded divisions of the integrate and allocation kernels against the hardware's IEEE
  * division -- all 2^23 mantissas x 9 exponents for 1/x, 511 integer divisors x 2^21 numerators for n/m, 2^28 general operand pairs
  * (incl. near-exact and near-half-way quotients) for a/b.  All three counts must be 0 (tests/test_gpu_tsdf.py). */

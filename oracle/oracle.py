@@ -516,3 +516,71 @@ def simplify_rounds(xyz, tris, rgba=None, target_perc=0.2, target_faces=0, quali
     if rc != 0:
         raise RuntimeError("or_simplify_rounds failed (%d)" % rc)
     return vo[:nv.value], (None if co is None else co[:nv.value]), to[:nf.value], {"rounds": rounds.value, "collapses": coll.value}
+
+
+# The same rule stage by stage (or_simplify_stage_*): what tests/test_simplify_stages.py holds the stage hooks of simplify_gpu.hip to, and
+# or_simplify_rounds is the composition of.  Same argument and result layout as scannet_amd.meshclean.stage_edges / stage_winners / stage_collapse.
+def _simplify_mesh_args(xyz, tris, alive):
+    import numpy as np
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    v = None if xyz is None else np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    a = np.ones(len(t), np.uint8) if alive is None else np.ascontiguousarray(alive, np.uint8).reshape(-1)
+    assert len(a) == len(t)
+    return v, t, a
+
+
+def simplify_stage_edges(xyz, tris, alive=None, Q=None, quality_thr=0.3, boundary_weight=1.0, optimal_placement=True, planar_quadric=False, scale=0.0, needed=0,
+                         stalled=0):
+    """-> {"E", "ukey" [E] u64, "ucnt" [E] u32, "Q" [V,10] f64, "pri" [E] f32, "x" [E,3] f32, "tau" f32, "scale"}"""
+    import numpy as np
+    L = lib()
+    vp = C.c_void_p
+    L.or_simplify_stage_edges.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_float, C.c_float, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int,
+                                          C.POINTER(C.c_uint32), vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    v, t, a = _simplify_mesh_args(xyz, tris, alive)
+    q = None if Q is None else np.ascontiguousarray(Q, np.float64).reshape(len(v), 10)
+    n = 3 * len(t)
+    ukey, ucnt, pri, x, Qo = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros((len(v), 10), np.float64)
+    E, tau, sc = C.c_uint32(0), C.c_float(0), C.c_double(0)
+    rc = L.or_simplify_stage_edges(len(v), len(t), v.ctypes.data, t.ctypes.data, a.ctypes.data, None if q is None else q.ctypes.data, float(quality_thr),
+                                   float(boundary_weight), int(bool(optimal_placement)), int(bool(planar_quadric)), float(scale), int(needed), int(stalled), C.byref(E),
+                                   ukey.ctypes.data, ucnt.ctypes.data, Qo.ctypes.data, pri.ctypes.data, x.ctypes.data, C.byref(tau), C.byref(sc))
+    if rc != 0:
+        raise RuntimeError("or_simplify_stage_edges failed (%d)" % rc)
+    e = E.value
+    return {"E": e, "ukey": ukey[:e], "ucnt": ucnt[:e], "Q": Qo, "pri": pri[:e], "x": x[:e], "tau": np.float32(tau.value), "scale": sc.value}
+
+
+def simplify_stage_winners(nv, tris, alive, pri, tau, round_no):
+    """-> {"passes" [E] u8 (0 = no win, 1..3), "taken" [V] u8, "counters" [3] u32 = winners, faces removed, top priority bits}"""
+    import numpy as np
+    L = lib()
+    vp = C.c_void_p
+    L.or_simplify_stage_winners.argtypes = [C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_float, C.c_uint32, vp, vp, vp]
+    _, t, a = _simplify_mesh_args(None, tris, alive)
+    p = np.ascontiguousarray(pri, np.float32).reshape(-1)
+    passes, taken, cnt = np.zeros(len(p), np.uint8), np.zeros(nv, np.uint8), np.zeros(3, np.uint32)
+    rc = L.or_simplify_stage_winners(int(nv), len(t), t.ctypes.data, a.ctypes.data, len(p), p.ctypes.data, float(tau), int(round_no), passes.ctypes.data,
+                                     taken.ctypes.data, cnt.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("or_simplify_stage_winners failed (%d)" % rc)
+    return {"passes": passes, "taken": taken, "counters": cnt}
+
+
+def simplify_stage_collapse(xyz, tris, alive, Q, edges, x):
+    """-> {"pos", "tri", "alive", "Q", "vdel"}: copies, the arguments are left alone"""
+    import numpy as np
+    L = lib()
+    vp = C.c_void_p
+    L.or_simplify_stage_collapse.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+    v, t, a = _simplify_mesh_args(xyz, tris, alive)
+    v, t, a = v.copy(), t.copy(), a.copy()
+    q = np.array(Q, np.float64).reshape(len(v), 10)
+    ed = np.ascontiguousarray(edges, np.uint32).reshape(-1)
+    xs = np.ascontiguousarray(x, np.float32).reshape(-1, 3)
+    vdel = np.zeros(len(v), np.uint8)
+    rc = L.or_simplify_stage_collapse(len(v), len(t), v.ctypes.data, t.ctypes.data, a.ctypes.data, q.ctypes.data, len(ed), ed.ctypes.data, len(xs), xs.ctypes.data,
+                                      vdel.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("or_simplify_stage_collapse failed (%d)" % rc)
+    return {"pos": v, "tri": t, "alive": a, "Q": q, "vdel": vdel}

@@ -191,7 +191,10 @@ __global__ __launch_bounds__(128) void k_priority(Mesh M, const uint64_t* __rest
       }
     }
   }
-  // link condition: distinct common neighbours == faces on the edge
+  // link condition: common neighbours == faces on the edge.  Counted PER CORNER of v1, not per distinct vertex: a neighbour of v1 counts once for
+  // every candidate slot that names it.  Where every edge has at most two consistently oriented faces each neighbour fills exactly one slot and the
+  // count is that of the distinct common neighbours; on a soup (three faces on an edge, duplicate or flipped faces) a neighbour can fill several, and
+  // the test then rejects or accepts by the slot count -- tests/test_simplify_stages.py holds soups to the checker alone for that reason.
   int common = 0;
   if (!reject) {
     for (uint32_t i = 0; i < M.vcnt[v1] && !reject; i++) {
@@ -320,7 +323,309 @@ __global__ void k_iota64(unsigned long long* p, unsigned long long v, uint32_t n
   if (i < n) p[i] = v;
 }
 
+constexpr int PASSES = 3;
+
+// ScaleFactor = 1e8 / diag^6 of the bounding box of ALL vertices, as the host filter takes it (simplify.cpp)
+int scale_factor(const float* pos, uint32_t V, double& scale) {
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+  for (uint32_t v = 0; v < V; v++)
+    for (int k = 0; k < 3; k++) {
+      const double c = pos[3 * (size_t)v + k];
+      if (!(c == c) || c > 1e30 || c < -1e30) return sf::fail(SF_ERR_FORMAT, "vertex %u has a non-finite coordinate", v);
+      lo[k] = std::min(lo[k], c);
+      hi[k] = std::max(hi[k], c);
+    }
+  scale = 1.0;
+  if (V) {
+    const double diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+    scale = diag > 0.0 ? 1e8 * std::pow(1.0 / diag, 6.0) : 1.0;
+  }
+  return SF_OK;
+}
+
+// The device state of one decimation and the launches of one round, step by step.  sf_mesh_simplify_gpu drives them in its round loop, the stage
+// hooks (include/scanfuse_internal.h) drive the same ones on arrays of the caller's: there is one launch sequence per step.
+struct Decimator {
+  StreamGuard sg;   // its own stream: host threads finishing several meshes, and the fuser of the next scan, share the device
+  hipStream_t s = nullptr;
+  DevBuf d_pos, d_tri, d_alive, d_vdel, d_Q, d_vbeg, d_vcnt, d_ckey, d_cval, d_ckey2, d_cval2, d_ekey, d_ekey2, d_ukey, d_ucnt, d_nruns, d_pri, d_pri2, d_pri3, d_x, d_lock,
+      d_win, d_win2, d_nwin, d_taken, d_tmp;
+  size_t tmp_bytes = 0;
+  Mesh M{};
+  uint32_t V = 0, Fc = 0;   // Fc: faces in the device arrays; dead ones are squeezed out (in order) when a quarter has gone, the sorts shrink with the mesh
+  std::vector<unsigned long long> win_h;
+  std::vector<uint32_t> ucnt_h;
+
+  int init(uint32_t V_, uint32_t F) {
+    V = V_;
+    Fc = F;
+    DEC_CHECK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    s = sg.s;
+    const size_t NC0 = 3 * (size_t)F;
+    DEC_CHECK(d_pos.alloc((size_t)V * 12)); DEC_CHECK(d_tri.alloc(NC0 * 4)); DEC_CHECK(d_alive.alloc(F)); DEC_CHECK(d_vdel.alloc(V));
+    DEC_CHECK(d_Q.alloc((size_t)V * sizeof(Quadric))); DEC_CHECK(d_vbeg.alloc((size_t)V * 4)); DEC_CHECK(d_vcnt.alloc((size_t)V * 4));
+    DEC_CHECK(d_ckey.alloc(NC0 * 4)); DEC_CHECK(d_cval.alloc(NC0 * 4)); DEC_CHECK(d_ckey2.alloc(NC0 * 4)); DEC_CHECK(d_cval2.alloc(NC0 * 4));
+    DEC_CHECK(d_ekey.alloc(NC0 * 8)); DEC_CHECK(d_ekey2.alloc(NC0 * 8)); DEC_CHECK(d_ukey.alloc(NC0 * 8)); DEC_CHECK(d_ucnt.alloc(NC0 * 4)); DEC_CHECK(d_nruns.alloc(8));
+    DEC_CHECK(d_pri.alloc(NC0 * 4)); DEC_CHECK(d_pri2.alloc(NC0 * 4)); DEC_CHECK(d_pri3.alloc(NC0 * 4)); DEC_CHECK(d_x.alloc(NC0 * 12)); DEC_CHECK(d_lock.alloc((size_t)V * 8));
+    DEC_CHECK(d_win.alloc(NC0 * 8)); DEC_CHECK(d_win2.alloc(NC0 * 8)); DEC_CHECK(d_nwin.alloc(16)); DEC_CHECK(d_taken.alloc(V));
+    // scratch for the rocprim calls: sized once for the largest request
+    size_t need = 0;
+    DEC_CHECK(rocprim::radix_sort_pairs(nullptr, need, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC0, 0, 32, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC0, 0, 64, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    DEC_CHECK(rocprim::run_length_encode(nullptr, need, d_ekey2.as<uint64_t>(), (unsigned int)NC0, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_pri.as<uint32_t>(), d_pri2.as<uint32_t>(), NC0, 0, 32, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), NC0, 0, 64, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    DEC_CHECK(rocprim::select(nullptr, need, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)F, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    DEC_CHECK(d_tmp.alloc(tmp_bytes));
+    M = Mesh{d_pos.as<float>(), d_tri.as<uint32_t>(), d_alive.as<uint8_t>(), d_vdel.as<uint8_t>(), d_Q.as<Quadric>(), d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>(),
+             d_cval2.as<uint32_t>(), V, F};
+    return SF_OK;
+  }
+  int upload(const float* pos, const uint32_t* tri, const uint8_t* alive, const double* Q /* nullable: V x 10 */) {
+    DEC_CHECK(hipMemcpyAsync(d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, s));
+    DEC_CHECK(hipMemcpyAsync(d_tri.p, tri, 3 * (size_t)Fc * 4, hipMemcpyHostToDevice, s));
+    DEC_CHECK(hipMemcpyAsync(d_alive.p, alive, Fc, hipMemcpyHostToDevice, s));
+    DEC_CHECK(hipMemsetAsync(d_vdel.p, 0, V, s));
+    if (Q) DEC_CHECK(hipMemcpyAsync(d_Q.p, Q, (size_t)V * sizeof(Quadric), hipMemcpyHostToDevice, s));
+    return SF_OK;
+  }
+  int download(float* pos, uint32_t* tri, uint8_t* alive, uint8_t* vdel, double* Q /* nullable */) {
+    DEC_CHECK(hipStreamSynchronize(s));
+    DEC_CHECK(hipMemcpyAsync(pos, d_pos.p, (size_t)V * 12, hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipMemcpyAsync(tri, d_tri.p, (size_t)Fc * 12, hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipMemcpyAsync(alive, d_alive.p, Fc, hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipMemcpyAsync(vdel, d_vdel.p, V, hipMemcpyDeviceToHost, s));
+    if (Q) DEC_CHECK(hipMemcpyAsync(Q, d_Q.p, (size_t)V * sizeof(Quadric), hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipStreamSynchronize(s));
+    return SF_OK;
+  }
+  // dead faces out of the device arrays, in order, once a quarter of them has gone
+  int squeeze(uint64_t nalive) {
+    if (!(nalive * 4 < (uint64_t)Fc * 3)) return SF_OK;
+    size_t tb = tmp_bytes;
+    DEC_CHECK(rocprim::select(d_tmp.p, tb, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)Fc, s));
+    uint32_t kept = 0;
+    DEC_CHECK(hipMemcpyAsync(&kept, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipStreamSynchronize(s));
+    if (kept != nalive) return sf::fail(SF_ERR_DEVICE, "simplify_gpu: %u faces alive on the device, %llu counted", kept, (unsigned long long)nalive);
+    DEC_CHECK(hipMemcpyAsync(d_tri.p, d_ckey.p, (size_t)kept * 12, hipMemcpyDeviceToDevice, s));
+    DEC_CHECK(hipMemsetAsync(d_alive.p, 1, kept, s));
+    Fc = kept;
+    M.F = Fc;
+    return SF_OK;
+  }
+  // 1. vertex -> corner lists and the unique edges (key order) of the live faces, each with its face count
+  int adjacency(uint32_t& E) {
+    const size_t NC = 3 * (size_t)Fc;
+    const unsigned gF = (Fc + 255) / 256, gC = (unsigned)((NC + 255) / 256), gV = (V + 255) / 256;
+    hipLaunchKernelGGL(k_emit, dim3(gF), dim3(256), 0, s, M.tri, M.alive, Fc, d_ckey.as<uint32_t>(), d_cval.as<uint32_t>(), d_ekey.as<uint64_t>());
+    size_t tb = tmp_bytes;
+    DEC_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC, 0, 32, s));
+    DEC_CHECK(hipMemsetAsync(d_vbeg.p, 0, (size_t)V * 4, s));
+    DEC_CHECK(hipMemsetAsync(d_vcnt.p, 0, (size_t)V * 4, s));
+    hipLaunchKernelGGL(k_vertex_ranges, dim3(gC), dim3(256), 0, s, d_ckey2.as<uint32_t>(), (uint32_t)NC, d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_fix_counts, dim3(gV), dim3(256), 0, s, d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>(), V);
+    tb = tmp_bytes;
+    DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC, 0, 64, s));
+    tb = tmp_bytes;
+    DEC_CHECK(rocprim::run_length_encode(d_tmp.p, tb, d_ekey2.as<uint64_t>(), (unsigned int)NC, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
+    E = 0;
+    DEC_CHECK(hipMemcpyAsync(&E, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipStreamSynchronize(s));
+    if (E > 0) {   // the run of dead faces' keys (~0) sorts last
+      uint64_t lastkey = 0;
+      DEC_CHECK(hipMemcpyAsync(&lastkey, d_ukey.as<uint64_t>() + (E - 1), 8, hipMemcpyDeviceToHost, s));
+      DEC_CHECK(hipStreamSynchronize(s));
+      if (lastkey == ~0ull) E--;
+    }
+    return SF_OK;
+  }
+  void init_quadrics(uint32_t E, const sf_simplify_params& p) {
+    hipLaunchKernelGGL(k_init_quadrics, dim3((V + 255) / 256), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), E, p.boundary_weight, p.planar_quadric);
+  }
+  // 2. priority, position and link test of every edge
+  void priorities(uint32_t E, double scale, const sf_simplify_params& p) {
+    hipLaunchKernelGGL(k_priority, dim3((E + 127) / 128), dim3(128), 0, s, M, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), E, scale, p.quality_thr, p.optimal_placement,
+                       d_pri.as<float>(), d_x.as<float>());
+  }
+  // 3. the candidates' threshold: the priority of rank min(E - 1, needed + needed / 2 + 64); none after a round without winners
+  int threshold(uint32_t E, uint64_t needed, int stalled, float& tau) {
+    tau = INFINITY;
+    if (stalled == 0) {
+      DEC_CHECK(hipMemcpyAsync(d_pri3.p, d_pri.p, (size_t)E * 4, hipMemcpyDeviceToDevice, s));
+      size_t tb = tmp_bytes;
+      DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_pri3.as<uint32_t>(), d_pri2.as<uint32_t>(), (size_t)E, 0, 32, s));
+      const uint64_t kth = std::min<uint64_t>((uint64_t)E - 1, needed + needed / 2 + 64);
+      DEC_CHECK(hipMemcpyAsync(&tau, d_pri2.as<float>() + kth, 4, hipMemcpyDeviceToHost, s));
+      DEC_CHECK(hipStreamSynchronize(s));
+    }
+    if (!(tau < 3.0e38f)) tau = 3.0e38f;   // never an edge the link test rejected (infinite priority)
+    return SF_OK;
+  }
+  // 4. one round's winners: winners_begin, PASSES x winners_pass, winners_read
+  int winners_begin() {
+    DEC_CHECK(hipMemsetAsync(d_nwin.p, 0, 16, s));
+    DEC_CHECK(hipMemsetAsync(d_taken.p, 0, V, s));
+    return SF_OK;
+  }
+  void winners_pass(uint32_t E, float tau, uint32_t round, int pass) {
+    const unsigned gV = (V + 255) / 256, gE = (E + 255) / 256;
+    const uint32_t salt = (round * PASSES + (uint32_t)pass) * 0x9E3779B9u;
+    hipLaunchKernelGGL(k_iota64, dim3(gV), dim3(256), 0, s, d_lock.as<unsigned long long>(), ~0ull, V);
+    hipLaunchKernelGGL(k_lock, dim3(gE), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), E, d_pri.as<float>(), tau, salt, d_taken.as<uint8_t>(), d_lock.as<unsigned long long>());
+    hipLaunchKernelGGL(k_winners, dim3(gE), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), E, d_pri.as<float>(), tau, salt,
+                       d_lock.as<unsigned long long>(), d_taken.as<uint8_t>(), d_win.as<unsigned long long>(), d_nwin.as<uint32_t>());
+  }
+  int winners_read(uint32_t cnt[4]) {
+    DEC_CHECK(hipMemcpyAsync(cnt, d_nwin.p, 16, hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipStreamSynchronize(s));
+    return SF_OK;
+  }
+  // the last round: the winners in (priority, edge) order in d_win2, and how many of them bring the face count to the target
+  int cut(uint32_t nwin, uint32_t E, uint64_t nalive, uint64_t target, uint32_t& take, uint64_t& removed, uint32_t& top) {
+    size_t tb = tmp_bytes;
+    DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), (size_t)nwin, 0, 64, s));
+    win_h.resize(nwin);
+    DEC_CHECK(hipMemcpyAsync(win_h.data(), d_win2.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, s));
+    ucnt_h.resize(E);
+    DEC_CHECK(hipMemcpyAsync(ucnt_h.data(), d_ucnt.p, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+    DEC_CHECK(hipStreamSynchronize(s));
+    removed = 0;
+    take = 0;
+    while (take < nwin && nalive - removed > target) {
+      removed += ucnt_h[(uint32_t)win_h[take]];
+      take++;
+    }
+    top = take ? (uint32_t)(win_h[take - 1] >> 32) : 0u;
+    return SF_OK;
+  }
+  // 5. collapse the edges named by the low words of d_take[0 .. take)
+  int collapse(const unsigned long long* d_take, uint32_t take) {
+    if (take == 0) return SF_OK;
+    hipLaunchKernelGGL(k_collapse, dim3((take + 255) / 256), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), d_x.as<float>(), d_take, take);
+    DEC_CHECK(hipGetLastError());
+    return SF_OK;
+  }
+};
+
+int stage_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device");
+  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
+  DEC_CHECK(hipSetDevice(device));
+  return SF_OK;
+}
+int stage_mesh(uint32_t V, uint32_t F, const uint32_t* tri) {
+  if (V == 0 || F == 0 || F > 0x2FFFFFFFu) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: empty or oversized mesh");
+  for (size_t i = 0; i < 3 * (size_t)F; i++)
+    if (tri[i] >= V) return sf::fail(SF_ERR_FORMAT, "face references vertex %u of %u", tri[i], V);
+  return SF_OK;
+}
+
 }  // namespace
+
+// ---- stage hooks (include/scanfuse_internal.h) ---------------------------------------------------------------------------------------------------
+SF_API int sf_simplify_stage_edges(int device, uint32_t V, uint32_t F, const float* pos, const uint32_t* tri, const uint8_t* alive, const double* Q_in,
+                                   const sf_simplify_params* p, double scale, uint64_t needed, int stalled, uint32_t* E_out, uint64_t* ukey, uint32_t* ucnt,
+                                   double* Q_out, float* pri, float* x, float* tau_out, double* scale_out) {
+  if (!pos || !tri || !alive || !p || !E_out || !ukey || !ucnt || !Q_out || !pri || !x || !tau_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (const int rc = stage_mesh(V, F, tri)) return rc;
+  if (!(scale > 0.0))
+    if (const int rc = scale_factor(pos, V, scale)) return rc;
+  if (scale_out) *scale_out = scale;
+  if (const int rc = stage_device(device)) return rc;
+  Decimator D;
+  if (const int rc = D.init(V, F)) return rc;
+  if (const int rc = D.upload(pos, tri, alive, Q_in)) return rc;
+  uint32_t E = 0;
+  if (const int rc = D.adjacency(E)) return rc;
+  *E_out = E;
+  *tau_out = 3.0e38f;
+  if (!Q_in) {
+    if (E) D.init_quadrics(E, *p);
+    else DEC_CHECK(hipMemsetAsync(D.d_Q.p, 0, (size_t)V * sizeof(Quadric), D.s));
+  }
+  if (E) {
+    D.priorities(E, scale, *p);
+    if (const int rc = D.threshold(E, needed, stalled, *tau_out)) return rc;
+    DEC_CHECK(hipMemcpyAsync(ukey, D.d_ukey.p, (size_t)E * 8, hipMemcpyDeviceToHost, D.s));
+    DEC_CHECK(hipMemcpyAsync(ucnt, D.d_ucnt.p, (size_t)E * 4, hipMemcpyDeviceToHost, D.s));
+    DEC_CHECK(hipMemcpyAsync(pri, D.d_pri.p, (size_t)E * 4, hipMemcpyDeviceToHost, D.s));
+    DEC_CHECK(hipMemcpyAsync(x, D.d_x.p, (size_t)E * 12, hipMemcpyDeviceToHost, D.s));
+  }
+  DEC_CHECK(hipMemcpyAsync(Q_out, D.d_Q.p, (size_t)V * sizeof(Quadric), hipMemcpyDeviceToHost, D.s));
+  DEC_CHECK(hipStreamSynchronize(D.s));
+  DEC_CHECK(hipGetLastError());
+  return SF_OK;
+}
+
+SF_API int sf_simplify_stage_winners(int device, uint32_t V, uint32_t F, const uint32_t* tri, const uint8_t* alive, uint32_t E_in, const float* pri, float tau,
+                                     uint32_t round, uint8_t* pass_out, uint8_t* taken_out, uint32_t counters[3]) {
+  if (!tri || !alive || !pri || !pass_out || !taken_out || !counters) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (const int rc = stage_mesh(V, F, tri)) return rc;
+  if (const int rc = stage_device(device)) return rc;
+  Decimator D;
+  if (const int rc = D.init(V, F)) return rc;
+  std::vector<float> pos0(3 * (size_t)V, 0.0f);   // the winner rule reads no position
+  if (const int rc = D.upload(pos0.data(), tri, alive, nullptr)) return rc;
+  uint32_t E = 0;
+  if (const int rc = D.adjacency(E)) return rc;
+  if (E != E_in || E == 0) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: %u priorities for %u edges", E_in, E);
+  DEC_CHECK(hipMemcpyAsync(D.d_pri.p, pri, (size_t)E * 4, hipMemcpyHostToDevice, D.s));
+  if (const int rc = D.winners_begin()) return rc;
+  std::memset(pass_out, 0, E);
+  uint32_t cnt[4] = {0, 0, 0, 0}, seen = 0;
+  std::vector<unsigned long long> w;
+  for (int pass = 0; pass < PASSES; pass++) {
+    D.winners_pass(E, tau, round, pass);
+    if (const int rc = D.winners_read(cnt)) return rc;
+    if (cnt[0] > E) return sf::fail(SF_ERR_DEVICE, "simplify stage: %u winners of %u edges", cnt[0], E);
+    w.resize(cnt[0] - seen);
+    if (cnt[0] > seen) {
+      DEC_CHECK(hipMemcpyAsync(w.data(), D.d_win.as<unsigned long long>() + seen, (size_t)(cnt[0] - seen) * 8, hipMemcpyDeviceToHost, D.s));
+      DEC_CHECK(hipStreamSynchronize(D.s));
+    }
+    for (unsigned long long k : w) {
+      const uint32_t e = (uint32_t)k;
+      if (e >= E || pass_out[e] != 0) return sf::fail(SF_ERR_DEVICE, "simplify stage: winner list names edge %u of %u twice or out of range", e, E);
+      pass_out[e] = (uint8_t)(pass + 1);
+    }
+    seen = cnt[0];
+  }
+  DEC_CHECK(hipMemcpyAsync(taken_out, D.d_taken.p, V, hipMemcpyDeviceToHost, D.s));
+  DEC_CHECK(hipStreamSynchronize(D.s));
+  DEC_CHECK(hipGetLastError());
+  for (int k = 0; k < 3; k++) counters[k] = cnt[k];
+  return SF_OK;
+}
+
+SF_API int sf_simplify_stage_collapse(int device, uint32_t V, uint32_t F, float* pos, uint32_t* tri, uint8_t* alive, double* Q, uint32_t n, const uint32_t* edges,
+                                      uint32_t E_in, const float* x, uint8_t* vdel_out) {
+  if (!pos || !tri || !alive || !Q || (n && !edges) || !x || !vdel_out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (const int rc = stage_mesh(V, F, tri)) return rc;
+  if (n > E_in) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: %u collapses of %u edges", n, E_in);
+  for (uint32_t i = 0; i < n; i++)
+    if (edges[i] >= E_in) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: edge %u of %u", edges[i], E_in);
+  if (const int rc = stage_device(device)) return rc;
+  Decimator D;
+  if (const int rc = D.init(V, F)) return rc;
+  if (const int rc = D.upload(pos, tri, alive, Q)) return rc;
+  uint32_t E = 0;
+  if (const int rc = D.adjacency(E)) return rc;
+  if (E != E_in || E == 0) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: positions for %u edges, the mesh has %u", E_in, E);
+  DEC_CHECK(hipMemcpyAsync(D.d_x.p, x, (size_t)E * 12, hipMemcpyHostToDevice, D.s));
+  std::vector<unsigned long long> w(n);
+  for (uint32_t i = 0; i < n; i++) w[i] = edges[i];
+  if (n) DEC_CHECK(hipMemcpyAsync(D.d_win.p, w.data(), (size_t)n * 8, hipMemcpyHostToDevice, D.s));
+  if (const int rc = D.collapse(D.d_win.as<unsigned long long>(), n)) return rc;
+  return D.download(pos, tri, alive, vdel_out, Q);
+}
 
 SF_API int sf_mesh_simplify_gpu(const sf_mesh* in, const sf_simplify_params* p, int device, sf_mesh** out, sf_simplify_stats* stats) {
   if (!in || !p || !out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
@@ -353,130 +658,35 @@ SF_API int sf_mesh_simplify_gpu(const sf_mesh* in, const sf_simplify_params* p, 
   }
   uint64_t target = p->target_faces;
   if (p->target_perc != 0.0f) target = (uint64_t)((double)F * (double)p->target_perc);
-  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-  for (uint32_t v = 0; v < V; v++)
-    for (int k = 0; k < 3; k++) {
-      const double c = pos[3 * (size_t)v + k];
-      if (!(c == c) || c > 1e30 || c < -1e30) return sf::fail(SF_ERR_FORMAT, "vertex %u has a non-finite coordinate", v);
-      lo[k] = std::min(lo[k], c);
-      hi[k] = std::max(hi[k], c);
-    }
   double scale = 1.0;
-  if (V) {
-    const double diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
-    scale = diag > 0.0 ? 1e8 * std::pow(1.0 / diag, 6.0) : 1.0;
-  }
+  if (const int rc = scale_factor(pos.data(), V, scale)) return rc;
   if (F > 0 && V > 0 && nalive > target) {
-    StreamGuard sg;   // its own stream: host threads finishing several meshes, and the fuser of the next scan, share the device
-    DEC_CHECK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    hipStream_t s = sg.s;
-    const size_t NC0 = 3 * (size_t)F;
-    DevBuf d_pos, d_tri, d_alive, d_vdel, d_Q, d_vbeg, d_vcnt, d_ckey, d_cval, d_ckey2, d_cval2, d_ekey, d_ekey2, d_ukey, d_ucnt, d_nruns, d_pri, d_pri2, d_pri3, d_x, d_lock,
-        d_win, d_win2, d_nwin, d_taken, d_tmp;
-    DEC_CHECK(d_pos.alloc((size_t)V * 12)); DEC_CHECK(d_tri.alloc(NC0 * 4)); DEC_CHECK(d_alive.alloc(F)); DEC_CHECK(d_vdel.alloc(V));
-    DEC_CHECK(d_Q.alloc((size_t)V * sizeof(Quadric))); DEC_CHECK(d_vbeg.alloc((size_t)V * 4)); DEC_CHECK(d_vcnt.alloc((size_t)V * 4));
-    DEC_CHECK(d_ckey.alloc(NC0 * 4)); DEC_CHECK(d_cval.alloc(NC0 * 4)); DEC_CHECK(d_ckey2.alloc(NC0 * 4)); DEC_CHECK(d_cval2.alloc(NC0 * 4));
-    DEC_CHECK(d_ekey.alloc(NC0 * 8)); DEC_CHECK(d_ekey2.alloc(NC0 * 8)); DEC_CHECK(d_ukey.alloc(NC0 * 8)); DEC_CHECK(d_ucnt.alloc(NC0 * 4)); DEC_CHECK(d_nruns.alloc(8));
-    DEC_CHECK(d_pri.alloc(NC0 * 4)); DEC_CHECK(d_pri2.alloc(NC0 * 4)); DEC_CHECK(d_pri3.alloc(NC0 * 4)); DEC_CHECK(d_x.alloc(NC0 * 12)); DEC_CHECK(d_lock.alloc((size_t)V * 8));
-    DEC_CHECK(d_win.alloc(NC0 * 8)); DEC_CHECK(d_win2.alloc(NC0 * 8)); DEC_CHECK(d_nwin.alloc(16)); DEC_CHECK(d_taken.alloc(V));
-    DEC_CHECK(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)V * 12, hipMemcpyHostToDevice, s));
-    DEC_CHECK(hipMemcpyAsync(d_tri.p, tri.data(), NC0 * 4, hipMemcpyHostToDevice, s));
-    DEC_CHECK(hipMemcpyAsync(d_alive.p, alive_h.data(), F, hipMemcpyHostToDevice, s));
-    DEC_CHECK(hipMemsetAsync(d_vdel.p, 0, V, s));
-    // scratch for the rocprim calls: sized once for the largest request
-    size_t tmp_bytes = 0, need = 0;
-    DEC_CHECK(rocprim::radix_sort_pairs(nullptr, need, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC0, 0, 32, s));
-    tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC0, 0, 64, s));
-    tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::run_length_encode(nullptr, need, d_ekey2.as<uint64_t>(), (unsigned int)NC0, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
-    tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_pri.as<uint32_t>(), d_pri2.as<uint32_t>(), NC0, 0, 32, s));
-    tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), NC0, 0, 64, s));
-    tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::select(nullptr, need, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)F, s));
-    tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(d_tmp.alloc(tmp_bytes));
-    Mesh M{d_pos.as<float>(), d_tri.as<uint32_t>(), d_alive.as<uint8_t>(), d_vdel.as<uint8_t>(), d_Q.as<Quadric>(), d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>(),
-           d_cval2.as<uint32_t>(), V, F};
-    const unsigned gV = (V + 255) / 256;
-    uint32_t Fc = F;   // faces in the device arrays: dead ones are squeezed out (in order) when a quarter has gone, the sorts shrink with the mesh
+    Decimator D;
+    if (const int rc = D.init(V, F)) return rc;
+    if (const int rc = D.upload(pos.data(), tri.data(), alive_h.data(), nullptr)) return rc;
     bool first = true;
     int stalled = 0;
-    constexpr int PASSES = 3;
-    std::vector<unsigned long long> win_h;
-    std::vector<uint32_t> ucnt_h;
     while (nalive > target) {
-      size_t tb = tmp_bytes;
-      if (nalive * 4 < (uint64_t)Fc * 3) {
-        DEC_CHECK(rocprim::select(d_tmp.p, tb, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)Fc, s));
-        uint32_t kept = 0;
-        DEC_CHECK(hipMemcpyAsync(&kept, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
-        DEC_CHECK(hipStreamSynchronize(s));
-        if (kept != nalive) return sf::fail(SF_ERR_DEVICE, "simplify_gpu: %u faces alive on the device, %llu counted", kept, (unsigned long long)nalive);
-        DEC_CHECK(hipMemcpyAsync(d_tri.p, d_ckey.p, (size_t)kept * 12, hipMemcpyDeviceToDevice, s));
-        DEC_CHECK(hipMemsetAsync(d_alive.p, 1, kept, s));
-        Fc = kept;
-        M.F = Fc;
-      }
-      const size_t NC = 3 * (size_t)Fc;
-      const unsigned gF = (Fc + 255) / 256, gC = (unsigned)((NC + 255) / 256);
+      if (const int rc = D.squeeze(nalive)) return rc;
       // 1. adjacency of the live faces
-      hipLaunchKernelGGL(k_emit, dim3(gF), dim3(256), 0, s, M.tri, M.alive, Fc, d_ckey.as<uint32_t>(), d_cval.as<uint32_t>(), d_ekey.as<uint64_t>());
-      tb = tmp_bytes;
-      DEC_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC, 0, 32, s));
-      DEC_CHECK(hipMemsetAsync(d_vbeg.p, 0, (size_t)V * 4, s));
-      DEC_CHECK(hipMemsetAsync(d_vcnt.p, 0, (size_t)V * 4, s));
-      hipLaunchKernelGGL(k_vertex_ranges, dim3(gC), dim3(256), 0, s, d_ckey2.as<uint32_t>(), (uint32_t)NC, d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>());
-      hipLaunchKernelGGL(k_fix_counts, dim3(gV), dim3(256), 0, s, d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>(), V);
-      tb = tmp_bytes;
-      DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC, 0, 64, s));
-      tb = tmp_bytes;
-      DEC_CHECK(rocprim::run_length_encode(d_tmp.p, tb, d_ekey2.as<uint64_t>(), (unsigned int)NC, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
       uint32_t E = 0;
-      DEC_CHECK(hipMemcpyAsync(&E, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
-      DEC_CHECK(hipStreamSynchronize(s));
-      if (E > 0) {   // the run of dead faces' keys (~0) sorts last
-        uint64_t lastkey = 0;
-        DEC_CHECK(hipMemcpyAsync(&lastkey, d_ukey.as<uint64_t>() + (E - 1), 8, hipMemcpyDeviceToHost, s));
-        DEC_CHECK(hipStreamSynchronize(s));
-        if (lastkey == ~0ull) E--;
-      }
+      if (const int rc = D.adjacency(E)) return rc;
       if (E == 0) break;
-      const unsigned gE = (E + 255) / 256;
       if (first) {
-        hipLaunchKernelGGL(k_init_quadrics, dim3(gV), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), E, p->boundary_weight, p->planar_quadric);
+        D.init_quadrics(E, *p);
         first = false;
       }
       // 2. priorities
-      hipLaunchKernelGGL(k_priority, dim3((E + 127) / 128), dim3(128), 0, s, M, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), E, scale, p->quality_thr,
-                         p->optimal_placement, d_pri.as<float>(), d_x.as<float>());
+      D.priorities(E, scale, *p);
       // 3. the priority the collapses still needed would reach: a quantile of this round's priorities (half as many again, the rounds overlap)
       const uint64_t needed = (nalive - target + 1) / 2;
       float tau = INFINITY;
-      if (stalled == 0) {
-        DEC_CHECK(hipMemcpyAsync(d_pri3.p, d_pri.p, (size_t)E * 4, hipMemcpyDeviceToDevice, s));
-        tb = tmp_bytes;
-        DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_pri3.as<uint32_t>(), d_pri2.as<uint32_t>(), (size_t)E, 0, 32, s));
-        const uint64_t kth = std::min<uint64_t>((uint64_t)E - 1, needed + needed / 2 + 64);
-        DEC_CHECK(hipMemcpyAsync(&tau, d_pri2.as<float>() + kth, 4, hipMemcpyDeviceToHost, s));
-        DEC_CHECK(hipStreamSynchronize(s));
-      }
-      if (!(tau < 3.0e38f)) tau = 3.0e38f;   // never an edge the link test rejected (infinite priority)
+      if (const int rc = D.threshold(E, needed, stalled, tau)) return rc;
       // 4. winners: up to PASSES independent sets per round, each among the candidates the earlier ones left untouched
-      DEC_CHECK(hipMemsetAsync(d_nwin.p, 0, 16, s));
-      DEC_CHECK(hipMemsetAsync(d_taken.p, 0, V, s));
-      for (int pass = 0; pass < PASSES; pass++) {
-        const uint32_t salt = ((uint32_t)st.rounds * PASSES + (uint32_t)pass) * 0x9E3779B9u;
-        hipLaunchKernelGGL(k_iota64, dim3(gV), dim3(256), 0, s, d_lock.as<unsigned long long>(), ~0ull, V);
-        hipLaunchKernelGGL(k_lock, dim3(gE), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), E, d_pri.as<float>(), tau, salt, d_taken.as<uint8_t>(), d_lock.as<unsigned long long>());
-        hipLaunchKernelGGL(k_winners, dim3(gE), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), E, d_pri.as<float>(), tau, salt,
-                           d_lock.as<unsigned long long>(), d_taken.as<uint8_t>(), d_win.as<unsigned long long>(), d_nwin.as<uint32_t>());
-      }
+      if (const int rc = D.winners_begin()) return rc;
+      for (int pass = 0; pass < PASSES; pass++) D.winners_pass(E, tau, st.rounds, pass);
       uint32_t cnt[4] = {0, 0, 0, 0};
-      DEC_CHECK(hipMemcpyAsync(cnt, d_nwin.p, 16, hipMemcpyDeviceToHost, s));
-      DEC_CHECK(hipStreamSynchronize(s));
+      if (const int rc = D.winners_read(cnt)) return rc;
       const uint32_t nwin = cnt[0];
       st.rounds++;
       if (nwin == 0) {
@@ -485,46 +695,29 @@ SF_API int sf_mesh_simplify_gpu(const sf_mesh* in, const sf_simplify_params* p, 
       }
       stalled = 0;
       uint32_t take = nwin;
-      const unsigned long long* d_take = d_win.as<unsigned long long>();
+      const unsigned long long* d_take = D.d_win.as<unsigned long long>();
       if (nalive - cnt[1] >= target) {   // every winner fits under the budget: winners are independent, their order does not matter
         float mp;
         std::memcpy(&mp, &cnt[2], 4);
         if (mp > st.max_priority) st.max_priority = mp;
         nalive -= cnt[1];
       } else {   // the last round: winners in (priority, edge) order until the face count reaches the target
-        tb = tmp_bytes;
-        DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), (size_t)nwin, 0, 64, s));
-        d_take = d_win2.as<unsigned long long>();
-        win_h.resize(nwin);
-        DEC_CHECK(hipMemcpyAsync(win_h.data(), d_win2.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, s));
-        ucnt_h.resize(E);
-        DEC_CHECK(hipMemcpyAsync(ucnt_h.data(), d_ucnt.p, (size_t)E * 4, hipMemcpyDeviceToHost, s));
-        DEC_CHECK(hipStreamSynchronize(s));
         uint64_t removed = 0;
-        take = 0;
-        while (take < nwin && nalive - removed > target) {
-          removed += ucnt_h[(uint32_t)win_h[take]];
-          take++;
-        }
+        uint32_t top = 0;
+        if (const int rc = D.cut(nwin, E, nalive, target, take, removed, top)) return rc;
+        d_take = D.d_win2.as<unsigned long long>();
         float mp;
-        const uint32_t top = (uint32_t)(win_h[take - 1] >> 32);
         std::memcpy(&mp, &top, 4);
         if (mp > st.max_priority) st.max_priority = mp;
         nalive -= removed;
       }
       st.collapses += take;
       // 5. collapse
-      hipLaunchKernelGGL(k_collapse, dim3((take + 255) / 256), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), d_x.as<float>(), d_take, take);
-      DEC_CHECK(hipGetLastError());
+      if (const int rc = D.collapse(d_take, take)) return rc;
     }
-    DEC_CHECK(hipStreamSynchronize(s));
-    DEC_CHECK(hipMemcpyAsync(pos.data(), d_pos.p, (size_t)V * 12, hipMemcpyDeviceToHost, s));
-    tri.resize(3 * (size_t)Fc);
-    alive_h.resize(Fc);
-    DEC_CHECK(hipMemcpyAsync(tri.data(), d_tri.p, (size_t)Fc * 12, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipMemcpyAsync(alive_h.data(), d_alive.p, Fc, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipMemcpyAsync(vdel_h.data(), d_vdel.p, V, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipStreamSynchronize(s));
+    tri.resize(3 * (size_t)D.Fc);
+    alive_h.resize(D.Fc);
+    if (const int rc = D.download(pos.data(), tri.data(), alive_h.data(), vdel_h.data(), nullptr)) return rc;
   }
   const size_t Fh = alive_h.size();   // the device squeezes dead faces out of its arrays as it goes
   std::vector<uint8_t> fdel(Fh);

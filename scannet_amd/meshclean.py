@@ -101,3 +101,76 @@ def clean_file(in_ply, out_ply, script_mlx):
     if s.simplify:
         res["simplify"] = {n: getattr(s.simplify_stats, n) for n, _ in SfSimplifyStats._fields_}
     return res
+
+
+# ---- stage hooks of the GPU decimation (include/scanfuse_internal.h; tests/test_simplify_stages.py): one part of a round of sf_mesh_simplify_gpu on
+# host arrays, launched through the helpers its round loop calls.  Same argument and result layout as oracle.simplify_stage_*.
+def _stage_params(overrides):
+    p = SfSimplifyParams()
+    _lib().sf_simplify_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown simplify parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _stage_mesh(xyz, tris, alive):
+    import numpy as np
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    v = None if xyz is None else np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    a = np.ones(len(t), np.uint8) if alive is None else np.ascontiguousarray(alive, np.uint8).reshape(-1)
+    if len(a) != len(t):
+        raise ValueError("one alive byte per face")
+    return v, t, a
+
+
+def stage_edges(xyz, tris, alive=None, Q=None, scale=0.0, needed=0, stalled=0, device=0, **overrides):
+    """Adjacency, initial quadrics (Q is None), priorities and the threshold of one round -> {"E", "ukey", "ucnt", "Q", "pri", "x", "tau", "scale"}."""
+    import numpy as np
+    L = _lib()
+    vp = C.c_void_p
+    L.sf_simplify_stage_edges.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(SfSimplifyParams), C.c_double, C.c_uint64, C.c_int,
+                                          C.POINTER(C.c_uint32), vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    p = _stage_params(overrides)
+    v, t, a = _stage_mesh(xyz, tris, alive)
+    q = None if Q is None else np.ascontiguousarray(Q, np.float64).reshape(len(v), 10)
+    n = 3 * len(t)
+    ukey, ucnt, pri, x, Qo = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros((len(v), 10), np.float64)
+    E, tau, sc = C.c_uint32(0), C.c_float(0), C.c_double(0)
+    check(L.sf_simplify_stage_edges(int(device), len(v), len(t), v.ctypes.data, t.ctypes.data, a.ctypes.data, None if q is None else q.ctypes.data, C.byref(p),
+                                    float(scale), int(needed), int(stalled), C.byref(E), ukey.ctypes.data, ucnt.ctypes.data, Qo.ctypes.data, pri.ctypes.data,
+                                    x.ctypes.data, C.byref(tau), C.byref(sc)))
+    e = E.value
+    return {"E": e, "ukey": ukey[:e], "ucnt": ucnt[:e], "Q": Qo, "pri": pri[:e], "x": x[:e], "tau": np.float32(tau.value), "scale": sc.value}
+
+
+def stage_winners(nv, tris, alive, pri, tau, round_no, device=0):
+    """The three winner passes of round `round_no` on the caller's priorities -> {"passes" (0 = no win, 1..3), "taken", "counters"}."""
+    import numpy as np
+    L = _lib()
+    vp = C.c_void_p
+    L.sf_simplify_stage_winners.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_float, C.c_uint32, vp, vp, vp]
+    _, t, a = _stage_mesh(None, tris, alive)
+    p = np.ascontiguousarray(pri, np.float32).reshape(-1)
+    passes, taken, cnt = np.zeros(len(p), np.uint8), np.zeros(nv, np.uint8), np.zeros(3, np.uint32)
+    check(L.sf_simplify_stage_winners(int(device), int(nv), len(t), t.ctypes.data, a.ctypes.data, len(p), p.ctypes.data, float(tau), int(round_no),
+                                      passes.ctypes.data, taken.ctypes.data, cnt.ctypes.data))
+    return {"passes": passes, "taken": taken, "counters": cnt}
+
+
+def stage_collapse(xyz, tris, alive, Q, edges, x, device=0):
+    """Collapse the (independent) edges named -> {"pos", "tri", "alive", "Q", "vdel"}: copies, the arguments are left alone."""
+    import numpy as np
+    L = _lib()
+    vp = C.c_void_p
+    L.sf_simplify_stage_collapse.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+    v, t, a = _stage_mesh(xyz, tris, alive)
+    v, t, a = v.copy(), t.copy(), a.copy()
+    q = np.array(Q, np.float64).reshape(len(v), 10)
+    ed = np.ascontiguousarray(edges, np.uint32).reshape(-1)
+    xs = np.ascontiguousarray(x, np.float32).reshape(-1, 3)
+    vdel = np.zeros(len(v), np.uint8)
+    check(L.sf_simplify_stage_collapse(int(device), len(v), len(t), v.ctypes.data, t.ctypes.data, a.ctypes.data, q.ctypes.data, len(ed), ed.ctypes.data, len(xs),
+                                       xs.ctypes.data, vdel.ctypes.data))
+    return {"pos": v, "tri": t, "alive": a, "Q": q, "vdel": vdel}
