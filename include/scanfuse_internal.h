@@ -118,6 +118,29 @@ int sf_simplify_stage_winners(int device, uint32_t V, uint32_t F, const uint32_t
 int sf_simplify_stage_collapse(int device, uint32_t V, uint32_t F, float* pos, uint32_t* tri, uint8_t* alive, double* Q, uint32_t n, const uint32_t* edges,
                                uint32_t E_in, const float* x, uint8_t* vdel_out);
 
+/* Stage hooks of the GPU mesh clean (tests/test_clean_stages.py; scannet_amd/csrc/clean_gpu.hip): each call runs ONE of the four helpers that
+ * sf_mesh_clean_gpu is the composition of, on host arrays -- same kernels, grids, workgroups, sorts and buffers -- and returns its result to the host.
+ *   merge       filter 1 on V >= 1 positions: target_out[V] (the vertex each is merged into, itself for a centre), the number of k_settle launches and of
+ *               occupied grid cells (both 0 for radius == 0, which takes the sort path), and what k_count_merged counted.  SF_ERR_FORMAT for a
+ *               non-finite coordinate and SF_ERR_UNSUPPORTED for more than 2^21 cells on an axis (radius > 0), as the product answers.
+ *   faces       k_remap_faces through the CALLER's target[V] (NULL: nobody merged -- the identity is written at the entries the faces name, V may be anything
+ *               below 0xFFFFFFF0 and no positions are needed), the select, the duplicate sorts and k_dup_flags, the second select: verdict_out[F] = 0 kept,
+ *               1 degenerate, 2 duplicate; tri_out = the F - degenerate - duplicate surviving triples (target applied) in order
+ *   components  k_edge_keys, the sort, k_link, k_roots, k_component_flags on F faces: root_out[F], size_out[F] (the component's size AT its root, 0
+ *               elsewhere), keep_out[F], counters = {components, components below min_faces, faces in them}
+ *   compact     k_mark_used, the scan, k_gather_vertices, k_remap_tris: used_out[V] (0 / 1), remap_out[V] (the exclusive scan: used vertices below v),
+ *               the *vertices_out gathered positions and colours (col NULL: none) and the F remapped triples (F may be 0)
+ * sf_clean_probe_merge: the host filter's clustering alone (clean.cpp's merge_close), target_out[V]. */
+int sf_clean_stage_merge(int device, uint32_t V, const float* pos, float radius, uint32_t* target_out, uint32_t* launches_out, uint32_t* cells_out,
+                         uint32_t* merged_out);
+int sf_clean_stage_faces(int device, uint32_t V, uint32_t F, const uint32_t* tri, const uint32_t* target /*nullable*/, uint8_t* verdict_out, uint32_t* tri_out,
+                         uint32_t* degenerate_out, uint32_t* duplicate_out);
+int sf_clean_stage_components(int device, uint32_t F, const uint32_t* tri, uint32_t min_faces, uint32_t* root_out, uint32_t* size_out, uint8_t* keep_out,
+                              uint32_t counters[3]);
+int sf_clean_stage_compact(int device, uint32_t V, uint32_t F, const float* pos, const uint8_t* col /*nullable*/, const uint32_t* tri, uint32_t* used_out,
+                           uint32_t* remap_out, float* pos_out, uint8_t* col_out, uint32_t* tri_out, uint32_t* vertices_out);
+int sf_clean_probe_merge(uint32_t V, const float* pos, float radius, uint32_t* target_out);
+
 /* Device self-test: the hand-expanded correctly rounded divisions of the integrate and allocation kernels against the hardware's IEEE
  * division -- all 2^23 mantissas x 9 exponents for 1/x, 511 integer divisors x 2^21 numerators for n/m, 2^28 general operand pairs
  * (incl. near-exact and near-half-way quotients) for a/b.  All three counts must be 0 (tests/test_gpu_tsdf.py). */

@@ -195,6 +195,17 @@ int merge_close(const sf::mesh_vec<float>& pos, float radius, std::vector<uint32
 
 }  // namespace
 
+// test probe (include/scanfuse_internal.h; tests/test_clean_stages_cpu.py): filter 1's clustering alone
+SF_API int sf_clean_probe_merge(uint32_t V, const float* pos, float radius, uint32_t* target_out) {
+  if ((V > 0 && (!pos || !target_out)) || !(radius >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "sf_clean_probe_merge: bad argument");
+  const sf::mesh_vec<float> p(pos, pos + 3 * (size_t)V);
+  std::vector<uint32_t> target;
+  const int rc = merge_close(p, radius, target);
+  if (rc != SF_OK) return rc;
+  std::copy(target.begin(), target.end(), target_out);
+  return SF_OK;
+}
+
 SF_API int sf_mesh_clean(const sf_mesh* in, float merge_distance, uint32_t min_component_faces, sf_mesh** out, sf_clean_stats* stats) {
   if (!in || !out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   if (!(merge_distance >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "merge distance must be >= 0");

@@ -246,85 +246,105 @@ __global__ void k_remap_tris(const Tri* __restrict__ tri, const uint32_t* __rest
 
 inline unsigned grid_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
-}  // namespace
+// ---- the work set of one call and the four filters as helpers on it: sf_mesh_clean_gpu is their composition, the stage hooks at the end of this file
+// (include/scanfuse_internal.h; tests/test_clean_stages.py) run one helper each -------------------------------------------------------------------------
+enum : unsigned { P_MERGE = 1, P_FACES = 2, P_COMPONENTS = 4, P_COMPACT = 8, P_ALL = 15 };
 
-SF_API int sf_mesh_clean_gpu(const sf_mesh* in, float merge_distance, uint32_t min_component_faces, int device, sf_mesh** out, sf_clean_stats* stats) {
-  if (!in || !out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  if (!(merge_distance >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "merge distance must be >= 0");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return sf::fail(SF_ERR_DEVICE, "no HIP device: sf_mesh_clean_gpu needs an MI355X (sf_mesh_clean is the host filter)");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  CL_CHECK(hipSetDevice(device));
-  const size_t nv = in->pos.size() / 3, nf = in->tri.size() / 3;
-  if (nv >= 0xFFFFFFF0ull || nf >= 0x55555550ull) return sf::fail(SF_ERR_CAPACITY, "mesh too large for 32-bit indices");
-  sf_clean_stats st;
-  std::memset(&st, 0, sizeof(st));
-  st.vertices_in = nv;
-  st.faces_in = nf;
-  for (uint32_t v : in->tri)
-    if (v >= nv) return sf::fail(SF_ERR_FORMAT, "face references vertex %u of %zu", v, nv);
-  sf_mesh* m = new sf_mesh();
-  if (nv == 0) {
-    if (stats) *stats = st;
-    *out = m;
-    return SF_OK;
-  }
-  struct Bail { sf_mesh* m; ~Bail() { delete m; } } bail{m};   // released on success
-  Grid G{0.0, {0, 0, 0}};
-  if (merge_distance > 0.0f) {
-    // the host filter's grid: cells 1e-5 larger than 2 r (the float distance test may accept a point a few 1e-7 relative beyond r)
-    G.inv = 0.5 / ((double)merge_distance * (1.0 + 1e-5));
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (size_t i = 0; i < nv; i++)
-      for (int c = 0; c < 3; c++) {
-        const double q = (double)in->pos[3 * i + c];
-        if (!(q == q) || q > 1e30 || q < -1e30) return sf::fail(SF_ERR_FORMAT, "vertex %zu has a non-finite coordinate", i);
-        lo[c] = std::min(lo[c], q); hi[c] = std::max(hi[c], q);
-      }
-    for (int c = 0; c < 3; c++) {
-      G.base[c] = (int64_t)std::floor(lo[c] * G.inv) - 1;
-      if ((int64_t)std::floor(hi[c] * G.inv) + 1 - G.base[c] >= (1ll << 21))
-        return sf::fail(SF_ERR_UNSUPPORTED, "mesh extent / merge distance exceeds 2^21 cells per axis");
-    }
-  }
+struct Work {
   StreamGuard sg;
-  CL_CHECK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-  hipStream_t s = sg.s;
-  const uint32_t V = (uint32_t)nv, F = (uint32_t)nf;
-  const size_t N = std::max<size_t>(nv, 3 * nf);   // the longest array any sort sees
+  hipStream_t s = nullptr;
+  size_t nv = 0, nf = 0, nfa = 1, tmp_bytes = 0;
   DevBuf d_pos, d_col, d_tri_in, d_target, d_k64a, d_k64b, d_k32a, d_k32b, d_p32a, d_p32b, d_cstart, d_ncells, d_pending_a, d_pending_b, d_count, d_tri, d_tri2, d_keep,
       d_parent, d_root, d_size, d_used, d_remap, d_out_pos, d_out_col, d_out_tri, d_tmp;
-  const size_t nfa = std::max<size_t>(nf, 1);   // a mesh without faces still has its vertices clustered (and then dropped as unreferenced)
-  CL_CHECK(d_pos.alloc(nv * 12)); CL_CHECK(d_tri_in.alloc(nfa * 12)); CL_CHECK(d_target.alloc(nv * 4));
-  if (!in->col.empty()) CL_CHECK(d_col.alloc(nv * 4));
-  CL_CHECK(d_k64a.alloc(N * 8)); CL_CHECK(d_k64b.alloc(N * 8)); CL_CHECK(d_k32a.alloc((N + 1) * 4)); CL_CHECK(d_k32b.alloc(N * 4));
-  CL_CHECK(d_p32a.alloc(N * 4)); CL_CHECK(d_p32b.alloc(N * 4)); CL_CHECK(d_cstart.alloc((nv + 1) * 4)); CL_CHECK(d_ncells.alloc(16));
-  CL_CHECK(d_pending_a.alloc(nv * 4)); CL_CHECK(d_pending_b.alloc(nv * 4)); CL_CHECK(d_count.alloc(64));
-  CL_CHECK(d_tri.alloc(nfa * 12)); CL_CHECK(d_tri2.alloc(nfa * 12)); CL_CHECK(d_keep.alloc(nfa));
-  CL_CHECK(d_parent.alloc(nfa * 4)); CL_CHECK(d_root.alloc(nfa * 4)); CL_CHECK(d_size.alloc(nfa * 4));
-  CL_CHECK(d_used.alloc(nv * 4)); CL_CHECK(d_remap.alloc(nv * 4));
-  size_t tmp_bytes = 0, need = 0;
-  CL_CHECK(rocprim::radix_sort_pairs(nullptr, need, d_k64a.as<uint64_t>(), d_k64b.as<uint64_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), N, 0, 64, s));
-  tmp_bytes = std::max(tmp_bytes, need);
-  CL_CHECK(rocprim::radix_sort_pairs(nullptr, need, d_k32a.as<uint32_t>(), d_k32b.as<uint32_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), N, 0, 32, s));
-  tmp_bytes = std::max(tmp_bytes, need);
-  CL_CHECK(rocprim::run_length_encode(nullptr, need, d_k64b.as<uint64_t>(), (unsigned int)nv, d_k64a.as<uint64_t>(), d_k32a.as<uint32_t>(), d_ncells.as<uint32_t>(), s));
-  tmp_bytes = std::max(tmp_bytes, need);
-  CL_CHECK(rocprim::exclusive_scan(nullptr, need, d_k32a.as<uint32_t>(), d_cstart.as<uint32_t>(), 0u, nv + 1, rocprim::plus<uint32_t>(), s));
-  tmp_bytes = std::max(tmp_bytes, need);
-  CL_CHECK(rocprim::inclusive_scan(nullptr, need, d_k32a.as<uint32_t>(), d_k32b.as<uint32_t>(), nv, rocprim::maximum<uint32_t>(), s));
-  tmp_bytes = std::max(tmp_bytes, need);
-  CL_CHECK(rocprim::select(nullptr, need, d_tri.as<Tri>(), d_keep.as<uint8_t>(), d_tri2.as<Tri>(), d_ncells.as<uint32_t>(), nfa, s));
-  tmp_bytes = std::max(tmp_bytes, need);
-  CL_CHECK(d_tmp.alloc(tmp_bytes));
-  CL_CHECK(hipMemcpyAsync(d_pos.p, in->pos.data(), nv * 12, hipMemcpyHostToDevice, s));
-  if (nf > 0) CL_CHECK(hipMemcpyAsync(d_tri_in.p, in->tri.data(), nf * 12, hipMemcpyHostToDevice, s));
-  if (!in->col.empty()) CL_CHECK(hipMemcpyAsync(d_col.p, in->col.data(), nv * 4, hipMemcpyHostToDevice, s));
-  size_t tb;
-  uint32_t* target = d_target.as<uint32_t>();
+};
 
-  // ---- 1. merge close vertices ---------------------------------------------------------------------------------------------------------
+int pick_device(int device, const char* who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: %s needs an MI355X (sf_mesh_clean is the host filter)", who);
+  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
+  CL_CHECK(hipSetDevice(device));
+  return SF_OK;
+}
+
+// the stream, the buffers of the filters named in `parts` (P_ALL: the product) and the scratch of their sorts, scans and selects
+int work_alloc(Work& W, size_t nv, size_t nf, bool has_col, unsigned parts) {
+  CL_CHECK(hipStreamCreateWithFlags(&W.sg.s, hipStreamNonBlocking));
+  W.s = W.sg.s;
+  hipStream_t s = W.s;
+  W.nv = nv;
+  W.nf = nf;
+  const size_t nfa = W.nfa = std::max<size_t>(nf, 1);   // a mesh without faces still has its vertices clustered (and then dropped as unreferenced)
+  const bool sorts = parts & (P_MERGE | P_FACES | P_COMPONENTS), faces = parts & (P_FACES | P_COMPONENTS | P_COMPACT);
+  // the longest array any sort sees
+  const size_t N = std::max<size_t>(std::max<size_t>((parts & P_MERGE) ? nv : 0, (parts & P_COMPONENTS) ? 3 * nf : ((parts & P_FACES) ? nf : 0)), 1);
+  if (parts & (P_MERGE | P_COMPACT)) CL_CHECK(W.d_pos.alloc(nv * 12));
+  if (parts & P_FACES) CL_CHECK(W.d_tri_in.alloc(nfa * 12));
+  if (parts & (P_MERGE | P_FACES)) CL_CHECK(W.d_target.alloc(nv * 4));
+  if (has_col) CL_CHECK(W.d_col.alloc(nv * 4));
+  if (sorts) {
+    CL_CHECK(W.d_k64a.alloc(N * 8)); CL_CHECK(W.d_k64b.alloc(N * 8)); CL_CHECK(W.d_k32a.alloc((N + 1) * 4)); CL_CHECK(W.d_k32b.alloc(N * 4));
+    CL_CHECK(W.d_p32a.alloc(N * 4)); CL_CHECK(W.d_p32b.alloc(N * 4));
+  }
+  if (parts & P_MERGE) { CL_CHECK(W.d_cstart.alloc((nv + 1) * 4)); CL_CHECK(W.d_pending_a.alloc(nv * 4)); CL_CHECK(W.d_pending_b.alloc(nv * 4)); }
+  CL_CHECK(W.d_ncells.alloc(16)); CL_CHECK(W.d_count.alloc(64));
+  if (faces) { CL_CHECK(W.d_tri.alloc(nfa * 12)); CL_CHECK(W.d_tri2.alloc(nfa * 12)); CL_CHECK(W.d_keep.alloc(nfa)); }
+  if (parts & P_COMPONENTS) { CL_CHECK(W.d_parent.alloc(nfa * 4)); CL_CHECK(W.d_root.alloc(nfa * 4)); CL_CHECK(W.d_size.alloc(nfa * 4)); }
+  if (parts & P_COMPACT) { CL_CHECK(W.d_used.alloc(nv * 4)); CL_CHECK(W.d_remap.alloc(nv * 4)); }
+  size_t tmp_bytes = 0, need = 0;
+  if (sorts) {
+    CL_CHECK(rocprim::radix_sort_pairs(nullptr, need, W.d_k64a.as<uint64_t>(), W.d_k64b.as<uint64_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), N, 0, 64, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    CL_CHECK(rocprim::radix_sort_pairs(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_k32b.as<uint32_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), N, 0, 32, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+  }
+  if (parts & P_MERGE) {
+    CL_CHECK(rocprim::run_length_encode(nullptr, need, W.d_k64b.as<uint64_t>(), (unsigned int)nv, W.d_k64a.as<uint64_t>(), W.d_k32a.as<uint32_t>(), W.d_ncells.as<uint32_t>(), s));
+    tmp_bytes = std::max(tmp_bytes, need);
+    CL_CHECK(rocprim::inclusive_scan(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_k32b.as<uint32_t>(), nv, rocprim::maximum<uint32_t>(), s));
+    tmp_bytes = std::max(tmp_bytes, need);
+  }
+  if (parts & (P_MERGE | P_COMPACT)) {
+    CL_CHECK(rocprim::exclusive_scan(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_cstart.as<uint32_t>(), 0u, nv + 1, rocprim::plus<uint32_t>(), s));
+    tmp_bytes = std::max(tmp_bytes, need);
+  }
+  if (parts & (P_FACES | P_COMPONENTS)) {
+    CL_CHECK(rocprim::select(nullptr, need, W.d_tri.as<Tri>(), W.d_keep.as<uint8_t>(), W.d_tri2.as<Tri>(), W.d_ncells.as<uint32_t>(), nfa, s));
+    tmp_bytes = std::max(tmp_bytes, need);
+  }
+  W.tmp_bytes = tmp_bytes;
+  CL_CHECK(W.d_tmp.alloc(tmp_bytes));
+  return SF_OK;
+}
+
+// the host filter's grid: cells 1e-5 larger than 2 r (the float distance test may accept a point a few 1e-7 relative beyond r)
+int grid_setup(const float* pos, size_t nv, float radius, Grid& G) {
+  G.inv = 0.5 / ((double)radius * (1.0 + 1e-5));
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+  for (size_t i = 0; i < nv; i++)
+    for (int c = 0; c < 3; c++) {
+      const double q = (double)pos[3 * i + c];
+      if (!(q == q) || q > 1e30 || q < -1e30) return sf::fail(SF_ERR_FORMAT, "vertex %zu has a non-finite coordinate", i);
+      lo[c] = std::min(lo[c], q); hi[c] = std::max(hi[c], q);
+    }
+  for (int c = 0; c < 3; c++) {
+    G.base[c] = (int64_t)std::floor(lo[c] * G.inv) - 1;
+    if ((int64_t)std::floor(hi[c] * G.inv) + 1 - G.base[c] >= (1ll << 21))
+      return sf::fail(SF_ERR_UNSUPPORTED, "mesh extent / merge distance exceeds 2^21 cells per axis");
+  }
+  return SF_OK;
+}
+
+// ---- 1. merge close vertices: d_pos -> d_target, the merged vertices counted into d_count[4] (d_count is cleared here) ------------------------------------
+int run_merge(Work& W, const Grid& G, float merge_distance, uint32_t* launches, uint32_t* cells) {
+  hipStream_t s = W.s;
+  const size_t nv = W.nv, tmp_bytes = W.tmp_bytes;
+  const uint32_t V = (uint32_t)nv;
+  DevBuf &d_pos = W.d_pos, &d_k64a = W.d_k64a, &d_k64b = W.d_k64b, &d_k32a = W.d_k32a, &d_k32b = W.d_k32b, &d_p32a = W.d_p32a, &d_p32b = W.d_p32b, &d_cstart = W.d_cstart,
+         &d_ncells = W.d_ncells, &d_count = W.d_count, &d_tmp = W.d_tmp;
+  uint32_t* target = W.d_target.as<uint32_t>();
+  size_t tb;
+  *launches = 0;
+  *cells = 0;
   if (merge_distance > 0.0f) {
     hipLaunchKernelGGL(k_cell_keys, dim3(grid_for(nv)), dim3(256), 0, s, d_pos.as<float>(), V, G, d_k64a.as<uint64_t>(), d_p32a.as<uint32_t>());
     tb = tmp_bytes;
@@ -335,17 +355,19 @@ SF_API int sf_mesh_clean_gpu(const sf_mesh* in, float merge_distance, uint32_t m
     uint32_t ncells = 0;
     CL_CHECK(hipMemcpyAsync(&ncells, d_ncells.p, 4, hipMemcpyDeviceToHost, s));
     CL_CHECK(hipStreamSynchronize(s));
+    *cells = ncells;
     CL_CHECK(hipMemsetAsync(d_k32a.as<uint32_t>() + ncells, 0, 4, s));   // the scan below reads one element past the counts
     tb = tmp_bytes;
     CL_CHECK(rocprim::exclusive_scan(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_cstart.as<uint32_t>(), 0u, (size_t)ncells + 1, rocprim::plus<uint32_t>(), s));
     CL_CHECK(hipMemsetAsync(target, 0xFF, nv * 4, s));
     uint32_t n_in = V;
     const uint32_t* pending_in = nullptr;
-    uint32_t* pend[2] = {d_pending_a.as<uint32_t>(), d_pending_b.as<uint32_t>()};
+    uint32_t* pend[2] = {W.d_pending_a.as<uint32_t>(), W.d_pending_b.as<uint32_t>()};
     for (int round = 0;; round++) {
       CL_CHECK(hipMemsetAsync(d_count.p, 0, 4, s));
       hipLaunchKernelGGL(k_settle, dim3(grid_for(n_in)), dim3(256), 0, s, d_pos.as<float>(), V, G, merge_distance, d_k64a.as<uint64_t>(), d_cstart.as<uint32_t>(), ncells,
                          d_p32b.as<uint32_t>(), pending_in, n_in, target, pend[round & 1], d_count.as<uint32_t>());
+      ++*launches;
       uint32_t left = 0;
       CL_CHECK(hipMemcpyAsync(&left, d_count.p, 4, hipMemcpyDeviceToHost, s));
       CL_CHECK(hipStreamSynchronize(s));
@@ -371,25 +393,32 @@ SF_API int sf_mesh_clean_gpu(const sf_mesh* in, float merge_distance, uint32_t m
   }
   CL_CHECK(hipMemsetAsync(d_count.p, 0, 64, s));
   hipLaunchKernelGGL(k_count_merged, dim3(grid_for(nv)), dim3(256), 0, s, target, V, d_count.as<uint32_t>() + 4);
+  return SF_OK;
+}
 
-  // ---- faces through the merge; degenerate ones out ---------------------------------------------------------------------------------------
-  if (F > 0) hipLaunchKernelGGL(k_remap_faces, dim3(grid_for(nf)), dim3(256), 0, s, d_tri_in.as<uint32_t>(), target, F, d_tri.as<Tri>(), d_keep.as<uint8_t>());
-  auto compact_faces = [&](uint32_t n, uint32_t* kept) -> int {   // d_tri -> (stable select by d_keep) -> d_tri
-    size_t t2 = tmp_bytes;
-    CL_CHECK(rocprim::select(d_tmp.p, t2, d_tri.as<Tri>(), d_keep.as<uint8_t>(), d_tri2.as<Tri>(), d_ncells.as<uint32_t>(), (size_t)n, s));
-    CL_CHECK(hipMemcpyAsync(kept, d_ncells.p, 4, hipMemcpyDeviceToHost, s));
-    CL_CHECK(hipStreamSynchronize(s));
-    std::swap(d_tri.p, d_tri2.p);
-    return SF_OK;
-  };
+int compact_faces(Work& W, uint32_t n, uint32_t* kept) {   // d_tri -> (stable select by d_keep) -> d_tri
+  size_t t2 = W.tmp_bytes;
+  CL_CHECK(rocprim::select(W.d_tmp.p, t2, W.d_tri.as<Tri>(), W.d_keep.as<uint8_t>(), W.d_tri2.as<Tri>(), W.d_ncells.as<uint32_t>(), (size_t)n, W.s));
+  CL_CHECK(hipMemcpyAsync(kept, W.d_ncells.p, 4, hipMemcpyDeviceToHost, W.s));
+  CL_CHECK(hipStreamSynchronize(W.s));
+  std::swap(W.d_tri.p, W.d_tri2.p);
+  return SF_OK;
+}
+
+// ---- faces through the merge, degenerate ones out (d_tri_in, d_target -> d_tri, n1 faces); 2. duplicate faces out (n2 faces) -----------------------------
+// keep1 / keep2 (the stage hook's; NULL in the product): the flags of the F input faces and of the n1 faces between the two selects
+int run_faces(Work& W, uint32_t F, uint32_t* n1_out, uint32_t* n2_out, uint8_t* keep1, uint8_t* keep2) {
+  hipStream_t s = W.s;
+  const size_t tmp_bytes = W.tmp_bytes;
+  DevBuf &d_k64a = W.d_k64a, &d_k64b = W.d_k64b, &d_k32a = W.d_k32a, &d_k32b = W.d_k32b, &d_p32a = W.d_p32a, &d_p32b = W.d_p32b, &d_keep = W.d_keep, &d_tmp = W.d_tmp;
+  size_t tb;
+  if (F > 0) hipLaunchKernelGGL(k_remap_faces, dim3(grid_for(F)), dim3(256), 0, s, W.d_tri_in.as<uint32_t>(), W.d_target.as<uint32_t>(), F, W.d_tri.as<Tri>(), d_keep.as<uint8_t>());
   uint32_t n1 = 0;
-  if (F > 0) { const int rc = compact_faces(F, &n1); if (rc != SF_OK) return rc; }
-  st.faces_degenerate = F - n1;
-
-  // ---- 2. duplicate faces -----------------------------------------------------------------------------------------------------------------
+  if (F > 0) { const int rc = compact_faces(W, F, &n1); if (rc != SF_OK) return rc; }
+  if (keep1 && F > 0) { CL_CHECK(hipMemcpyAsync(keep1, d_keep.p, F, hipMemcpyDeviceToHost, s)); CL_CHECK(hipStreamSynchronize(s)); }
   uint32_t n2 = n1;
   if (n1 > 0) {
-    hipLaunchKernelGGL(k_face_keys, dim3(grid_for(n1)), dim3(256), 0, s, d_tri.as<Tri>(), n1, d_k32a.as<uint32_t>(), d_k64a.as<uint64_t>());
+    hipLaunchKernelGGL(k_face_keys, dim3(grid_for(n1)), dim3(256), 0, s, W.d_tri.as<Tri>(), n1, d_k32a.as<uint32_t>(), d_k64a.as<uint64_t>());
     hipLaunchKernelGGL(k_iota, dim3(grid_for(n1)), dim3(256), 0, s, d_p32a.as<uint32_t>(), n1);
     tb = tmp_bytes;
     CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_k32b.as<uint32_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), (size_t)n1, 0, 32, s));
@@ -397,39 +426,113 @@ SF_API int sf_mesh_clean_gpu(const sf_mesh* in, float merge_distance, uint32_t m
     tb = tmp_bytes;
     CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64b.as<uint64_t>(), d_k64a.as<uint64_t>(), d_p32b.as<uint32_t>(), d_p32a.as<uint32_t>(), (size_t)n1, 0, 64, s));
     hipLaunchKernelGGL(k_dup_flags, dim3(grid_for(n1)), dim3(256), 0, s, d_k64a.as<uint64_t>(), d_k32a.as<uint32_t>(), d_p32a.as<uint32_t>(), n1, d_keep.as<uint8_t>());
-    const int rc = compact_faces(n1, &n2);
+    const int rc = compact_faces(W, n1, &n2);
     if (rc != SF_OK) return rc;
+    if (keep2) { CL_CHECK(hipMemcpyAsync(keep2, d_keep.p, n1, hipMemcpyDeviceToHost, s)); CL_CHECK(hipStreamSynchronize(s)); }
   }
-  st.faces_duplicate = n1 - n2;
+  *n1_out = n1;
+  *n2_out = n2;
+  return SF_OK;
+}
 
-  // ---- 3. small connected components ------------------------------------------------------------------------------------------------------
+// ---- 3. small connected components: the n2 faces of d_tri -> d_root, d_size, d_keep, d_count[0..2] += the counters; n3 faces stay in d_tri ----------------
+int run_components(Work& W, uint32_t n2, uint32_t min_component_faces, uint32_t* n3_out) {
+  hipStream_t s = W.s;
   uint32_t n3 = n2;
   if (n2 > 0) {
     const size_t ne = 3 * (size_t)n2;
-    hipLaunchKernelGGL(k_edge_keys, dim3(grid_for(n2)), dim3(256), 0, s, d_tri.as<Tri>(), n2, d_k64a.as<uint64_t>(), d_p32a.as<uint32_t>());
-    tb = tmp_bytes;
-    CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64a.as<uint64_t>(), d_k64b.as<uint64_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), ne, 0, 64, s));
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(n2)), dim3(256), 0, s, d_parent.as<uint32_t>(), n2);
-    hipLaunchKernelGGL(k_link, dim3(grid_for(ne)), dim3(256), 0, s, d_k64b.as<uint64_t>(), d_p32b.as<uint32_t>(), ne, d_parent.as<uint32_t>());
-    CL_CHECK(hipMemsetAsync(d_size.p, 0, (size_t)n2 * 4, s));
-    hipLaunchKernelGGL(k_roots, dim3(grid_for(n2)), dim3(256), 0, s, d_parent.as<uint32_t>(), n2, d_root.as<uint32_t>(), d_size.as<uint32_t>());
-    hipLaunchKernelGGL(k_component_flags, dim3(grid_for(n2)), dim3(256), 0, s, d_root.as<uint32_t>(), d_size.as<uint32_t>(), n2, min_component_faces, d_keep.as<uint8_t>(),
-                       d_count.as<uint32_t>());
-    const int rc = compact_faces(n2, &n3);
+    hipLaunchKernelGGL(k_edge_keys, dim3(grid_for(n2)), dim3(256), 0, s, W.d_tri.as<Tri>(), n2, W.d_k64a.as<uint64_t>(), W.d_p32a.as<uint32_t>());
+    size_t tb = W.tmp_bytes;
+    CL_CHECK(rocprim::radix_sort_pairs(W.d_tmp.p, tb, W.d_k64a.as<uint64_t>(), W.d_k64b.as<uint64_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), ne, 0, 64, s));
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(n2)), dim3(256), 0, s, W.d_parent.as<uint32_t>(), n2);
+    hipLaunchKernelGGL(k_link, dim3(grid_for(ne)), dim3(256), 0, s, W.d_k64b.as<uint64_t>(), W.d_p32b.as<uint32_t>(), ne, W.d_parent.as<uint32_t>());
+    CL_CHECK(hipMemsetAsync(W.d_size.p, 0, (size_t)n2 * 4, s));
+    hipLaunchKernelGGL(k_roots, dim3(grid_for(n2)), dim3(256), 0, s, W.d_parent.as<uint32_t>(), n2, W.d_root.as<uint32_t>(), W.d_size.as<uint32_t>());
+    hipLaunchKernelGGL(k_component_flags, dim3(grid_for(n2)), dim3(256), 0, s, W.d_root.as<uint32_t>(), W.d_size.as<uint32_t>(), n2, min_component_faces, W.d_keep.as<uint8_t>(),
+                       W.d_count.as<uint32_t>());
+    const int rc = compact_faces(W, n2, &n3);
     if (rc != SF_OK) return rc;
   }
+  *n3_out = n3;
+  return SF_OK;
+}
 
-  // ---- 4. unreferenced vertices, compaction ------------------------------------------------------------------------------------------------
+// ---- 4. unreferenced vertices, compaction: d_pos, d_col, the n3 faces of d_tri -> d_used, d_remap and the arrays of m; counters = d_count as it stands -----
+int run_compact(Work& W, uint32_t n3, bool has_col, sf_mesh* m, uint32_t* vout_out, uint32_t counters[16]) {
+  hipStream_t s = W.s;
+  const size_t nv = W.nv;
+  DevBuf &d_used = W.d_used, &d_remap = W.d_remap, &d_out_pos = W.d_out_pos, &d_out_col = W.d_out_col, &d_out_tri = W.d_out_tri;
   CL_CHECK(hipMemsetAsync(d_used.p, 0, nv * 4, s));
-  if (n3 > 0) hipLaunchKernelGGL(k_mark_used, dim3(grid_for(n3)), dim3(256), 0, s, d_tri.as<Tri>(), n3, d_used.as<uint32_t>());
-  tb = tmp_bytes;
-  CL_CHECK(rocprim::exclusive_scan(d_tmp.p, tb, d_used.as<uint32_t>(), d_remap.as<uint32_t>(), 0u, nv, rocprim::plus<uint32_t>(), s));
-  uint32_t last_used = 0, last_remap = 0, counters[16];
+  if (n3 > 0) hipLaunchKernelGGL(k_mark_used, dim3(grid_for(n3)), dim3(256), 0, s, W.d_tri.as<Tri>(), n3, d_used.as<uint32_t>());
+  size_t tb = W.tmp_bytes;
+  CL_CHECK(rocprim::exclusive_scan(W.d_tmp.p, tb, d_used.as<uint32_t>(), d_remap.as<uint32_t>(), 0u, nv, rocprim::plus<uint32_t>(), s));
+  uint32_t last_used = 0, last_remap = 0;
   CL_CHECK(hipMemcpyAsync(&last_used, d_used.as<uint32_t>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
   CL_CHECK(hipMemcpyAsync(&last_remap, d_remap.as<uint32_t>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipMemcpyAsync(counters, d_count.p, 64, hipMemcpyDeviceToHost, s));
+  CL_CHECK(hipMemcpyAsync(counters, W.d_count.p, 64, hipMemcpyDeviceToHost, s));
   CL_CHECK(hipStreamSynchronize(s));
   const uint32_t vout = last_remap + last_used;
+  *vout_out = vout;
+  m->pos.resize((size_t)vout * 3);
+  if (has_col) m->col.resize((size_t)vout * 4);
+  m->tri.resize((size_t)n3 * 3);
+  if (vout > 0) {
+    CL_CHECK(d_out_pos.alloc((size_t)vout * 12));
+    if (has_col) CL_CHECK(d_out_col.alloc((size_t)vout * 4));
+    hipLaunchKernelGGL(k_gather_vertices, dim3(grid_for(nv)), dim3(256), 0, s, W.d_pos.as<float>(), has_col ? W.d_col.as<uint8_t>() : nullptr, d_used.as<uint32_t>(),
+                       d_remap.as<uint32_t>(), (uint32_t)nv, d_out_pos.as<float>(), has_col ? d_out_col.as<uint8_t>() : nullptr);
+    CL_CHECK(hipMemcpyAsync(m->pos.data(), d_out_pos.p, (size_t)vout * 12, hipMemcpyDeviceToHost, s));
+    if (has_col) CL_CHECK(hipMemcpyAsync(m->col.data(), d_out_col.p, (size_t)vout * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (n3 > 0) {
+    CL_CHECK(d_out_tri.alloc((size_t)n3 * 12));
+    hipLaunchKernelGGL(k_remap_tris, dim3(grid_for(n3)), dim3(256), 0, s, W.d_tri.as<Tri>(), d_remap.as<uint32_t>(), n3, d_out_tri.as<uint32_t>());
+    CL_CHECK(hipMemcpyAsync(m->tri.data(), d_out_tri.p, (size_t)n3 * 12, hipMemcpyDeviceToHost, s));
+  }
+  CL_CHECK(hipStreamSynchronize(s));
+  CL_CHECK(hipGetLastError());
+  return SF_OK;
+}
+
+}  // namespace
+
+SF_API int sf_mesh_clean_gpu(const sf_mesh* in, float merge_distance, uint32_t min_component_faces, int device, sf_mesh** out, sf_clean_stats* stats) {
+  if (!in || !out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (!(merge_distance >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "merge distance must be >= 0");
+  int rc = pick_device(device, "sf_mesh_clean_gpu");
+  if (rc != SF_OK) return rc;
+  const size_t nv = in->pos.size() / 3, nf = in->tri.size() / 3;
+  if (nv >= 0xFFFFFFF0ull || nf >= 0x55555550ull) return sf::fail(SF_ERR_CAPACITY, "mesh too large for 32-bit indices");
+  sf_clean_stats st;
+  std::memset(&st, 0, sizeof(st));
+  st.vertices_in = nv;
+  st.faces_in = nf;
+  for (uint32_t v : in->tri)
+    if (v >= nv) return sf::fail(SF_ERR_FORMAT, "face references vertex %u of %zu", v, nv);
+  sf_mesh* m = new sf_mesh();
+  if (nv == 0) {
+    if (stats) *stats = st;
+    *out = m;
+    return SF_OK;
+  }
+  struct Bail { sf_mesh* m; ~Bail() { delete m; } } bail{m};   // released on success
+  Grid G{0.0, {0, 0, 0}};
+  if (merge_distance > 0.0f && (rc = grid_setup(in->pos.data(), nv, merge_distance, G)) != SF_OK) return rc;
+  const bool has_col = !in->col.empty();
+  Work W;
+  if ((rc = work_alloc(W, nv, nf, has_col, P_ALL)) != SF_OK) return rc;
+  hipStream_t s = W.s;
+  const uint32_t F = (uint32_t)nf;
+  CL_CHECK(hipMemcpyAsync(W.d_pos.p, in->pos.data(), nv * 12, hipMemcpyHostToDevice, s));
+  if (nf > 0) CL_CHECK(hipMemcpyAsync(W.d_tri_in.p, in->tri.data(), nf * 12, hipMemcpyHostToDevice, s));
+  if (has_col) CL_CHECK(hipMemcpyAsync(W.d_col.p, in->col.data(), nv * 4, hipMemcpyHostToDevice, s));
+  uint32_t launches = 0, cells = 0, n1 = 0, n2 = 0, n3 = 0, vout = 0, counters[16];
+  if ((rc = run_merge(W, G, merge_distance, &launches, &cells)) != SF_OK) return rc;
+  if ((rc = run_faces(W, F, &n1, &n2, nullptr, nullptr)) != SF_OK) return rc;
+  if ((rc = run_components(W, n2, min_component_faces, &n3)) != SF_OK) return rc;
+  if ((rc = run_compact(W, n3, has_col, m, &vout, counters)) != SF_OK) return rc;
+  st.faces_degenerate = F - n1;
+  st.faces_duplicate = n1 - n2;
   st.vertices_merged = counters[4];
   st.components_in = counters[0];
   st.components_removed = counters[1];
@@ -437,26 +540,108 @@ SF_API int sf_mesh_clean_gpu(const sf_mesh* in, float merge_distance, uint32_t m
   st.vertices_out = vout;
   st.faces_out = n3;
   st.vertices_unreferenced = nv - st.vertices_merged - st.vertices_out;
-  m->pos.resize((size_t)vout * 3);
-  if (!in->col.empty()) m->col.resize((size_t)vout * 4);
-  m->tri.resize((size_t)n3 * 3);
-  if (vout > 0) {
-    CL_CHECK(d_out_pos.alloc((size_t)vout * 12));
-    if (!in->col.empty()) CL_CHECK(d_out_col.alloc((size_t)vout * 4));
-    hipLaunchKernelGGL(k_gather_vertices, dim3(grid_for(nv)), dim3(256), 0, s, d_pos.as<float>(), in->col.empty() ? nullptr : d_col.as<uint8_t>(), d_used.as<uint32_t>(),
-                       d_remap.as<uint32_t>(), V, d_out_pos.as<float>(), in->col.empty() ? nullptr : d_out_col.as<uint8_t>());
-    CL_CHECK(hipMemcpyAsync(m->pos.data(), d_out_pos.p, (size_t)vout * 12, hipMemcpyDeviceToHost, s));
-    if (!in->col.empty()) CL_CHECK(hipMemcpyAsync(m->col.data(), d_out_col.p, (size_t)vout * 4, hipMemcpyDeviceToHost, s));
-  }
-  if (n3 > 0) {
-    CL_CHECK(d_out_tri.alloc((size_t)n3 * 12));
-    hipLaunchKernelGGL(k_remap_tris, dim3(grid_for(n3)), dim3(256), 0, s, d_tri.as<Tri>(), d_remap.as<uint32_t>(), n3, d_out_tri.as<uint32_t>());
-    CL_CHECK(hipMemcpyAsync(m->tri.data(), d_out_tri.p, (size_t)n3 * 12, hipMemcpyDeviceToHost, s));
-  }
-  CL_CHECK(hipStreamSynchronize(s));
-  CL_CHECK(hipGetLastError());
   bail.m = nullptr;
   if (stats) *stats = st;
   *out = m;
   return SF_OK;
 }
+
+// ---- stage hooks (include/scanfuse_internal.h): one helper of sf_mesh_clean_gpu on host arrays ------------------------------------------------------------
+SF_API int sf_clean_stage_merge(int device, uint32_t V, const float* pos, float radius, uint32_t* target_out, uint32_t* launches_out, uint32_t* cells_out,
+                                uint32_t* merged_out) {
+  if (!pos || !target_out || !launches_out || !cells_out || !merged_out || V == 0 || V >= 0xFFFFFFF0u) return sf::fail(SF_ERR_INVALID_ARG, "sf_clean_stage_merge: bad argument");
+  if (!(radius >= 0.0f)) return sf::fail(SF_ERR_INVALID_ARG, "merge distance must be >= 0");
+  int rc = pick_device(device, "sf_clean_stage_merge");
+  if (rc != SF_OK) return rc;
+  Grid G{0.0, {0, 0, 0}};
+  if (radius > 0.0f && (rc = grid_setup(pos, V, radius, G)) != SF_OK) return rc;
+  Work W;
+  if ((rc = work_alloc(W, V, 0, false, P_MERGE)) != SF_OK) return rc;
+  CL_CHECK(hipMemcpyAsync(W.d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, W.s));
+  if ((rc = run_merge(W, G, radius, launches_out, cells_out)) != SF_OK) return rc;
+  CL_CHECK(hipMemcpyAsync(target_out, W.d_target.p, (size_t)V * 4, hipMemcpyDeviceToHost, W.s));
+  CL_CHECK(hipMemcpyAsync(merged_out, W.d_count.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, W.s));
+  CL_CHECK(hipStreamSynchronize(W.s));
+  CL_CHECK(hipGetLastError());
+  return SF_OK;
+}
+
+SF_API int sf_clean_stage_faces(int device, uint32_t V, uint32_t F, const uint32_t* tri, const uint32_t* target, uint8_t* verdict_out, uint32_t* tri_out,
+                                uint32_t* degenerate_out, uint32_t* duplicate_out) {
+  if (!tri || !verdict_out || !tri_out || !degenerate_out || !duplicate_out || V == 0 || V >= 0xFFFFFFF0u || F == 0 || F >= 0x55555550u)
+    return sf::fail(SF_ERR_INVALID_ARG, "sf_clean_stage_faces: bad argument");
+  for (size_t i = 0; i < 3 * (size_t)F; i++)
+    if (tri[i] >= V) return sf::fail(SF_ERR_FORMAT, "face references vertex %u of %u", tri[i], V);
+  if (target)
+    for (size_t v = 0; v < V; v++)
+      if (target[v] >= V) return sf::fail(SF_ERR_FORMAT, "target names vertex %u of %u", target[v], V);
+  int rc = pick_device(device, "sf_clean_stage_faces");
+  if (rc != SF_OK) return rc;
+  Work W;
+  if ((rc = work_alloc(W, V, F, false, P_FACES)) != SF_OK) return rc;
+  hipStream_t s = W.s;
+  CL_CHECK(hipMemcpyAsync(W.d_tri_in.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
+  if (target) CL_CHECK(hipMemcpyAsync(W.d_target.p, target, (size_t)V * 4, hipMemcpyHostToDevice, s));
+  else   // nobody merged: target[v] = v, written where a face reads it (V may be 2^32 - 17: 16 GiB that nobody fills)
+    for (size_t i = 0; i < 3 * (size_t)F; i++) CL_CHECK(hipMemcpyAsync(W.d_target.as<uint32_t>() + tri[i], tri + i, 4, hipMemcpyHostToDevice, s));
+  std::vector<uint8_t> keep1(F), keep2(F);
+  uint32_t n1 = 0, n2 = 0;
+  if ((rc = run_faces(W, F, &n1, &n2, keep1.data(), keep2.data())) != SF_OK) return rc;
+  if (n2 > 0) CL_CHECK(hipMemcpyAsync(tri_out, W.d_tri.p, (size_t)n2 * 12, hipMemcpyDeviceToHost, s));
+  CL_CHECK(hipStreamSynchronize(s));
+  CL_CHECK(hipGetLastError());
+  for (uint32_t f = 0, k = 0; f < F; f++) verdict_out[f] = !keep1[f] ? 1 : (keep2[k++] ? 0 : 2);   // 0 kept, 1 degenerate, 2 duplicate
+  *degenerate_out = F - n1;
+  *duplicate_out = n1 - n2;
+  return SF_OK;
+}
+
+SF_API int sf_clean_stage_components(int device, uint32_t F, const uint32_t* tri, uint32_t min_faces, uint32_t* root_out, uint32_t* size_out, uint8_t* keep_out,
+                                     uint32_t counters[3]) {
+  if (!tri || !root_out || !size_out || !keep_out || !counters || F == 0 || F >= 0x55555550u) return sf::fail(SF_ERR_INVALID_ARG, "sf_clean_stage_components: bad argument");
+  int rc = pick_device(device, "sf_clean_stage_components");
+  if (rc != SF_OK) return rc;
+  Work W;
+  if ((rc = work_alloc(W, 1, F, false, P_COMPONENTS)) != SF_OK) return rc;
+  hipStream_t s = W.s;
+  CL_CHECK(hipMemcpyAsync(W.d_tri.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
+  CL_CHECK(hipMemsetAsync(W.d_count.p, 0, 64, s));
+  uint32_t n3 = 0;
+  if ((rc = run_components(W, F, min_faces, &n3)) != SF_OK) return rc;
+  CL_CHECK(hipMemcpyAsync(root_out, W.d_root.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+  CL_CHECK(hipMemcpyAsync(size_out, W.d_size.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));   // by root; 0 elsewhere
+  CL_CHECK(hipMemcpyAsync(keep_out, W.d_keep.p, F, hipMemcpyDeviceToHost, s));
+  CL_CHECK(hipMemcpyAsync(counters, W.d_count.p, 12, hipMemcpyDeviceToHost, s));
+  CL_CHECK(hipStreamSynchronize(s));
+  CL_CHECK(hipGetLastError());
+  return SF_OK;
+}
+
+SF_API int sf_clean_stage_compact(int device, uint32_t V, uint32_t F, const float* pos, const uint8_t* col, const uint32_t* tri, uint32_t* used_out, uint32_t* remap_out,
+                                  float* pos_out, uint8_t* col_out, uint32_t* tri_out, uint32_t* vertices_out) {
+  if (!pos || !used_out || !remap_out || !pos_out || !vertices_out || (col && !col_out) || (F > 0 && (!tri || !tri_out)) || V == 0 || V >= 0xFFFFFFF0u || F >= 0x55555550u)
+    return sf::fail(SF_ERR_INVALID_ARG, "sf_clean_stage_compact: bad argument");
+  for (size_t i = 0; i < 3 * (size_t)F; i++)
+    if (tri[i] >= V) return sf::fail(SF_ERR_FORMAT, "face references vertex %u of %u", tri[i], V);
+  int rc = pick_device(device, "sf_clean_stage_compact");
+  if (rc != SF_OK) return rc;
+  Work W;
+  if ((rc = work_alloc(W, V, F, col != nullptr, P_COMPACT)) != SF_OK) return rc;
+  hipStream_t s = W.s;
+  CL_CHECK(hipMemcpyAsync(W.d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, s));
+  if (col) CL_CHECK(hipMemcpyAsync(W.d_col.p, col, (size_t)V * 4, hipMemcpyHostToDevice, s));
+  if (F > 0) CL_CHECK(hipMemcpyAsync(W.d_tri.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
+  CL_CHECK(hipMemsetAsync(W.d_count.p, 0, 64, s));
+  sf_mesh m;
+  uint32_t vout = 0, counters[16];
+  if ((rc = run_compact(W, F, col != nullptr, &m, &vout, counters)) != SF_OK) return rc;
+  CL_CHECK(hipMemcpyAsync(used_out, W.d_used.p, (size_t)V * 4, hipMemcpyDeviceToHost, s));
+  CL_CHECK(hipMemcpyAsync(remap_out, W.d_remap.p, (size_t)V * 4, hipMemcpyDeviceToHost, s));
+  CL_CHECK(hipStreamSynchronize(s));
+  std::memcpy(pos_out, m.pos.data(), m.pos.size() * 4);
+  if (col) std::memcpy(col_out, m.col.data(), m.col.size());
+  if (F > 0) std::memcpy(tri_out, m.tri.data(), m.tri.size() * 4);
+  *vertices_out = vout;
+  return SF_OK;
+}
+

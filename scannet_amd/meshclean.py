@@ -174,3 +174,76 @@ def stage_collapse(xyz, tris, alive, Q, edges, x, device=0):
     check(L.sf_simplify_stage_collapse(int(device), len(v), len(t), v.ctypes.data, t.ctypes.data, a.ctypes.data, q.ctypes.data, len(ed), ed.ctypes.data, len(xs),
                                        xs.ctypes.data, vdel.ctypes.data))
     return {"pos": v, "tri": t, "alive": a, "Q": q, "vdel": vdel}
+
+
+# ---- stage hooks of the GPU mesh clean (include/scanfuse_internal.h; tests/test_clean_stages.py): one of the four helpers sf_mesh_clean_gpu is the
+# composition of, on host arrays.  Same result layout as tests/clean_exact.py.  An error code of the library comes back as ScanfuseError(.code).
+def clean_stage_merge(xyz, radius, device=0):
+    """Filter 1 -> {"target", "launches" (k_settle), "cells" (occupied), "merged" (k_count_merged)}."""
+    import numpy as np
+    L = _lib()
+    vp, u32p = C.c_void_p, C.POINTER(C.c_uint32)
+    L.sf_clean_stage_merge.argtypes = [C.c_int, C.c_uint32, vp, C.c_float, vp, u32p, u32p, u32p]
+    v = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    target = np.zeros(len(v), np.uint32)
+    launches, cells, merged = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(L.sf_clean_stage_merge(int(device), len(v), v.ctypes.data, float(radius), target.ctypes.data, C.byref(launches), C.byref(cells), C.byref(merged)))
+    return {"target": target, "launches": launches.value, "cells": cells.value, "merged": merged.value}
+
+
+def clean_probe_merge(xyz, radius):
+    """The host filter's clustering alone (clean.cpp's merge_close) -> target[V]."""
+    import numpy as np
+    L = _lib()
+    L.sf_clean_probe_merge.argtypes = [C.c_uint32, C.c_void_p, C.c_float, C.c_void_p]
+    v = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    target = np.zeros(len(v), np.uint32)
+    check(L.sf_clean_probe_merge(len(v), v.ctypes.data, float(radius), target.ctypes.data))
+    return target
+
+
+def clean_stage_faces(nv, tris, target=None, device=0):
+    """Degenerate and duplicate faces through the caller's target (None: nobody merged; nv may then be anything below 0xFFFFFFF0)
+    -> {"verdict" (0 kept, 1 degenerate, 2 duplicate), "tri", "degenerate", "duplicate"}."""
+    import numpy as np
+    L = _lib()
+    vp, u32p = C.c_void_p, C.POINTER(C.c_uint32)
+    L.sf_clean_stage_faces.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, u32p, u32p]
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    tg = None if target is None else np.ascontiguousarray(target, np.uint32).reshape(-1)
+    if tg is not None and len(tg) != nv:
+        raise ValueError("one target per vertex")
+    verdict, out = np.zeros(len(t), np.uint8), np.zeros((len(t), 3), np.uint32)
+    deg, dup = C.c_uint32(0), C.c_uint32(0)
+    check(L.sf_clean_stage_faces(int(device), int(nv), len(t), t.ctypes.data, None if tg is None else tg.ctypes.data, verdict.ctypes.data, out.ctypes.data,
+                                 C.byref(deg), C.byref(dup)))
+    return {"verdict": verdict, "tri": out[:len(t) - deg.value - dup.value].copy(), "degenerate": deg.value, "duplicate": dup.value}
+
+
+def clean_stage_components(tris, min_faces, device=0):
+    """-> {"root", "size" (of each face's component), "keep", "counters" {components, components below min_faces, faces in them}}."""
+    import numpy as np
+    L = _lib()
+    vp = C.c_void_p
+    L.sf_clean_stage_components.argtypes = [C.c_int, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    root, size, keep, cnt = np.zeros(len(t), np.uint32), np.zeros(len(t), np.uint32), np.zeros(len(t), np.uint8), np.zeros(3, np.uint32)
+    check(L.sf_clean_stage_components(int(device), len(t), t.ctypes.data, int(min_faces), root.ctypes.data, size.ctypes.data, keep.ctypes.data, cnt.ctypes.data))
+    return {"root": root, "size": size[root], "keep": keep, "counters": cnt}
+
+
+def clean_stage_compact(xyz, rgba, tris, device=0):
+    """-> {"used", "remap", "pos", "col" (None without colour), "tri", "vertices_out"}."""
+    import numpy as np
+    L = _lib()
+    vp = C.c_void_p
+    L.sf_clean_stage_compact.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
+    v = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    c = None if rgba is None else np.ascontiguousarray(rgba, np.uint8).reshape(len(v), 4)
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    used, remap = np.zeros(len(v), np.uint32), np.zeros(len(v), np.uint32)
+    pos, col, tri = np.zeros((len(v), 3), np.float32), np.zeros((len(v), 4), np.uint8), np.zeros((len(t), 3), np.uint32)
+    n = C.c_uint32(0)
+    check(L.sf_clean_stage_compact(int(device), len(v), len(t), v.ctypes.data, None if c is None else c.ctypes.data, t.ctypes.data if len(t) else None,
+                                   used.ctypes.data, remap.ctypes.data, pos.ctypes.data, col.ctypes.data, tri.ctypes.data if len(t) else None, C.byref(n)))
+    return {"used": used, "remap": remap, "pos": pos[:n.value].copy(), "col": None if c is None else col[:n.value].copy(), "tri": tri, "vertices_out": n.value}
