@@ -145,6 +145,11 @@ int sf_clean_probe_merge(uint32_t V, const float* pos, float radius, uint32_t* t
  * division -- all 2^23 mantissas x 9 exponents for 1/x, 511 integer divisors x 2^21 numerators for n/m, 2^28 general operand pairs
  * (incl. near-exact and near-half-way quotients) for a/b.  All three counts must be 0 (tests/test_gpu_tsdf.py). */
 int sf_selftest_division(int device, uint64_t* recip_mismatches, uint64_t* quot_mismatches, uint64_t* div_mismatches);
+/* Device self-test: 1 / b by ONE Newton step from the hardware's reciprocal seed, for every one of the 2^32 bit patterns as b; every normal b whose
+ * correctly rounded reciprocal is normal is compared with 1.0f / b.  *mismatches = how many differ; patterns_out[0 .. min(*mismatches, capacity)) = bit
+ * patterns of b that do (which ones, when there are more than `capacity`, is up to the scheduling; capacity 0: none).  *shipped (may be NULL) = 1 when
+ * the kernels' reciprocal (recip_rn, fuser_internal.h) IS that one step, 0 when it takes two.  A few milliseconds. */
+int sf_selftest_recip_one_step(int device, uint64_t* mismatches, uint32_t* patterns_out, uint32_t capacity, int* shipped);
 
 /* Measurement aid (bench.py roofline_single_frame.pattern_ceiling): the memory traffic of the most recent integrate pass
  * without its arithmetic -- every tile of that pass's list is read and (read_only == 0) written back unchanged, with the

@@ -105,7 +105,49 @@ __global__ __launch_bounds__(256) void k_selftest_div(unsigned long long* bad) {
   n += __float_as_uint(rb) != __float_as_uint(1.0f / b);
   if (n) atomicAdd(bad, (unsigned long long)n);
 }
+// 1 / b by ONE Newton step from the v_rcp_f32 seed (recip_one_step, fuser_internal.h) for every one of the 2^32 bit patterns: 16 per thread.  Counted:
+// normal b whose correctly rounded reciprocal is normal as well.  tools/check_division.c part (4) shows what the outcome hangs on: from a seed that
+// is one of the two floats either side of 1 / b the step is exact for every mantissa but all-ones, and for that one from the round-up seed -- so
+// whether the step suffices is a property of this part's v_rcp_f32, decided by running it.
+__global__ __launch_bounds__(256) void k_selftest_recip_one_step(unsigned long long* bad, uint32_t* first, uint32_t capacity) {
+  const uint32_t base = (blockIdx.x * 256u + threadIdx.x) << 4;   // 2^28 threads
+  for (uint32_t k = 0; k < 16u; k++) {
+    const uint32_t bits = base | k;
+    const float b = __uint_as_float(bits);
+    const uint32_t ref = __float_as_uint(1.0f / b);
+    const uint32_t eb = (bits >> 23) & 0xFFu, er = (ref >> 23) & 0xFFu;
+    if (eb == 0u || eb == 255u || er == 0u || er == 255u) continue;
+    if (__float_as_uint(recip_one_step(b)) != ref) {
+      const unsigned long long slot = atomicAdd(bad, 1ull);
+      if (slot < (unsigned long long)capacity) first[slot] = bits;
+    }
+  }
+}
 }  // namespace
+
+SF_API int sf_selftest_recip_one_step(int device, uint64_t* mismatches, uint32_t* patterns_out, uint32_t capacity, int* shipped) {
+  if (!mismatches || (capacity > 0 && !patterns_out)) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(device));
+  unsigned long long* d = nullptr;
+  uint32_t* p = nullptr;
+  SF_HIP_CHECK(hipMalloc((void**)&d, 8));
+  if (hipMalloc((void**)&p, 4 * (size_t)(capacity ? capacity : 1)) != hipSuccess) { (void)hipFree(d); return sf::fail(SF_ERR_DEVICE, "self-test: hipMalloc failed"); }
+  hipError_t e = hipMemset(d, 0, 8);
+  if (e == hipSuccess) e = hipMemset(p, 0, 4 * (size_t)(capacity ? capacity : 1));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_selftest_recip_one_step, dim3(1u << 20), dim3(256), 0, nullptr, d, p, capacity);
+    e = hipGetLastError();
+  }
+  unsigned long long h = 0;
+  if (e == hipSuccess) e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && capacity > 0) e = hipMemcpy(patterns_out, p, 4 * (size_t)capacity, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  (void)hipFree(p);
+  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "self-test failed: %s", hipGetErrorString(e));
+  *mismatches = h;
+  if (shipped) *shipped = RECIP_ONE_STEP ? 1 : 0;
+  return SF_OK;
+}
 
 SF_API int sf_selftest_division(int device, uint64_t* recip_mismatches, uint64_t* quot_mismatches, uint64_t* div_mismatches) {
   if (!recip_mismatches || !quot_mismatches || !div_mismatches) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");

@@ -602,7 +602,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
     if (in_image) {
       const uint16_t u = fuse_depth16[(size_t)(y * P.W + x)];
       float v = (float)u / P.depth_shift;
-      if (u == 0 || v < P.dmin || v > P.dmax) v = -INFINITY;
+      if (u == 0 || v < P.dmin || v > P.dmax || !(v < P.maxd)) v = -INFINITY;   // k_prepass's gates, the integration distance included
       depthf_out[(size_t)(y * P.W + x)] = v;
       d_next = v;
     }

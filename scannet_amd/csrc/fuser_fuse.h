@@ -13,14 +13,18 @@ namespace {
 // (SQ_INSTS_VALU x 2 clk / SIMD clk = 0.57 of the guide's issue peak, the texture addresser busy 0.56 of the time, HBM at 9 %: bench.py `roofline`,
 // profiles/r06_integrate_xrow_ab.txt), so the update is written for instruction count:
 //   * two straight-line phases: phase A projects all eight voxels and issues the eight depth gathers together at
-//     clamped addresses, phase B applies the update under a select (a per-voxel early-out chain serialises eight
-//     L2 round trips and costs a scalar branch pair per test);
+//     clamped addresses, phase B applies the update (a per-voxel early-out chain serialises eight
+//     L2 round trips and costs a scalar branch pair per test) -- under a select, or, for the shipped parameters, with the
+//     instruction that produces a new word writing the tile register under the voxel's update mask (fuse_update);
+//   * what is a property of the pixel or of the lane is not tested per voxel: the integration distance is gated by the pre-pass (-inf fails the
+//     band test by itself), "in front of the camera" is two compares and a vote per lane in the x-row layout (fuse_project_xr);
 //   * the lane's voxel pairs are written as v2f pairs (fuser_internal.h) and compiled as two plain fp32 operations each: on gfx950 a v_pk_*_f32 holds the
 //     SIMD as long as two plain ones and issues beside nothing (rounds 1-4 shipped the packed form);
-//   * the two IEEE divisions of DESIGN.md 3.5 are expanded by hand.  1/pcz: v_rcp_f32 seed + two Newton steps --
-//     the arithmetic core of the compiler's own correctly rounded expansion without the div_scale / div_fixup
-//     range handling (pcz is a camera-space depth in metres; exhaustive check over all mantissas and seed errors up
-//     to 2 ulp: tools/check_division.c).  (old*w + sdf*wn) / (w + wn): the divisor is a small integer, its
+//   * the two IEEE divisions of DESIGN.md 3.5 are expanded by hand.  1/pcz: v_rcp_f32 seed + ONE Newton step --
+//     correctly rounded from a seed that is one of the two floats either side of 1/pcz (tools/check_division.c part 4), which
+//     gfx950's v_rcp_f32 delivers for every normal argument (sf_selftest_recip_one_step: all 2^32 bit patterns on the device, 0
+//     mismatches; recip_rn, fuser_internal.h); no div_scale / div_fixup range handling (pcz is a camera-space depth in
+//     metres).  (old*w + sdf*wn) / (w + wn): the divisor is a small integer, its
 //     correctly rounded reciprocal comes from an LDS table and ONE Markstein correction q1 = fma(fma(-m, q0, n), r, q0)
 //     yields the correctly rounded quotient (same tool: 1.4e9 cases incl. near-halfway); numerators below 2^-100
 //     take the plain division so that underflow cannot bite.
@@ -55,6 +59,15 @@ __device__ inline uint32_t add_sat_u32(uint32_t a, uint32_t b) {
   uint32_t r;
   asm("v_add_u32_e64 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "s"(b));
   return r;
+}
+
+// The producing instruction of a new voxel word, writing the tile register in place: called under `if (mask)`, i.e. with EXEC = the voxel's update mask
+// (fuse_update).  Volatile: an asm the compiler may speculate is computed for every lane and selected afterwards.
+__device__ inline void write_fma(uint32_t& dst, float a, float b, float c) {   // dst = fma(a, b, c)
+  asm volatile("v_fma_f32 %0, %1, %2, %3" : "+v"(dst) : "v"(a), "v"(b), "v"(c));
+}
+__device__ inline void write_bfi(uint32_t& dst, uint32_t mask, uint32_t a, uint32_t b) {   // dst = (a & mask) | (b & ~mask); the mask in a scalar register
+  asm volatile("v_bfi_b32 %0, %1, %2, %3" : "+v"(dst) : "s"(mask), "v"(a), "v"(b));
 }
 
 // weight_mode 1 (VoxelHashing): the weight of an observation falls with its depth; (uchar) of the float, at most 255
@@ -123,19 +136,30 @@ __device__ inline void fuse_project_xr(const ParamsK& P, const FrameV& FV, const
   const float ay = fmaf(Ti[5], wy, fmaf(Ti[6], wz, Ti[7]));
   const float az = fmaf(Ti[9], wy, fmaf(Ti[10], wz, Ti[11]));
 #pragma unroll
+  for (int j = 0; j < NJ; j++) pz[j] = pk_fma(splat(Ti[8]), wxp[J0 + j], splat(az));
+  // "in front of the camera" once per lane: the lane's voxels differ in x only, wx rises along the row and fma rounds monotonically, so every pcz of the
+  // row lies between the two end voxels' -- all are positive exactly when both ends are (a NaN az makes both ends NaN: the vote fails).  Two compares
+  // and a wave vote instead of eight compares; only a wave the camera plane cuts (rare, wave-uniform) tests voxel by voxel.
+  // (a ballot per compare: the ballot of an i1 that is not itself a compare costs a v_cndmask and a v_cmp)
+  const bool front = (__ballot(pz[0].x > 0.0f) & __ballot(pz[NJ - 1].y > 0.0f)) == __ballot(1);
+  bool zpos[2 * NJ];
+#pragma unroll
+  for (int k = 0; k < 2 * NJ; k++) zpos[k] = true;
+  if (__builtin_expect(!front, 0)) {
+#pragma unroll
+    for (int k = 0; k < 2 * NJ; k++) zpos[k] = pz[k >> 1][k & 1] > 0.0f;
+  }
+#pragma unroll
   for (int j = 0; j < NJ; j++) {
     const v2f pcx = pk_fma(splat(Ti[0]), wxp[J0 + j], splat(ax));
     const v2f pcy = pk_fma(splat(Ti[4]), wxp[J0 + j], splat(ay));
-    const v2f pcz = pk_fma(splat(Ti[8]), wxp[J0 + j], splat(az));
-    const v2f rz = recip_rn(pcz);
+    const v2f rz = recip_rn(pz[j]);
     const v2f uf = pk_add(pk_fma(pcx * splat(FV.fx), rz, splat(FV.mx)), splat(0.5f));
     const v2f vf = pk_add(pk_fma(pcy * splat(FV.fy), rz, splat(FV.my)), splat(0.5f));
-    pz[j] = pcz;
 #pragma unroll
     for (int hx = 0; hx < 2; hx++) {
       const uint32_t px = (uint32_t)cvt_i32(uf[hx]), py = (uint32_t)cvt_i32(vf[hx]);
-      const bool in = (pcz[hx] > 0.0f) && (px < uw) && (py < uh);
-      ok[2 * j + hx] = in;
+      ok[2 * j + hx] = zpos[2 * j + hx] && (px < uw) && (py < uh);
       pix[2 * j + hx] = __umul24(py, uw) + px;
     }
   }
@@ -149,9 +173,11 @@ __device__ inline void fuse_project_xr(const ParamsK& P, const FrameV& FV, const
 // COLOR: 0 = geometry only, 1 = colour (every switch a wave-uniform mask), 2 = colour with colour_first == 0 compiled in.
 // ROWS: dirty[] holds one lane mask per row (one frame per launch: the HBM-bound schedule writes back only the rows some lane changed); without
 // it dirty[0] is a wave-uniform "some frame touched this tile" flag and the caller writes the whole tile back -- a ballot of an i1 that is not
-// itself a compare costs a v_cndmask + v_cmp per row (8 of the 241 VALU instructions of a lane's frame), and a pass of 32 frames is VALU-bound
+// itself a compare costs a v_cndmask + v_cmp per row (8 VALU instructions on top of the 291 of a lane's RGB-D frame), and a pass of 32 frames is VALU-bound
 // with HBM at 8 % of its peak.
-template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS = true>
+// PRED: the shipped parameters write the new voxel under its update mask (below); false keeps the select tail for them too (k_reintegrate, whose two
+// bodies leave no registers for the regions).
+template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS = true, bool PRED = true>
 __device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f (&rcp_m)[NJ], const float (&d)[2 * NJ], const uint32_t (&c)[2 * NJ], const v2f (&pz)[NJ],
                                    const bool (&ok)[2 * NJ], uint4 (&v)[4], uint64_t (&dirty)[4]) {
   constexpr bool WS1 = WM == 1 || WM == 2;
@@ -163,7 +189,6 @@ __device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f
   const uint32_t round_mask = P.colour_round ? 0x010101u : 0u;             // scalar registers
   const uint32_t first_mask = P.colour_first ? 0x00FFFFFFu : 0xFF000000u;
   constexpr bool wdep = WM == 3;   // depth-dependent observation weight (sf_params::weight_mode 1): its own instantiation, the generic path pays nothing for it
-  const uint32_t maxd_bits = __float_as_uint(P.maxd);
   v2f q[NJ], sdfc[NJ];
   v2f wnv[NJ];          // weight of this observation per voxel (a splat unless wdep)
   int wni[2 * NJ];
@@ -178,8 +203,10 @@ __device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f
     const v2f t = pk_fma(splat(FV.tscale), dk, splat(FV.tbase));
 #pragma unroll
     for (int hx = 0; hx < 2; hx++) {
-      // valid depth (-inf has the sign bit set, valid depths are positive) below the integration distance, not behind the band
-      upd[2 * j + hx] = ok[2 * j + hx] && (__float_as_uint(dk[hx]) < maxd_bits) && (sdf[hx] > -t[hx]);
+      // not behind the band.  No test of the depth itself: the pre-pass writes -inf for a pixel without a measurement, out of the sensor's range or at /
+      // beyond the integration distance (a property of the pixel, gated once per pixel), and -inf fails this compare by itself --
+      // t = fma(tscale, -inf, tbase) is -inf (NaN for tscale 0), sdf = -inf - pcz is -inf (NaN for pcz = -inf), and neither is greater than anything
+      upd[2 * j + hx] = ok[2 * j + hx] && (sdf[hx] > -t[hx]);
       sdf[hx] = min_f32(sdf[hx], t[hx]);
       sat[2 * j + hx] = false;
       any_upd = any_upd || upd[2 * j + hx];
@@ -189,7 +216,70 @@ __device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f
     sdfc[j] = sdf;
   }
   if (!__any((int)any_upd)) return;
-  // ---- phase B2: new values into temporaries (the tile itself stays untouched until the end)
+  // ---- phase B2 of the shipped parameters (integration, table division, weight byte + 1 saturating at 255): no select between the new and the old
+  // voxel.  upd[k] is a lane mask in a scalar register pair; the instruction that PRODUCES a new word -- the last fma of the quotient, the merge of
+  // {rgb, weight} -- writes the tile register itself with EXEC = upd[k], one exec region per voxel (write_fma / write_bfi: volatile, so that the
+  // compiler cannot compute them for every lane and select afterwards).  16 v_cndmask fewer per lane and frame with colour, 8 without: geometry only
+  // keeps the select on the {rgb, weight} word, whose "weight already 255" carry has to be produced by an instruction either way.
+  if constexpr (PRED && SIGN > 0 && TAB && WM == 2) {
+    v2f q0[NJ], e[NJ];   // q = fma(e, r, q0) (quot_rn); its last fma is left to the write below
+    bool tiny = false;
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+      const v2f wo = {(float)(v[J0 + j].y >> 24), (float)(v[J0 + j].w >> 24)};
+      const v2f old = {__uint_as_float(v[J0 + j].x), __uint_as_float(v[J0 + j].z)};
+      const v2f n = pk_fma(old, wo, sdfc[j]);   // weight_sample == 1: sdf * 1.0f == sdf bit for bit
+      const v2f m = wo + splat(wn);             // wn == 1.0f, as a run-time value: one add, not a second conversion
+      q0[j] = n * rcp_m[j];
+      e[j] = pk_fma(-m, q0[j], n);
+      tiny = tiny || (fabsf(n.x) < 0x1p-100f) || (fabsf(n.y) < 0x1p-100f);
+    }
+    if (__builtin_expect(__any((int)tiny) != 0, 0)) {
+      // some numerator of the wave is in the underflow range (practically: never): the plain IEEE quotient q, handed to the same write as
+      // fma(-0, r, q) = q + (-0) = q for every q, the zeros' signs included.  (ONE write-back body: a second one for this case met the first at the
+      // loop's end with the tile in other registers, and the live path copied the tile aside and back -- 32 v_mov per frame.)
+#pragma unroll
+      for (int j = 0; j < NJ; j++) {
+        const v2f wo = {(float)(v[J0 + j].y >> 24), (float)(v[J0 + j].w >> 24)};
+        const v2f old = {__uint_as_float(v[J0 + j].x), __uint_as_float(v[J0 + j].z)};
+        const v2f n = pk_fma(old, wo, sdfc[j]);
+        const v2f m = wo + splat(wn);
+        q0[j] = (v2f){n.x / m.x, n.y / m.y};
+        e[j] = splat(-0.0f);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+#pragma unroll
+      for (int hx = 0; hx < 2; hx++) {
+        const int k = 2 * j + hx;
+        uint32_t& sdf_word = hx ? v[J0 + j].z : v[J0 + j].x;
+        uint32_t& cw_word = hx ? v[J0 + j].w : v[J0 + j].y;
+        const uint32_t cw = cw_word;
+        uint32_t rgb = cw, wsum = 0u;
+        bool keep = false;   // geometry only: the weight is 255 already, the word stays
+        if (COLOR) {
+          // the blend of the generic path below (v_lerp_u8; "first observation" by the weight byte or the colour_first mask)
+          const uint32_t ck = c[k];
+          const uint32_t avg = __builtin_amdgcn_lerp(cw, ck, round_mask);
+          const bool first = COLOR == 2 ? cw < 0x01000000u : (cw & first_mask) == 0u;
+          rgb = first ? ck : avg;
+          wsum = add_sat_u32(cw, 0x01000000u);   // 0xFFFFFFFF exactly when the weight was 255; only byte 3 is kept
+        } else {
+          keep = __builtin_add_overflow(cw, 0x01000000u, &wsum);
+        }
+        if (upd[k]) {
+          write_fma(sdf_word, e[j][hx], rcp_m[j][hx], q0[j][hx]);
+          if (COLOR) write_bfi(cw_word, 0x00FFFFFFu, rgb, wsum);
+        }
+        if (!COLOR) cw_word = (upd[k] && !keep) ? wsum : cw_word;
+      }
+      if (ROWS) dirty[J0 + j] |= __ballot(upd[2 * j] || upd[2 * j + 1]);
+    }
+    if (!ROWS) dirty[0] = ~0ull;
+    return;
+  }
+  // ---- phase B2, every other variant: new values into temporaries (the tile itself stays untouched until the end)
   bool slow = false;
 #pragma unroll
   for (int j = 0; j < NJ; j++) {
@@ -284,7 +374,7 @@ __device__ inline __amdgpu_buffer_rsrc_t image_rsrc(const void* base, uint32_t b
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);   // raw buffer, dword data format (gfx9)
 }
 
-template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS, bool XR = false>
+template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS, bool XR = false, bool PRED = true>
 __device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti, const float* __restrict__ depthf,
                                  const uint2* __restrict__ texel, const float* rtab, v2f wx, float wy, const float (&wz)[4], const v2f (&wxp)[4],
                                  uint4 (&v)[4], uint64_t (&dirty)[4]) {
@@ -323,7 +413,7 @@ __device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti,
 #pragma unroll
     for (int k = 0; k < 2 * NJ; k++) d[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, pix[k] << 2, 0, 0));
   }
-  fuse_update<SIGN, COLOR, TAB, WM, J0, NJ, ROWS>(P, FV, rcp_m, d, c, pz, ok, v, dirty);
+  fuse_update<SIGN, COLOR, TAB, WM, J0, NJ, ROWS, PRED>(P, FV, rcp_m, d, c, pz, ok, v, dirty);
 }
 
 }  // namespace

@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256, PIPE_WGS) void k_integrate_pipe(uint4* __restr
     float d[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) d[k] = gath[par * 512 + k * 64 + lane];
-    // RN(1 / (weight + sample)) by v_rcp_f32 + two Newton steps (recip_rn: correctly rounded for every normal divisor, the same bits
+    // RN(1 / (weight + sample)) by v_rcp_f32 + a Newton step (recip_rn: correctly rounded for every normal divisor, the same bits
     // as k_integrate's LDS table) -- this kernel has VALU slots to spare and its LDS decides who may run beside it: 48 KiB per
     // workgroup x 3 leaves 16 KiB per CU, room for one workgroup of the NEXT frame's allocation / compaction on the front stream
     v2f rcp_m[4];

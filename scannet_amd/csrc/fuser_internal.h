@@ -237,8 +237,19 @@ __device__ inline v2f operator-(v2f a) { return v2f{-a.x, -a.y}; }
 __device__ inline v2f pk_fma(v2f a, v2f b, v2f c) { return v2f{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)}; }
 __device__ inline v2f splat(float x) { return v2f{x, x}; }
 __device__ inline v2f pk_add(v2f a, v2f b) { return a + b; }
-// RN(1 / b) for normal-range b: v_rcp_f32 seed (1 ulp) + two Newton steps
+// 1 / b by ONE Newton step from the v_rcp_f32 seed.  From a seed that is one of the two floats either side of 1 / b the step is RN(1 / b) for every
+// mantissa but all-ones (and for that one from the round-up seed); one ulp further out it is wrong for some mantissas (tools/check_division.c part 4).
+// Whether that suffices is therefore a property of the part's v_rcp_f32: sf_selftest_recip_one_step (calib.hip) runs all 2^32 bit patterns through
+// this function.  On the MI355X (gfx950): 0 mismatches over every normal b with a normal reciprocal (profiles/integrate_instruction_cuts.txt;
+// tests/test_gpu_integrate_cuts.py holds every device the suite runs on to it), so the second step is dropped.
+__device__ inline float recip_one_step(float b) {
+  const float r = __builtin_amdgcn_rcpf(b);
+  return fmaf(fmaf(-b, r, 1.0f), r, r);
+}
+constexpr bool RECIP_ONE_STEP = true;   // recip_rn below is recip_one_step; false: the two-step form (correct from any seed within 2 ulp)
+// RN(1 / b) for normal-range b: v_rcp_f32 seed + one Newton step (two with RECIP_ONE_STEP false)
 __device__ inline v2f recip_rn(v2f b) {
+  if (RECIP_ONE_STEP) return v2f{recip_one_step(b.x), recip_one_step(b.y)};
   v2f r = {__builtin_amdgcn_rcpf(b.x), __builtin_amdgcn_rcpf(b.y)};
   const v2f one = splat(1.0f);
   r = pk_fma(pk_fma(-b, r, one), r, r);
@@ -249,6 +260,7 @@ __device__ inline v2f recip_rn(v2f b) {
 // y = RN(1 / b) it costs 5 instructions where the full expansion costs ten and a quarter-rate v_rcp_f32.  k_alloc divides twelve times per
 // ray (world -> block through / voxel, the DDA's tMax / tDelta through / direction); device self-test: sf_selftest_division.
 __device__ inline float recip_rn(float b) {
+  if (RECIP_ONE_STEP) return recip_one_step(b);
   float r = __builtin_amdgcn_rcpf(b);
   r = fmaf(fmaf(-b, r, 1.0f), r, r);
   return fmaf(fmaf(-b, r, 1.0f), r, r);

@@ -85,7 +85,9 @@ __global__ __launch_bounds__(256) void k_prepass(BatchIn in, float* __restrict__
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     float v = (float)u[k] / shift;
-    if (u[k] == 0 || v < dmin || v > dmax) v = -INFINITY;
+    // ... and the integration distance (zParametersScanNet.txt:51), the oracle's "if (!(d < max_integration_dist)) continue": a property of the pixel,
+    // gated here once instead of per voxel and frame in fuse_update.  The allocation kernels test d < maxd themselves: -inf changes nothing for them.
+    if (u[k] == 0 || v < dmin || v > dmax || !(v < P.maxd)) v = -INFINITY;
     d[k] = v;
   }
   if (i0 + 8 <= n) {

@@ -32,7 +32,8 @@ namespace {
 //           depth plane alone -- the pre-pass writes the metres of an RGB-D frame twice, beside the colour and on their own.
 // Tiles go back whole when some slot changed them (ROWS false), as in the multi-frame pass.
 // Registers: the two bodies are live one after the other, not together, so the budget is the larger body's -- see DESIGN.md 4d for the figures
-// tests/test_reintegrate_plan.py holds the kernel to.
+// tests/test_reintegrate_plan.py holds the kernel to.  The + body keeps the select tail of fuse_update (PRED false): with the predicated write-back of
+// k_integrate the colour x-row variant needs 96 registers and spills four.
 // ---------------------------------------------------------------------------------------------------
 constexpr int REINT_WAVES = 5;   // workgroups (of 4 waves) per CU = waves per SIMD the register budget is set for: k_integrate's
 
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256, REINT_WAVES) void k_reintegrate(uint4* __restr
       const float* __restrict__ depthf = depthf_all + im * npx;
       const uint2* __restrict__ texel = texel_all + im * npx;
       if ((R.neg >> q) & 1u) fuse_rows<-1, 0, false, WMN, 0, 4, false, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
-      else fuse_rows<1, COLOR, TAB, WM, 0, 4, false, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+      else fuse_rows<1, COLOR, TAB, WM, 0, 4, false, XR, false>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);   // PRED false: see above
     }
     if (dirty[0] != 0ull) {   // wave-uniform: some slot changed a voxel of this tile
 #pragma unroll

@@ -14,6 +14,10 @@
  *     y = RN(1/b), q0 = RN(a*y), q1 = fma(fma(-b, q0, a), y, q0), q = fma(fma(-b, q1, a), y, q1) -- the quotient part of the compiler's
  *     own expansion without div_scale / div_fixup.  Claim: q == RN(a/b).  Checked on 2^30 operand pairs: random bit patterns in the
  *     ranges k_alloc sees, dividends within 3 ulp of exact multiples and of half-way multiples of the divisor.
+ * (4) 1 / b by ONE Newton step, by where the seed lies (all 2^23 mantissas x 3 exponents, as in (2)).  From a seed that is one of the two floats
+ *     either side of 1/b the step is RN(1/b) for every mantissa but all-ones, and for that one from the upper seed; a seed one ulp further out is
+ *     not enough.  So whether recip_rn may drop its second step is a property of the hardware's v_rcp_f32, decided on the device by
+ *     sf_selftest_recip_one_step (calib.hip).  Reported on stderr; stdout carries the three zero-mismatch claims.
  */
 #include <math.h>
 #include <stdint.h>
@@ -73,5 +77,33 @@ int main(void) {
     }
   }
   printf("(3) reciprocal + two residual corrections: %ld cases, %ld mismatches vs a/b\n", tot3, bad3);
-  return (bad1 || differ || wrong_exact_seed || bad3) ? 1 : 0;
+  /* (4) ONE Newton step r1 = fma(fma(-b, r0, 1), r0, r0), by the seed's position.  `lo` / `hi` are the two floats either side of 1/b (lo <= 1/b <= hi; both
+   * are 1/b itself when it is a float): a seed "accurate to 1 ulp" is one of them.  Same sweep as (2).  Its figures are not zero by nature, so the report goes
+   * to stderr and stdout keeps the three claims above; what (4) asserts is the structure the device self-test (sf_selftest_recip_one_step) rests on:
+   * from a bracketing seed the step is wrong for the all-ones mantissa only, and there only from the lower seed. */
+  long wrong_lo = 0, wrong_hi = 0, wrong_lo_other = 0, wrong_hi_any_allones = 0, wrong_out = 0, mant_out = 0;
+  for (uint32_t mant = 0; mant < (1u << 23); mant++) {
+    int out_this = 0;
+    for (int ex = 0; ex < 3; ex++) {
+      const float b = asf((ex == 0 ? 0x3f800000u : ex == 1 ? 0x3c000000u : 0x43000000u) | mant), ref = 1.0f / b;
+      const double exact = 1.0 / (double)b;
+      float lo = ref, hi = ref;
+      if ((double)ref > exact) lo = asf(asu(ref) - 1);
+      else if ((double)ref < exact) hi = asf(asu(ref) + 1);
+      const float seeds[4] = {lo, hi, asf(asu(lo) - 1), asf(asu(hi) + 1)};
+      for (int k = 0; k < 4; k++) {
+        const float r0 = seeds[k], r1 = fmaf(fmaf(-b, r0, 1.0f), r0, r0);
+        if (asu(r1) == asu(ref)) continue;
+        if (k == 0) { wrong_lo++; if (mant != 0x7fffffu) wrong_lo_other++; }
+        else if (k == 1) { wrong_hi++; if (mant == 0x7fffffu) wrong_hi_any_allones++; }
+        else { wrong_out++; out_this = 1; }
+      }
+    }
+    mant_out += out_this;
+  }
+  fprintf(stderr, "(4) one Newton step: from the lower bracketing seed wrong %ld times (%ld of them not the all-ones mantissa), from the upper one %ld times "
+                  "(%ld at all-ones); one ulp beyond the bracket wrong %ld times, on %ld mantissas\n", wrong_lo, wrong_lo_other, wrong_hi, wrong_hi_any_allones,
+          wrong_out, mant_out);
+  const int bad4 = wrong_lo_other != 0 || wrong_hi != 0 || wrong_lo == 0 || wrong_out == 0;
+  return (bad1 || differ || wrong_exact_seed || bad3 || bad4) ? 1 : 0;
 }

@@ -67,7 +67,29 @@ def frame_loop(lines):
         return lines
     last = max(i for i, l in enumerate(lines) if l.startswith(("s_cbranch", "s_branch")))
     tile_store = next((i for i, l in enumerate(lines) if i > first and l.startswith("global_store_dwordx4")), last)
-    return lines[first:min(last, tile_store)]
+    end = min(last, tile_store)
+    # the live path ends at the unconditional branch back to the loop head behind the gathers; what the compiler lays out between that branch and the tile
+    # store are the loop's cold blocks (the per-voxel "in front of the camera" tests of a wave the camera plane cuts, the underflow tail with its
+    # plain divisions): wave-uniform, practically never run, not part of a frame's work
+    gathers = [i for i, l in enumerate(lines[:end]) if i > first and l.startswith("buffer_load")]
+    if gathers:
+        back = next((i for i in range(gathers[-1], end) if lines[i].startswith("s_branch") and int(lines[i].split()[1]) >= 0x8000), None)
+        if back is not None:
+            end = back
+    return lines[first:end]
+
+
+def phases(lines):
+    """VALU instructions of the frame loop's live path by phase: A = projection, addresses, bounds (up to the last gather), B1 = the band test (up to the
+    wave-uniform early-out branch), B2 = the update.  A + B1 is what a (tile, frame) pair that updates nothing costs."""
+    loop = frame_loop(lines)
+    valu = lambda ls: sum(1 for l in ls if l.startswith("v_"))
+    g = [i for i, l in enumerate(loop) if l.startswith("buffer_load")]
+    if not g:
+        return None
+    out = next((i for i in range(g[-1], len(loop)) if loop[i].startswith("s_cbranch_vcc")), len(loop))
+    a, b1, b2 = valu(loop[:g[-1] + 1]), valu(loop[g[-1] + 1:out]), valu(loop[out:])
+    return {"A": a, "B1": b1, "B2": b2, "early_out_path": a + b1, "live_path": a + b1 + b2}
 
 
 def price(lines):
@@ -111,7 +133,7 @@ def main():
            "kernels": {}}
     for pat in (a.kernel or ["k_integrateILi1ELi2ELb1ELi2ELb0ELi4E", "k_integrateILi1ELi0ELb1ELi2ELb0ELi4E"]):
         name, lines = kernel_body(text, pat)
-        out["kernels"][pat] = {"whole_kernel": price(lines), "frame_loop": price(frame_loop(lines))}
+        out["kernels"][pat] = {"whole_kernel": price(lines), "frame_loop": price(frame_loop(lines)), "frame_loop_valu_by_phase": phases(lines)}
     print(json.dumps(out, indent=1))
 
 
