@@ -150,6 +150,9 @@ int sf_selftest_division(int device, uint64_t* recip_mismatches, uint64_t* quot_
  * patterns of b that do (which ones, when there are more than `capacity`, is up to the scheduling; capacity 0: none).  *shipped (may be NULL) = 1 when
  * the kernels' reciprocal (recip_rn, fuser_internal.h) IS that one step, 0 when it takes two.  A few milliseconds. */
 int sf_selftest_recip_one_step(int device, uint64_t* mismatches, uint32_t* patterns_out, uint32_t capacity, int* shipped);
+/* Device self-test: the 256 per-weight records of the multi-frame integrate kernels' LDS table, built on the device by the function the kernels
+ * call.  out[4 w .. 4 w + 3] = bits of (float)w, of (float)(w + 1), of 1.0f / (float)(w + 1), and min(w + 1, 255) << 24 | (w == 0 ? 0x00FFFFFF : 0). */
+int sf_selftest_weight_records(int device, uint32_t* out /* 256 x 4 */);
 
 /* Measurement aid (bench.py roofline_single_frame.pattern_ceiling): the memory traffic of the most recent integrate pass
  * without its arithmetic -- every tile of that pass's list is read and (read_only == 0) written back unchanged, with the

@@ -123,7 +123,27 @@ __global__ __launch_bounds__(256) void k_selftest_recip_one_step(unsigned long l
     }
   }
 }
+// the per-weight records of k_integrate's LDS table, built by the function the kernel calls, copied out word for word
+__global__ __launch_bounds__(256) void k_selftest_weight_records(uint4* out) {
+  __shared__ uint4 s_rec[WREC];
+  fill_weight_records(s_rec, (int)threadIdx.x, 256);
+  __syncthreads();
+  for (int i = threadIdx.x; i < WREC; i += 256) out[i] = s_rec[i];
+}
 }  // namespace
+
+SF_API int sf_selftest_weight_records(int device, uint32_t* out) {
+  if (!out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  SF_HIP_CHECK(hipSetDevice(device));
+  uint4* d = nullptr;
+  SF_HIP_CHECK(hipMalloc((void**)&d, WREC * sizeof(uint4)));
+  hipLaunchKernelGGL(k_selftest_weight_records, dim3(1), dim3(256), 0, nullptr, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(out, d, WREC * sizeof(uint4), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "self-test failed: %s", hipGetErrorString(e));
+  return SF_OK;
+}
 
 SF_API int sf_selftest_recip_one_step(int device, uint64_t* mismatches, uint32_t* patterns_out, uint32_t capacity, int* shipped) {
   if (!mismatches || (capacity > 0 && !patterns_out)) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");

@@ -27,7 +27,11 @@ namespace {
 //     metres).  (old*w + sdf*wn) / (w + wn): the divisor is a small integer, its
 //     correctly rounded reciprocal comes from an LDS table and ONE Markstein correction q1 = fma(fma(-m, q0, n), r, q0)
 //     yields the correctly rounded quotient (same tool: 1.4e9 cases incl. near-halfway); numerators below 2^-100
-//     take the plain division so that underflow cannot bite.
+//     take the plain division so that underflow cannot bite;
+//   * what depends on the voxel's 8-bit weight alone is not computed per voxel and frame: the multi-frame passes of the shipped parameters read
+//     (float)w, (float)(w + 1), 1/(w + 1) and T = {new weight byte, "first observation" mask} as ONE 16-byte LDS record per voxel
+//     (fill_weight_records, fuser_internal.h; fuse_update REC) -- no conversion, add, compare, select or saturating add per voxel;
+//     every other variant keeps the float table of 1/m (RTAB).
 // Every value stored is bit-identical to oracle/tsdf_oracle.c fuse_block.
 // (v2f, pk_fma, splat, recip_rn, quot_rn live in fuser_internal.h: the device self-test in calib.hip runs the same code)
 
@@ -177,9 +181,12 @@ __device__ inline void fuse_project_xr(const ParamsK& P, const FrameV& FV, const
 // with HBM at 8 % of its peak.
 // PRED: the shipped parameters write the new voxel under its update mask (below); false keeps the select tail for them too (k_reintegrate, whose two
 // bodies leave no registers for the regions).
-template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS = true, bool PRED = true>
+// REC: the constants of the update that depend on the voxel's weight alone come from `rec`, the LDS table of per-weight records (fill_weight_records,
+// fuser_internal.h), read behind the early-out; rcp_m is not used then.  Only with the predicated write-back of the shipped parameters.
+template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS = true, bool PRED = true, bool REC = false>
 __device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f (&rcp_m)[NJ], const float (&d)[2 * NJ], const uint32_t (&c)[2 * NJ], const v2f (&pz)[NJ],
-                                   const bool (&ok)[2 * NJ], uint4 (&v)[4], uint64_t (&dirty)[4]) {
+                                   const bool (&ok)[2 * NJ], uint4 (&v)[4], uint64_t (&dirty)[4], const uint4* rec = nullptr) {
+  static_assert(!REC || (PRED && SIGN > 0 && TAB && WM == 2), "the weight records serve the predicated write-back of the shipped parameters");
   constexpr bool WS1 = WM == 1 || WM == 2;
   // ---- phase B1: which voxels does this frame update?  Then a wave-uniform early-out: 10-25 % of the (block, frame) pairs the frustum
   // test lets through update nothing (blocks behind the surface, beyond the integration distance, over invalid depth, in the sliver
@@ -223,14 +230,29 @@ __device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f
   // keeps the select on the {rgb, weight} word, whose "weight already 255" carry has to be produced by an instruction either way.
   if constexpr (PRED && SIGN > 0 && TAB && WM == 2) {
     v2f q0[NJ], e[NJ];   // q = fma(e, r, q0) (quot_rn); its last fma is left to the write below
+    v2f r[NJ];           // RN(1 / m)
+    uint32_t T[2 * NJ];  // REC with colour: word .w of the voxel's record
     bool tiny = false;
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
-      const v2f wo = {(float)(v[J0 + j].y >> 24), (float)(v[J0 + j].w >> 24)};
+      v2f wo, m;
+      if constexpr (REC) {
+        // everything here that depends on the weight alone is one LDS read per voxel: no conversion, no add, and for colour no compare, select or
+        // saturating add below (geometry only reads 12 bytes: its weight word keeps the carry logic)
+        const uint4* ra = rec + (v[J0 + j].y >> 24);
+        const uint4* rb = rec + (v[J0 + j].w >> 24);
+        wo = (v2f){__uint_as_float(ra->x), __uint_as_float(rb->x)};
+        m = (v2f){__uint_as_float(ra->y), __uint_as_float(rb->y)};
+        r[j] = (v2f){__uint_as_float(ra->z), __uint_as_float(rb->z)};
+        if (COLOR) { T[2 * j] = ra->w; T[2 * j + 1] = rb->w; }
+      } else {
+        wo = (v2f){(float)(v[J0 + j].y >> 24), (float)(v[J0 + j].w >> 24)};
+        m = wo + splat(wn);             // wn == 1.0f, as a run-time value: one add, not a second conversion
+        r[j] = rcp_m[j];
+      }
       const v2f old = {__uint_as_float(v[J0 + j].x), __uint_as_float(v[J0 + j].z)};
       const v2f n = pk_fma(old, wo, sdfc[j]);   // weight_sample == 1: sdf * 1.0f == sdf bit for bit
-      const v2f m = wo + splat(wn);             // wn == 1.0f, as a run-time value: one add, not a second conversion
-      q0[j] = n * rcp_m[j];
+      q0[j] = n * r[j];
       e[j] = pk_fma(-m, q0[j], n);
       tiny = tiny || (fabsf(n.x) < 0x1p-100f) || (fabsf(n.y) < 0x1p-100f);
     }
@@ -262,14 +284,18 @@ __device__ inline void fuse_update(const ParamsK& P, const FrameV& FV, const v2f
           // the blend of the generic path below (v_lerp_u8; "first observation" by the weight byte or the colour_first mask)
           const uint32_t ck = c[k];
           const uint32_t avg = __builtin_amdgcn_lerp(cw, ck, round_mask);
-          const bool first = COLOR == 2 ? cw < 0x01000000u : (cw & first_mask) == 0u;
-          rgb = first ? ck : avg;
-          wsum = add_sat_u32(cw, 0x01000000u);   // 0xFFFFFFFF exactly when the weight was 255; only byte 3 is kept
+          if (REC && COLOR == 2) {
+            rgb = (ck & T[k]) | (avg & ~T[k]);   // one bit select: the low 24 bits of T are set exactly on a first observation
+          } else {
+            const bool first = COLOR == 2 ? cw < 0x01000000u : (cw & first_mask) == 0u;   // colour_first: by the colour bytes, not by the weight
+            rgb = first ? ck : avg;
+          }
+          wsum = REC ? T[k] : add_sat_u32(cw, 0x01000000u);   // 0xFFFFFFFF exactly when the weight was 255; only byte 3 is kept (of T: the new weight)
         } else {
           keep = __builtin_add_overflow(cw, 0x01000000u, &wsum);
         }
         if (upd[k]) {
-          write_fma(sdf_word, e[j][hx], rcp_m[j][hx], q0[j][hx]);
+          write_fma(sdf_word, e[j][hx], r[j][hx], q0[j][hx]);
           if (COLOR) write_bfi(cw_word, 0x00FFFFFFu, rgb, wsum);
         }
         if (!COLOR) cw_word = (upd[k] && !keep) ? wsum : cw_word;
@@ -374,7 +400,8 @@ __device__ inline __amdgpu_buffer_rsrc_t image_rsrc(const void* base, uint32_t b
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);   // raw buffer, dword data format (gfx9)
 }
 
-template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS, bool XR = false, bool PRED = true>
+// REC: rtab is the table of per-weight records (256 x uint4) instead of the float table, read by fuse_update
+template <int SIGN, int COLOR, bool TAB, int WM, int J0, int NJ, bool ROWS, bool XR = false, bool PRED = true, bool REC = false>
 __device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti, const float* __restrict__ depthf,
                                  const uint2* __restrict__ texel, const float* rtab, v2f wx, float wy, const float (&wz)[4], const v2f (&wxp)[4],
                                  uint4 (&v)[4], uint64_t (&dirty)[4]) {
@@ -384,7 +411,7 @@ __device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti,
   bool ok[2 * NJ];
   uint32_t pix[2 * NJ];
   // the weights are known before anything else: start the eight table reads now, they are consumed in phase B
-  if (TAB) {
+  if (TAB && !REC) {
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
       // weight_sample == 1 in the shipped parameters (WM >= 1): a constant index offset folds into the LDS instruction's immediate
@@ -413,7 +440,7 @@ __device__ inline void fuse_rows(const ParamsK& P, const float* __restrict__ Ti,
 #pragma unroll
     for (int k = 0; k < 2 * NJ; k++) d[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, pix[k] << 2, 0, 0));
   }
-  fuse_update<SIGN, COLOR, TAB, WM, J0, NJ, ROWS, PRED>(P, FV, rcp_m, d, c, pz, ok, v, dirty);
+  fuse_update<SIGN, COLOR, TAB, WM, J0, NJ, ROWS, PRED, REC>(P, FV, rcp_m, d, c, pz, ok, v, dirty, reinterpret_cast<const uint4*>(rtab));
 }
 
 }  // namespace

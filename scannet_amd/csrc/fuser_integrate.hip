@@ -35,8 +35,15 @@ __global__ __launch_bounds__(256, NJ == 2 ? (XR ? 7 : 8) : INT_WAVES) void k_int
                                                    const float* __restrict__ depthf_all, const uint2* __restrict__ texel_all,
                                                    int32_t* counters, int32_t* host_mirror, int compact_counter, int xcd_walk, ParamsK P,
                                                    BatchTi B) {
-  __shared__ float s_rtab[RTAB];  // correctly rounded 1/m for the weighted-mean division (fuse_tile)
-  if (TAB) {
+  // The passes of several frames with the shipped parameters (predicated write-back, x-row layout) keep one 16-byte record per weight in LDS: everything
+  // the update derives from the voxel's weight alone, 1/m among it (fill_weight_records).  Every other variant: the float table of 1/m.
+  constexpr bool REC = SIGN > 0 && TAB && WM == 2 && !ROWS && XR;
+  __shared__ uint4 s_tab[REC ? WREC : RTAB / 4];
+  float* const s_rtab = reinterpret_cast<float*>(s_tab);  // correctly rounded 1/m for the weighted-mean division (fuse_update)
+  if (REC) {
+    fill_weight_records(s_tab, (int)threadIdx.x, 256);
+    __syncthreads();
+  } else if (TAB) {
     for (int i = threadIdx.x; i < RTAB; i += 256) s_rtab[i] = 1.0f / (float)(i > 0 ? i : 1);
     __syncthreads();
   }
@@ -93,10 +100,10 @@ __global__ __launch_bounds__(256, NJ == 2 ? (XR ? 7 : 8) : INT_WAVES) void k_int
       const uint2* __restrict__ texel = texel_all + (size_t)q * npx;
 #pragma unroll
       for (int j0 = 0; j0 < 4; j0 += NJ) {
-        if (j0 == 0) fuse_rows<SIGN, COLOR, TAB, WM, 0, NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
-        if (j0 == 1) fuse_rows<SIGN, COLOR, TAB, WM, 1 % (5 - NJ), NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
-        if (j0 == 2) fuse_rows<SIGN, COLOR, TAB, WM, 2 % (5 - NJ), NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
-        if (j0 == 3) fuse_rows<SIGN, COLOR, TAB, WM, 3 % (5 - NJ), NJ, ROWS, XR>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+        if (j0 == 0) fuse_rows<SIGN, COLOR, TAB, WM, 0, NJ, ROWS, XR, true, REC>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+        if (j0 == 1) fuse_rows<SIGN, COLOR, TAB, WM, 1 % (5 - NJ), NJ, ROWS, XR, true, REC>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+        if (j0 == 2) fuse_rows<SIGN, COLOR, TAB, WM, 2 % (5 - NJ), NJ, ROWS, XR, true, REC>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
+        if (j0 == 3) fuse_rows<SIGN, COLOR, TAB, WM, 3 % (5 - NJ), NJ, ROWS, XR, true, REC>(P, Ti, depthf, texel, s_rtab, wx, wy, wz, wxp, v, dirty);
       }
     }
     if (ROWS) {

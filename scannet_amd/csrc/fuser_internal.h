@@ -275,6 +275,19 @@ __device__ inline v2f quot_rn(v2f n, v2f m, v2f r) {
   const v2f q0 = n * r;
   return pk_fma(pk_fma(-m, q0, n), r, q0);
 }
+// What the update of the shipped parameters (weight_sample 1, weight_max 255) needs of a voxel's 8-bit weight w, one 16-byte record per w: the passes
+// of several frames read it from LDS with one instruction instead of recomputing it per voxel and frame (fuse_update, fuser_fuse.h).
+//   .x = (float)w   .y = (float)(w + 1)   .z = 1.0f / (float)(w + 1), the IEEE division   .w = T: byte 3 = the new weight min(w + 1, 255); the
+//   low 24 bits all ones exactly when w == 0 -- "no observation yet: take the frame's colour", as a bit-select mask
+// k_integrate fills its LDS table with this function; sf_selftest_weight_records (calib.hip) copies one out.
+constexpr int WREC = 256;
+__device__ inline void fill_weight_records(uint4* tab, int tid, int nthreads) {
+  for (int w = tid; w < WREC; w += nthreads) {
+    const float m = (float)(w + 1);
+    tab[w] = make_uint4(__float_as_uint((float)w), __float_as_uint(m), __float_as_uint(1.0f / m),
+                        ((uint32_t)min(w + 1, 255) << 24) | (w == 0 ? 0x00FFFFFFu : 0u));
+  }
+}
 #endif
 
 struct sf_fuser {
