@@ -291,6 +291,35 @@ int sf_render_tune(const char* key, int value);
  * (width / 2) x (height / 2) x n_slices floats each, before the division; images / used (nullable) = how many were added / passed the angle filter. */
 int sf_lut_estimator_sums(sf_lut_estimator* e, float* acc, float* div, uint64_t* images, uint64_t* used);
 
+/* Stage hooks of the fusion front chain (tests/test_front_stages.py; scannet_amd/csrc/fuser_prepass.hip, fuser_alloc.hip, fuser_compact.hip, fuser_blocks.hip;
+ * DESIGN.md section 3): each call runs ONE stage of a pass on an existing fuser through the launcher run_batch itself uses for it (sf_launch_prepass,
+ * sf_launch_alloc, sf_launch_compact, sf_compact_live: the same choice of kernel, grid and workgroup, the buffers of batch slot 0), on the fuser's main
+ * stream, with both streams drained before and after.  n = 1..32 frames; depth = n host frames of the fuser's INPUT size, poses = n x 16 floats.  Every
+ * argument is checked before anything is launched: anything else is SF_ERR_INVALID_ARG and no launch.
+ *   prepass  k_prepass.  Colour is none, OR rgb (n tight RGB8 pictures at the colour size, or the integration size where the fuser has none; the device copy
+ *            is placed `misalign` = 0..7 bytes past an aligned address), OR jpeg (one baseline stream per frame, taken through the library's own
+ *            jpeg_decode_coef -> jpeg_gpu_planes, the planes and layout handed to the kernel as sf_fuse_run hands them; what that path leaves to the host
+ *            decoder is SF_ERR_UNSUPPORTED).  depthf_out: n x W*H floats; texel_out (with colour, else NULL): n x W*H texels {depth bits | rgb << 32}
+ *   alloc    the front chain up to and including the allocation as ONE pass: seq0 = the fuser's next sequence number, which advances by n.  head: the
+ *            pass is the first of a multi-pass call (groups of at most 4 frames).  fuse_pre 1: k_alloc_ray converts the depth itself -- an error unless
+ *            run_batch would pick that variant (one frame, ray-space window, no resampling).  depthf_out (nullable): the float depth the pass wrote.
+ *            deltas = what the pass added to {blocks taken to the table one by one, look-ups that went to the table, failures}
+ *   compact  sf_launch_compact alone on the present directory for n poses and an explicit seq0: the list (directory slots; order is scheduling, ascending
+ *            within a workgroup's stretch), the masks, the 64-bit counter word (list length | last frame's count << 32) and what the launch added to
+ *            {sum of the per-frame counts, sum of the list lengths}.  capacity (entries of list_out / mask_out) must hold the directory's used stretch.
+ *            n == 1 reads no birth stamp: a one-frame pass only meets blocks born by its own frame or earlier
+ *   live     sf_compact_live: every live block (include_ghosts 1) or every live block this fuser owns (0)
+ *   dump     host copies of the whole table (key, ptr, birth: total slots each), the heap, block_keys, block_entry, block_flags (num_sdf_blocks each) and the
+ *            48 counter words */
+int sf_fuser_stage_prepass(sf_fuser* f, int n, const uint16_t* depth, const uint8_t* rgb /*nullable*/, int misalign, const uint8_t* const* jpeg /*nullable*/,
+                           const uint64_t* jpeg_bytes, float* depthf_out, uint64_t* texel_out /*nullable*/);
+int sf_fuser_stage_alloc(sf_fuser* f, int n, const uint16_t* depth, const float* poses, int head, int fuse_pre, float* depthf_out /*nullable*/, uint64_t deltas[3]);
+int sf_fuser_stage_compact(sf_fuser* f, int n, const float* poses, uint32_t seq0, int32_t* list_out, uint32_t* mask_out, uint64_t capacity, uint64_t* counter_word,
+                           uint64_t deltas[2]);
+int sf_fuser_stage_live(sf_fuser* f, int include_ghosts, int32_t* list_out, uint64_t capacity, uint64_t* n_out);
+int sf_fuser_stage_dump(sf_fuser* f, uint64_t* key_out, int32_t* ptr_out, uint32_t* birth_out, int32_t* heap_out, uint64_t* block_keys_out, int32_t* block_entry_out,
+                        uint8_t* block_flags_out, int32_t* counters_out);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

@@ -65,6 +65,10 @@ def lib():
         L.or_export.restype = C.c_int64
         L.or_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.or_depth_to_float.argtypes = [C.POINTER(OrParams), C.c_void_p, C.c_void_p]
+        L.or_stage_alloc.restype = C.c_int64
+        L.or_stage_alloc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        L.or_stage_frustum.restype = C.c_int64
+        L.or_stage_frustum.argtypes = [C.POINTER(OrParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.or_mc_extract.restype = C.c_void_p
         L.or_mc_extract.argtypes = [C.c_void_p]
         L.or_mc_num_verts.restype = C.c_int64
@@ -116,6 +120,16 @@ class Volume:
     def garbage_collect(self):
         return int(lib().or_garbage_collect(self._h))
 
+    def stage_alloc(self, depth, pose):
+        """One frame's NEW blocks against the present set (or_stage_alloc): they are inserted, nothing is fused -> coords int32 [m, 3] in insertion order."""
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(16)
+        assert depth.size == self.params.width * self.params.height
+        out = np.empty((1 << 18, 3), np.int32)
+        m = int(lib().or_stage_alloc(self._h, _ptr(depth), _ptr(pose), _ptr(out), len(out)))
+        assert 0 <= m <= len(out), m
+        return out[:m].copy()
+
     @property
     def num_blocks(self):
         return int(lib().or_num_blocks(self._h))
@@ -152,6 +166,15 @@ def depth_to_float(params, depth):
     out = np.zeros(depth.shape, np.float32)
     lib().or_depth_to_float(C.byref(params), _ptr(depth), _ptr(out))
     return out
+
+
+def stage_frustum(params, pose, coords):
+    """block_in_frustum of coords [n, 3] for one pose under params.frustum_mode (or_stage_frustum) -> bool [n]."""
+    coords = np.ascontiguousarray(coords, np.int32).reshape(-1, 3)
+    pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(16)
+    out = np.zeros(len(coords), np.uint8)
+    assert lib().or_stage_frustum(C.byref(params), _ptr(pose), _ptr(coords), len(coords), _ptr(out)) == len(coords)
+    return out.astype(bool)
 
 
 # ---------------------------------------------------------------- compiled REFERENCE (oracle/_ref)

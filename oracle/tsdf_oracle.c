@@ -334,6 +334,27 @@ static void alloc_frame(or_volume* v, const or_frame* f) {
   free(cand);
 }
 
+/* ---- stage entries of the front chain (tests/test_front_stages_cpu.py, tests/test_front_stages.py) ----
+ * or_stage_alloc: spec 3.1 + 3.4 of ONE frame against the volume's present block set: the new blocks are inserted (nothing is fused) and their coordinates
+ * returned, up to `capacity` triples; the return value is how many there were, -1 for an invalid pose.
+ * or_stage_frustum: spec 3.3 of n blocks for one pose under p->frustum_mode, one byte per block; -1 for an invalid pose. */
+int64_t or_stage_alloc(or_volume* v, const uint16_t* depth, const float* pose, int32_t* coords_out, int64_t capacity) {
+  or_frame f;
+  if (!frame_setup(&v->p, pose, &f)) return -1;
+  or_depth_to_float(&v->p, depth, v->depthf);
+  const int64_t before = v->n_slots;
+  alloc_frame(v, &f);
+  const int64_t n = v->n_slots - before;
+  for (int64_t i = 0; i < n && i < capacity; i++) memcpy(coords_out + 3 * i, v->coords + 3 * (before + i), 3 * sizeof(int32_t));
+  return n;
+}
+int64_t or_stage_frustum(const or_params* p, const float* pose, const int32_t* coords, int64_t n, uint8_t* out) {
+  or_frame f;
+  if (!frame_setup(p, pose, &f)) return -1;
+  for (int64_t i = 0; i < n; i++) out[i] = (uint8_t)block_in_frustum(p, &f, coords[3 * i], coords[3 * i + 1], coords[3 * i + 2]);
+  return n;
+}
+
 /* weight_mode 1: (uchar)max(weightSample * 1.5f * (1 - depthZeroOne), 1.0f), depthZeroOne over the sensor depth range; at most 255 */
 static int depth_weight(const or_params* p, float d) {
   const float z01 = (d - p->depth_min) / (p->depth_max - p->depth_min);

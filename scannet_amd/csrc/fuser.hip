@@ -2,6 +2,7 @@
 // events), the integrate entry points, tuning, statistics and profiling.  The kernels live with their launchers, one stage per file:
 // fuser_prepass.hip (depth pre-pass), fuser_alloc.hip (sparse block allocation), fuser_compact.hip (frustum compaction), fuser_integrate.hip
 // (integrate / deintegrate), fuser_blocks.hip (garbage collection, block export / import); fuser_device.h holds what several of them share.
+// At the end of this file: the stage hooks of the front chain (sf_fuser_stage_*, scanfuse_internal.h), which run one stage of a pass for the tests.
 //
 // Replaces the scene-representation part of the external DepthSensing.exe / FriedLiver.exe that the
 // reference pipeline shells out to (Server/scan_processor.py:126,138); the arithmetic is the specification
@@ -27,7 +28,10 @@
 #include <string>
 #include <vector>
 
+#include "codecs_internal.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
+#include "jpeg_idct.h"
 
 // ======================================================================================================
 // host side
@@ -810,3 +814,205 @@ SF_API int sf_device_malloc(int device, uint64_t bytes, void** out) {
 SF_API int sf_device_free(void* p) { SF_HIP_CHECK(hipFree(p)); return SF_OK; }
 SF_API int sf_device_upload(void* dst, const void* src, uint64_t bytes) { SF_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return SF_OK; }
 SF_API int sf_device_download(void* dst, const void* src, uint64_t bytes) { SF_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return SF_OK; }
+
+// ======================================================================================================
+// Stage hooks of the front chain (scanfuse_internal.h; tests/test_front_stages.py): ONE stage of a pass on an existing fuser, through the launcher run_batch
+// uses for it, on the main stream and the buffers of batch slot 0, between two sf_quiesce.  Every argument is checked before the first launch.
+// ======================================================================================================
+namespace {
+
+int stage_enter(sf_fuser* f, int n, const char* who) {
+  if (!f) return sf::fail(SF_ERR_INVALID_ARG, "%s: NULL fuser", who);
+  if (n < 1 || n > MAX_BATCH) return sf::fail(SF_ERR_INVALID_ARG, "%s: %d frames (1..%d)", who, n, MAX_BATCH);
+  SF_HIP_CHECK(hipSetDevice(f->device));
+  SF_HIP_CHECK(sf_quiesce(f));
+  return SF_OK;
+}
+
+int stage_counters(sf_fuser* f, int32_t* c) {
+  SF_HIP_CHECK(hipMemcpyAsync(c, f->counters, C_COUNT * 4, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(sf_quiesce(f));
+  return SF_OK;
+}
+
+uint64_t counter64(const int32_t* c, int at) {
+  uint64_t v;
+  std::memcpy(&v, c + at, 8);
+  return v;
+}
+
+bool stage_frames(const sf_fuser* f, int n, const float* poses, uint32_t seq0, BatchFrames& bf) {
+  std::memset(&bf, 0, sizeof(bf));
+  bf.n = n;
+  bf.seq0 = seq0;
+  for (int j = 0; j < n; j++)
+    if (!frame_setup(f->p, poses + 16 * j, bf.f[j])) return false;
+  return true;
+}
+
+}  // namespace
+
+SF_API int sf_fuser_stage_prepass(sf_fuser* f, int n, const uint16_t* depth, const uint8_t* rgb, int misalign, const uint8_t* const* jpeg, const uint64_t* jpeg_bytes,
+                                  float* depthf_out, uint64_t* texel_out) {
+  const int rc0 = stage_enter(f, n, "sf_fuser_stage_prepass");
+  if (rc0 != SF_OK) return rc0;
+  const bool col = rgb != nullptr || jpeg != nullptr;
+  if (!depth || !depthf_out || (rgb && jpeg) || (col && !texel_out) || (!col && texel_out) || (jpeg && !jpeg_bytes) || misalign < 0 || misalign > 7 || (!rgb && misalign != 0))
+    return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_prepass: depth and depthf_out; colour as ONE of rgb (misalign 0..7) or jpeg + jpeg_bytes, with texel_out");
+  const size_t npx = (size_t)f->pk.W * f->pk.H;
+  const uint32_t cw = (uint32_t)(f->pk.cW ? f->pk.cW : f->pk.W), ch = (uint32_t)(f->pk.cW ? f->pk.cH : f->pk.H);
+  const size_t rgb_bytes = (size_t)cw * ch * 3;
+  // the entropy decoding of every picture comes first: a stream the device path does not take is an error before any launch
+  std::vector<std::vector<uint32_t>> pay((size_t)(jpeg ? n : 0));
+  uint32_t max_blocks = 0;
+  for (int j = 0; jpeg && j < n; j++) {
+    if (!jpeg[j] || jpeg_bytes[j] == 0) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_prepass: picture %d is empty", j);
+    const uint64_t padded = (uint64_t)((cw + 15) & ~15u) * ((ch + 15) & ~15u);
+    pay[j].resize((sizeof(SfJpegLayout) + padded * 3 / 64 * 4 + padded * 3 * 4) / 4 + 64);
+    const int rc = jpeg_decode_coef(jpeg[j], jpeg_bytes[j], cw, ch, reinterpret_cast<uint8_t*>(pay[j].data()), pay[j].size() * 4);
+    if (rc != SF_OK) return rc;
+    max_blocks = std::max(max_blocks, reinterpret_cast<const SfJpegLayout*>(pay[j].data())->nblocks);
+  }
+  sf::DevBuf d_depth, d_rgb, d_pay[MAX_BATCH], d_planes[MAX_BATCH];
+  SF_HIP_CHECK(d_depth.alloc((size_t)n * f->in_px * 2));
+  SF_HIP_CHECK(hipMemcpyAsync(d_depth.p, depth, (size_t)n * f->in_px * 2, hipMemcpyHostToDevice, f->stream));
+  BatchIn in;
+  std::memset(&in, 0, sizeof(in));
+  for (int j = 0; j < n; j++) in.depth[j] = d_depth.as<uint16_t>() + (size_t)j * f->in_px;
+  if (rgb) {
+    SF_HIP_CHECK(d_rgb.alloc((size_t)n * rgb_bytes + 8));
+    SF_HIP_CHECK(hipMemcpyAsync(d_rgb.as<uint8_t>() + misalign, rgb, (size_t)n * rgb_bytes, hipMemcpyHostToDevice, f->stream));
+    for (int j = 0; j < n; j++) in.rgb[j] = d_rgb.as<uint8_t>() + misalign + (size_t)j * rgb_bytes;
+  }
+  if (jpeg) {
+    const uint8_t* pp[MAX_BATCH];
+    uint8_t* pl[MAX_BATCH];
+    for (int j = 0; j < n; j++) {
+      const SfJpegLayout& L = *reinterpret_cast<const SfJpegLayout*>(pay[j].data());
+      SF_HIP_CHECK(d_pay[j].alloc(sf_jpeg_payload_bytes(L)));
+      SF_HIP_CHECK(d_planes[j].alloc(sf_jpeg_plane_bytes(L)));
+      SF_HIP_CHECK(hipMemcpyAsync(d_pay[j].p, pay[j].data(), sf_jpeg_payload_bytes(L), hipMemcpyHostToDevice, f->stream));
+      pp[j] = d_pay[j].as<uint8_t>();
+      pl[j] = d_planes[j].as<uint8_t>();
+      in.rgb[j] = pl[j];
+      in.lay[j] = pp[j];   // the payload begins with the picture's SfJpegLayout
+    }
+    for (int q0 = 0; q0 < n; q0 += 16) {   // (a launch of jpeg_gpu_planes takes up to 16 pictures)
+      const int rc = jpeg_gpu_planes(f->stream, std::min(16, n - q0), pp + q0, pl + q0, max_blocks);
+      if (rc != SF_OK) { (void)sf_quiesce(f); return rc; }
+    }
+  }
+  sf_launch_prepass(f, 0, n, in, f->stream);
+  const hipError_t le = hipGetLastError();
+  SF_HIP_CHECK(hipMemcpyAsync(depthf_out, f->depthf2[0], (size_t)n * npx * 4, hipMemcpyDeviceToHost, f->stream));
+  if (col) SF_HIP_CHECK(hipMemcpyAsync(texel_out, f->color2[0], (size_t)n * npx * 8, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(sf_quiesce(f));
+  if (le != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_fuser_stage_prepass: launch failed: %s", hipGetErrorString(le));
+  return SF_OK;
+}
+
+SF_API int sf_fuser_stage_alloc(sf_fuser* f, int n, const uint16_t* depth, const float* poses, int head, int fuse_pre, float* depthf_out, uint64_t deltas[3]) {
+  const int rc0 = stage_enter(f, n, "sf_fuser_stage_alloc");
+  if (rc0 != SF_OK) return rc0;
+  if (!depth || !poses || !deltas || (head & ~1) || (fuse_pre & ~1)) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_alloc: NULL argument, or head / fuse_pre not 0 or 1");
+  // the fused variant exactly where run_batch picks it: one colourless frame at the integration size through the ray-space kernel
+  if (fuse_pre && !(f->alloc_ray && n == 1 && f->pk.inW == 0)) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_alloc: a pass of this shape does not fuse the pre-pass");
+  BatchFrames bf;
+  if (!stage_frames(f, n, poses, f->frame_seq, bf)) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_alloc: invalid pose in batch");
+  int32_t c0[C_COUNT], c1[C_COUNT];
+  int rc = stage_counters(f, c0);
+  if (rc != SF_OK) return rc;
+  sf::DevBuf d_depth;
+  SF_HIP_CHECK(d_depth.alloc((size_t)n * f->in_px * 2));
+  SF_HIP_CHECK(hipMemcpyAsync(d_depth.p, depth, (size_t)n * f->in_px * 2, hipMemcpyHostToDevice, f->stream));
+  BatchIn in;
+  std::memset(&in, 0, sizeof(in));
+  for (int j = 0; j < n; j++) in.depth[j] = d_depth.as<uint16_t>() + (size_t)j * f->in_px;
+  f->frame_seq += (uint32_t)n;
+  if (!fuse_pre) sf_launch_prepass(f, 0, n, in, f->stream);
+  f->head_pass = head != 0;
+  sf_launch_alloc(f, 0, n, bf, in, f->stream, fuse_pre != 0);
+  f->head_pass = false;
+  const hipError_t le = hipGetLastError();
+  if (depthf_out) SF_HIP_CHECK(hipMemcpyAsync(depthf_out, f->depthf2[0], (size_t)n * f->pk.W * f->pk.H * 4, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(sf_quiesce(f));
+  if (le != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_fuser_stage_alloc: launch failed: %s", hipGetErrorString(le));
+  rc = stage_counters(f, c1);
+  if (rc != SF_OK) return rc;
+  deltas[0] = (uint32_t)(c1[C_ALLOC_DIRECT] - c0[C_ALLOC_DIRECT]);
+  deltas[1] = (uint32_t)(c1[C_ALLOC_PROBED] - c0[C_ALLOC_PROBED]);
+  deltas[2] = (uint32_t)(c1[C_ALLOC_FAIL] - c0[C_ALLOC_FAIL]);
+  return SF_OK;
+}
+
+SF_API int sf_fuser_stage_compact(sf_fuser* f, int n, const float* poses, uint32_t seq0, int32_t* list_out, uint32_t* mask_out, uint64_t capacity, uint64_t* counter_word,
+                                  uint64_t deltas[2]) {
+  const int rc0 = stage_enter(f, n, "sf_fuser_stage_compact");
+  if (rc0 != SF_OK) return rc0;
+  if (!poses || !list_out || !mask_out || !counter_word || !deltas) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_compact: NULL argument");
+  BatchFrames bf;
+  if (!stage_frames(f, n, poses, seq0, bf)) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_compact: invalid pose in batch");
+  int32_t c0[C_COUNT], c1[C_COUNT];
+  int rc = stage_counters(f, c0);
+  if (rc != SF_OK) return rc;
+  if (c0[C_HIGH_WATER] < 0 || (uint64_t)c0[C_HIGH_WATER] > capacity)   // the list never holds more than the directory's used stretch
+    return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_compact: capacity %llu below the directory's %d entries", (unsigned long long)capacity, c0[C_HIGH_WATER]);
+  SF_HIP_CHECK(hipMemsetAsync(&f->counters[sf_compact_counter(0)], 0, 8, f->stream));   // what the pass's pre-pass does
+  sf_launch_compact(f, 0, bf, f->stream);
+  const hipError_t le = hipGetLastError();
+  SF_HIP_CHECK(sf_quiesce(f));
+  if (le != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_fuser_stage_compact: launch failed: %s", hipGetErrorString(le));
+  rc = stage_counters(f, c1);
+  if (rc != SF_OK) return rc;
+  const uint64_t word = counter64(c1, sf_compact_counter(0));
+  const uint64_t len = word & 0xFFFFFFFFull;
+  if (len > capacity) return sf::fail(SF_ERR_BOUNDS, "sf_fuser_stage_compact: the list holds %llu entries, capacity %llu", (unsigned long long)len, (unsigned long long)capacity);
+  if (len) {
+    SF_HIP_CHECK(hipMemcpyAsync(list_out, f->compact2[0], len * 4, hipMemcpyDeviceToHost, f->stream));
+    SF_HIP_CHECK(hipMemcpyAsync(mask_out, f->cmask2[0], len * 4, hipMemcpyDeviceToHost, f->stream));
+    SF_HIP_CHECK(sf_quiesce(f));
+  }
+  *counter_word = word;
+  deltas[0] = counter64(c1, C_TOTAL_LO) - counter64(c0, C_TOTAL_LO);
+  deltas[1] = counter64(c1, C_TILES_LO) - counter64(c0, C_TILES_LO);
+  return SF_OK;
+}
+
+SF_API int sf_fuser_stage_live(sf_fuser* f, int include_ghosts, int32_t* list_out, uint64_t capacity, uint64_t* n_out) {
+  const int rc0 = stage_enter(f, 1, "sf_fuser_stage_live");
+  if (rc0 != SF_OK) return rc0;
+  if (!list_out || !n_out || (include_ghosts & ~1)) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_live: NULL argument, or include_ghosts not 0 or 1");
+  int32_t c0[C_COUNT];
+  int rc = stage_counters(f, c0);
+  if (rc != SF_OK) return rc;
+  if (c0[C_HIGH_WATER] < 0 || (uint64_t)c0[C_HIGH_WATER] > capacity)
+    return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_live: capacity %llu below the directory's %d entries", (unsigned long long)capacity, c0[C_HIGH_WATER]);
+  int32_t n = 0;
+  rc = sf_compact_live(f, &n, include_ghosts);
+  if (rc != SF_OK) return rc;
+  if (n > 0) {
+    SF_HIP_CHECK(hipMemcpyAsync(list_out, f->compact, (size_t)n * 4, hipMemcpyDeviceToHost, f->stream));
+    SF_HIP_CHECK(sf_quiesce(f));
+  }
+  *n_out = (uint64_t)n;
+  return SF_OK;
+}
+
+SF_API int sf_fuser_stage_dump(sf_fuser* f, uint64_t* key_out, int32_t* ptr_out, uint32_t* birth_out, int32_t* heap_out, uint64_t* block_keys_out, int32_t* block_entry_out,
+                               uint8_t* block_flags_out, int32_t* counters_out) {
+  const int rc0 = stage_enter(f, 1, "sf_fuser_stage_dump");
+  if (rc0 != SF_OK) return rc0;
+  if (!key_out || !ptr_out || !birth_out || !heap_out || !block_keys_out || !block_entry_out || !block_flags_out || !counters_out)
+    return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_stage_dump: NULL argument");
+  const size_t slots = f->pk.total_slots, nb = f->pk.num_blocks;
+  std::vector<HashEntry> t(slots);
+  SF_HIP_CHECK(hipMemcpyAsync(t.data(), f->table, slots * sizeof(HashEntry), hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(heap_out, f->heap, nb * 4, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(block_keys_out, f->block_keys, nb * 8, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(block_entry_out, f->block_entry, nb * 4, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(block_flags_out, f->block_flags, nb, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(hipMemcpyAsync(counters_out, f->counters, C_COUNT * 4, hipMemcpyDeviceToHost, f->stream));
+  SF_HIP_CHECK(sf_quiesce(f));
+  for (size_t i = 0; i < slots; i++) { key_out[i] = t[i].key; ptr_out[i] = t[i].ptr; birth_out[i] = t[i].birth; }
+  return SF_OK;
+}

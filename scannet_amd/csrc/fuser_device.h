@@ -98,8 +98,10 @@ __device__ inline int give_block_quiet(const HashRefs& h, HashEntry* e, uint64_t
     h.block_flags[idx] = 0;
     return idx + 1;
   }
-  // heap exhausted: the entry stays claimed without a block; undo the pop
+  // heap exhausted: the entry stays claimed without a block; undo the pop and the caller's count of it as a used slot (a block that does not exist is counted
+  // as a failure and nowhere else: hash_slots_used stays blocks_allocated, tests/front_exact.py check_directory)
   atomicAdd(&h.counters[C_HEAP_FREE], 1);
+  atomicSub(&h.counters[C_SLOTS_USED], 1);
   atomicAdd(&h.counters[C_ALLOC_FAIL], 1);
   return 0;
 }

@@ -942,3 +942,93 @@ class Fuser:
             check(_abi.lib().sf_fuser_export_blocks(self._h, _ptr(coords), _ptr(vox), n.value, C.byref(n)))
         order = np.lexsort((coords[:, 2], coords[:, 1], coords[:, 0]))
         return coords[order], vox[order]
+
+    # -- stage hooks of the front chain (scanfuse_internal.h sf_fuser_stage_*; tests/test_front_stages.py) ----------------------------------
+    def _stage_sizes(self):
+        p = self.params
+        resampled = p.integration_width > 0 and p.integration_height > 0
+        W, H = (p.integration_width, p.integration_height) if resampled else (p.depth_width, p.depth_height)
+        return p.depth_width * p.depth_height, W * H
+
+    def _stage_frames(self, depth, poses=None):
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        in_px, _ = self._stage_sizes()
+        if depth.size == 0 or depth.size % in_px:
+            raise ValueError("depth must hold whole frames of %d pixels" % in_px)
+        n = depth.size // in_px
+        if poses is not None:
+            poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+            if len(poses) != n:
+                raise ValueError("%d frames, %d poses" % (n, len(poses)))
+        return depth, poses, n
+
+    def stage_prepass(self, depth, rgb=None, misalign=0, jpeg=None):
+        """k_prepass alone on n host frames: depthf float32 [n, W*H] and, with colour (rgb: n tight RGB8 pictures, the device copy `misalign` bytes past an
+        aligned address; or jpeg: a list of n baseline streams), the texels uint64 [n, W*H] = depth bits | rgb << 32."""
+        depth, _, n = self._stage_frames(depth)
+        _, npx = self._stage_sizes()
+        depthf = np.zeros((n, npx), np.float32)
+        texel = np.zeros((n, npx), np.uint64) if (rgb is not None or jpeg is not None) else None
+        streams = sizes = None
+        if rgb is not None:
+            rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+            p = self.params
+            cw, ch = (p.color_width, p.color_height) if p.color_width > 0 and p.color_height > 0 else (p.depth_width, p.depth_height)
+            if rgb.size != n * cw * ch * 3:
+                raise ValueError("rgb must hold %d pictures of %dx%dx3" % (n, cw, ch))
+        if jpeg is not None:
+            keep = [np.frombuffer(bytes(b), np.uint8) for b in jpeg]
+            streams = (C.c_void_p * len(keep))(*[b.ctypes.data for b in keep])
+            sizes = (C.c_uint64 * len(keep))(*[b.size for b in keep])
+            if len(keep) != n:
+                raise ValueError("%d frames, %d pictures" % (n, len(keep)))
+        L = _abi.lib()
+        L.sf_fuser_stage_prepass.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(L.sf_fuser_stage_prepass(self._h, n, _ptr(depth), _ptr(rgb), int(misalign), streams, sizes, _ptr(depthf), _ptr(texel)))
+        return depthf, texel
+
+    def stage_alloc(self, depth, poses, head=False, fuse_pre=False, want_depth=False):
+        """The front chain up to and including the allocation as one pass (seq0 = the fuser's next sequence number) -> dict(direct, probed, failed[, depthf])."""
+        depth, poses, n = self._stage_frames(depth, poses)
+        _, npx = self._stage_sizes()
+        depthf = np.zeros((n, npx), np.float32) if want_depth else None
+        d = (C.c_uint64 * 3)()
+        L = _abi.lib()
+        L.sf_fuser_stage_alloc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        check(L.sf_fuser_stage_alloc(self._h, n, _ptr(depth), _ptr(poses), int(bool(head)), int(bool(fuse_pre)), _ptr(depthf), d))
+        out = {"direct": int(d[0]), "probed": int(d[1]), "failed": int(d[2])}
+        if want_depth:
+            out["depthf"] = depthf
+        return out
+
+    def stage_compact(self, poses, seq0):
+        """sf_launch_compact alone on the present directory -> dict(slots int32 [len], masks uint32 [len], length, last, total, tiles)."""
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 16)
+        cap = int(self.params.num_sdf_blocks)
+        slots, masks = np.zeros(cap, np.int32), np.zeros(cap, np.uint32)
+        word, d = C.c_uint64(0), (C.c_uint64 * 2)()
+        L = _abi.lib()
+        L.sf_fuser_stage_compact.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        check(L.sf_fuser_stage_compact(self._h, len(poses), _ptr(poses), int(seq0), _ptr(slots), _ptr(masks), cap, C.byref(word), d))
+        n = word.value & 0xFFFFFFFF
+        return {"slots": slots[:n].copy(), "masks": masks[:n].copy(), "length": int(n), "last": int(word.value >> 32), "total": int(d[0]), "tiles": int(d[1])}
+
+    def stage_live(self, include_ghosts=True):
+        """sf_compact_live: the directory slots of every live block (or of those this fuser owns: include_ghosts False), int32."""
+        cap = int(self.params.num_sdf_blocks)
+        slots, n = np.zeros(cap, np.int32), C.c_uint64(0)
+        L = _abi.lib()
+        L.sf_fuser_stage_live.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        check(L.sf_fuser_stage_live(self._h, int(bool(include_ghosts)), _ptr(slots), cap, C.byref(n)))
+        return slots[:n.value].copy()
+
+    def stage_dump(self):
+        """Host copies of the table (key, ptr, birth), heap, block_keys, block_entry, block_flags and the counter words."""
+        p = self.params
+        slots, nb = int(p.hash_num_buckets) * int(p.hash_bucket_size), int(p.num_sdf_blocks)
+        out = {"key": np.zeros(slots, np.uint64), "ptr": np.zeros(slots, np.int32), "birth": np.zeros(slots, np.uint32), "heap": np.zeros(nb, np.int32),
+               "block_keys": np.zeros(nb, np.uint64), "block_entry": np.zeros(nb, np.int32), "block_flags": np.zeros(nb, np.uint8), "counters": np.zeros(48, np.int32)}
+        L = _abi.lib()
+        L.sf_fuser_stage_dump.argtypes = [C.c_void_p] * 9
+        check(L.sf_fuser_stage_dump(self._h, *[_ptr(out[k]) for k in ("key", "ptr", "birth", "heap", "block_keys", "block_entry", "block_flags", "counters")]))
+        return out
