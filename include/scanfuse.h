@@ -162,6 +162,21 @@ void* sf_fuser_stream(sf_fuser* f);            /* the hipStream_t all work of th
  * bytes ({float sdf; uchar r,g,b,weight} x 512, index z*64+y*8+x).  Pass NULLs to query n only. */
 int sf_fuser_export_blocks(sf_fuser* f, int32_t* coords, void* voxels, uint64_t capacity, uint64_t* n);
 
+/* The sparse volume as a dense one (scannet_amd/csrc/fuser_dense.hip; what the `freespace` stage below is made of).
+ *   sf_fuser_allocate_box   every block of [lo_block, hi_block] (inclusive) that is not in the table is inserted with zeroed voxels, on the device; blocks
+ *                           that exist, ghosts among them, keep their bytes and their state; *allocated = how many were new (a second call on the same box: 0).
+ *                           SF_ERR_CAPACITY, with nothing changed, when the free heap cannot hold the box's missing blocks; SF_ERR_CAPACITY when an insertion
+ *                           found no hash slot (the caller may sf_fuser_reset); SF_ERR_INVALID_ARG for lo > hi, 2^31 or more blocks or a coordinate outside the
+ *                           table's 21 bits; SF_ERR_UNSUPPORTED while a slab or stripe partition is set.
+ *   sf_fuser_known_bounds   the inclusive box, in global voxel indices, of the owned voxels with weight > 0, and their count; known == 0 leaves the boxes as they are.
+ *   sf_fuser_export_dense   region [lo_voxel, lo_voxel + dims) as [z][y][x] arrays, x fastest (rgb: 3 bytes per voxel); any output may be NULL.  A voxel of a
+ *                           block that is not allocated reads as {0, 0, 0}.  mode 0: sdf as stored; mode 1: the task volume, -INFINITY where weight == 0, else
+ *                           sdf / voxel_size.  The region may be unaligned, negative, partly or wholly outside the allocated space.  Ordered behind everything
+ *                           queued on the handle; changes nothing in the volume.  SF_ERR_INVALID_ARG for a dimension <= 0 or 2^40 or more voxels. */
+int sf_fuser_allocate_box(sf_fuser* f, const int32_t lo_block[3], const int32_t hi_block[3], uint64_t* allocated);
+int sf_fuser_known_bounds(sf_fuser* f, int32_t lo_voxel[3], int32_t hi_voxel[3], uint64_t* known);
+int sf_fuser_export_dense(sf_fuser* f, const int32_t lo_voxel[3], const int32_t dims[3], int mode, float* sdf, uint8_t* weight, uint8_t* rgb, int dst_on_device);
+
 /* One large scan over several GPUs (BASELINE configs[4]): the block space is cut into slabs along `axis`; a fuser with a
  * slab set still sees every frame but only allocates (hence fuses) the blocks whose coordinate on `axis` lies in
  * [lo_block, hi_block).  axis < 0 removes the partition.  Before meshing, each fuser imports -- as GHOST blocks, which are
@@ -1078,6 +1093,59 @@ typedef struct sf_calibrate_depth_stats {
  * PNG decode and encode run on `threads` host threads (<= 0: the CPUs this process may use). */
 int sf_calibrate_depth(const char* config, const char* estimate_path /*nullable*/, const char* apply_path /*nullable*/,
                        const sf_calibrate_depth_options* options /*nullable*/, int device, int threads, sf_calibrate_depth_stats* stats /*nullable*/);
+
+/* ------------------------------------------------------------------------------------------------
+ * Free-space grids: the `freespace` stage (Server/scan_processor.py:15; FreeSpace.exe, "exe to call for computing occupancy grids",
+ * Server/config.py:20; product ${id}.grid, Server/config/scan_stages.json:43-47).  Neither the binary nor its file format is in the reference
+ * tree: the rule and the format are this library's statement, unpinned.  What the tree says is what a consumer reads: a
+ * float volume in voxel units whose "known/unknown" channel is value >= -1 (Tasks/SemanticVoxelLabeling/torch/provider.lua:80-97,
+ * Tasks/README.md:20), laid out [z][y][x] beside a world2grid matrix (BenchmarkScripts/3d_helpers/export_semantic_label_grid_for_evaluation.py:35-47).
+ * The rule is the fuser's own: a voxel a frame sees in front of the surface by more than the truncation is integrated as sdf = +trunc with a
+ * weight, so known = weight > 0.  The stage allocates every block a frame can reach (sf_fuser_allocate_box), fuses the scan through sf_fuse_run and
+ * reads the box of the known voxels back (sf_fuser_known_bounds, sf_fuser_export_dense mode 1).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sf_freespace_params {
+  float voxel_size;                 /* metres: 0.05 (this library's choice)                                                          */
+  uint32_t max_blocks;              /* the largest box of 8^3-voxel blocks (4 KiB each) the stage will allocate: 1 << 21             */
+  int32_t every;                    /* every N-th frame of the scan, >= 1: 1                                                        */
+  int32_t reserved[5];
+  char params_file[1024];           /* an mLib ParameterFile for the other TSDF constants; "": sf_params_default                     */
+} sf_freespace_params;
+void sf_freespace_params_default(sf_freespace_params* p);
+/* Host only, double: the box of blocks (inclusive) that holds every voxel the frames used can update -- the box of the camera centres of the
+ * frames with a valid pose, widened by R + one voxel, R = zfar sqrt(1 + ax^2 + ay^2), zfar = max_dist + trunc_base + trunc_scale max_dist,
+ * ax = max(mx + 1.5, W - 0.5 - mx) / fx (ay likewise; the effective integration camera) -- and the fuser parameters for it (the file's camera,
+ * the heap and the table sized from the box, colour and garbage collection off).  SF_ERR_CAPACITY: more than max_blocks blocks (the count is in
+ * sf_last_error()); SF_ERR_INVALID_ARG: no frame with a valid pose. */
+int sf_freespace_plan(const struct sf_sens* s, const sf_freespace_params* p, sf_params* fuser_params, int32_t lo_block[3], int32_t hi_block[3]);
+typedef struct sf_freespace_stats {
+  uint64_t box_blocks, frames_used;
+  uint64_t known, free_voxels, near_voxels;   /* weight > 0; of those, sdf >= trunc_base; the others                                */
+  int32_t lo_block[3], hi_block[3];
+  double seconds_plan, seconds_create, seconds_allocate, seconds_fuse, seconds_bounds, seconds_export, seconds_total;
+} sf_freespace_stats;
+/* The grid: value[nz][ny][nx] (x fastest) = sdf / voxel_size, -inf where weight == 0; weight[nz][ny][nx]; lattice node (x, y, z) of the grid lies at
+ * (lo_voxel + (x, y, z)) * voxel_size metres; world2grid (row-major) maps metres to g = w / voxel_size - lo_voxel + 0.5, so floor(g) is the nearest node. */
+typedef struct sf_grid sf_grid;
+typedef struct sf_grid_header {
+  int32_t nx, ny, nz;
+  float voxel_size;
+  int32_t lo_voxel[3];
+  float world2grid[16];
+  uint64_t frames_used;
+} sf_grid_header;
+/* plan, fuser (on `device`), allocate_box, sf_fuse_run (decode_threads as there), known_bounds, export.  No known voxel: a grid of dims 0.
+ * SF_ERR_DEVICE without a GPU (the fuser has no host fall-back); SF_ERR_CAPACITY when a block could not be allocated.  Free with sf_grid_free. */
+int sf_freespace_sens(const struct sf_sens* s, const sf_freespace_params* p, int device, int decode_threads, sf_grid** out, sf_freespace_stats* stats /*nullable*/);
+int sf_grid_create(const sf_grid_header* h, const float* value, const uint8_t* weight, sf_grid** out);   /* copies */
+int sf_grid_info(const sf_grid* g, sf_grid_header* out);
+int sf_grid_data(const sf_grid* g, const float** value, const uint8_t** weight);   /* owned by the grid */
+/* The file, little-endian: char magic[8] = "SFGRID1\0"; int32 nx, ny, nz; float voxel_size; int32 lo_voxel[3]; float world2grid[16]; uint64
+ * frames_used; float value[nz][ny][nx]; uint8 weight[nz][ny][nx].  sf_grid_load: SF_ERR_FORMAT for a bad magic, negative dims, a size that does not
+ * match the file, a voxel_size that is not finite. */
+int sf_grid_save(const sf_grid* g, const char* path);
+int sf_grid_load(const char* path, sf_grid** out);
+void sf_grid_free(sf_grid* g);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,9 @@ int sf_jpeg_decode_gpu_huffman(const uint8_t* data, uint64_t bytes, uint32_t wid
  * by an event pair; sf_fuser_profile_read sums and clears them (synchronises). */
 int sf_fuser_profile_enable(sf_fuser* f, int on);
 int sf_fuser_profile_read(sf_fuser* f, double* integrate_ms, uint64_t* launches, uint64_t* blocks);
+/* With profiling enabled, sf_fuser_export_dense brackets k_export_dense with an event pair of its own: the microseconds of the calling thread's most
+ * recent export (tools/freespace_bench.py); SF_ERR_INVALID_ARG when there was none. */
+int sf_fuser_export_dense_kernel_us(float* us);
 
 /* Synthetic stream source (benchmark input): renders frames
  * [first_frame, first_frame+n) of the `total_frames`-frame box-room walk as u16 millimetre depth directly

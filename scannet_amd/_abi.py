@@ -138,6 +138,9 @@ def _declare_optional(L):
         "sf_fuser_reintegrate_batch_device": ([vp, vp, u64, vp, u64, vp, vp, u64], C.c_int),
         "sf_reint_plan": ([vp, vp, u64, vp, vp, u64, C.POINTER(u64)], C.c_int),
         "sf_fuse_update_trajectory": ([vp, vp, vp, vp, vp, u64, C.c_int, C.c_int, vp], C.c_int),
+        "sf_fuser_allocate_box": ([vp, vp, vp, C.POINTER(u64)], C.c_int),
+        "sf_fuser_known_bounds": ([vp, vp, vp, C.POINTER(u64)], C.c_int),
+        "sf_fuser_export_dense": ([vp, vp, vp, C.c_int, vp, vp, vp, C.c_int], C.c_int),
     }
     for name, (args, res) in table.items():
         if hasattr(L, name):

@@ -1,5 +1,5 @@
 // fuser_internal.h -- device-side layout and the sf_fuser handle, shared by the fusion core (fuser.hip: the host side; fuser_prepass / _alloc / _compact /
-// _integrate / _blocks.hip: one stage each, kernels and their launchers) and by mc.hip, raycast.hip, track.hip, align.hip, pipeline.hip and calib.hip
+// _integrate / _blocks / _dense.hip: one stage each, kernels and their launchers) and by mc.hip, raycast.hip, track.hip, align.hip, pipeline.hip and calib.hip
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -943,6 +943,50 @@ class Fuser:
         order = np.lexsort((coords[:, 2], coords[:, 1], coords[:, 0]))
         return coords[order], vox[order]
 
+    # -- the sparse volume as a dense one (scannet_amd/csrc/fuser_dense.hip) ------------------------------------------
+    def allocate_box(self, lo_block, hi_block):
+        """Insert every block of [lo_block, hi_block] (inclusive block coordinates) that the table does not hold, with zeroed voxels, on the
+        device; blocks that exist keep their bytes.  Returns how many were new."""
+        L = _abi.lib()
+        lo = np.ascontiguousarray(lo_block, np.int32).reshape(3)
+        hi = np.ascontiguousarray(hi_block, np.int32).reshape(3)
+        n = C.c_uint64(0)
+        check(L.sf_fuser_allocate_box(self._h, _ptr(lo), _ptr(hi), C.byref(n)))
+        return n.value
+
+    def known_bounds(self):
+        """-> (lo int32 [3], hi int32 [3], known): the inclusive box, in global voxel indices, of the owned voxels with weight > 0 and their
+        count; (None, None, 0) when there is none."""
+        L = _abi.lib()
+        lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        n = C.c_uint64(0)
+        check(L.sf_fuser_known_bounds(self._h, _ptr(lo), _ptr(hi), C.byref(n)))
+        return (lo, hi, n.value) if n.value else (None, None, 0)
+
+    def export_dense(self, lo, dims, task=False, rgb=False, device=False):
+        """Region [lo, lo + dims) (global voxel indices, x y z) of the volume as dense [z][y][x] arrays -> (sdf float32, weight uint8) or, with
+        rgb, (sdf, weight, rgb uint8 [..., 3]).  task: the task volume (-inf where weight == 0, else sdf / voxel_size) instead of sdf as stored.
+        device: torch tensors on the fuser's GPU, written in place, instead of numpy arrays."""
+        L = _abi.lib()
+        lo = np.ascontiguousarray(lo, np.int32).reshape(3)
+        dims = np.ascontiguousarray(dims, np.int32).reshape(3)
+        if (dims <= 0).any():
+            raise ValueError("dims must be positive")
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            sdf = torch.empty(shape, dtype=torch.float32, device=dev)
+            w = torch.empty(shape, dtype=torch.uint8, device=dev)
+            c = torch.empty(shape + (3,), dtype=torch.uint8, device=dev) if rgb else None
+            torch.cuda.synchronize(dev)
+        else:
+            sdf = np.empty(shape, np.float32)
+            w = np.empty(shape, np.uint8)
+            c = np.empty(shape + (3,), np.uint8) if rgb else None
+        check(L.sf_fuser_export_dense(self._h, _ptr(lo), _ptr(dims), 1 if task else 0, _ptr(sdf), _ptr(w), _ptr(c), 1 if device else 0))
+        return (sdf, w, c) if rgb else (sdf, w)
+
     # -- stage hooks of the front chain (scanfuse_internal.h sf_fuser_stage_*; tests/test_front_stages.py) ----------------------------------
     def _stage_sizes(self):
         p = self.params
