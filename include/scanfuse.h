@@ -1147,6 +1147,43 @@ int sf_grid_save(const sf_grid* g, const char* path);
 int sf_grid_load(const char* path, sf_grid** out);
 void sf_grid_free(sf_grid* g);
 
+/* ------------------------------------------------------------------------------------------------
+ * Voxel-task data: label grids and column samples.  The reference's generator for the data of
+ * Tasks/SemanticVoxelLabeling is "to come soon" (Tasks/README.md:14); what the tree does say is what reads it: datasets `data` [n][1][62][31][31]
+ * and `label` [n][62] (Tasks/SemanticVoxelLabeling/torch/provider.lua:59-60; the sizes in test_scenes.lua:44), label 0 = empty and 255 = unannotated
+ * (provider.lua:63-75), channel data from the free-space volume above (provider.lua:80-97), and the per-vertex read of a [z][y][x] label grid
+ * (BenchmarkScripts/3d_helpers/export_semantic_label_grid_for_evaluation.py:35-47).  The rule -- the nearest face of a lattice node, the label of a
+ * face, which columns become samples -- is this library's statement, unpinned.  device = -1 is the host path (at most 16 threads), which writes the
+ * bytes the device writes; device >= 0 without a GPU is SF_ERR_DEVICE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sf_voxlabel_params {
+  float band;                       /* voxels: a node takes a face within band * voxel_size; 0.8660254f, the half diagonal of a cell  */
+  int32_t wx, wy, wz;               /* the sample window, x and y odd: 31, 31, 62 (test_scenes.lua:44)                               */
+  int32_t z0;                       /* the window's first grid layer when z0_default == 0; any value                                 */
+  int32_t z0_default;               /* != 0: z0 = -lo_voxel[2], the layer of world z = 0: 1                                          */
+  int32_t stride;                   /* every stride-th column in x and in y, >= 1: 1                                                 */
+  int32_t reserved[9];
+} sf_voxlabel_params;
+void sf_voxlabel_params_default(sf_voxlabel_params* p);
+/* face[nz][ny][nx] = the face with the smallest (squared distance, index) among the faces within band * voxel_size of the node, -1 where there is
+ * none; dist2 (nullable) = that squared distance in metres^2, +inf at those nodes.  Of the header only nx, ny, nz, voxel_size and lo_voxel are read.
+ * Faces with a repeated index, a non-finite coordinate or no area (as binary32 sees it) are skipped.  With device >= 0, face and dist2 may be device
+ * memory.  SF_ERR_INVALID_ARG, before anything is launched or written: an index >= num_vertices, a band or voxel_size that is not finite and
+ * positive, nodes beyond +-2^22 or more than 2^40 of them. */
+int sf_voxlabel_nearest_faces(const sf_grid_header* h, const float* xyz, uint64_t num_vertices, const uint32_t* tris, uint64_t num_faces, float band,
+                              int device /* -1: host */, int32_t* face, float* dist2 /*nullable*/);
+/* Host.  A face takes the value two of its vertices share, else its first vertex's; labels and instances apart.  label / instance: the winning
+ * face's, 0 where face == -1; byte_label, the task's: 0 where face == -1, 255 where the face's label is 0 or above 254, else the label.  Any output
+ * may be NULL; vertex_instance may be NULL when instance is. */
+int sf_voxlabel_labels(const int32_t* face, uint64_t num_nodes, const uint32_t* tris, uint64_t num_faces, uint64_t num_vertices, const uint16_t* vertex_label,
+                       const uint8_t* vertex_instance /*nullable*/, uint16_t* label, uint8_t* instance, uint8_t* byte_label);
+/* Column (x, y) is a sample iff x and y are multiples of stride and its own column holds a byte label other than 0 and 255 in the layers
+ * z0 .. z0 + wz - 1 that lie in the grid; samples are numbered y-major.  *total = how many there are; samples first .. first + n - 1,
+ * n = min(max_samples, total - first), go to data[n][1][wz][wy][wx] (the grid's value, -inf outside it), label[n][wz] (the centre column's byte
+ * label, 0 outside) and xy[n][2].  max_samples = 0 with NULL outputs counts only.  With device >= 0 the outputs may be device memory. */
+int sf_voxlabel_sample_columns(const sf_grid* g, const uint8_t* byte_label, const sf_voxlabel_params* p, int device /* -1: host */, uint64_t first,
+                               uint64_t max_samples, float* data, uint8_t* label, int32_t* xy, uint64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

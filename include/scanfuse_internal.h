@@ -323,6 +323,17 @@ int sf_fuser_stage_live(sf_fuser* f, int include_ghosts, int32_t* list_out, uint
 int sf_fuser_stage_dump(sf_fuser* f, uint64_t* key_out, int32_t* ptr_out, uint32_t* birth_out, int32_t* heap_out, uint64_t* block_keys_out, int32_t* block_entry_out,
                         uint8_t* block_flags_out, int32_t* counters_out);
 
+/* The bin stage of the nearest-face search alone (tests/test_voxel_labels_gpu.py; scannet_amd/csrc/voxel_labels.hip): on a device
+ * k_vl_count, k_vl_scan and k_vl_fill as sf_voxlabel_nearest_faces launches them, on the host (device = -1) the host path's bins.  counts / offsets: one
+ * per tile of 8^3 nodes, x fastest; list: *total face indices, tile after tile (the order within a tile is free); SF_ERR_BOUNDS when capacity is short.
+ * Any output may be NULL. */
+int sf_voxlabel_stage_bins(const sf_grid_header* h, const float* xyz, uint64_t num_vertices, const uint32_t* tris, uint64_t num_faces, float band, int device,
+                           uint32_t* counts, uint32_t* offsets, int32_t* list, uint64_t capacity, uint64_t* total);
+
+/* Device microseconds (HIP events) of the most recent device call of this process: the bin stage (k_vl_count, k_vl_scan, k_vl_fill), the search
+ * (k_vl_clear, k_vl_nearest), and k_vl_sample (tools/voxel_labels_bench.py).  Any pointer may be NULL. */
+int sf_voxlabel_kernel_us(float* bins_us, float* nearest_us, float* sample_us);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 
