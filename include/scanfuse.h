@@ -1184,6 +1184,50 @@ int sf_voxlabel_labels(const int32_t* face, uint64_t num_nodes, const uint32_t* 
 int sf_voxlabel_sample_columns(const sf_grid* g, const uint8_t* byte_label, const sf_voxlabel_params* p, int device /* -1: host */, uint64_t first,
                                uint64_t max_samples, float* data, uint8_t* label, int32_t* xy, uint64_t* total);
 
+/* ------------------------------------------------------------------------------------------------
+ * Object-task data: an occupancy and a known grid per annotated object.  The generator of this data is "to come soon" as well
+ * (Tasks/README.md:14); what reads it: Tasks/ObjectClassification/torch/provider.lua:40-47 and train_partial.lua, and
+ * Tasks/ObjectRetrieval/generate_feat.lua:32,74-81,101-109 -- datasets `data` [n][2][30][30][30] (channel 0 the "partially-scanned objects, voxelized to
+ * 30x30x30", channel 1 the "additional data channel encoding known/unknown voxels according to the camera scanning trajectory", Tasks/README.md:20)
+ * and `label` [n], 0-based: the first column of Tasks/Benchmark/classes_ObjClassification-ShapeNetCore55.txt (generate_feat.lua:42 against :78 and
+ * :109).  Objects are told apart as BenchmarkScripts/3d_helpers/export_train_mesh_for_evaluation.py:38-54,86-90 does: by the segGroup's objectId.  The
+ * rule -- the cube of an object, the quantisation, which cells a face sets, which cells are known -- is this library's statement, unpinned.
+ * device = -1 is the host path (at most 16 threads), which writes the bytes the device writes; device >= 0 without a GPU is SF_ERR_DEVICE.
+ * ---------------------------------------------------------------------------------------------- */
+/* vertex_object[v] = objectId + 1 of the segGroup whose `segments` hold the vertex's segment (a later group overwrites an earlier one), 0: no group.
+ * *num_objects = the largest objectId + 1 (0 without a group).  *labels (nullable): one "objectId\tlabel\n" line per objectId that a group names, ascending,
+ * the label of the last such group; malloc'ed (sf_free).  SF_ERR_FORMAT: a segs.json of another vertex count, no segGroups, an objectId above 65 535. */
+int sf_annotation_vertex_objects(const char* segs_json, const char* aggregation_json, uint64_t num_vertices, uint32_t* vertex_object, uint32_t* num_objects,
+                                 char** labels /*nullable*/);
+/* Host.  object_class[i] for the lines of `object_labels` (the text above), -1 where the object has no class or no line: the label is looked up in the
+ * label map (key column label_from; NULL: "raw_category", or "category" when the file has no such column; value column label_to, NULL:
+ * "ShapeNetCore55"), the value is matched against the classes file (lines of `<id> <name>`): it equals a name, or parses as an integer equal to an
+ * id.  SF_ERR_IO: a file that cannot be read; SF_ERR_FORMAT: a column that is not there, a classes file with an id outside 0 .. 254. */
+int sf_objvox_classes(const char* object_labels, const char* label_map_tsv, const char* classes_txt, const char* label_from /*nullable*/,
+                      const char* label_to /*nullable*/, uint32_t num_objects, int32_t* object_class);
+typedef struct sf_objvox_params {
+  int32_t dim;                      /* cells per axis, 1 .. 32: 30 (provider.lua:40-47)                                               */
+  int32_t fit;                      /* the object's largest extent in cells, 1 .. dim: 24                                             */
+  int32_t min_faces;                /* objects with fewer counted faces are left out: 1                                               */
+  int32_t all_objects;              /* != 0: objects without a class are kept, with label 255: 0                                      */
+  int32_t reserved[12];
+} sf_objvox_params;
+void sf_objvox_params_default(sf_objvox_params* p);
+/* Host.  The objects sf_objvox_voxelize keeps, in ascending objectId order: *count of them; the first min(*count, capacity) go to object_id[],
+ * origin[][3] (the corner of cell (0, 0, 0), metres) and cell[] (the cell's edge) -- each nullable.  vertex_object: num_vertices values 0 .. num_objects;
+ * object_class: num_objects values -1 .. 254.  Refusals as in sf_objvox_voxelize. */
+int sf_objvox_plan(const float* xyz, uint64_t num_vertices, const uint32_t* tris, uint64_t num_faces, const uint32_t* vertex_object, const int32_t* object_class,
+                   uint32_t num_objects, const sf_objvox_params* p, int32_t* object_id, float* origin, float* cell, uint64_t capacity, uint64_t* count);
+/* *total = how many objects are kept; objects first .. first + n - 1 of them, n = min(max_objects, total - first), go to data[n][2][dim][dim][dim]
+ * ([c][z][y][x]; channel 0: 1 where a face of the object meets the closed cell, channel 1: 1 where the cell is occupied or the grid's node nearest to
+ * its centre has weight > 0; all ones without a grid), label[n] (the class id; 255 without a class), object_id[n] (objectId, 0-based), origin[n][3] and
+ * cell[n].  max_objects = 0 with NULL outputs counts only.  With device >= 0 the outputs may be device memory.  SF_ERR_INVALID_ARG, before anything
+ * is launched or written: an index >= num_vertices, dim outside 1 .. 32, fit outside 1 .. dim, a vertex_object value above num_objects, num_objects
+ * above 65 536, a class outside -1 .. 254, more than 2^31 faces. */
+int sf_objvox_voxelize(const float* xyz, uint64_t num_vertices, const uint32_t* tris, uint64_t num_faces, const uint32_t* vertex_object, const int32_t* object_class,
+                       uint32_t num_objects, const sf_grid* grid /*nullable*/, const sf_objvox_params* p, int device /* -1: host */, uint64_t first,
+                       uint64_t max_objects, uint8_t* data, uint8_t* label, int32_t* object_id, float* origin, float* cell, uint64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

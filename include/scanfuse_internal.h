@@ -334,6 +334,18 @@ int sf_voxlabel_stage_bins(const sf_grid_header* h, const float* xyz, uint64_t n
  * (k_vl_clear, k_vl_nearest), and k_vl_sample (tools/voxel_labels_bench.py).  Any pointer may be NULL. */
 int sf_voxlabel_kernel_us(float* bins_us, float* nearest_us, float* sample_us);
 
+/* The key, scan and fill stage of the object voxeliser alone (tests/test_object_voxels_gpu.py; scannet_amd/csrc/object_voxels.hip, DESIGN.md section
+ * 4n): on a device k_ov_key, k_ov_scan and k_ov_fill as sf_objvox_voxelize launches them, on the host (device = -1) the host path's grouping.
+ * face_object: one per face, 0 where the face has no object or is not counted; counts / offsets: num_objects + 1 entries, indexed by the
+ * vertex_object value (entry 0 holds nothing); list: the faces, object after object, in no particular order within one.  list may be NULL (then
+ * capacity is not read); *total = entries in all.  Any output may be NULL. */
+int sf_objvox_stage_faces(const float* xyz, uint64_t num_vertices, const uint32_t* tris, uint64_t num_faces, const uint32_t* vertex_object, uint32_t num_objects,
+                          int device, uint32_t* face_object, uint32_t* counts, uint32_t* offsets, uint32_t* list, uint64_t capacity, uint64_t* total);
+
+/* Device microseconds (HIP events) of the most recent device call of this process: grouping and cubes (k_ov_key .. k_ov_box), k_ov_raster, k_ov_emit
+ * (tools/object_voxels_bench.py).  Any pointer may be NULL. */
+int sf_objvox_kernel_us(float* group_us, float* raster_us, float* emit_us);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

@@ -30,6 +30,7 @@ bool slurp(const char* path, std::string& out) {
 
 struct SegGroup {
   unsigned id = 0;
+  unsigned object_id = 0;   // "objectId"; the "id" where the group has none
   std::string label;
   std::vector<unsigned> segments;
 };
@@ -92,6 +93,8 @@ bool parse_seg_groups(const std::string& t, std::vector<SegGroup>& out) {
       if (pi == std::string::npos || pl == std::string::npos || ps == std::string::npos) return false;
       SegGroup g;
       g.id = json_uint(o, pi);
+      size_t po = member(o, "objectId");
+      g.object_id = po == std::string::npos ? g.id : json_uint(o, po);
       size_t q = o.find('"', pl);
       if (q == std::string::npos) return false;
       for (q++; q < o.size() && o[q] != '"'; q++) { if (o[q] == '\\' && q + 1 < o.size()) q++; g.label.push_back(o[q]); }
@@ -222,6 +225,52 @@ SF_API int sf_annotation_vertex_ids(const char* segs_json, const char* aggregati
     }
   }
   if (num_labels) *num_labels = (uint32_t)colour.size();
+  return SF_OK;
+}
+
+// BenchmarkScripts/3d_helpers/export_train_mesh_for_evaluation.py:38-54,86-90: vertex -> objectId + 1, group after group in file order, so a later group
+// overwrites an earlier one; 0 = no group.  This tells one chair from the next, which the instance value above does not.
+SF_API int sf_annotation_vertex_objects(const char* segs_json, const char* aggregation_json, uint64_t num_vertices, uint32_t* vertex_object, uint32_t* num_objects,
+                                        char** labels) {
+  if (!segs_json || !aggregation_json || !num_objects || (num_vertices && !vertex_object)) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (labels) *labels = nullptr;
+  *num_objects = 0;
+  std::string t;
+  std::vector<unsigned> seg;
+  if (!slurp(segs_json, t)) return sf::fail(SF_ERR_IO, "[parse] failed to open file %s", segs_json);
+  if (!parse_seg_indices(t, seg)) return sf::fail(SF_ERR_FORMAT, "no segIndices array in %s", segs_json);
+  if (seg.size() != num_vertices)
+    return sf::fail(SF_ERR_FORMAT, "%s holds %llu segment ids for a mesh of %llu vertices", segs_json, (unsigned long long)seg.size(), (unsigned long long)num_vertices);
+  std::vector<SegGroup> groups;
+  if (!slurp(aggregation_json, t)) return sf::fail(SF_ERR_IO, "failed to open file %s", aggregation_json);
+  if (!parse_seg_groups(t, groups)) return sf::fail(SF_ERR_FORMAT, "no segGroups array in %s", aggregation_json);
+  std::map<unsigned, std::string> label_of;   // ascending objectId; the last group's label
+  for (const SegGroup& g : groups) {
+    if (g.object_id > 65535u) return sf::fail(SF_ERR_FORMAT, "%s: objectId %u (at most 65535)", aggregation_json, g.object_id);
+    label_of[g.object_id] = g.label;
+  }
+  std::unordered_map<unsigned, std::vector<uint32_t>> verts_of_seg;
+  for (uint64_t v = 0; v < num_vertices; v++) verts_of_seg[seg[v]].push_back((uint32_t)v);
+  for (uint64_t v = 0; v < num_vertices; v++) vertex_object[v] = 0;
+  for (const SegGroup& g : groups)
+    for (unsigned s : g.segments) {
+      const auto it = verts_of_seg.find(s);
+      if (it == verts_of_seg.end()) continue;
+      for (uint32_t v : it->second) vertex_object[v] = g.object_id + 1;
+    }
+  if (!label_of.empty()) *num_objects = label_of.rbegin()->first + 1;
+  if (labels) {
+    std::string text;
+    for (const auto& kv : label_of) {
+      text += std::to_string(kv.first) + "\t";
+      for (char c : kv.second) text.push_back(c == '\n' || c == '\t' || c == '\r' ? ' ' : c);
+      text += "\n";
+    }
+    char* out = (char*)std::malloc(text.size() + 1);
+    if (!out) return sf::fail(SF_ERR_IO, "sf_annotation_vertex_objects: out of memory");
+    std::memcpy(out, text.c_str(), text.size() + 1);
+    *labels = out;
+  }
   return SF_OK;
 }
 
