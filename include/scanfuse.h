@@ -1228,6 +1228,85 @@ int sf_objvox_voxelize(const float* xyz, uint64_t num_vertices, const uint32_t* 
                        uint32_t num_objects, const sf_grid* grid /*nullable*/, const sf_objvox_params* p, int device /* -1: host */, uint64_t first,
                        uint64_t max_objects, uint8_t* data, uint8_t* label, int32_t* object_id, float* origin, float* cell, uint64_t* total);
 
+/* ------------------------------------------------------------------------------------------------
+ * Benchmark scores: label IoU and instance AP from predictions.  What they replace:
+ * BenchmarkScripts/3d_evaluation/evaluate_semantic_label.py:48-82 (confusion matrix and IoU), evaluate_semantic_instance.py:75-309 with
+ * util_3d.py:148-159 (instances, overlaps, AP), 2d_evaluation/evalPixelLevelSemanticLabeling.py:226-264 with addToConfusionMatrix_impl.c (the 2-D
+ * matrix after a nearest-neighbour resize to 640 x 480).  Every count is an integer: device = -1 is the host path (at most 16 threads), which gives
+ * the counts the device gives; device >= 0 without a GPU is SF_ERR_DEVICE.  The _device twins take device memory and a HIP stream (hipStream_t as
+ * void*, NULL: the default stream): they copy nothing, wait for nothing and add into counters that stay on the device.  Every pointer must be device
+ * memory of one device (looked up with hipPointerGetAttributes, a host-side query); that device is current during the call and the caller's current
+ * device is put back before it returns.  A refused call writes nothing.
+ * Elements are unsigned integers of elem_bytes = 1, 2 or 4 bytes, both arrays alike; a negative value of a signed type reads as a large one, which is
+ * no valid class.  valid_ids: n_valid distinct class ids 0 .. 61; dim = the largest + 2.
+ * ---------------------------------------------------------------------------------------------- */
+#define SF_EVAL_MODE_3D 0 /* gt not a valid class: skipped; pred not a valid class: column dim - 1 (evaluate_semantic_label.py:60-65) */
+#define SF_EVAL_MODE_2D 1 /* every element counts at [gt][pred]; an id >= dim in either array: counted in *out_of_range instead      */
+#define SF_EVAL_IMAGE_WIDTH 640
+#define SF_EVAL_IMAGE_HEIGHT 480
+#define SF_EVAL_AP_OVERLAPS 10 /* 0.5, 0.55 .. 0.9, then 0.25 (evaluate_semantic_instance.py:66) */
+/* confusion[dim][dim] and *out_of_range (nullable in the 3-D mode) are ADDED to: zero them before the first call.  n up to 2^40. */
+int sf_eval_confusion(const void* gt, const void* pred, int elem_bytes, uint64_t n, const int32_t* valid_ids, uint32_t n_valid, int mode,
+                      int device /* -1: host */, uint64_t* confusion, uint64_t* out_of_range);
+int sf_eval_confusion_device(const void* gt, const void* pred, int elem_bytes, uint64_t n, const int32_t* valid_ids /* host */, uint32_t n_valid, int mode,
+                             void* stream, uint64_t* confusion, uint64_t* out_of_range);
+/* The 2-D mode on `batch` pairs gt[batch][gt_height][gt_width], pred[batch][pred_height][pred_width]: both are resized to 640 x 480 by nearest
+ * neighbour, source index = floor((dst + 0.5) * src / dst size) per axis, and counted as SF_EVAL_MODE_2D with the dim given (41 for NYU40).
+ * SF_ERR_INVALID_ARG unless pred_width == gt_width or the prediction is 640 x 480 (evalPixelLevelSemanticLabeling.py:240); sides up to 32768. */
+int sf_eval_confusion_images(const void* gt, const void* pred, int elem_bytes, uint32_t batch, uint32_t gt_width, uint32_t gt_height, uint32_t pred_width,
+                             uint32_t pred_height, uint32_t dim, int device /* -1: host */, uint64_t* confusion, uint64_t* out_of_range);
+int sf_eval_confusion_images_device(const void* gt, const void* pred, int elem_bytes, uint32_t batch, uint32_t gt_width, uint32_t gt_height,
+                                    uint32_t pred_width, uint32_t pred_height, uint32_t dim, void* stream, uint64_t* confusion, uint64_t* out_of_range);
+/* Host.  Per valid class i: tp = the diagonal, fn = the row sum - tp, fp = the column sum over the other valid rows, denom[i] = tp + fp + fn,
+ * iou[i] = tp / denom in binary64, NaN when denom is 0 (get_iou, evaluate_semantic_label.py:68-82).  tp and denom nullable.  dim: the matrix's. */
+int sf_eval_iou(const uint64_t* confusion, uint32_t dim, const int32_t* valid_ids, uint32_t n_valid, double* iou, uint64_t* tp, uint64_t* denom);
+/* Host.  gt_ids[n] are label * 1000 + k.  The instances are the distinct ids > 0 whose id / 1000 is a valid class, ascending: *count of them (G); the
+ * first min(G, capacity) go to instance_id[] and instance_verts[] (nullable; SF_ERR_BOUNDS when capacity < G).  slot[n] (nullable): the index of the
+ * vertex's instance, G where the vertex is void (id / 1000 no valid class) -- by the G of this call. */
+int sf_eval_instance_plan(const int32_t* gt_ids, uint64_t n, const int32_t* valid_ids, uint32_t n_valid, int32_t* instance_id, uint32_t* instance_verts,
+                          uint32_t capacity, uint32_t* slot, uint32_t* count);
+/* masks[P][stride] bytes, a vertex is covered where the byte is non-zero; stride >= n.  table[P][G + 2] is WRITTEN: [p][g] = covered vertices of
+ * prediction p in instance g, [p][G] = in void (a slot >= G), [p][G + 1] = covered vertices in all.  n below 2^32, P up to 65535, G up to 2^24. */
+int sf_eval_instance_overlaps(const uint32_t* slot, uint64_t n, uint32_t G, const uint8_t* masks, uint32_t P, uint64_t stride, int device /* -1: host */,
+                              uint32_t* table);
+int sf_eval_instance_overlaps_device(const uint32_t* slot, uint64_t n, uint32_t G, const uint8_t* masks, uint32_t P, uint64_t stride, void* stream,
+                                     uint32_t* table);
+/* The AP over scans (evaluate_matches and compute_averages, evaluate_semantic_instance.py:75-242).  add_scan takes a scan's plan, its predictions in
+ * the order of the prediction file (label, confidence) and their overlap table; a prediction whose label is no valid class or that covers fewer than
+ * min_region_size vertices is dropped.  finish: ap[n_valid][SF_EVAL_AP_OVERLAPS] (NaN: the class has no ground truth), class_averages[n_valid][3]
+ * (nullable) = {mean over the nine overlaps 0.5 .. 0.9, at 0.5, at 0.25}, averages[3] (nullable) = their means over the classes that are not NaN. */
+typedef struct sf_eval_ap sf_eval_ap;
+int sf_eval_ap_create(const int32_t* valid_ids, uint32_t n_valid, uint32_t min_region_size /* 100 */, sf_eval_ap** out);
+int sf_eval_ap_add_scan(sf_eval_ap* acc, uint32_t G, const int32_t* instance_id, const uint32_t* instance_verts, uint32_t P, const int32_t* pred_label,
+                        const double* pred_conf, const uint32_t* table);
+int sf_eval_ap_finish(const sf_eval_ap* acc, double* ap, double* class_averages, double* averages);
+void sf_eval_ap_destroy(sf_eval_ap* acc);
+/* The three scores from the benchmark's files, as the scripts take them (NYU40: the 20 label classes, the 18 instance classes).  Every `.txt` file of
+ * pred_path (label, instance) or every file (pixel: PNG images, 8 or 16 bits, one channel) needs a file of its name in gt_path; the result file itself
+ * is left out.  output_file NULL or "": pred_path/semantic_label_evaluation.txt, semantic_instance_evaluation.txt, semantic_label.txt.  The result
+ * file is written in the script's layout (evaluate_semantic_label.py:85-103, evaluate_semantic_instance.py:350-360 with each number printed so that
+ * it parses back to the same binary64, evalPixelLevelSemanticLabeling.py:157-173); *report (nullable; malloc'ed, sf_free) is the text of the tables the
+ * script prints.  A class whose denominator is 0 prints nan.  SF_ERR_IO: no result files, a file without ground truth, an unreadable file;
+ * SF_ERR_FORMAT: a line that is no integer, arrays of different lengths, a mask path that is absolute or leaves pred_path
+ * (util_3d.py:125-145), an image of the wrong size or with several channels, a pixel id of 41 or more (named with its file). */
+int sf_eval_label_dir(const char* pred_path, const char* gt_path, const char* output_file /*nullable*/, int device /* -1: host */, char** report);
+int sf_eval_instance_dir(const char* pred_path, const char* gt_path, const char* output_file /*nullable*/, uint32_t min_region_size /* 100 */,
+                         int device /* -1: host */, char** report);
+int sf_eval_pixel_dir(const char* pred_path, const char* gt_path, const char* output_file /*nullable*/, int device /* -1: host */, char** report);
+/* Host.  The ground truth of a scan per vertex (3d_helpers/export_train_mesh_for_evaluation.py:38-90): the segGroups in file order, a later group
+ * overwrites an earlier one; label_ids[v] = the nyu40id the label map gives the group's label (columns raw_category -> nyu40id, util.py:32-42),
+ * instance_ids[v] = the group's objectId + 1; 0 where no group holds the vertex's segment.  *num_vertices = the length of segIndices; the arrays
+ * (each nullable) hold `capacity` values: SF_ERR_BOUNDS when that is too few.  SF_ERR_FORMAT: a label that is no raw_category of the map, a map
+ * without the two columns, an nyu40id cell that is no integer. */
+int sf_eval_export_ids(const char* segs_json, const char* aggregation_json, const char* label_map_tsv, uint64_t capacity, uint32_t* label_ids,
+                       uint32_t* instance_ids, uint64_t* num_vertices);
+/* The same to files, for the scan folder scan_path = .../<id> with <id>.aggregation.json and <id>_vh_clean_2.0.010000.segs.json in it.  type "label":
+ * one label id per line (the reference's bytes); "instance": the prediction format -- a line `pred_mask/<name>_<k>.txt <label id> 1.000000` per
+ * object, <name> the output file's name without its extension, k the object's position among the sorted distinct instance ids (0 counts where a
+ * vertex is unannotated), and the 0/1 masks under pred_mask/ beside the output file (util_3d.py:57-77); "instance-gt": label id * 1000 + objectId + 1
+ * per line, 0 where unannotated: what sf_eval_instance_dir reads as ground truth. */
+int sf_eval_export_scan(const char* scan_path, const char* label_map_file, const char* type, const char* output_file);
+
 #ifdef __cplusplus
 }
 #endif

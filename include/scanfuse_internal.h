@@ -346,6 +346,9 @@ int sf_objvox_stage_faces(const float* xyz, uint64_t num_vertices, const uint32_
  * (tools/object_voxels_bench.py).  Any pointer may be NULL. */
 int sf_objvox_kernel_us(float* group_us, float* raster_us, float* emit_us);
 
+/* The SF_EVAL_AP_OVERLAPS overlap thresholds sf_eval_ap_finish compares against, bit for bit (tests/test_evaluation.py holds them against numpy's). */
+int sf_eval_ap_thresholds(double* thresholds);
+
 /* PMC calibration stream (tools/pmc_calibrate.py): known-byte-count 16 B/lane RMW + read-only launches. */
 int sf_calib_stream(int device, uint64_t bytes, int iters);
 

@@ -274,6 +274,71 @@ SF_API int sf_annotation_vertex_objects(const char* segs_json, const char* aggre
   return SF_OK;
 }
 
+// BenchmarkScripts/3d_helpers/export_train_mesh_for_evaluation.py:38-90 with util.read_label_mapping(label_from = "raw_category", label_to = "nyu40id"):
+// the ground truth of a scan per vertex.  Groups are taken in file order and a later group overwrites an earlier one: label_ids[v] = the nyu40id of
+// the group's label, instance_ids[v] = its objectId + 1; 0 where no group holds the vertex's segment.  (The reference walks a dict of labels and a
+// dict of object ids; the orders agree with the file order wherever no segment is listed under two groups, which is all the format intends.)
+SF_API int sf_eval_export_ids(const char* segs_json, const char* aggregation_json, const char* label_map_tsv, uint64_t capacity, uint32_t* label_ids,
+                              uint32_t* instance_ids, uint64_t* num_vertices) {
+  if (!segs_json || !aggregation_json || !label_map_tsv || !num_vertices) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  *num_vertices = 0;
+  std::string t;
+  std::vector<unsigned> seg;
+  if (!slurp(segs_json, t)) return sf::fail(SF_ERR_IO, "[parse] failed to open file %s", segs_json);
+  if (!parse_seg_indices(t, seg)) return sf::fail(SF_ERR_FORMAT, "no segIndices array in %s", segs_json);
+  std::vector<SegGroup> groups;
+  if (!slurp(aggregation_json, t)) return sf::fail(SF_ERR_IO, "failed to open file %s", aggregation_json);
+  if (!parse_seg_groups(t, groups)) return sf::fail(SF_ERR_FORMAT, "no segGroups array in %s", aggregation_json);
+  // the label map: a tab-separated table with a header row; cells are taken as they stand (no quoting)
+  std::ifstream f(label_map_tsv);
+  std::string line;
+  if (!f || !std::getline(f, line)) return sf::fail(SF_ERR_IO, "error reading label mapping file %s", label_map_tsv);
+  auto split = [](const std::string& s) {
+    std::vector<std::string> v;
+    std::string cur;
+    for (char c : s) { if (c == '\t') { v.push_back(cur); cur.clear(); } else if (c != '\r') cur.push_back(c); }
+    v.push_back(cur);
+    return v;
+  };
+  const std::vector<std::string> header = split(line);
+  int from = -1, to = -1;
+  for (size_t i = 0; i < header.size(); i++) {
+    if (header[i] == "raw_category") from = (int)i;
+    if (header[i] == "nyu40id") to = (int)i;
+  }
+  if (from < 0 || to < 0) return sf::fail(SF_ERR_FORMAT, "%s has no raw_category / nyu40id columns", label_map_tsv);
+  std::unordered_map<std::string, uint32_t> nyu40;
+  for (unsigned row = 2; std::getline(f, line); row++) {
+    if (line.empty() || line == "\r") continue;
+    const std::vector<std::string> parts = split(line);
+    if ((int)parts.size() <= from || (int)parts.size() <= to) return sf::fail(SF_ERR_FORMAT, "%s: line %u is short of a column", label_map_tsv, row);
+    const std::string& cell = parts[(size_t)to];
+    char* end = nullptr;
+    const long long v = std::strtoll(cell.c_str(), &end, 10);
+    if (cell.empty() || *end || v < 0 || v > 4000000) return sf::fail(SF_ERR_FORMAT, "%s: line %u: nyu40id \"%s\" is no id", label_map_tsv, row, cell.c_str());
+    nyu40[parts[(size_t)from]] = (uint32_t)v;
+  }
+  std::vector<uint32_t> group_label(groups.size());
+  for (size_t i = 0; i < groups.size(); i++) {
+    const auto it = nyu40.find(groups[i].label);
+    if (it == nyu40.end()) return sf::fail(SF_ERR_FORMAT, "%s: the label \"%s\" of %s is no raw_category", label_map_tsv, groups[i].label.c_str(), aggregation_json);
+    if (groups[i].object_id > 4000000u) return sf::fail(SF_ERR_FORMAT, "%s: objectId %u", aggregation_json, groups[i].object_id);
+    group_label[i] = it->second;
+  }
+  *num_vertices = seg.size();
+  if (!label_ids && !instance_ids) return SF_OK;
+  if (capacity < seg.size()) return sf::fail(SF_ERR_BOUNDS, "sf_eval_export_ids: %zu vertices, capacity %llu", seg.size(), (unsigned long long)capacity);
+  std::unordered_map<unsigned, size_t> group_of_seg;   // the last group that lists the segment
+  for (size_t i = 0; i < groups.size(); i++)
+    for (unsigned sgm : groups[i].segments) group_of_seg[sgm] = i;
+  for (size_t v = 0; v < seg.size(); v++) {
+    const auto it = group_of_seg.find(seg[v]);
+    if (label_ids) label_ids[v] = it == group_of_seg.end() ? 0u : group_label[it->second];
+    if (instance_ids) instance_ids[v] = it == group_of_seg.end() ? 0u : groups[it->second].object_id + 1u;
+  }
+  return SF_OK;
+}
+
 // Visualizer::propagateAnnotations (:297-377): every vertex of the high-resolution mesh takes the ids of one of its three nearest
 // annotated vertices of the decimated mesh -- the first (by distance) within maxThresh whose normal is within normal_thresh radians,
 // else the nearest one's ids if all three are within maxThresh and agree on the instance, else none.  The reference asks FLANN
