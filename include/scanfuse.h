@@ -1307,6 +1307,65 @@ int sf_eval_export_ids(const char* segs_json, const char* aggregation_json, cons
  * per line, 0 where unannotated: what sf_eval_instance_dir reads as ground truth. */
 int sf_eval_export_scan(const char* scan_path, const char* label_map_file, const char* type, const char* output_file);
 
+/* ------------------------------------------------------------------------------------------------
+ * Benchmark scores, 2-D instances: the image-level instance AP.  What they replace:
+ * BenchmarkScripts/2d_evaluation/evalInstanceLevelSemanticLabeling.py:204-298 (assignGt2Preds), :301-496 (evaluateMatches), :498-515
+ * (computeAverages) with instances2dict.py:27-46 and instance.py:13-24.  Ground truth is a batch of id images gt[batch][height][width] of
+ * elem_bytes = 1, 2 or 4 bytes per pixel, all of one size, with fewer than 2^32 pixels each; a pixel is value = label * 1000 + k.  valid_ids: n_valid
+ * distinct class ids 1 .. 999 (anything else: SF_ERR_INVALID_ARG), so that a void value can never be an instance id:
+ *   instance  value / 1000 is a valid class (instances2dict.py:40-43)
+ *   void      the raw value is itself a valid class id (evalInstanceLevelSemanticLabeling.py:226-230) -- not the 3-D void
+ * Every count is an integer: device = -1 is the host path (at most 16 threads) and gives the counts the kernels give.  The _device twins follow the
+ * rules of the _device calls above: device memory of one device, a HIP stream, nothing copied, nothing waited for, results left on the device,
+ * the caller's current device put back, and a refused call has written nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define SF_EVAL_AP2D_OVERLAPS 10 /* numpy's arange(0.5, 1., 0.05) (evalInstanceLevelSemanticLabeling.py:74) */
+/* The plan of every image: count[b] = its number of instances, instance_id[b][capacity] = their ids ascending, instance_pixels[b][capacity] = their
+ * pixel counts; entries from count[b] on are not written.  The two arrays may both be NULL: only count[] is written.  Otherwise SF_ERR_BOUNDS when
+ * some image holds more than `capacity` instances, and nothing is written then.  batch up to 65535, capacity up to 2^20. */
+int sf_eval_image_plan(const void* gt, int elem_bytes, uint32_t batch, uint32_t width, uint32_t height, const int32_t* valid_ids, uint32_t n_valid,
+                       uint32_t capacity, int device /* -1: host */, uint32_t* count, int32_t* instance_id, uint32_t* instance_pixels);
+/* Bytes of the counter array the device plan needs: batch * (largest valid id + 1) * 1000 * 4; 0 for arguments sf_eval_image_plan refuses. */
+uint64_t sf_eval_image_plan_scratch(uint32_t batch, const int32_t* valid_ids /* host */, uint32_t n_valid);
+/* scratch: sf_eval_image_plan_scratch() bytes, aligned to 16.  count[b] is the image's true number of instances, of which the first
+ * min(count[b], capacity) are written: the caller compares count[] with its capacity once it has read it. */
+int sf_eval_image_plan_device(const void* gt, int elem_bytes, uint32_t batch, uint32_t width, uint32_t height, const int32_t* valid_ids /* host */,
+                              uint32_t n_valid, uint32_t capacity, void* stream, void* scratch, uint32_t* count, int32_t* instance_id,
+                              uint32_t* instance_pixels);
+/* masks[P][stride] bytes (stride >= width * height), a pixel is covered where the byte is non-zero; mask p lies over image mask_image[p].
+ * table[P][capacity + 2] is WRITTEN: [p][g] = covered pixels of mask p in instance g of its image (0 from count[] on), [p][capacity] = covered void
+ * pixels, [p][capacity + 1] = covered pixels in all.  count and instance_id are sf_eval_image_plan's.  P up to 65535.  The host call refuses
+ * (SF_ERR_INVALID_ARG) a count above capacity, ids that do not ascend and a mask_image >= batch; the _device twin cannot read them: it counts a
+ * count above capacity as capacity and leaves the row of a mask without an image zero. */
+int sf_eval_overlaps_images(const void* gt, int elem_bytes, uint32_t batch, uint32_t width, uint32_t height, const int32_t* valid_ids, uint32_t n_valid,
+                            uint32_t capacity, const uint32_t* count, const int32_t* instance_id, const uint8_t* masks, uint32_t P, uint64_t stride,
+                            const uint32_t* mask_image, int device /* -1: host */, uint32_t* table);
+int sf_eval_overlaps_images_device(const void* gt, int elem_bytes, uint32_t batch, uint32_t width, uint32_t height, const int32_t* valid_ids /* host */,
+                                   uint32_t n_valid, uint32_t capacity, const uint32_t* count, const int32_t* instance_id, const uint8_t* masks, uint32_t P,
+                                   uint64_t stride, const uint32_t* mask_image, void* stream, uint32_t* table);
+/* The AP over images (evaluateMatches and computeAverages).  add_image takes one image's plan (G instances), its P predictions (label,
+ * confidence; a NaN confidence is refused) and their rows table[P][capacity + 2], G <= capacity.  A prediction whose label is no valid class or that
+ * covers no pixel is dropped; there is no minimum size for predictions.  Ground truth below min_region_size pixels is ignored, not matched.
+ * finish: ap[n_valid][SF_EVAL_AP2D_OVERLAPS] (NaN: the class has no ground truth), class_averages[n_valid][2] (nullable) = {mean over the ten
+ * thresholds, at 0.5}, averages[2] (nullable) = the mean of the ap entries that are not NaN, and of those at 0.5.  The result depends on neither
+ * the order of the images nor the order of an image's predictions.  thresholds[SF_EVAL_AP2D_OVERLAPS]: the ten values, bit for bit numpy's. */
+typedef struct sf_eval_ap2d sf_eval_ap2d;
+int sf_eval_ap2d_create(const int32_t* valid_ids, uint32_t n_valid, uint32_t min_region_size /* 100 */, sf_eval_ap2d** out);
+int sf_eval_ap2d_add_image(sf_eval_ap2d* acc, uint32_t G, const int32_t* instance_id, const uint32_t* instance_pixels, uint32_t P, const int32_t* pred_label,
+                           const double* pred_conf, const uint32_t* table, uint32_t capacity);
+int sf_eval_ap2d_finish(const sf_eval_ap2d* acc, double* ap, double* class_averages, double* averages);
+void sf_eval_ap2d_destroy(sf_eval_ap2d* acc);
+int sf_eval_ap2d_thresholds(double* thresholds);
+/* evalInstanceLevelSemanticLabeling.py on its files, for the 18 instance classes.  Every `.txt` under pred_path, sub-folders included (:609-612),
+ * is the prediction list of one image: lines `<relative path of a mask> <label id> <confidence>` split at single blanks (:122-137); its ground
+ * truth is gt_path/<base name>.png, one channel of 8 or 16 bits; a mask is a one-channel 8-bit PNG of the same size, relative to the list's folder.
+ * The result file (default pred_path/semantic_instance.txt; left out of the walk) has the lines of :567-576 with 17 significant digits per number;
+ * *report (nullable; malloc'ed, sf_free) is the table of printResults (:517-553).  SF_ERR_IO: no lists, a list without ground truth, an unreadable
+ * file; SF_ERR_FORMAT: a line that is not three fields, a number that is none, a NaN confidence, a mask path that is absolute or leaves pred_path,
+ * two lists of one base name, an image that is not one channel of the bits above, a mask of another size (each named with its file). */
+int sf_eval_instance2d_dir(const char* pred_path, const char* gt_path, const char* output_file /*nullable*/, uint32_t min_region_size /* 100 */,
+                           int device /* -1: host */, char** report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 // path of the two counting stages (the rules of evaluation_internal.h on at most 16 threads), the IoU, the instance plan and the AP accumulator.  The
 // counts are integers, so the host path gives the bits the kernels of evaluation.hip give.  What it replaces:
 // BenchmarkScripts/3d_evaluation/evaluate_semantic_label.py, evaluate_semantic_instance.py with util_3d.py, and
-// 2d_evaluation/evalPixelLevelSemanticLabeling.py with addToConfusionMatrix_impl.c.
+// 2d_evaluation/evalPixelLevelSemanticLabeling.py with addToConfusionMatrix_impl.c.  The AP over images of the 2-D instance task (section 4p,
+// evalInstanceLevelSemanticLabeling.py:301-515) is here too, beside the AP over scans whose curve it shares; its counting stages are instance2d.cpp.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -20,25 +21,9 @@ namespace {
 using sf::ev::MODE_2D;
 using sf::ev::MODE_3D;
 
-constexpr int MAX_THREADS = 16;
 constexpr uint64_t GRAIN = 1u << 16;   // elements of one job of the host path
 
-template <typename F>
-void parallel_for(uint64_t jobs, F&& body) {   // body(job): jobs are handed out one by one
-  int n = sf::usable_cpus();
-  if (n > MAX_THREADS) n = MAX_THREADS;
-  if ((uint64_t)n > jobs) n = (int)jobs;
-  if (n < 1) n = 1;
-  std::atomic<uint64_t> next{0};
-  auto run = [&]() {
-    for (uint64_t j = next.fetch_add(1); j < jobs; j = next.fetch_add(1)) body(j);
-  };
-  if (n == 1) { run(); return; }
-  std::vector<std::thread> pool;
-  for (int i = 1; i < n; i++) pool.emplace_back(run);
-  run();
-  for (auto& t : pool) t.join();
-}
+using sf::ev::parallel_for;   // at most 16 threads
 
 int check_width(int elem_bytes, const char* who) {
   if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) return sf::fail(SF_ERR_INVALID_ARG, "%s: elements of %d bytes (1, 2 or 4)", who, elem_bytes);
@@ -149,6 +134,20 @@ int check_valid(const int32_t* valid_ids, uint32_t n_valid, uint64_t* mask, uint
   }
   *mask = m;
   *dim = (uint32_t)top + 2u;
+  return SF_OK;
+}
+
+// the 2-D instance task (section 4p): ids 1 .. 999, so that a void value (a valid id) can never be an instance id (1000 and up)
+int check_valid_2d(const int32_t* valid_ids, uint32_t n_valid, ValidSet* vs, const char* who) {
+  if (!valid_ids || n_valid == 0) return sf::fail(SF_ERR_INVALID_ARG, "%s: no valid class ids", who);
+  std::memset(vs, 0, sizeof(*vs));
+  for (uint32_t i = 0; i < n_valid; i++) {
+    const int32_t id = valid_ids[i];
+    if (id < 1 || id > 999) return sf::fail(SF_ERR_INVALID_ARG, "%s: class id %d (1 .. 999)", who, id);
+    if (in_set(vs->bits, (uint32_t)id)) return sf::fail(SF_ERR_INVALID_ARG, "%s: class id %d twice", who, id);
+    vs->bits[id >> 5] |= 1u << (id & 31);
+    vs->top = std::max(vs->top, (uint32_t)id);
+  }
   return SF_OK;
 }
 
@@ -371,6 +370,35 @@ void thresholds(double* th) {
 
 double iou_of(uint32_t inter, uint32_t a, uint32_t b) { return (double)inter / (double)((uint64_t)a + b - inter); }
 
+// the precision-recall curve and its step-wise integral (evaluate_semantic_instance.py:169-217; evalInstanceLevelSemanticLabeling.py:435-488, the same
+// lines): y = (score, true) in any order, hard_fn = the ground truth no prediction matched.  Both accumulators end here.
+double curve_ap(std::vector<std::pair<double, double>>& y, uint64_t hard_fn) {
+  std::sort(y.begin(), y.end(), [](const std::pair<double, double>& a, const std::pair<double, double>& b) { return a.first < b.first; });
+  const size_t n = y.size();
+  std::vector<double> cum(n);
+  double run = 0.0;
+  for (size_t i = 0; i < n; i++) { run += y[i].second; cum[i] = run; }
+  const double num_true = n ? cum[n - 1] : 0.0;   // the reference indexes an empty array here (IndexError); the curve is the artificial point alone: 0
+  std::vector<double> precision, recall;
+  for (size_t i = 0; i < n; i++) {
+    if (i && y[i].first == y[i - 1].first) continue;   // the first index of each distinct score
+    const double before = i ? cum[i - 1] : 0.0;
+    const double tp = num_true - before, fp = (double)n - (double)i - tp, fn = before + (double)hard_fn;
+    precision.push_back(tp / (tp + fp));
+    recall.push_back(tp / (tp + fn));
+  }
+  precision.push_back(1.0);
+  recall.push_back(0.0);
+  // recall_for_conv = [r0, r0 .. r(K-1), 0, 0]; np.convolve(., [-0.5, 0, 0.5], 'valid')[j] = 0.5 a[j] - 0.5 a[j + 2]
+  std::vector<double> a;
+  a.push_back(recall[0]);
+  a.insert(a.end(), recall.begin(), recall.end());
+  a.push_back(0.0);
+  double ap = 0.0;
+  for (size_t j = 0; j < precision.size(); j++) ap += precision[j] * (0.5 * a[j] + -0.5 * a[j + 2]);
+  return ap;
+}
+
 double class_ap(const std::vector<ClassScan>& scans, double th, uint32_t min_region) {
   std::vector<std::pair<double, double>> y;   // (score, true)
   uint64_t hard_fn = 0;
@@ -417,30 +445,7 @@ double class_ap(const std::vector<ClassScan>& scans, double th, uint32_t min_reg
   }
   if (!has_gt) return std::numeric_limits<double>::quiet_NaN();
   if (!has_pred) return 0.0;
-  std::sort(y.begin(), y.end(), [](const std::pair<double, double>& a, const std::pair<double, double>& b) { return a.first < b.first; });
-  const size_t n = y.size();
-  std::vector<double> cum(n);
-  double run = 0.0;
-  for (size_t i = 0; i < n; i++) { run += y[i].second; cum[i] = run; }
-  const double num_true = n ? cum[n - 1] : 0.0;   // the reference indexes an empty array here (IndexError); the curve is the artificial point alone: 0
-  std::vector<double> precision, recall;
-  for (size_t i = 0; i < n; i++) {
-    if (i && y[i].first == y[i - 1].first) continue;   // the first index of each distinct score
-    const double before = i ? cum[i - 1] : 0.0;
-    const double tp = num_true - before, fp = (double)n - (double)i - tp, fn = before + (double)hard_fn;
-    precision.push_back(tp / (tp + fp));
-    recall.push_back(tp / (tp + fn));
-  }
-  precision.push_back(1.0);
-  recall.push_back(0.0);
-  // recall_for_conv = [r0, r0 .. r(K-1), 0, 0]; np.convolve(., [-0.5, 0, 0.5], 'valid')[j] = 0.5 a[j] - 0.5 a[j + 2]
-  std::vector<double> a;
-  a.push_back(recall[0]);
-  a.insert(a.end(), recall.begin(), recall.end());
-  a.push_back(0.0);
-  double ap = 0.0;
-  for (size_t j = 0; j < precision.size(); j++) ap += precision[j] * (0.5 * a[j] + -0.5 * a[j + 2]);
-  return ap;
+  return curve_ap(y, hard_fn);
 }
 
 double nanmean(const std::vector<double>& v) {
@@ -485,6 +490,167 @@ SF_API int sf_eval_ap_finish(const sf_eval_ap* acc, double* ap, double* class_av
     averages[0] = nanmean(all);
     averages[1] = nanmean(all50);
     averages[2] = nanmean(all25);
+  }
+  return SF_OK;
+}
+
+// ---- the AP over images (evaluateMatches and computeAverages, evalInstanceLevelSemanticLabeling.py:301-515) ----
+
+struct sf_eval_ap2d {
+  std::vector<int32_t> valid_ids;
+  std::vector<int> class_of;   // [1000]: the position of a class id among valid_ids, or -1
+  uint32_t min_region = 100;
+  std::vector<std::vector<ClassScan>> images;   // [class][image]
+};
+
+SF_API int sf_eval_ap2d_create(const int32_t* valid_ids, uint32_t n_valid, uint32_t min_region_size, sf_eval_ap2d** out) {
+  if (!out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  *out = nullptr;
+  sf::ev::ValidSet vs;
+  if (int rc = sf::ev::check_valid_2d(valid_ids, n_valid, &vs, "sf_eval_ap2d_create")) return rc;
+  sf_eval_ap2d* a = new sf_eval_ap2d;
+  a->valid_ids.assign(valid_ids, valid_ids + n_valid);
+  a->class_of.assign(1000, -1);
+  for (uint32_t i = 0; i < n_valid; i++) a->class_of[valid_ids[i]] = (int)i;
+  a->min_region = min_region_size;
+  a->images.resize(n_valid);
+  *out = a;
+  return SF_OK;
+}
+
+SF_API void sf_eval_ap2d_destroy(sf_eval_ap2d* acc) { delete acc; }
+
+SF_API int sf_eval_ap2d_add_image(sf_eval_ap2d* acc, uint32_t G, const int32_t* instance_id, const uint32_t* instance_pixels, uint32_t P,
+                                  const int32_t* pred_label, const double* pred_conf, const uint32_t* table, uint32_t capacity) {
+  if (!acc || (G && (!instance_id || !instance_pixels)) || (P && (!pred_label || !pred_conf || !table))) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  if (G > capacity) return sf::fail(SF_ERR_INVALID_ARG, "sf_eval_ap2d_add_image: %u instances in rows of capacity %u", G, capacity);
+  const size_t bins = (size_t)capacity + 2;
+  auto class_of = [&](int64_t label) -> int { return label < 1 || label > 999 ? -1 : acc->class_of[(size_t)label]; };
+  for (uint32_t g = 0; g < G; g++) {
+    if (instance_id[g] <= 0 || class_of(instance_id[g] / 1000) < 0)
+      return sf::fail(SF_ERR_INVALID_ARG, "sf_eval_ap2d_add_image: instance %u has id %d, which names no valid class", g, instance_id[g]);
+    if (g && instance_id[g] <= instance_id[g - 1]) return sf::fail(SF_ERR_INVALID_ARG, "sf_eval_ap2d_add_image: the instance ids do not ascend at %u", g);
+  }
+  for (uint32_t p = 0; p < P; p++) {
+    if (std::isnan(pred_conf[p])) return sf::fail(SF_ERR_INVALID_ARG, "sf_eval_ap2d_add_image: prediction %u has no confidence (NaN)", p);
+    const uint32_t* row = table + p * bins;
+    uint64_t sum = row[capacity];
+    for (uint32_t g = 0; g < G; g++) {
+      sum += row[g];
+      if (row[g] > instance_pixels[g]) return sf::fail(SF_ERR_INVALID_ARG, "sf_eval_ap2d_add_image: prediction %u shares %u pixels with an instance of %u", p, row[g], instance_pixels[g]);
+    }
+    // pixels that are neither of an instance nor void count in the total alone
+    if (sum > row[capacity + 1]) return sf::fail(SF_ERR_INVALID_ARG, "sf_eval_ap2d_add_image: the counts of prediction %u add up to %llu, above its %u pixels", p, (unsigned long long)sum, row[capacity + 1]);
+  }
+  std::vector<ClassScan> add(acc->valid_ids.size());
+  std::vector<uint32_t> index(G);   // of an instance within its class
+  for (uint32_t g = 0; g < G; g++) {
+    ClassScan& cs = add[class_of(instance_id[g] / 1000)];
+    index[g] = (uint32_t)cs.gts.size();
+    cs.gts.push_back(Gt{instance_id[g], instance_pixels[g], {}});
+  }
+  for (uint32_t p = 0; p < P; p++) {
+    const int c = class_of(pred_label[p]);
+    const uint32_t* row = table + p * bins;
+    if (c < 0 || row[capacity + 1] == 0) continue;   // dropped: no valid class (:239), or empty (:255); no minimum size
+    ClassScan& cs = add[c];
+    Pred pr{pred_conf[p], row[capacity + 1], row[capacity], {}};
+    const uint32_t pi = (uint32_t)cs.preds.size();
+    for (uint32_t g = 0; g < G; g++)
+      if (row[g] > 0 && class_of(instance_id[g] / 1000) == c) {
+        pr.gts.push_back(Match{index[g], row[g]});
+        cs.gts[index[g]].preds.push_back(Match{pi, row[g]});
+      }
+    cs.preds.push_back(std::move(pr));
+  }
+  for (size_t c = 0; c < add.size(); c++) acc->images[c].push_back(std::move(add[c]));
+  return SF_OK;
+}
+
+namespace {
+
+// numpy's arange(0.5, 1., 0.05): ten values start + i * ((start + step) - start)
+void thresholds_2d(double* th) {
+  volatile double start = 0.5, step = 0.05;
+  volatile double next = start + step;
+  const double delta = next - start;
+  for (int i = 0; i < SF_EVAL_AP2D_OVERLAPS; i++) th[i] = start + (double)i * delta;
+}
+
+// evalInstanceLevelSemanticLabeling.py:349-432 for one class and threshold: no visited flag, no minimum prediction size; small ground truth is ignored
+double class_ap_2d(const std::vector<ClassScan>& images, double th, uint32_t min_region) {
+  std::vector<std::pair<double, double>> y;   // (score, true)
+  uint64_t hard_fn = 0;
+  bool has_gt = false, has_pred = false;
+  for (const ClassScan& cs : images) {
+    if (!cs.preds.empty()) has_pred = true;   // :365, the predictions that are ignored below included
+    for (const Gt& gt : cs.gts) {
+      if (gt.verts < min_region) continue;    // :361; instID >= 1000 always holds, the distance fields have no effect
+      has_gt = true;
+      bool matched = false;
+      double score = 0.0;
+      for (const Match& m : gt.preds) {
+        const Pred& pr = cs.preds[m.other];
+        if (!(iou_of(m.intersection, gt.verts, pr.verts) > th)) continue;
+        if (matched) {   // :383-390: the lower of the two scores is a false positive, the instance keeps the higher
+          const double hi = std::max(score, pr.conf), lo = std::min(score, pr.conf);
+          score = hi;
+          y.emplace_back(lo, 0.0);
+        } else {
+          matched = true;
+          score = pr.conf;
+        }
+      }
+      if (matched) y.emplace_back(score, 1.0);
+      else hard_fn++;
+    }
+    for (const Pred& pr : cs.preds) {   // :405-428
+      bool found = false;
+      for (const Match& m : pr.gts)
+        if (iou_of(m.intersection, cs.gts[m.other].verts, pr.verts) > th) { found = true; break; }
+      if (found) continue;
+      uint64_t ignore = pr.void_intersection;
+      for (const Match& m : pr.gts)
+        if (cs.gts[m.other].verts < min_region) ignore += m.intersection;
+      if ((double)ignore / (double)pr.verts <= th) y.emplace_back(pr.conf, 0.0);
+    }
+  }
+  if (!has_gt) return std::numeric_limits<double>::quiet_NaN();
+  if (!has_pred) return 0.0;
+  return curve_ap(y, hard_fn);
+}
+
+}  // namespace
+
+SF_API int sf_eval_ap2d_thresholds(double* th) {
+  if (!th) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  thresholds_2d(th);
+  return SF_OK;
+}
+
+SF_API int sf_eval_ap2d_finish(const sf_eval_ap2d* acc, double* ap, double* class_averages, double* averages) {
+  if (!acc || !ap) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
+  double th[SF_EVAL_AP2D_OVERLAPS];
+  thresholds_2d(th);
+  const size_t C = acc->valid_ids.size();
+  parallel_for(C * SF_EVAL_AP2D_OVERLAPS, [&](uint64_t j) {
+    const size_t c = j / SF_EVAL_AP2D_OVERLAPS, o = j % SF_EVAL_AP2D_OVERLAPS;
+    ap[j] = class_ap_2d(acc->images[c], th[o], acc->min_region);
+  });
+  std::vector<double> all, all50;
+  for (size_t c = 0; c < C; c++) {
+    const double* row = ap + c * SF_EVAL_AP2D_OVERLAPS;
+    double s = 0.0;
+    for (int o = 0; o < SF_EVAL_AP2D_OVERLAPS; o++) { s += row[o]; all.push_back(row[o]); }
+    all50.push_back(row[0]);
+    if (class_averages) {
+      class_averages[2 * c] = s / (double)SF_EVAL_AP2D_OVERLAPS;   // :512
+      class_averages[2 * c + 1] = row[0];                          // :513
+    }
+  }
+  if (averages) {
+    averages[0] = nanmean(all);     // :506
+    averages[1] = nanmean(all50);   // :507
   }
   return SF_OK;
 }

@@ -2,7 +2,10 @@
 // path (evaluation.cpp) and the kernels (evaluation.hip): which cell of the confusion matrix an element counts in, the source pixel of the nearest-neighbour
 // resize, and the bin of a vertex in a prediction's overlap histogram.  Everything here is integer arithmetic, so every schedule gives the same counts.
 #pragma once
+#include <atomic>
 #include <cstdint>
+#include <thread>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define SF_EV_HD __host__ __device__ inline
@@ -11,7 +14,27 @@
 #endif
 
 namespace sf {
+int usable_cpus();   // common.h
+
 namespace ev {
+
+// the host paths' loop: body(job) on at most 16 threads, jobs handed out one by one
+template <typename F>
+void parallel_for(uint64_t jobs, F&& body) {
+  int n = sf::usable_cpus();
+  if (n > 16) n = 16;
+  if ((uint64_t)n > jobs) n = (int)jobs;
+  if (n < 1) n = 1;
+  std::atomic<uint64_t> next{0};
+  auto run = [&]() {
+    for (uint64_t j = next.fetch_add(1); j < jobs; j = next.fetch_add(1)) body(j);
+  };
+  if (n == 1) { run(); return; }
+  std::vector<std::thread> pool;
+  for (int i = 1; i < n; i++) pool.emplace_back(run);
+  run();
+  for (auto& t : pool) t.join();
+}
 
 constexpr uint32_t MAX_DIM = 63;             // the valid-class set is one 64-bit mask: membership is a shift; four LDS copies of 63 x 63 + 1 counters stay under 64 KiB
 constexpr uint32_t KEY_SKIP = 0xFFFFFFFFu;   // the element is not counted
@@ -59,6 +82,35 @@ int confusion_on_device(const void* gt, const void* pred, int elem_bytes, uint64
 int confusion_images_on_device(const void* gt, const void* pred, int elem_bytes, uint32_t batch, uint32_t gw, uint32_t gh, uint32_t pw, uint32_t ph, uint32_t dw,
                                uint32_t dh, uint32_t dim, int device, uint64_t* confusion, uint64_t* out_of_range);
 int overlaps_on_device(const uint32_t* slot, uint64_t n, uint32_t G, const uint8_t* masks, uint32_t P, uint64_t stride, int device, uint32_t* table);
+
+// ---- 2-D instances (include/scanfuse.h "Benchmark scores, 2-D instances") ----
+
+// The valid classes of the 2-D instance task, ids 1 .. 999, as a bitmap: a kernel takes it by value and copies it into LDS.
+struct ValidSet {
+  uint32_t bits[32];
+  uint32_t top;   // the largest valid id: the per-image counters cover ids below (top + 1) * 1000
+};
+
+SF_EV_HD bool in_set(const uint32_t* bits, uint32_t v) { return v < 1024u && ((bits[v >> 5] >> (v & 31u)) & 1u) != 0u; }
+// a pixel is void where its raw value is a valid class id (evalInstanceLevelSemanticLabeling.py:226-230), and of an instance where value / 1000 is
+// one (instances2dict.py:40-43); valid ids are below 1000, so no value is both
+SF_EV_HD bool is_void_2d(const uint32_t* bits, uint32_t v) { return in_set(bits, v); }
+SF_EV_HD bool is_instance_2d(const uint32_t* bits, uint32_t v) { return in_set(bits, v / 1000u); }
+inline uint32_t id_range(const ValidSet& vs) { return (vs.top + 1u) * 1000u; }
+
+constexpr uint32_t MAX_BATCH_2D = 65535, MAX_CAPACITY_2D = 1u << 20;
+
+int check_valid_2d(const int32_t* valid_ids, uint32_t n_valid, ValidSet* vs, const char* who);
+int check_image_plan(const void* gt, int elem_bytes, uint32_t batch, uint32_t width, uint32_t height, uint32_t capacity, const uint32_t* count,
+                     const int32_t* instance_id, const uint32_t* instance_pixels, const char* who);
+int check_overlaps_images(const void* gt, int elem_bytes, uint32_t batch, uint32_t width, uint32_t height, uint32_t capacity, const uint32_t* count,
+                          const int32_t* instance_id, const uint8_t* masks, uint32_t P, uint64_t stride, const uint32_t* mask_image, const uint32_t* table,
+                          const char* who);
+int image_plan_on_device(const void* gt, int elem_bytes, uint32_t batch, uint32_t n, const ValidSet& vs, uint32_t capacity, int device, uint32_t* count,
+                         int32_t* instance_id, uint32_t* instance_pixels);
+int overlaps_images_on_device(const void* gt, int elem_bytes, uint32_t batch, uint32_t n, const ValidSet& vs, uint32_t capacity, const uint32_t* count,
+                              const int32_t* instance_id, const uint8_t* masks, uint32_t P, uint64_t stride, const uint32_t* mask_image, int device,
+                              uint32_t* table);
 
 }  // namespace ev
 }  // namespace sf

@@ -1,14 +1,15 @@
 // tool_evaluate.cpp -> bin/evaluate: the benchmark's scores from the benchmark's files, a drop-in for
-// BenchmarkScripts/3d_evaluation/evaluate_semantic_label.py, evaluate_semantic_instance.py and 2d_evaluation/evalPixelLevelSemanticLabeling.py
-// (DESIGN.md section 4o).
+// BenchmarkScripts/3d_evaluation/evaluate_semantic_label.py, evaluate_semantic_instance.py, 2d_evaluation/evalPixelLevelSemanticLabeling.py
+//  and 2d_evaluation/evalInstanceLevelSemanticLabeling.py (section 4p).
 //
 //   bin/evaluate label3d    --pred_path D --gt_path D [--output_file F] [--host | --device=N]
 //   bin/evaluate instance3d --pred_path D --gt_path D [--output_file F] [--min-region=N] [--host | --device=N]
 //   bin/evaluate label2d    --pred_path D --gt_path D [--output_file F] [--host | --device=N]
+//   bin/evaluate instance2d --pred_path D --gt_path D [--output_file F] [--min-region=N] [--host | --device=N]
 //   bin/evaluate export     --scan_path D --label_map_file F --type label|instance|instance-gt --output_file F
 //
 // The tables go to stdout in the scripts' layout, the result file to --output_file (default: the script's name inside pred_path).  The host path is the
-// default (DESIGN.md section 4o gives the measurement behind that); --device=N runs the counting kernels on that GPU and writes the same bytes.
+// default (DESIGN.md sections 4o and 4p say why); --device=N runs the counting kernels on that GPU and writes the same bytes.
 // Exit status 0, or 2 with one line on stderr.
 #include <cstdio>
 #include <cstdlib>
@@ -18,7 +19,7 @@
 #include "scanfuse.h"
 
 static int usage() {
-  std::fprintf(stderr, "usage: evaluate label3d|instance3d|label2d --pred_path D --gt_path D [--output_file F] [--min-region=N] [--host | --device=N]\n"
+  std::fprintf(stderr, "usage: evaluate label3d|instance3d|label2d|instance2d --pred_path D --gt_path D [--output_file F] [--min-region=N] [--host | --device=N]\n"
                        "       evaluate export --scan_path D --label_map_file F --type label|instance|instance-gt --output_file F\n");
   return 2;
 }
@@ -59,6 +60,7 @@ int main(int argc, char** argv) {
   if (mode == "label3d") rc = sf_eval_label_dir(pred.c_str(), gt.c_str(), out.c_str(), device, &report);
   else if (mode == "instance3d") rc = sf_eval_instance_dir(pred.c_str(), gt.c_str(), out.c_str(), (uint32_t)min_region, device, &report);
   else if (mode == "label2d") rc = sf_eval_pixel_dir(pred.c_str(), gt.c_str(), out.c_str(), device, &report);
+  else if (mode == "instance2d") rc = sf_eval_instance2d_dir(pred.c_str(), gt.c_str(), out.c_str(), (uint32_t)min_region, device, &report);
   else return usage();
   if (rc != SF_OK) {
     std::fprintf(stderr, "ERROR: %s\n", sf_last_error());

@@ -1,7 +1,9 @@
 """The benchmark's scores from predictions: the label confusion matrix and IoU (3-D and 2-D), and the instance AP, over the C ABI (include/scanfuse.h
 "Benchmark scores"; scannet_amd/csrc/evaluation.cpp, evaluation.hip; the rules are DESIGN.md section 4o).  What they replace in the reference tree:
 BenchmarkScripts/3d_evaluation/evaluate_semantic_label.py, evaluate_semantic_instance.py with util_3d.py, and
-2d_evaluation/evalPixelLevelSemanticLabeling.py, and 3d_helpers/export_train_mesh_for_evaluation.py (export_ground_truth).
+2d_evaluation/evalPixelLevelSemanticLabeling.py, and 3d_helpers/export_train_mesh_for_evaluation.py (export_ground_truth); and the 2-D instance AP
+(scannet_amd/csrc/instance2d.cpp, instance2d_files.cpp): 2d_evaluation/evalInstanceLevelSemanticLabeling.py with
+instances2dict.py and instance.py.
 
 The array functions take numpy arrays or torch tensors on `cuda:N`.  numpy: `device=None` is the host path (at most 16 threads), an int copies to that
 GPU and runs the kernels; the counts are the same.  Tensors on a GPU go to the `_device` entry points on torch's current stream: nothing is copied to
@@ -45,6 +47,19 @@ def _lib():
     L.sf_eval_label_dir.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
     L.sf_eval_instance_dir.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, i32, C.POINTER(vp)]
     L.sf_eval_pixel_dir.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+    L.sf_eval_image_plan.argtypes = [vp, i32, u32, u32, u32, vp, u32, u32, i32, vp, vp, vp]
+    L.sf_eval_image_plan_scratch.argtypes = [u32, vp, u32]
+    L.sf_eval_image_plan_scratch.restype = u64
+    L.sf_eval_image_plan_device.argtypes = [vp, i32, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp]
+    L.sf_eval_overlaps_images.argtypes = [vp, i32, u32, u32, u32, vp, u32, u32, vp, vp, vp, u32, u64, vp, i32, vp]
+    L.sf_eval_overlaps_images_device.argtypes = [vp, i32, u32, u32, u32, vp, u32, u32, vp, vp, vp, u32, u64, vp, vp, vp]
+    L.sf_eval_ap2d_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+    L.sf_eval_ap2d_add_image.argtypes = [vp, u32, vp, vp, u32, vp, vp, vp, u32]
+    L.sf_eval_ap2d_finish.argtypes = [vp, vp, vp, vp]
+    L.sf_eval_ap2d_destroy.argtypes = [vp]
+    L.sf_eval_ap2d_destroy.restype = None
+    L.sf_eval_ap2d_thresholds.argtypes = [vp]
+    L.sf_eval_instance2d_dir.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u32, i32, C.POINTER(vp)]
     L.sf_eval_export_ids.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, u64, vp, vp, C.POINTER(u64)]
     L.sf_eval_export_scan.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
     L.sf_free.argtypes = [vp]
@@ -327,6 +342,208 @@ class InstanceAP:
         return {"ap": ap, "classes": classes, "all_ap": avg[0], "all_ap_50%": avg[1], "all_ap_25%": avg[2]}
 
 
+# ---- 2-D instances: the image-level instance AP ----
+
+AP2D_OVERLAPS = 10
+
+
+def _images(gt):
+    """-> (images [B, H, W] contiguous, unsigned pixels of 1, 2 or 4 bytes; width in bytes; tensors?)"""
+    if _is_tensor(gt):
+        if not gt.is_cuda:
+            raise ValueError("a tensor on a GPU (or a numpy array)")
+        if gt.ndim == 2:
+            gt = gt[None]
+        width = min(4, gt.element_size())
+        gt = _torch_elements(gt, width)
+        tensors = True
+    else:
+        gt = np.asarray(gt)
+        if gt.ndim == 2:
+            gt = gt[None]
+        width = min(4, gt.dtype.itemsize)
+        gt = _np_elements(gt, width)
+        tensors = False
+    if gt.ndim != 3:
+        raise ValueError("id images [B, H, W], not %s" % (tuple(gt.shape),))
+    return gt, width, tensors
+
+
+def image_plan(gt, valid_ids=INSTANCE_IDS, capacity=None, device=None):
+    """sf_eval_image_plan(_device) -> (count uint32 [B], instance_id int32 [B, capacity] ascending, instance_pixels uint32 [B, capacity]); torch: int32
+    tensors on the device.  gt [B, H, W] (or [H, W]): id images, a pixel is label * 1000 + k.  capacity None (numpy): the largest count of the batch;
+    tensors need a capacity (the counts stay on the device); count[b] > capacity there means image b has more instances than were written."""
+    L = _lib()
+    v = _valid(valid_ids)
+    gt, width, tensors = _images(gt)
+    B, H, W = (int(x) for x in gt.shape)
+    if tensors:
+        import torch
+        if capacity is None:
+            raise ValueError("tensors need a capacity: the counts stay on the device")
+        capacity = int(capacity)
+        scratch = torch.empty(max(1, int(L.sf_eval_image_plan_scratch(B, _ptr(v), len(v))) // 4), dtype=torch.int32, device=gt.device)
+        count = torch.zeros(B, dtype=torch.int32, device=gt.device)
+        iid = torch.zeros((B, capacity), dtype=torch.int32, device=gt.device)
+        px = torch.zeros((B, capacity), dtype=torch.int32, device=gt.device)
+        check(L.sf_eval_image_plan_device(_ptr(gt), width, B, W, H, _ptr(v), len(v), capacity, _stream(gt), _ptr(scratch), _ptr(count), _ptr(iid), _ptr(px)))
+        scratch.record_stream(torch.cuda.current_stream(gt.device))
+        return count, iid, px
+    dev = -1 if device is None else int(device)
+    count = np.zeros(B, np.uint32)
+    if capacity is None:
+        check(L.sf_eval_image_plan(_ptr(gt), width, B, W, H, _ptr(v), len(v), 0, dev, _ptr(count), None, None))
+        capacity = int(count.max()) if B else 0
+    capacity = int(capacity)
+    iid, px = np.zeros((B, capacity), np.int32), np.zeros((B, capacity), np.uint32)
+    check(L.sf_eval_image_plan(_ptr(gt), width, B, W, H, _ptr(v), len(v), capacity, dev, _ptr(count), _ptr(iid), _ptr(px)))
+    return count, iid, px
+
+
+def overlaps_images(gt, count, instance_id, masks, mask_image, valid_ids=INSTANCE_IDS, device=None):
+    """sf_eval_overlaps_images(_device) -> table uint32 [P, capacity + 2] (torch: int32 on the device): per mask the covered pixels in each instance
+    of its image, in void at [capacity], in all at [capacity + 1].  gt [B, H, W]; count [B] and instance_id [B, capacity]: image_plan's; masks
+    [P, H * W] (or [P, H, W]) of bytes or bools, rows may be further apart than H * W; mask_image [P]: the image of each mask."""
+    L = _lib()
+    v = _valid(valid_ids)
+    gt, width, tensors = _images(gt)
+    B, H, W = (int(x) for x in gt.shape)
+    n = H * W
+    if tensors:
+        import torch
+        same = all(_is_tensor(t) and t.is_cuda and t.device == gt.device for t in (count, instance_id, masks, mask_image))
+        if not same:
+            raise ValueError("every array must be a tensor on the GPU of the images (or every one a numpy array)")
+        if masks.dtype == torch.bool:
+            masks = masks.view(torch.uint8)
+        if masks.element_size() != 1:
+            raise TypeError("masks of bytes")
+        if masks.ndim == 3:
+            masks = masks.reshape(masks.shape[0], -1)
+        if masks.ndim != 2 or masks.shape[1] != n:
+            raise ValueError("masks %s over images of %d pixels" % (tuple(masks.shape), n))
+        P = int(masks.shape[0])
+        if P > 1 and (masks.stride(1) != 1 or masks.stride(0) < n):
+            masks = masks.contiguous()
+        elif P == 1 and n > 1 and masks.stride(1) != 1:
+            masks = masks.contiguous()
+        stride = int(masks.stride(0)) if P > 1 else n
+        for t in (count, instance_id, mask_image):
+            if t.element_size() != 4 or t.dtype.is_floating_point:
+                raise TypeError("counts, ids and mask_image of 32-bit integers")
+        count, instance_id, mask_image = count.contiguous(), instance_id.contiguous(), mask_image.contiguous()
+        capacity = int(instance_id.shape[1])
+        if tuple(instance_id.shape) != (B, capacity) or count.numel() != B or mask_image.numel() != P:
+            raise ValueError("a plan of %s / %s for %d images, %d image indices for %d masks" % (tuple(count.shape), tuple(instance_id.shape), B, mask_image.numel(), P))
+        table = torch.zeros((P, capacity + 2), dtype=torch.int32, device=gt.device)
+        check(L.sf_eval_overlaps_images_device(_ptr(gt), width, B, W, H, _ptr(v), len(v), capacity, _ptr(count), _ptr(instance_id), _ptr(masks), P, stride,
+                                               _ptr(mask_image), _stream(gt), _ptr(table)))
+        return table
+    masks = np.asarray(masks)
+    if masks.dtype == np.bool_:
+        masks = masks.view(np.uint8)
+    if masks.dtype.itemsize != 1:
+        raise TypeError("masks of bytes")
+    if masks.ndim == 3:
+        masks = masks.reshape(masks.shape[0], -1)
+    if masks.ndim != 2 or masks.shape[1] != n:
+        raise ValueError("masks %s over images of %d pixels" % (masks.shape, n))
+    P = masks.shape[0]
+    if P > 1 and (masks.strides[1] != 1 or masks.strides[0] < n):
+        masks = np.ascontiguousarray(masks)
+    elif P == 1:
+        masks = np.ascontiguousarray(masks)
+    stride = int(masks.strides[0]) if P > 1 else n
+    count = np.ascontiguousarray(count, np.uint32).reshape(-1)
+    instance_id = np.ascontiguousarray(instance_id, np.int32)
+    mask_image = np.ascontiguousarray(mask_image, np.uint32).reshape(-1)
+    if instance_id.ndim != 2 or instance_id.shape[0] != B or len(count) != B or len(mask_image) != P:
+        raise ValueError("a plan of %s / %s for %d images, %d image indices for %d masks" % (count.shape, instance_id.shape, B, len(mask_image), P))
+    capacity = int(instance_id.shape[1])
+    table = np.zeros((P, capacity + 2), np.uint32)
+    check(L.sf_eval_overlaps_images(_ptr(gt), width, B, W, H, _ptr(v), len(v), capacity, _ptr(count), _ptr(instance_id), _ptr(masks), P, stride,
+                                    _ptr(mask_image), -1 if device is None else int(device), _ptr(table)))
+    return table
+
+
+def ap2d_thresholds():
+    """The ten overlap thresholds of the 2-D instance AP, bit for bit numpy's arange(0.5, 1., 0.05) (sf_eval_ap2d_thresholds)."""
+    th = np.zeros(AP2D_OVERLAPS, np.float64)
+    check(_lib().sf_eval_ap2d_thresholds(_ptr(th)))
+    return th
+
+
+class InstanceAP2D:
+    """The AP over images (sf_eval_ap2d_*).  add(): a batch of images from their ids and masks; add_image(): one image from its plan and its rows of
+    an overlap table; finish() -> {"ap": [n_valid, 10], "classes": {name: {"ap", "ap50%"}}, "all_ap", "all_ap_50%"}.  The result depends on neither
+    the order of the images nor the order of an image's predictions."""
+
+    def __init__(self, valid_ids=INSTANCE_IDS, names=INSTANCE_NAMES, min_region_size=100):
+        self._L = _lib()
+        self._h = C.c_void_p()
+        self.valid_ids = _valid(valid_ids)
+        self.names = tuple(names)
+        if len(self.names) != len(self.valid_ids):
+            raise ValueError("one name per valid class id")
+        check(self._L.sf_eval_ap2d_create(_ptr(self.valid_ids), len(self.valid_ids), int(min_region_size), C.byref(self._h)))
+
+    def close(self):
+        if self._h.value:
+            self._L.sf_eval_ap2d_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add_image(self, instance_id, instance_pixels, pred_label, pred_conf, table):
+        """instance_id, instance_pixels [G]; table [P, capacity + 2] with capacity >= G."""
+        if _is_tensor(table):
+            table = table.cpu().numpy()
+        iid = np.ascontiguousarray(instance_id, np.int32).reshape(-1)
+        px = np.ascontiguousarray(instance_pixels).astype(np.uint32, copy=False).reshape(-1)
+        label = np.ascontiguousarray(pred_label, np.int32).reshape(-1)
+        conf = np.ascontiguousarray(pred_conf, np.float64).reshape(-1)
+        table = np.ascontiguousarray(table).view(np.uint32) if np.asarray(table).dtype.itemsize == 4 else np.ascontiguousarray(table, np.uint32)
+        G, P = len(iid), len(label)
+        if len(px) != G or len(conf) != P or table.ndim != 2 or table.shape[0] != P or table.shape[1] < G + 2:
+            raise ValueError("a table of %s for %d predictions and %d instances" % (table.shape, P, G))
+        check(self._L.sf_eval_ap2d_add_image(self._h, G, _ptr(iid), _ptr(px), P, _ptr(label), _ptr(conf), _ptr(table), table.shape[1] - 2))
+
+    def add(self, gt, masks, mask_image, pred_label, pred_conf, device=None, capacity=None):
+        """gt [B, H, W]; masks [P, H * W]; mask_image, pred_label, pred_conf [P].  numpy arrays (device: None = host), or tensors on a GPU with a
+        capacity: the plan and the table are made there, and the counts and the table are read back once."""
+        if _is_tensor(gt):
+            import torch
+            count, iid, px = image_plan(gt, self.valid_ids, capacity)
+            mi = mask_image if _is_tensor(mask_image) else torch.from_numpy(np.ascontiguousarray(mask_image, np.int32)).to(gt.device)
+            table = overlaps_images(gt, count, iid, masks, mi, self.valid_ids).cpu().numpy().view(np.uint32)
+            count, iid, px = count.cpu().numpy().view(np.uint32), iid.cpu().numpy(), px.cpu().numpy().view(np.uint32)
+            if len(count) and int(count.max()) > int(capacity):
+                raise ValueError("an image holds %d instances, capacity %d" % (int(count.max()), int(capacity)))
+            mask_image = mi.cpu().numpy()
+        else:
+            count, iid, px = image_plan(gt, self.valid_ids, capacity, device)
+            table = overlaps_images(gt, count, iid, masks, mask_image, self.valid_ids, device)
+        mask_image = np.asarray(mask_image).reshape(-1)
+        label, conf = np.asarray(pred_label).reshape(-1), np.asarray(pred_conf, np.float64).reshape(-1)
+        for b in range(len(count)):
+            mine = np.flatnonzero(mask_image == b)
+            G = int(count[b])
+            self.add_image(iid[b, :G], px[b, :G], label[mine], conf[mine], table[mine])
+
+    def finish(self):
+        n = len(self.valid_ids)
+        ap, cls, avg = np.zeros((n, AP2D_OVERLAPS), np.float64), np.zeros((n, 2), np.float64), np.zeros(2, np.float64)
+        check(self._L.sf_eval_ap2d_finish(self._h, _ptr(ap), _ptr(cls), _ptr(avg)))
+        classes = {name: {"ap": cls[i, 0], "ap50%": cls[i, 1]} for i, name in enumerate(self.names)}
+        return {"ap": ap, "classes": classes, "all_ap": avg[0], "all_ap_50%": avg[1]}
+
+
 def _dir_call(fn, pred_path, gt_path, output_file, device, *extra):
     L = _lib()
     text = C.c_void_p()
@@ -352,6 +569,12 @@ def evaluate_instance_dir(pred_path, gt_path, output_file=None, min_region_size=
 def evaluate_pixel_dir(pred_path, gt_path, output_file=None, device=None):
     """sf_eval_pixel_dir: evalPixelLevelSemanticLabeling.py on its PNG files (default result file pred_path/semantic_label.txt)."""
     return _dir_call("sf_eval_pixel_dir", pred_path, gt_path, output_file, device)
+
+
+def evaluate_instance2d_dir(pred_path, gt_path, output_file=None, min_region_size=100, device=None):
+    """sf_eval_instance2d_dir: evalInstanceLevelSemanticLabeling.py on its files -> the text of its table; the result file (default
+    pred_path/semantic_instance.txt) is written.  device=None (the default) is the host path: DESIGN.md section 4p."""
+    return _dir_call("sf_eval_instance2d_dir", pred_path, gt_path, output_file, device, int(min_region_size))
 
 
 def export_ids(segs_json, aggregation_json, label_map_tsv):
