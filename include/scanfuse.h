@@ -51,7 +51,8 @@ typedef struct sf_params {
   uint32_t hash_num_buckets;           /* s_hashNumBuckets                  (:56)                 */
   uint32_t hash_bucket_size;           /* HASH_BUCKET_SIZE (pound-defined upstream, :55) = 10     */
   uint32_t num_sdf_blocks;             /* s_hashNumSDFBlocks                (:57)                 */
-  uint32_t mc_max_triangles;           /* s_marchingCubesMaxNumTriangles (:106); 0 = unlimited    */
+  uint32_t mc_max_triangles;           /* s_marchingCubesMaxNumTriangles (:106): parsed and kept, NOT applied -- upstream's 5 000 000 is a buffer size
+                                          that real scans (7.85 M faces) exceed; sf_fuser_extract_mesh sizes its buffers from the count pass */
   int32_t gc_enabled;                  /* s_garbageCollectionEnabled        (:83)                 */
   /* Colour frames at their own resolution (real ScanNet scans: 1296x968 colour, 640x480 depth, sensorData.h:1269-1272).
    * color_width == 0: rgb buffers are depth_width x depth_height.  Otherwise rgb buffers are color_width x color_height
@@ -248,7 +249,10 @@ int sf_fuse_run_prepare(const struct sf_sens* s, const sf_params* p, int device)
 
 /* Iso-surface extraction (marching cubes over all live blocks, exact weld): the `<id>_vh.ply` product of the
  * improve stage (Server/scan_processor.py:141, scan_stages.json:33-42).  Vertices are ordered by grid-edge key,
- * triangles by cube; the result is deterministic.  Free with sf_mesh_free; write with sf_mesh_write_ply. */
+ * triangles by cube; the result is deterministic.  Free with sf_mesh_free; write with sf_mesh_write_ply.
+ * The number of triangles is bounded by the 32-bit indices alone (sf_params.mc_max_triangles is not applied).  SF_ERR_CAPACITY, with a message that names
+ * the block, when a block that takes part lies outside block coordinates -65536 .. 65535 on an axis: the grid-edge key of a vertex holds 20 bits per
+ * voxel coordinate. */
 struct sf_mesh;
 int sf_fuser_extract_mesh(sf_fuser* f, struct sf_mesh** out);
 

@@ -58,21 +58,48 @@ static int cmp_tri(const void* a, const void* b) {
   return 0; /* qsort is not stable: the emitter below appends a per-cube ordinal into the low bits of `cube` */
 }
 
-static const mc_voxel* fetch(const or_volume* v, int32_t gx, int32_t gy, int32_t gz) {
-  const mc_voxel* blk = (const mc_voxel*)or_find_block(v, gx >> 3, gy >> 3, gz >> 3);
+/* Where the voxels come from: a fused or_volume (or_mc_extract) or a plain list of blocks with an ownership mask (or_mc_extract_blocks). */
+typedef struct {
+  const or_volume* v;
+  const int32_t* coords; const mc_voxel* vox; const uint8_t* owned; const int64_t* order; int64_t n;   /* order: blocks sorted by (x, y, z) */
+} mc_source;
+
+static int cmp_coords(const int32_t* a, const int32_t* b) {
+  for (int q = 0; q < 3; q++) if (a[q] != b[q]) return a[q] < b[q] ? -1 : 1;
+  return 0;
+}
+static const mc_voxel* find_block(const mc_source* src, int32_t bx, int32_t by, int32_t bz) {
+  if (src->v) return (const mc_voxel*)or_find_block(src->v, bx, by, bz);
+  const int32_t want[3] = {bx, by, bz};
+  int64_t lo = 0, hi = src->n - 1;
+  while (lo <= hi) {
+    const int64_t mid = (lo + hi) >> 1, i = src->order[mid];
+    const int c = cmp_coords(src->coords + 3 * i, want);
+    if (c == 0) return src->vox + 512 * i;
+    if (c < 0) lo = mid + 1; else hi = mid - 1;
+  }
+  return NULL;
+}
+static const mc_voxel* fetch(const mc_source* src, int32_t gx, int32_t gy, int32_t gz) {
+  const mc_voxel* blk = find_block(src, gx >> 3, gy >> 3, gz >> 3);
   if (!blk) return NULL;
   return &blk[(gz & 7) * 64 + (gy & 7) * 8 + (gx & 7)];
 }
+/* the i-th block to mesh: 0 = none here, 1 = b filled in */
+static int source_block(const mc_source* src, int64_t i, int32_t* b) {
+  if (src->v) return or_slot_coords(src->v, i, b);
+  if (!src->owned[i]) return 0;
+  memcpy(b, src->coords + 3 * i, 12);
+  return 1;
+}
 
-mc_mesh* or_mc_extract(const or_volume* v) {
-  const mc_params* p = or_get_params(v);
+static mc_mesh* extract(const mc_source* v, const mc_params* p, int64_t ns) {
   const float voxel = p->voxel_size;
   const float thresh = p->mc_thresh_factor * voxel;
   mc_mesh* m = (mc_mesh*)calloc(1, sizeof(mc_mesh));
-  const int64_t ns = or_num_slots(v);
   for (int64_t s = 0; s < ns; s++) {
     int32_t b[3];
-    if (!or_slot_coords(v, s, b)) continue;
+    if (!source_block(v, s, b)) continue;
     for (int lz = 0; lz < 8; lz++) for (int ly = 0; ly < 8; ly++) for (int lx = 0; lx < 8; lx++) {
       const int32_t g[3] = {8 * b[0] + lx, 8 * b[1] + ly, 8 * b[2] + lz};
       const mc_voxel* cv[8];
@@ -130,6 +157,45 @@ mc_mesh* or_mc_extract(const or_volume* v) {
     m->idx[3 * i + k] = (int32_t)lo;
   }
   free(m->tris); m->tris = NULL; free(m->verts); m->verts = NULL;
+  return m;
+}
+
+mc_mesh* or_mc_extract(const or_volume* v) {
+  const mc_source src = {v, NULL, NULL, NULL, NULL, 0};
+  return extract(&src, or_get_params(v), or_num_slots(v));
+}
+
+/* The edge key holds 20 bits per voxel coordinate around KEY_BIAS: blocks -65536 .. 65535 on every axis. */
+#define MC_BLOCK_MIN (-(KEY_BIAS >> 3))
+#define MC_BLOCK_MAX ((KEY_BIAS >> 3) - 1)
+
+static const int32_t* g_sort_coords;
+static int cmp_order(const void* a, const void* b) { return cmp_coords(g_sort_coords + 3 * *(const int64_t*)a, g_sort_coords + 3 * *(const int64_t*)b); }
+
+/* Marching cubes over n blocks given directly (no fused volume): cubes of the blocks with owned[i] != 0 are meshed, every block is readable as a
+ * neighbour.  NULL when a block that takes part -- an owned one, or a +1 neighbour of an owned one -- lies outside the key range; then bad[3], if given,
+ * names it.  Not thread-safe (the sort's comparator reads a static). */
+mc_mesh* or_mc_extract_blocks(const mc_params* p, const int32_t* coords, const mc_voxel* vox, const uint8_t* owned, int64_t n, int32_t* bad) {
+  int64_t* order = (int64_t*)malloc((size_t)(n ? n : 1) * sizeof(int64_t));
+  for (int64_t i = 0; i < n; i++) order[i] = i;
+  g_sort_coords = coords;
+  qsort(order, (size_t)n, sizeof(int64_t), cmp_order);
+  const mc_source src = {NULL, coords, vox, owned, order, n};
+  for (int64_t i = 0; i < n; i++) {
+    if (!owned[i]) continue;
+    for (int k = 0; k < 8; k++) {
+      const int32_t c[3] = {coords[3 * i] + (k & 1), coords[3 * i + 1] + ((k >> 1) & 1), coords[3 * i + 2] + (k >> 2)};
+      int out = 0;
+      for (int q = 0; q < 3; q++) if (c[q] < MC_BLOCK_MIN || c[q] > MC_BLOCK_MAX) out = 1;
+      if (out && (k == 0 || find_block(&src, c[0], c[1], c[2]))) {
+        if (bad) memcpy(bad, c, 12);
+        free(order);
+        return NULL;
+      }
+    }
+  }
+  mc_mesh* m = extract(&src, p, n);
+  free(order);
   return m;
 }
 

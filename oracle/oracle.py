@@ -77,6 +77,8 @@ def lib():
         L.or_mc_num_tris.argtypes = [C.c_void_p]
         L.or_mc_copy.argtypes = [C.c_void_p] * 5
         L.or_mc_free.argtypes = [C.c_void_p]
+        L.or_mc_extract_blocks.restype = C.c_void_p
+        L.or_mc_extract_blocks.argtypes = [C.POINTER(OrParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -144,16 +146,41 @@ class Volume:
 
     def extract_mesh(self):
         """-> dict(pos f32[nv,3], col u8[nv,3], idx i32[nt,3], keys u64[nv]) in canonical order."""
-        L = lib()
-        m = L.or_mc_extract(self._h)
-        nv, nt = int(L.or_mc_num_verts(m)), int(L.or_mc_num_tris(m))
-        pos = np.zeros((nv, 3), np.float32)
-        col = np.zeros((nv, 3), np.uint8)
-        idx = np.zeros((nt, 3), np.int32)
-        keys = np.zeros(nv, np.uint64)
-        L.or_mc_copy(m, _ptr(pos), _ptr(col), _ptr(idx), _ptr(keys))
-        L.or_mc_free(m)
-        return dict(pos=pos, col=col, idx=idx, keys=keys)
+        return _mc_result(lib().or_mc_extract(self._h))
+
+
+def _mc_result(m):
+    L = lib()
+    nv, nt = int(L.or_mc_num_verts(m)), int(L.or_mc_num_tris(m))
+    pos = np.zeros((nv, 3), np.float32)
+    col = np.zeros((nv, 3), np.uint8)
+    idx = np.zeros((nt, 3), np.int32)
+    keys = np.zeros(nv, np.uint64)
+    L.or_mc_copy(m, _ptr(pos), _ptr(col), _ptr(idx), _ptr(keys))
+    L.or_mc_free(m)
+    return dict(pos=pos, col=col, idx=idx, keys=keys)
+
+
+class KeyRangeError(ValueError):
+    """A block that takes part in the mesh lies outside what the edge key holds; .block names it."""
+
+    def __init__(self, block):
+        super().__init__("block (%d, %d, %d) lies outside the edge-key range" % tuple(block))
+        self.block = tuple(int(c) for c in block)
+
+
+def mc_extract_blocks(params, coords, voxels, owned=None):
+    """or_mc_extract_blocks: marching cubes over blocks given directly (coords int32 [n,3], voxels VOXEL_DTYPE [n,512]); only cubes of blocks with
+    owned[i] are meshed, every block is readable as a neighbour -> the dict of Volume.extract_mesh.  KeyRangeError beyond the key range."""
+    coords = np.ascontiguousarray(coords, np.int32).reshape(-1, 3)
+    voxels = np.ascontiguousarray(voxels, VOXEL_DTYPE).reshape(len(coords), 512)
+    own = np.ones(len(coords), np.uint8) if owned is None else np.ascontiguousarray(np.asarray(owned).astype(bool), np.uint8)
+    assert own.shape == (len(coords),)
+    bad = np.zeros(3, np.int32)
+    m = lib().or_mc_extract_blocks(C.byref(params), _ptr(coords), _ptr(voxels), _ptr(own), len(coords), _ptr(bad))
+    if not m:
+        raise KeyRangeError(bad)
+    return _mc_result(m)
 
 
 def sort_blocks(coords, vox):

@@ -3,7 +3,7 @@ from the text and sharing no code with oracle/mc_oracle.c or scannet_amd/csrc/mc
 sits, what colour it has, and how many triangles there are.  The case table only enters through its triangle COUNT per case (the table
 itself is verified from first principles by tests/test_mc_tables.py); vertex sets, positions and colours do not depend on it.
 
-    evaluate(coords, vox, voxel, thresh_factor, ntri_per_case) -> dict(keys u64[nv] ascending, pos f64[nv,3], col f64[nv,3] (unrounded), n_tris)
+    evaluate(coords, vox, voxel, thresh_factor, ntri_per_case, owned=None) -> dict(keys u64[nv] ascending, pos f64[nv,3], col f64[nv,3] (unrounded), n_tris)
 
 A cube (8 voxels g + {0,1}^3) takes part iff all 8 exist, have weight > 0 and |sdf| <= thresh_factor * voxel; corner i is inside iff sdf < 0;
 an edge of such a cube whose end points differ in sign carries a vertex at mu = s_lo / (s_lo - s_hi) from its lower end point, colour
@@ -20,7 +20,8 @@ def _pack(g):
     return ((g[..., 0] + KEY_BIAS) << 42) | ((g[..., 1] + KEY_BIAS) << 22) | ((g[..., 2] + KEY_BIAS) << 2)
 
 
-def evaluate(coords, vox, voxel, thresh_factor, ntri_per_case):
+def evaluate(coords, vox, voxel, thresh_factor, ntri_per_case, owned=None):
+    """owned (bool per block, default all): only cubes whose lowest voxel lies in an owned block are meshed; every block is read as a neighbour."""
     coords = np.asarray(coords, np.int64)
     l = np.arange(512)
     local = np.stack([l & 7, (l >> 3) & 7, l >> 6], 1)                      # index z*64 + y*8 + x
@@ -45,6 +46,8 @@ def evaluate(coords, vox, voxel, thresh_factor, ntri_per_case):
     corner = np.stack([lookup(g + CORNERS[i]) for i in range(8)], 1)        # [N, 8]
     ok = (corner >= 0).all(1)
     ok &= good[np.where(corner >= 0, corner, 0)].all(1)
+    if owned is not None:
+        ok &= np.repeat(np.asarray(owned, bool), 512)
     cube = np.nonzero(ok)[0]
     cidx = corner[cube]                                                      # [M, 8]
     s = sdf[cidx]

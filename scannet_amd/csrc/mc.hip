@@ -35,6 +35,11 @@
 namespace {
 
 constexpr int KEY_BIAS = 1 << 19;
+// edge_key holds 20 bits per voxel coordinate: blocks MC_BLOCK_MIN .. MC_BLOCK_MAX on every axis (the block table's pack_key holds 21 bits per BLOCK
+// coordinate, 16 times as far).  Beyond, the y and z fields would carry into the field above and two grid edges would share a key: the count pass
+// reports such a block and sf_fuser_extract_mesh refuses the volume.
+constexpr int MC_BLOCK_MIN = -(KEY_BIAS >> 3), MC_BLOCK_MAX = (KEY_BIAS >> 3) - 1;
+constexpr unsigned long long MC_BAD_TAG = 1ull << 63;   // pack_key uses 63 bits
 
 __device__ inline uint64_t edge_key(int gx, int gy, int gz, int axis) {
   return ((uint64_t)(uint32_t)(gx + KEY_BIAS) << 42) | ((uint64_t)(uint32_t)(gy + KEY_BIAS) << 22) |
@@ -94,7 +99,7 @@ __global__ __launch_bounds__(512) void k_mc(const uint4* __restrict__ voxels, co
                                             const McTables* __restrict__ tables, ParamsK P, float thresh, int emit,
                                             uint32_t* __restrict__ tri_count, const uint32_t* __restrict__ tri_off,
                                             uint64_t* __restrict__ tri_key, uint64_t* __restrict__ vkey, float* __restrict__ vpos,
-                                            uint32_t* __restrict__ vcol) {
+                                            uint32_t* __restrict__ vcol, unsigned long long* __restrict__ bad_block) {
   __shared__ Tile tile;
   __shared__ McTables T;
   __shared__ int s_nb[8];
@@ -105,6 +110,11 @@ __global__ __launch_bounds__(512) void k_mc(const uint4* __restrict__ voxels, co
   for (int bi = blockIdx.x; bi < n_live; bi += gridDim.x) {
     int bx, by, bz;
     load_tile(tile, s_nb, voxels, table, block_keys, P, live[bi], bx, by, bz);
+    if (!emit && threadIdx.x < 8) {   // a block that takes part (this one, or a +1 neighbour that exists) outside what edge_key can hold
+      const int i = threadIdx.x, nx = bx + (i & 1), ny = by + ((i >> 1) & 1), nz = bz + (i >> 2);
+      const bool out = nx < MC_BLOCK_MIN || nx > MC_BLOCK_MAX || ny < MC_BLOCK_MIN || ny > MC_BLOCK_MAX || nz < MC_BLOCK_MIN || nz > MC_BLOCK_MAX;
+      if (out && s_nb[i] >= 0) atomicMax(bad_block, (unsigned long long)pack_key(nx, ny, nz) | MC_BAD_TAG);
+    }
     float d[8];
     uint32_t c[8];
     const int cs = classify(tile, T, lx, ly, lz, thresh, d, c);
@@ -308,30 +318,42 @@ SF_API int sf_fuser_extract_mesh(sf_fuser* f, sf_mesh** out) {
   int rc = sf_compact_live(f, &n_live, 0);  // ghost copies of a neighbour slab's blocks are read as neighbours, never meshed
   if (rc != SF_OK) return rc;
   std::unique_ptr<sf_mesh> m(new sf_mesh());
+  f->mc_timing[9] = (double)n_live;
   if (n_live == 0) { *out = m.release(); return SF_OK; }
   hipStream_t s = f->stream;
   McClock clk(s);
   const double t_compact = wall_ms();
   const float thresh = f->p.mc_thresh_factor * f->p.voxel_size;
   const McTables ht = host_tables();
-  DevBuf d_tab, d_cnt, d_off, d_tmp;
+  DevBuf d_tab, d_cnt, d_off, d_tmp, d_bad;
   MC_CHECK(d_tab.alloc(sizeof(McTables)));
   MC_CHECK(hipMemcpyAsync(d_tab.p, &ht, sizeof(McTables), hipMemcpyHostToDevice, s));
   MC_CHECK(d_cnt.alloc((size_t)(n_live + 1) * 4));
   MC_CHECK(d_off.alloc((size_t)(n_live + 1) * 4));
   MC_CHECK(hipMemsetAsync(d_cnt.p, 0, (size_t)(n_live + 1) * 4, s));
+  MC_CHECK(d_bad.alloc(8));
+  MC_CHECK(hipMemsetAsync(d_bad.p, 0, 8, s));
   const int grid = n_live < f->num_cus * 8 ? n_live : f->num_cus * 8;
   clk.mark();   // 0
   hipLaunchKernelGGL(k_mc, dim3(grid), dim3(512), 0, s, f->voxels, f->table, f->block_keys, f->compact, n_live, d_tab.as<McTables>(), f->pk,
-                     thresh, 0, d_cnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr);
+                     thresh, 0, d_cnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr,
+                     d_bad.as<unsigned long long>());
   clk.mark();   // 1: count pass done
   size_t tmp_bytes = 0;
   MC_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), 0u, (size_t)(n_live + 1), rocprim::plus<uint32_t>(), s));
   MC_CHECK(d_tmp.alloc(tmp_bytes));
   MC_CHECK(rocprim::exclusive_scan(d_tmp.p, tmp_bytes, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), 0u, (size_t)(n_live + 1), rocprim::plus<uint32_t>(), s));
   uint32_t T = 0;
+  unsigned long long bad = 0;
   MC_CHECK(hipMemcpyAsync(&T, d_off.as<uint32_t>() + n_live, 4, hipMemcpyDeviceToHost, s));
+  MC_CHECK(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, s));
   MC_CHECK(hipStreamSynchronize(s));
+  if (bad) {
+    int bx, by, bz;
+    unpack_key(bad & ~MC_BAD_TAG, bx, by, bz);
+    return sf::fail(SF_ERR_CAPACITY, "block (%d, %d, %d) lies outside the range of the mesh's edge keys: blocks %d .. %d on every axis", bx, by, bz, MC_BLOCK_MIN,
+                    MC_BLOCK_MAX);
+  }
   if (T == 0) { *out = m.release(); return SF_OK; }
   if ((uint64_t)T * 3 > 0xFFFFFFF0ull) { return sf::fail(SF_ERR_CAPACITY, "mesh too large: %u triangles", T); }
   const uint32_t NV = 3 * T;
@@ -343,7 +365,7 @@ SF_API int sf_fuser_extract_mesh(sf_fuser* f, sf_mesh** out) {
   MC_CHECK(d_vcol.alloc((size_t)NV * 4));
   hipLaunchKernelGGL(k_mc, dim3(grid), dim3(512), 0, s, f->voxels, f->table, f->block_keys, f->compact, n_live, d_tab.as<McTables>(), f->pk,
                      thresh, 1, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), d_tkey.as<uint64_t>(), d_vkey.as<uint64_t>(), d_vpos.as<float>(),
-                     d_vcol.as<uint32_t>());
+                     d_vcol.as<uint32_t>(), (unsigned long long*)nullptr);
   clk.mark();   // 2: emit pass queued behind this
   // ---- weld: sort edge keys, flag heads, scan, scatter
   DevBuf d_vkey_s, d_src, d_src_s, d_flag, d_excl, d_tmp2;

@@ -607,8 +607,8 @@ SF_API int sf_mesh_copy(const sf_mesh* m, float* xyz, uint8_t* rgba, uint32_t* t
   }
   if (tris && !m->tri.empty()) std::memcpy(tris, m->tri.data(), m->tri.size() * 4);
   if (keys) {
-    if (m->keys.empty()) return sf::fail(SF_ERR_INVALID_ARG, "mesh has no vertex keys");
-    std::memcpy(keys, m->keys.data(), m->keys.size() * 8);
+    if (m->keys.size() * 3 != m->pos.size()) return sf::fail(SF_ERR_INVALID_ARG, "mesh has no vertex keys");
+    if (!m->keys.empty()) std::memcpy(keys, m->keys.data(), m->keys.size() * 8);   // an empty mesh (live blocks, no triangle) has its keys: none
   }
   return SF_OK;
 }
