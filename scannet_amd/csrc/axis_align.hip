@@ -523,9 +523,7 @@ namespace sf {
 namespace aa {
 
 int make_gpu_ops(int device, Ops** out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: the axis alignment on a device needs one (device = -1 is the host path)");
-  if (device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "the axis alignment on a device needs one (device = -1 is the host path)")) return rc;
   GpuOps* g = new GpuOps;
   g->device = device;
   *out = g;

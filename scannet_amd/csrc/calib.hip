@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 
 namespace {
 __global__ __launch_bounds__(256) void k_calib_rmw(uint4* __restrict__ buf, size_t n16) {
@@ -28,16 +29,13 @@ __global__ __launch_bounds__(256) void k_calib_read(const uint4* __restrict__ bu
 // Runs `iters` launches of a read+write stream and `iters` of a read-only stream over `bytes` bytes.
 SF_API int sf_calib_stream(int device, uint64_t bytes, int iters) {
   SF_HIP_CHECK(hipSetDevice(device));
-  uint4* buf = nullptr;
-  uint32_t* sink = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&buf, bytes));
-  SF_HIP_CHECK(hipMalloc((void**)&sink, 4));
-  SF_HIP_CHECK(hipMemset(buf, 1, bytes));
-  for (int i = 0; i < iters; i++) hipLaunchKernelGGL(k_calib_rmw, dim3(8192), dim3(256), 0, 0, buf, (size_t)(bytes / 16));
-  for (int i = 0; i < iters; i++) hipLaunchKernelGGL(k_calib_read, dim3(8192), dim3(256), 0, 0, buf, (size_t)(bytes / 16), sink);
+  sf::DevBuf buf, sink;
+  SF_HIP_CHECK(buf.alloc(bytes));
+  SF_HIP_CHECK(sink.alloc(4));
+  SF_HIP_CHECK(hipMemset(buf.p, 1, bytes));
+  for (int i = 0; i < iters; i++) hipLaunchKernelGGL(k_calib_rmw, dim3(8192), dim3(256), 0, 0, buf.as<uint4>(), (size_t)(bytes / 16));
+  for (int i = 0; i < iters; i++) hipLaunchKernelGGL(k_calib_read, dim3(8192), dim3(256), 0, 0, buf.as<uint4>(), (size_t)(bytes / 16), sink.as<uint32_t>());
   SF_HIP_CHECK(hipDeviceSynchronize());
-  (void)hipFree(buf);
-  (void)hipFree(sink);
   return SF_OK;
 }
 
@@ -135,35 +133,28 @@ __global__ __launch_bounds__(256) void k_selftest_weight_records(uint4* out) {
 SF_API int sf_selftest_weight_records(int device, uint32_t* out) {
   if (!out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   SF_HIP_CHECK(hipSetDevice(device));
-  uint4* d = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&d, WREC * sizeof(uint4)));
-  hipLaunchKernelGGL(k_selftest_weight_records, dim3(1), dim3(256), 0, nullptr, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(out, d, WREC * sizeof(uint4), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "self-test failed: %s", hipGetErrorString(e));
+  sf::DevBuf d;
+  SF_HIP_CHECK(d.alloc(WREC * sizeof(uint4)));
+  hipLaunchKernelGGL(k_selftest_weight_records, dim3(1), dim3(256), 0, nullptr, d.as<uint4>());
+  SF_HIP_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpy(out, d.p, WREC * sizeof(uint4), hipMemcpyDeviceToHost));
   return SF_OK;
 }
 
 SF_API int sf_selftest_recip_one_step(int device, uint64_t* mismatches, uint32_t* patterns_out, uint32_t capacity, int* shipped) {
   if (!mismatches || (capacity > 0 && !patterns_out)) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   SF_HIP_CHECK(hipSetDevice(device));
-  unsigned long long* d = nullptr;
-  uint32_t* p = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&d, 8));
-  if (hipMalloc((void**)&p, 4 * (size_t)(capacity ? capacity : 1)) != hipSuccess) { (void)hipFree(d); return sf::fail(SF_ERR_DEVICE, "self-test: hipMalloc failed"); }
-  hipError_t e = hipMemset(d, 0, 8);
-  if (e == hipSuccess) e = hipMemset(p, 0, 4 * (size_t)(capacity ? capacity : 1));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_selftest_recip_one_step, dim3(1u << 20), dim3(256), 0, nullptr, d, p, capacity);
-    e = hipGetLastError();
-  }
+  sf::DevBuf d, p;
+  const size_t pbytes = 4 * (size_t)(capacity ? capacity : 1);
+  SF_HIP_CHECK(d.alloc(8));
+  SF_HIP_CHECK(p.alloc(pbytes));
+  SF_HIP_CHECK(hipMemset(d.p, 0, 8));
+  SF_HIP_CHECK(hipMemset(p.p, 0, pbytes));
+  hipLaunchKernelGGL(k_selftest_recip_one_step, dim3(1u << 20), dim3(256), 0, nullptr, d.as<unsigned long long>(), p.as<uint32_t>(), capacity);
+  SF_HIP_CHECK(hipGetLastError());
   unsigned long long h = 0;
-  if (e == hipSuccess) e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && capacity > 0) e = hipMemcpy(patterns_out, p, 4 * (size_t)capacity, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  (void)hipFree(p);
-  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "self-test failed: %s", hipGetErrorString(e));
+  SF_HIP_CHECK(hipMemcpy(&h, d.p, 8, hipMemcpyDeviceToHost));
+  if (capacity > 0) SF_HIP_CHECK(hipMemcpy(patterns_out, p.p, 4 * (size_t)capacity, hipMemcpyDeviceToHost));
   *mismatches = h;
   if (shipped) *shipped = RECIP_ONE_STEP ? 1 : 0;
   return SF_OK;
@@ -172,16 +163,15 @@ SF_API int sf_selftest_recip_one_step(int device, uint64_t* mismatches, uint32_t
 SF_API int sf_selftest_division(int device, uint64_t* recip_mismatches, uint64_t* quot_mismatches, uint64_t* div_mismatches) {
   if (!recip_mismatches || !quot_mismatches || !div_mismatches) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   SF_HIP_CHECK(hipSetDevice(device));
-  unsigned long long* d = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&d, 24));
-  SF_HIP_CHECK(hipMemset(d, 0, 24));
+  sf::DevBuf buf;
+  SF_HIP_CHECK(buf.alloc(24));
+  SF_HIP_CHECK(hipMemset(buf.p, 0, 24));
+  unsigned long long* d = buf.as<unsigned long long>();
   hipLaunchKernelGGL(k_selftest_recip, dim3((1u << 23) / 256), dim3(256), 0, nullptr, d);
   hipLaunchKernelGGL(k_selftest_quot, dim3((1u << 20) / 256, 511), dim3(256), 0, nullptr, d + 1);
   hipLaunchKernelGGL(k_selftest_div, dim3((1u << 26) / 256), dim3(256), 0, nullptr, d + 2);
   unsigned long long h[3] = {0, 0, 0};
-  const hipError_t e = hipMemcpy(h, d, 24, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "self-test failed: %s", hipGetErrorString(e));
+  SF_HIP_CHECK(hipMemcpy(h, d, 24, hipMemcpyDeviceToHost));
   *recip_mismatches = h[0];
   *quot_mismatches = h[1];
   *div_mismatches = h[2];

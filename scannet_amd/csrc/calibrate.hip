@@ -32,6 +32,7 @@
 
 #include "codecs_internal.h"
 #include "common.h"
+#include "hip_util.h"
 #include "jpeg_idct.h"
 #include "lut_value.h"
 
@@ -378,11 +379,7 @@ SF_API int sf_calibrator_create(const sf_calib_params* p, const sf_lut* lut, flo
     return sf::fail(SF_ERR_INVALID_ARG, "implausible look-up table %d x %d x %d, max distance %g", lut->xres, lut->yres, lut->zres, (double)lut->max_dist);
   if (lut && lut->data && (lut->xres > (int)p->depth_width || lut->yres > (int)p->depth_height))
     return sf::fail(SF_ERR_INVALID_ARG, "look-up table is finer than the depth image");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return sf::fail(SF_ERR_DEVICE, "no HIP device: libscanfuse has no CPU fallback, the calibrator needs an MI355X");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "libscanfuse has no CPU fallback, the calibrator needs an MI355X")) return rc;
   sf_calibrator* c = new sf_calibrator();
   c->p = *p;
   c->device = device;

@@ -35,12 +35,6 @@ using sf::StreamGuard;
 
 struct Tri { uint32_t a, b, c; };
 
-#define CL_CHECK(call)                                                                                                                    \
-  do {                                                                                                                                    \
-    hipError_t e_ = (call);                                                                                                               \
-    if (e_ != hipSuccess) return sf::fail(SF_ERR_DEVICE, "%s failed: %s (clean_gpu.hip:%d)", #call, hipGetErrorString(e_), __LINE__);    \
-  } while (0)
-
 constexpr uint32_t UNSETTLED = 0xFFFFFFFFu;
 
 struct Grid {
@@ -258,17 +252,11 @@ struct Work {
       d_parent, d_root, d_size, d_used, d_remap, d_out_pos, d_out_col, d_out_tri, d_tmp;
 };
 
-int pick_device(int device, const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: %s needs an MI355X (sf_mesh_clean is the host filter)", who);
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  CL_CHECK(hipSetDevice(device));
-  return SF_OK;
-}
+int pick_device(int device, const char* who) { return sf::open_device(device, SF_ERR_INVALID_ARG, "%s needs an MI355X (sf_mesh_clean is the host filter)", who); }
 
 // the stream, the buffers of the filters named in `parts` (P_ALL: the product) and the scratch of their sorts, scans and selects
 int work_alloc(Work& W, size_t nv, size_t nf, bool has_col, unsigned parts) {
-  CL_CHECK(hipStreamCreateWithFlags(&W.sg.s, hipStreamNonBlocking));
+  SF_HIP_CHECK(hipStreamCreateWithFlags(&W.sg.s, hipStreamNonBlocking));
   W.s = W.sg.s;
   hipStream_t s = W.s;
   W.nv = nv;
@@ -277,42 +265,42 @@ int work_alloc(Work& W, size_t nv, size_t nf, bool has_col, unsigned parts) {
   const bool sorts = parts & (P_MERGE | P_FACES | P_COMPONENTS), faces = parts & (P_FACES | P_COMPONENTS | P_COMPACT);
   // the longest array any sort sees
   const size_t N = std::max<size_t>(std::max<size_t>((parts & P_MERGE) ? nv : 0, (parts & P_COMPONENTS) ? 3 * nf : ((parts & P_FACES) ? nf : 0)), 1);
-  if (parts & (P_MERGE | P_COMPACT)) CL_CHECK(W.d_pos.alloc(nv * 12));
-  if (parts & P_FACES) CL_CHECK(W.d_tri_in.alloc(nfa * 12));
-  if (parts & (P_MERGE | P_FACES)) CL_CHECK(W.d_target.alloc(nv * 4));
-  if (has_col) CL_CHECK(W.d_col.alloc(nv * 4));
+  if (parts & (P_MERGE | P_COMPACT)) SF_HIP_CHECK(W.d_pos.alloc(nv * 12));
+  if (parts & P_FACES) SF_HIP_CHECK(W.d_tri_in.alloc(nfa * 12));
+  if (parts & (P_MERGE | P_FACES)) SF_HIP_CHECK(W.d_target.alloc(nv * 4));
+  if (has_col) SF_HIP_CHECK(W.d_col.alloc(nv * 4));
   if (sorts) {
-    CL_CHECK(W.d_k64a.alloc(N * 8)); CL_CHECK(W.d_k64b.alloc(N * 8)); CL_CHECK(W.d_k32a.alloc((N + 1) * 4)); CL_CHECK(W.d_k32b.alloc(N * 4));
-    CL_CHECK(W.d_p32a.alloc(N * 4)); CL_CHECK(W.d_p32b.alloc(N * 4));
+    SF_HIP_CHECK(W.d_k64a.alloc(N * 8)); SF_HIP_CHECK(W.d_k64b.alloc(N * 8)); SF_HIP_CHECK(W.d_k32a.alloc((N + 1) * 4)); SF_HIP_CHECK(W.d_k32b.alloc(N * 4));
+    SF_HIP_CHECK(W.d_p32a.alloc(N * 4)); SF_HIP_CHECK(W.d_p32b.alloc(N * 4));
   }
-  if (parts & P_MERGE) { CL_CHECK(W.d_cstart.alloc((nv + 1) * 4)); CL_CHECK(W.d_pending_a.alloc(nv * 4)); CL_CHECK(W.d_pending_b.alloc(nv * 4)); }
-  CL_CHECK(W.d_ncells.alloc(16)); CL_CHECK(W.d_count.alloc(64));
-  if (faces) { CL_CHECK(W.d_tri.alloc(nfa * 12)); CL_CHECK(W.d_tri2.alloc(nfa * 12)); CL_CHECK(W.d_keep.alloc(nfa)); }
-  if (parts & P_COMPONENTS) { CL_CHECK(W.d_parent.alloc(nfa * 4)); CL_CHECK(W.d_root.alloc(nfa * 4)); CL_CHECK(W.d_size.alloc(nfa * 4)); }
-  if (parts & P_COMPACT) { CL_CHECK(W.d_used.alloc(nv * 4)); CL_CHECK(W.d_remap.alloc(nv * 4)); }
+  if (parts & P_MERGE) { SF_HIP_CHECK(W.d_cstart.alloc((nv + 1) * 4)); SF_HIP_CHECK(W.d_pending_a.alloc(nv * 4)); SF_HIP_CHECK(W.d_pending_b.alloc(nv * 4)); }
+  SF_HIP_CHECK(W.d_ncells.alloc(16)); SF_HIP_CHECK(W.d_count.alloc(64));
+  if (faces) { SF_HIP_CHECK(W.d_tri.alloc(nfa * 12)); SF_HIP_CHECK(W.d_tri2.alloc(nfa * 12)); SF_HIP_CHECK(W.d_keep.alloc(nfa)); }
+  if (parts & P_COMPONENTS) { SF_HIP_CHECK(W.d_parent.alloc(nfa * 4)); SF_HIP_CHECK(W.d_root.alloc(nfa * 4)); SF_HIP_CHECK(W.d_size.alloc(nfa * 4)); }
+  if (parts & P_COMPACT) { SF_HIP_CHECK(W.d_used.alloc(nv * 4)); SF_HIP_CHECK(W.d_remap.alloc(nv * 4)); }
   size_t tmp_bytes = 0, need = 0;
   if (sorts) {
-    CL_CHECK(rocprim::radix_sort_pairs(nullptr, need, W.d_k64a.as<uint64_t>(), W.d_k64b.as<uint64_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), N, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, W.d_k64a.as<uint64_t>(), W.d_k64b.as<uint64_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), N, 0, 64, s));
     tmp_bytes = std::max(tmp_bytes, need);
-    CL_CHECK(rocprim::radix_sort_pairs(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_k32b.as<uint32_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), N, 0, 32, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_k32b.as<uint32_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), N, 0, 32, s));
     tmp_bytes = std::max(tmp_bytes, need);
   }
   if (parts & P_MERGE) {
-    CL_CHECK(rocprim::run_length_encode(nullptr, need, W.d_k64b.as<uint64_t>(), (unsigned int)nv, W.d_k64a.as<uint64_t>(), W.d_k32a.as<uint32_t>(), W.d_ncells.as<uint32_t>(), s));
+    SF_HIP_CHECK(rocprim::run_length_encode(nullptr, need, W.d_k64b.as<uint64_t>(), (unsigned int)nv, W.d_k64a.as<uint64_t>(), W.d_k32a.as<uint32_t>(), W.d_ncells.as<uint32_t>(), s));
     tmp_bytes = std::max(tmp_bytes, need);
-    CL_CHECK(rocprim::inclusive_scan(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_k32b.as<uint32_t>(), nv, rocprim::maximum<uint32_t>(), s));
+    SF_HIP_CHECK(rocprim::inclusive_scan(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_k32b.as<uint32_t>(), nv, rocprim::maximum<uint32_t>(), s));
     tmp_bytes = std::max(tmp_bytes, need);
   }
   if (parts & (P_MERGE | P_COMPACT)) {
-    CL_CHECK(rocprim::exclusive_scan(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_cstart.as<uint32_t>(), 0u, nv + 1, rocprim::plus<uint32_t>(), s));
+    SF_HIP_CHECK(rocprim::exclusive_scan(nullptr, need, W.d_k32a.as<uint32_t>(), W.d_cstart.as<uint32_t>(), 0u, nv + 1, rocprim::plus<uint32_t>(), s));
     tmp_bytes = std::max(tmp_bytes, need);
   }
   if (parts & (P_FACES | P_COMPONENTS)) {
-    CL_CHECK(rocprim::select(nullptr, need, W.d_tri.as<Tri>(), W.d_keep.as<uint8_t>(), W.d_tri2.as<Tri>(), W.d_ncells.as<uint32_t>(), nfa, s));
+    SF_HIP_CHECK(rocprim::select(nullptr, need, W.d_tri.as<Tri>(), W.d_keep.as<uint8_t>(), W.d_tri2.as<Tri>(), W.d_ncells.as<uint32_t>(), nfa, s));
     tmp_bytes = std::max(tmp_bytes, need);
   }
   W.tmp_bytes = tmp_bytes;
-  CL_CHECK(W.d_tmp.alloc(tmp_bytes));
+  SF_HIP_CHECK(W.d_tmp.alloc(tmp_bytes));
   return SF_OK;
 }
 
@@ -348,29 +336,29 @@ int run_merge(Work& W, const Grid& G, float merge_distance, uint32_t* launches, 
   if (merge_distance > 0.0f) {
     hipLaunchKernelGGL(k_cell_keys, dim3(grid_for(nv)), dim3(256), 0, s, d_pos.as<float>(), V, G, d_k64a.as<uint64_t>(), d_p32a.as<uint32_t>());
     tb = tmp_bytes;
-    CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64a.as<uint64_t>(), d_k64b.as<uint64_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), nv, 0, 63, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64a.as<uint64_t>(), d_k64b.as<uint64_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), nv, 0, 63, s));
     // unique cells -> d_k64a, their sizes -> d_k32a, their first member -> d_cstart; members (vertex ids, index order inside a cell) = d_p32b
     tb = tmp_bytes;
-    CL_CHECK(rocprim::run_length_encode(d_tmp.p, tb, d_k64b.as<uint64_t>(), (unsigned int)nv, d_k64a.as<uint64_t>(), d_k32a.as<uint32_t>(), d_ncells.as<uint32_t>(), s));
+    SF_HIP_CHECK(rocprim::run_length_encode(d_tmp.p, tb, d_k64b.as<uint64_t>(), (unsigned int)nv, d_k64a.as<uint64_t>(), d_k32a.as<uint32_t>(), d_ncells.as<uint32_t>(), s));
     uint32_t ncells = 0;
-    CL_CHECK(hipMemcpyAsync(&ncells, d_ncells.p, 4, hipMemcpyDeviceToHost, s));
-    CL_CHECK(hipStreamSynchronize(s));
+    SF_HIP_CHECK(hipMemcpyAsync(&ncells, d_ncells.p, 4, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipStreamSynchronize(s));
     *cells = ncells;
-    CL_CHECK(hipMemsetAsync(d_k32a.as<uint32_t>() + ncells, 0, 4, s));   // the scan below reads one element past the counts
+    SF_HIP_CHECK(hipMemsetAsync(d_k32a.as<uint32_t>() + ncells, 0, 4, s));   // the scan below reads one element past the counts
     tb = tmp_bytes;
-    CL_CHECK(rocprim::exclusive_scan(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_cstart.as<uint32_t>(), 0u, (size_t)ncells + 1, rocprim::plus<uint32_t>(), s));
-    CL_CHECK(hipMemsetAsync(target, 0xFF, nv * 4, s));
+    SF_HIP_CHECK(rocprim::exclusive_scan(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_cstart.as<uint32_t>(), 0u, (size_t)ncells + 1, rocprim::plus<uint32_t>(), s));
+    SF_HIP_CHECK(hipMemsetAsync(target, 0xFF, nv * 4, s));
     uint32_t n_in = V;
     const uint32_t* pending_in = nullptr;
     uint32_t* pend[2] = {W.d_pending_a.as<uint32_t>(), W.d_pending_b.as<uint32_t>()};
     for (int round = 0;; round++) {
-      CL_CHECK(hipMemsetAsync(d_count.p, 0, 4, s));
+      SF_HIP_CHECK(hipMemsetAsync(d_count.p, 0, 4, s));
       hipLaunchKernelGGL(k_settle, dim3(grid_for(n_in)), dim3(256), 0, s, d_pos.as<float>(), V, G, merge_distance, d_k64a.as<uint64_t>(), d_cstart.as<uint32_t>(), ncells,
                          d_p32b.as<uint32_t>(), pending_in, n_in, target, pend[round & 1], d_count.as<uint32_t>());
       ++*launches;
       uint32_t left = 0;
-      CL_CHECK(hipMemcpyAsync(&left, d_count.p, 4, hipMemcpyDeviceToHost, s));
-      CL_CHECK(hipStreamSynchronize(s));
+      SF_HIP_CHECK(hipMemcpyAsync(&left, d_count.p, 4, hipMemcpyDeviceToHost, s));
+      SF_HIP_CHECK(hipStreamSynchronize(s));
       if (left == 0) break;
       if (left == n_in && round > 0) return sf::fail(SF_ERR_DEVICE, "sf_mesh_clean_gpu: clustering made no progress (%u vertices)", left);
       pending_in = pend[round & 1];
@@ -381,26 +369,26 @@ int run_merge(Work& W, const Grid& G, float merge_distance, uint32_t* launches, 
     hipLaunchKernelGGL(k_pos_keys, dim3(grid_for(nv)), dim3(256), 0, s, d_pos.as<float>(), V, d_k32a.as<uint32_t>(), d_k64a.as<uint64_t>());
     hipLaunchKernelGGL(k_iota, dim3(grid_for(nv)), dim3(256), 0, s, d_p32a.as<uint32_t>(), V);
     tb = tmp_bytes;
-    CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_k32b.as<uint32_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), nv, 0, 32, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_k32b.as<uint32_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), nv, 0, 32, s));
     hipLaunchKernelGGL(k_gather64, dim3(grid_for(nv)), dim3(256), 0, s, d_k64a.as<uint64_t>(), d_p32b.as<uint32_t>(), V, d_k64b.as<uint64_t>());
     tb = tmp_bytes;
-    CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64b.as<uint64_t>(), d_k64a.as<uint64_t>(), d_p32b.as<uint32_t>(), d_p32a.as<uint32_t>(), nv, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64b.as<uint64_t>(), d_k64a.as<uint64_t>(), d_p32b.as<uint32_t>(), d_p32a.as<uint32_t>(), nv, 0, 64, s));
     // sorted (x, y) keys in d_k64a, permutation in d_p32a, z keys by vertex in d_k32a
     hipLaunchKernelGGL(k_run_heads, dim3(grid_for(nv)), dim3(256), 0, s, d_k64a.as<uint64_t>(), d_k32a.as<uint32_t>(), d_p32a.as<uint32_t>(), V, d_k32b.as<uint32_t>());
     tb = tmp_bytes;
-    CL_CHECK(rocprim::inclusive_scan(d_tmp.p, tb, d_k32b.as<uint32_t>(), d_p32b.as<uint32_t>(), nv, rocprim::maximum<uint32_t>(), s));
+    SF_HIP_CHECK(rocprim::inclusive_scan(d_tmp.p, tb, d_k32b.as<uint32_t>(), d_p32b.as<uint32_t>(), nv, rocprim::maximum<uint32_t>(), s));
     hipLaunchKernelGGL(k_targets_from_heads, dim3(grid_for(nv)), dim3(256), 0, s, d_p32b.as<uint32_t>(), d_p32a.as<uint32_t>(), V, target);
   }
-  CL_CHECK(hipMemsetAsync(d_count.p, 0, 64, s));
+  SF_HIP_CHECK(hipMemsetAsync(d_count.p, 0, 64, s));
   hipLaunchKernelGGL(k_count_merged, dim3(grid_for(nv)), dim3(256), 0, s, target, V, d_count.as<uint32_t>() + 4);
   return SF_OK;
 }
 
 int compact_faces(Work& W, uint32_t n, uint32_t* kept) {   // d_tri -> (stable select by d_keep) -> d_tri
   size_t t2 = W.tmp_bytes;
-  CL_CHECK(rocprim::select(W.d_tmp.p, t2, W.d_tri.as<Tri>(), W.d_keep.as<uint8_t>(), W.d_tri2.as<Tri>(), W.d_ncells.as<uint32_t>(), (size_t)n, W.s));
-  CL_CHECK(hipMemcpyAsync(kept, W.d_ncells.p, 4, hipMemcpyDeviceToHost, W.s));
-  CL_CHECK(hipStreamSynchronize(W.s));
+  SF_HIP_CHECK(rocprim::select(W.d_tmp.p, t2, W.d_tri.as<Tri>(), W.d_keep.as<uint8_t>(), W.d_tri2.as<Tri>(), W.d_ncells.as<uint32_t>(), (size_t)n, W.s));
+  SF_HIP_CHECK(hipMemcpyAsync(kept, W.d_ncells.p, 4, hipMemcpyDeviceToHost, W.s));
+  SF_HIP_CHECK(hipStreamSynchronize(W.s));
   std::swap(W.d_tri.p, W.d_tri2.p);
   return SF_OK;
 }
@@ -415,20 +403,20 @@ int run_faces(Work& W, uint32_t F, uint32_t* n1_out, uint32_t* n2_out, uint8_t* 
   if (F > 0) hipLaunchKernelGGL(k_remap_faces, dim3(grid_for(F)), dim3(256), 0, s, W.d_tri_in.as<uint32_t>(), W.d_target.as<uint32_t>(), F, W.d_tri.as<Tri>(), d_keep.as<uint8_t>());
   uint32_t n1 = 0;
   if (F > 0) { const int rc = compact_faces(W, F, &n1); if (rc != SF_OK) return rc; }
-  if (keep1 && F > 0) { CL_CHECK(hipMemcpyAsync(keep1, d_keep.p, F, hipMemcpyDeviceToHost, s)); CL_CHECK(hipStreamSynchronize(s)); }
+  if (keep1 && F > 0) { SF_HIP_CHECK(hipMemcpyAsync(keep1, d_keep.p, F, hipMemcpyDeviceToHost, s)); SF_HIP_CHECK(hipStreamSynchronize(s)); }
   uint32_t n2 = n1;
   if (n1 > 0) {
     hipLaunchKernelGGL(k_face_keys, dim3(grid_for(n1)), dim3(256), 0, s, W.d_tri.as<Tri>(), n1, d_k32a.as<uint32_t>(), d_k64a.as<uint64_t>());
     hipLaunchKernelGGL(k_iota, dim3(grid_for(n1)), dim3(256), 0, s, d_p32a.as<uint32_t>(), n1);
     tb = tmp_bytes;
-    CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_k32b.as<uint32_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), (size_t)n1, 0, 32, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k32a.as<uint32_t>(), d_k32b.as<uint32_t>(), d_p32a.as<uint32_t>(), d_p32b.as<uint32_t>(), (size_t)n1, 0, 32, s));
     hipLaunchKernelGGL(k_gather64, dim3(grid_for(n1)), dim3(256), 0, s, d_k64a.as<uint64_t>(), d_p32b.as<uint32_t>(), n1, d_k64b.as<uint64_t>());
     tb = tmp_bytes;
-    CL_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64b.as<uint64_t>(), d_k64a.as<uint64_t>(), d_p32b.as<uint32_t>(), d_p32a.as<uint32_t>(), (size_t)n1, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_k64b.as<uint64_t>(), d_k64a.as<uint64_t>(), d_p32b.as<uint32_t>(), d_p32a.as<uint32_t>(), (size_t)n1, 0, 64, s));
     hipLaunchKernelGGL(k_dup_flags, dim3(grid_for(n1)), dim3(256), 0, s, d_k64a.as<uint64_t>(), d_k32a.as<uint32_t>(), d_p32a.as<uint32_t>(), n1, d_keep.as<uint8_t>());
     const int rc = compact_faces(W, n1, &n2);
     if (rc != SF_OK) return rc;
-    if (keep2) { CL_CHECK(hipMemcpyAsync(keep2, d_keep.p, n1, hipMemcpyDeviceToHost, s)); CL_CHECK(hipStreamSynchronize(s)); }
+    if (keep2) { SF_HIP_CHECK(hipMemcpyAsync(keep2, d_keep.p, n1, hipMemcpyDeviceToHost, s)); SF_HIP_CHECK(hipStreamSynchronize(s)); }
   }
   *n1_out = n1;
   *n2_out = n2;
@@ -443,10 +431,10 @@ int run_components(Work& W, uint32_t n2, uint32_t min_component_faces, uint32_t*
     const size_t ne = 3 * (size_t)n2;
     hipLaunchKernelGGL(k_edge_keys, dim3(grid_for(n2)), dim3(256), 0, s, W.d_tri.as<Tri>(), n2, W.d_k64a.as<uint64_t>(), W.d_p32a.as<uint32_t>());
     size_t tb = W.tmp_bytes;
-    CL_CHECK(rocprim::radix_sort_pairs(W.d_tmp.p, tb, W.d_k64a.as<uint64_t>(), W.d_k64b.as<uint64_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), ne, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(W.d_tmp.p, tb, W.d_k64a.as<uint64_t>(), W.d_k64b.as<uint64_t>(), W.d_p32a.as<uint32_t>(), W.d_p32b.as<uint32_t>(), ne, 0, 64, s));
     hipLaunchKernelGGL(k_iota, dim3(grid_for(n2)), dim3(256), 0, s, W.d_parent.as<uint32_t>(), n2);
     hipLaunchKernelGGL(k_link, dim3(grid_for(ne)), dim3(256), 0, s, W.d_k64b.as<uint64_t>(), W.d_p32b.as<uint32_t>(), ne, W.d_parent.as<uint32_t>());
-    CL_CHECK(hipMemsetAsync(W.d_size.p, 0, (size_t)n2 * 4, s));
+    SF_HIP_CHECK(hipMemsetAsync(W.d_size.p, 0, (size_t)n2 * 4, s));
     hipLaunchKernelGGL(k_roots, dim3(grid_for(n2)), dim3(256), 0, s, W.d_parent.as<uint32_t>(), n2, W.d_root.as<uint32_t>(), W.d_size.as<uint32_t>());
     hipLaunchKernelGGL(k_component_flags, dim3(grid_for(n2)), dim3(256), 0, s, W.d_root.as<uint32_t>(), W.d_size.as<uint32_t>(), n2, min_component_faces, W.d_keep.as<uint8_t>(),
                        W.d_count.as<uint32_t>());
@@ -462,35 +450,35 @@ int run_compact(Work& W, uint32_t n3, bool has_col, sf_mesh* m, uint32_t* vout_o
   hipStream_t s = W.s;
   const size_t nv = W.nv;
   DevBuf &d_used = W.d_used, &d_remap = W.d_remap, &d_out_pos = W.d_out_pos, &d_out_col = W.d_out_col, &d_out_tri = W.d_out_tri;
-  CL_CHECK(hipMemsetAsync(d_used.p, 0, nv * 4, s));
+  SF_HIP_CHECK(hipMemsetAsync(d_used.p, 0, nv * 4, s));
   if (n3 > 0) hipLaunchKernelGGL(k_mark_used, dim3(grid_for(n3)), dim3(256), 0, s, W.d_tri.as<Tri>(), n3, d_used.as<uint32_t>());
   size_t tb = W.tmp_bytes;
-  CL_CHECK(rocprim::exclusive_scan(W.d_tmp.p, tb, d_used.as<uint32_t>(), d_remap.as<uint32_t>(), 0u, nv, rocprim::plus<uint32_t>(), s));
+  SF_HIP_CHECK(rocprim::exclusive_scan(W.d_tmp.p, tb, d_used.as<uint32_t>(), d_remap.as<uint32_t>(), 0u, nv, rocprim::plus<uint32_t>(), s));
   uint32_t last_used = 0, last_remap = 0;
-  CL_CHECK(hipMemcpyAsync(&last_used, d_used.as<uint32_t>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipMemcpyAsync(&last_remap, d_remap.as<uint32_t>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipMemcpyAsync(counters, W.d_count.p, 64, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipStreamSynchronize(s));
+  SF_HIP_CHECK(hipMemcpyAsync(&last_used, d_used.as<uint32_t>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipMemcpyAsync(&last_remap, d_remap.as<uint32_t>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipMemcpyAsync(counters, W.d_count.p, 64, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipStreamSynchronize(s));
   const uint32_t vout = last_remap + last_used;
   *vout_out = vout;
   m->pos.resize((size_t)vout * 3);
   if (has_col) m->col.resize((size_t)vout * 4);
   m->tri.resize((size_t)n3 * 3);
   if (vout > 0) {
-    CL_CHECK(d_out_pos.alloc((size_t)vout * 12));
-    if (has_col) CL_CHECK(d_out_col.alloc((size_t)vout * 4));
+    SF_HIP_CHECK(d_out_pos.alloc((size_t)vout * 12));
+    if (has_col) SF_HIP_CHECK(d_out_col.alloc((size_t)vout * 4));
     hipLaunchKernelGGL(k_gather_vertices, dim3(grid_for(nv)), dim3(256), 0, s, W.d_pos.as<float>(), has_col ? W.d_col.as<uint8_t>() : nullptr, d_used.as<uint32_t>(),
                        d_remap.as<uint32_t>(), (uint32_t)nv, d_out_pos.as<float>(), has_col ? d_out_col.as<uint8_t>() : nullptr);
-    CL_CHECK(hipMemcpyAsync(m->pos.data(), d_out_pos.p, (size_t)vout * 12, hipMemcpyDeviceToHost, s));
-    if (has_col) CL_CHECK(hipMemcpyAsync(m->col.data(), d_out_col.p, (size_t)vout * 4, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipMemcpyAsync(m->pos.data(), d_out_pos.p, (size_t)vout * 12, hipMemcpyDeviceToHost, s));
+    if (has_col) SF_HIP_CHECK(hipMemcpyAsync(m->col.data(), d_out_col.p, (size_t)vout * 4, hipMemcpyDeviceToHost, s));
   }
   if (n3 > 0) {
-    CL_CHECK(d_out_tri.alloc((size_t)n3 * 12));
+    SF_HIP_CHECK(d_out_tri.alloc((size_t)n3 * 12));
     hipLaunchKernelGGL(k_remap_tris, dim3(grid_for(n3)), dim3(256), 0, s, W.d_tri.as<Tri>(), d_remap.as<uint32_t>(), n3, d_out_tri.as<uint32_t>());
-    CL_CHECK(hipMemcpyAsync(m->tri.data(), d_out_tri.p, (size_t)n3 * 12, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipMemcpyAsync(m->tri.data(), d_out_tri.p, (size_t)n3 * 12, hipMemcpyDeviceToHost, s));
   }
-  CL_CHECK(hipStreamSynchronize(s));
-  CL_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipStreamSynchronize(s));
+  SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }
 
@@ -523,9 +511,9 @@ SF_API int sf_mesh_clean_gpu(const sf_mesh* in, float merge_distance, uint32_t m
   if ((rc = work_alloc(W, nv, nf, has_col, P_ALL)) != SF_OK) return rc;
   hipStream_t s = W.s;
   const uint32_t F = (uint32_t)nf;
-  CL_CHECK(hipMemcpyAsync(W.d_pos.p, in->pos.data(), nv * 12, hipMemcpyHostToDevice, s));
-  if (nf > 0) CL_CHECK(hipMemcpyAsync(W.d_tri_in.p, in->tri.data(), nf * 12, hipMemcpyHostToDevice, s));
-  if (has_col) CL_CHECK(hipMemcpyAsync(W.d_col.p, in->col.data(), nv * 4, hipMemcpyHostToDevice, s));
+  SF_HIP_CHECK(hipMemcpyAsync(W.d_pos.p, in->pos.data(), nv * 12, hipMemcpyHostToDevice, s));
+  if (nf > 0) SF_HIP_CHECK(hipMemcpyAsync(W.d_tri_in.p, in->tri.data(), nf * 12, hipMemcpyHostToDevice, s));
+  if (has_col) SF_HIP_CHECK(hipMemcpyAsync(W.d_col.p, in->col.data(), nv * 4, hipMemcpyHostToDevice, s));
   uint32_t launches = 0, cells = 0, n1 = 0, n2 = 0, n3 = 0, vout = 0, counters[16];
   if ((rc = run_merge(W, G, merge_distance, &launches, &cells)) != SF_OK) return rc;
   if ((rc = run_faces(W, F, &n1, &n2, nullptr, nullptr)) != SF_OK) return rc;
@@ -557,12 +545,12 @@ SF_API int sf_clean_stage_merge(int device, uint32_t V, const float* pos, float 
   if (radius > 0.0f && (rc = grid_setup(pos, V, radius, G)) != SF_OK) return rc;
   Work W;
   if ((rc = work_alloc(W, V, 0, false, P_MERGE)) != SF_OK) return rc;
-  CL_CHECK(hipMemcpyAsync(W.d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, W.s));
+  SF_HIP_CHECK(hipMemcpyAsync(W.d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, W.s));
   if ((rc = run_merge(W, G, radius, launches_out, cells_out)) != SF_OK) return rc;
-  CL_CHECK(hipMemcpyAsync(target_out, W.d_target.p, (size_t)V * 4, hipMemcpyDeviceToHost, W.s));
-  CL_CHECK(hipMemcpyAsync(merged_out, W.d_count.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, W.s));
-  CL_CHECK(hipStreamSynchronize(W.s));
-  CL_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(target_out, W.d_target.p, (size_t)V * 4, hipMemcpyDeviceToHost, W.s));
+  SF_HIP_CHECK(hipMemcpyAsync(merged_out, W.d_count.as<uint32_t>() + 4, 4, hipMemcpyDeviceToHost, W.s));
+  SF_HIP_CHECK(hipStreamSynchronize(W.s));
+  SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }
 
@@ -580,16 +568,16 @@ SF_API int sf_clean_stage_faces(int device, uint32_t V, uint32_t F, const uint32
   Work W;
   if ((rc = work_alloc(W, V, F, false, P_FACES)) != SF_OK) return rc;
   hipStream_t s = W.s;
-  CL_CHECK(hipMemcpyAsync(W.d_tri_in.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
-  if (target) CL_CHECK(hipMemcpyAsync(W.d_target.p, target, (size_t)V * 4, hipMemcpyHostToDevice, s));
+  SF_HIP_CHECK(hipMemcpyAsync(W.d_tri_in.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
+  if (target) SF_HIP_CHECK(hipMemcpyAsync(W.d_target.p, target, (size_t)V * 4, hipMemcpyHostToDevice, s));
   else   // nobody merged: target[v] = v, written where a face reads it (V may be 2^32 - 17: 16 GiB that nobody fills)
-    for (size_t i = 0; i < 3 * (size_t)F; i++) CL_CHECK(hipMemcpyAsync(W.d_target.as<uint32_t>() + tri[i], tri + i, 4, hipMemcpyHostToDevice, s));
+    for (size_t i = 0; i < 3 * (size_t)F; i++) SF_HIP_CHECK(hipMemcpyAsync(W.d_target.as<uint32_t>() + tri[i], tri + i, 4, hipMemcpyHostToDevice, s));
   std::vector<uint8_t> keep1(F), keep2(F);
   uint32_t n1 = 0, n2 = 0;
   if ((rc = run_faces(W, F, &n1, &n2, keep1.data(), keep2.data())) != SF_OK) return rc;
-  if (n2 > 0) CL_CHECK(hipMemcpyAsync(tri_out, W.d_tri.p, (size_t)n2 * 12, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipStreamSynchronize(s));
-  CL_CHECK(hipGetLastError());
+  if (n2 > 0) SF_HIP_CHECK(hipMemcpyAsync(tri_out, W.d_tri.p, (size_t)n2 * 12, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipStreamSynchronize(s));
+  SF_HIP_CHECK(hipGetLastError());
   for (uint32_t f = 0, k = 0; f < F; f++) verdict_out[f] = !keep1[f] ? 1 : (keep2[k++] ? 0 : 2);   // 0 kept, 1 degenerate, 2 duplicate
   *degenerate_out = F - n1;
   *duplicate_out = n1 - n2;
@@ -604,16 +592,16 @@ SF_API int sf_clean_stage_components(int device, uint32_t F, const uint32_t* tri
   Work W;
   if ((rc = work_alloc(W, 1, F, false, P_COMPONENTS)) != SF_OK) return rc;
   hipStream_t s = W.s;
-  CL_CHECK(hipMemcpyAsync(W.d_tri.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
-  CL_CHECK(hipMemsetAsync(W.d_count.p, 0, 64, s));
+  SF_HIP_CHECK(hipMemcpyAsync(W.d_tri.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
+  SF_HIP_CHECK(hipMemsetAsync(W.d_count.p, 0, 64, s));
   uint32_t n3 = 0;
   if ((rc = run_components(W, F, min_faces, &n3)) != SF_OK) return rc;
-  CL_CHECK(hipMemcpyAsync(root_out, W.d_root.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipMemcpyAsync(size_out, W.d_size.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));   // by root; 0 elsewhere
-  CL_CHECK(hipMemcpyAsync(keep_out, W.d_keep.p, F, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipMemcpyAsync(counters, W.d_count.p, 12, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipStreamSynchronize(s));
-  CL_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(root_out, W.d_root.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipMemcpyAsync(size_out, W.d_size.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));   // by root; 0 elsewhere
+  SF_HIP_CHECK(hipMemcpyAsync(keep_out, W.d_keep.p, F, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipMemcpyAsync(counters, W.d_count.p, 12, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipStreamSynchronize(s));
+  SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }
 
@@ -628,16 +616,16 @@ SF_API int sf_clean_stage_compact(int device, uint32_t V, uint32_t F, const floa
   Work W;
   if ((rc = work_alloc(W, V, F, col != nullptr, P_COMPACT)) != SF_OK) return rc;
   hipStream_t s = W.s;
-  CL_CHECK(hipMemcpyAsync(W.d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, s));
-  if (col) CL_CHECK(hipMemcpyAsync(W.d_col.p, col, (size_t)V * 4, hipMemcpyHostToDevice, s));
-  if (F > 0) CL_CHECK(hipMemcpyAsync(W.d_tri.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
-  CL_CHECK(hipMemsetAsync(W.d_count.p, 0, 64, s));
+  SF_HIP_CHECK(hipMemcpyAsync(W.d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, s));
+  if (col) SF_HIP_CHECK(hipMemcpyAsync(W.d_col.p, col, (size_t)V * 4, hipMemcpyHostToDevice, s));
+  if (F > 0) SF_HIP_CHECK(hipMemcpyAsync(W.d_tri.p, tri, (size_t)F * 12, hipMemcpyHostToDevice, s));
+  SF_HIP_CHECK(hipMemsetAsync(W.d_count.p, 0, 64, s));
   sf_mesh m;
   uint32_t vout = 0, counters[16];
   if ((rc = run_compact(W, F, col != nullptr, &m, &vout, counters)) != SF_OK) return rc;
-  CL_CHECK(hipMemcpyAsync(used_out, W.d_used.p, (size_t)V * 4, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipMemcpyAsync(remap_out, W.d_remap.p, (size_t)V * 4, hipMemcpyDeviceToHost, s));
-  CL_CHECK(hipStreamSynchronize(s));
+  SF_HIP_CHECK(hipMemcpyAsync(used_out, W.d_used.p, (size_t)V * 4, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipMemcpyAsync(remap_out, W.d_remap.p, (size_t)V * 4, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipStreamSynchronize(s));
   std::memcpy(pos_out, m.pos.data(), m.pos.size() * 4);
   if (col) std::memcpy(col_out, m.col.data(), m.col.size());
   if (F > 0) std::memcpy(tri_out, m.tri.data(), m.tri.size() * 4);

@@ -15,9 +15,11 @@
 #include <cstring>
 
 #include "depth_lut_internal.h"
+#include "hip_util.h"
 
 namespace {
 
+constexpr const char* LUT_NEEDS_DEVICE = "pass device -1 for the host path, there is no silent fallback";
 constexpr int LUT_GROUP = 8;   // images whose loads are in flight together
 
 template <int T>
@@ -91,20 +93,12 @@ int pick_block(int ns) {   // the largest workgroup whose sums fit the LDS budge
   return 0;
 }
 
-int need_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: pass device -1 for the host path, there is no silent fallback");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
-  return SF_OK;
-}
-
 }  // namespace
 
 int lut_dev_create(sf_lut_estimator* e) {
   e->block = pick_block(e->g.ns);
   if (!e->block) return sf::fail(SF_ERR_PARAM, "n_slices %d: a lane's sums do not fit the LDS (limit %d)", e->g.ns, LUT_MAX_SLICES);
-  const int rc = need_device(e->device);
+  const int rc = sf::open_device(e->device, SF_ERR_INVALID_ARG, LUT_NEEDS_DEVICE);
   if (rc != SF_OK) return rc;
   const size_t cells = (size_t)e->g.xres * e->g.yres * e->g.ns, px = (size_t)e->g.w * e->g.h;
   SF_HIP_CHECK(hipMalloc((void**)&e->d_acc, cells * 4));
@@ -121,7 +115,7 @@ int lut_dev_create(sf_lut_estimator* e) {
 }
 
 void lut_dev_destroy(sf_lut_estimator* e) {
-  (void)hipSetDevice(e->device);
+  if (hipSetDevice(e->device) != hipSuccess) (void)hipGetLastError();   // an estimator whose device was refused at create: no error is left for the next launch check
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   for (void* p : {(void*)e->d_acc, (void*)e->d_div, (void*)e->d_out, (void*)e->d_tab, (void*)e->d_stage})
     if (p) (void)hipFree(p);
@@ -186,52 +180,33 @@ int lut_dev_finish(sf_lut_estimator* e, float* table) {
 // n images of k.w x k.h through `table` (host memory).  Synchronous.
 int lut_dev_apply(int device, const LutApplyK& k, const float* table, int n, const void* const* in, void* const* out, bool host_pixels, float* kernel_us) {
   if (n < 1 || n > 65535) return sf::fail(SF_ERR_INVALID_ARG, "batch of %d images (limit 65535)", n);
-  const int rc = need_device(device);
+  const int rc = sf::open_device(device, SF_ERR_INVALID_ARG, LUT_NEEDS_DEVICE);
   if (rc != SF_OK) return rc;
   const size_t cells = (size_t)k.xr * k.yr * k.zr, px = (size_t)k.w * k.h;
-  float* d_table = nullptr;
-  LutApplyImage* d_tab = nullptr;
-  uint16_t* d_px = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  sf::DevBuf d_table, d_tab, d_px;
+  sf::EventSpan span;
   std::vector<LutApplyImage> t(n);
-  auto run = [&]() -> int {
-    SF_HIP_CHECK(hipMalloc((void**)&d_table, cells * 4));
-    SF_HIP_CHECK(hipMalloc((void**)&d_tab, sizeof(LutApplyImage) * n));
-    SF_HIP_CHECK(hipMemcpy(d_table, table, cells * 4, hipMemcpyHostToDevice));
-    if (host_pixels) {
-      SF_HIP_CHECK(hipMalloc((void**)&d_px, px * 2 * 2 * (size_t)n));
-      for (int j = 0; j < n; j++) {
-        t[j].in = d_px + px * (2 * (size_t)j);
-        t[j].out = d_px + px * (2 * (size_t)j + 1);
-        SF_HIP_CHECK(hipMemcpy((void*)t[j].in, in[j], px * 2, hipMemcpyHostToDevice));
-      }
-    } else {
-      for (int j = 0; j < n; j++) t[j] = LutApplyImage{(const uint16_t*)in[j], (uint16_t*)out[j]};
+  SF_HIP_CHECK(d_table.alloc(cells * 4));
+  SF_HIP_CHECK(d_tab.alloc(sizeof(LutApplyImage) * n));
+  SF_HIP_CHECK(hipMemcpy(d_table.p, table, cells * 4, hipMemcpyHostToDevice));
+  if (host_pixels) {
+    SF_HIP_CHECK(d_px.alloc(px * 2 * 2 * (size_t)n));
+    for (int j = 0; j < n; j++) {
+      t[j].in = d_px.as<uint16_t>() + px * (2 * (size_t)j);
+      t[j].out = d_px.as<uint16_t>() + px * (2 * (size_t)j + 1);
+      SF_HIP_CHECK(hipMemcpy((void*)t[j].in, in[j], px * 2, hipMemcpyHostToDevice));
     }
-    SF_HIP_CHECK(hipMemcpy(d_tab, t.data(), sizeof(LutApplyImage) * n, hipMemcpyHostToDevice));
-    if (kernel_us) {
-      SF_HIP_CHECK(hipEventCreate(&e0));
-      SF_HIP_CHECK(hipEventCreate(&e1));
-      SF_HIP_CHECK(hipEventRecord(e0, nullptr));
-    }
-    hipLaunchKernelGGL(k_lut_apply, dim3((unsigned)((px + 255) / 256), (unsigned)n), dim3(256), 0, nullptr, k, d_table, d_tab);
-    SF_HIP_CHECK(hipGetLastError());
-    if (kernel_us) {
-      SF_HIP_CHECK(hipEventRecord(e1, nullptr));
-      SF_HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0;
-      SF_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      *kernel_us = ms * 1e3f;
-    }
-    SF_HIP_CHECK(hipDeviceSynchronize());
-    if (host_pixels)
-      for (int j = 0; j < n; j++) SF_HIP_CHECK(hipMemcpy(out[j], t[j].out, px * 2, hipMemcpyDeviceToHost));
-    return SF_OK;
-  };
-  const int r = run();
-  for (void* p : {(void*)d_table, (void*)d_tab, (void*)d_px})
-    if (p) (void)hipFree(p);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return r;
+  } else {
+    for (int j = 0; j < n; j++) t[j] = LutApplyImage{(const uint16_t*)in[j], (uint16_t*)out[j]};
+  }
+  SF_HIP_CHECK(hipMemcpy(d_tab.p, t.data(), sizeof(LutApplyImage) * n, hipMemcpyHostToDevice));
+  if (kernel_us) span.begin(nullptr);
+  hipLaunchKernelGGL(k_lut_apply, dim3((unsigned)((px + 255) / 256), (unsigned)n), dim3(256), 0, nullptr, k, d_table.as<float>(), d_tab.as<LutApplyImage>());
+  SF_HIP_CHECK(hipGetLastError());
+  if (kernel_us) span.end(nullptr);
+  SF_HIP_CHECK(hipDeviceSynchronize());
+  if (kernel_us) *kernel_us = span.us();
+  if (host_pixels)
+    for (int j = 0; j < n; j++) SF_HIP_CHECK(hipMemcpy(out[j], t[j].out, px * 2, hipMemcpyDeviceToHost));
+  return SF_OK;
 }

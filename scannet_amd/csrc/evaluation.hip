@@ -29,6 +29,8 @@ namespace {
 using sf::ev::KEY_SKIP;
 using sf::ev::MODE_2D;
 using sf::ev::MODE_3D;
+using sf::DeviceScope;
+using sf::same_device;
 
 constexpr uint32_t THREADS = 256, WAVES = THREADS / 64;
 constexpr uint32_t MAX_BLOCKS = 2048;
@@ -450,61 +452,6 @@ __global__ __launch_bounds__(THREADS) void k_eval_overlaps_images(const T* __res
   }
 }
 
-bool on_device(const void* p, int* device) {
-  if (!p) return false;
-  hipPointerAttribute_t a;
-  std::memset(&a, 0, sizeof(a));
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (device) *device = a.device;
-  return a.type == hipMemoryTypeDevice;
-}
-
-int need_device(int device, const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    return sf::fail(SF_ERR_DEVICE, "no HIP device: %s on a device needs an MI355X (device = -1 is the host path)", who);
-  }
-  if (device >= ndev) return sf::fail(SF_ERR_DEVICE, "%s: device %d of %d", who, device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
-  return SF_OK;
-}
-
-// the device of a _device call is current for the launch only: the caller's current device is put back when the call returns
-struct DeviceScope {
-  int old = -1;
-  bool changed = false;
-  DeviceScope() = default;
-  DeviceScope(const DeviceScope&) = delete;
-  DeviceScope& operator=(const DeviceScope&) = delete;
-  ~DeviceScope() { if (changed) (void)hipSetDevice(old); }
-  hipError_t enter(int dev) {
-    hipError_t e = hipGetDevice(&old);
-    if (e != hipSuccess || old == dev) return e;
-    e = hipSetDevice(dev);
-    changed = e == hipSuccess;
-    return e;
-  }
-};
-
-// every pointer of a _device call must be device memory, all on one device: that device is made current for the life of `scope`.  The look-ups are
-// hipPointerGetAttributes, a query on the host that waits for nothing on the device.
-int same_device(const void* const* ptrs, int count, const char* who, DeviceScope& scope) {
-  int dev = -1;
-  for (int i = 0; i < count; i++) {
-    if (!ptrs[i]) continue;
-    int d = -1;
-    if (!on_device(ptrs[i], &d)) return sf::fail(SF_ERR_INVALID_ARG, "%s: argument %d is not device memory", who, i);
-    if (dev >= 0 && d != dev) return sf::fail(SF_ERR_INVALID_ARG, "%s: arguments on devices %d and %d", who, dev, d);
-    dev = d;
-  }
-  if (dev >= 0) SF_HIP_CHECK(scope.enter(dev));
-  return SF_OK;
-}
-
 template <typename T>
 int launch_confusion_t(const T* gt, const T* pred, uint64_t n, uint64_t valid, uint32_t dim, int mode, hipStream_t s, unsigned long long* confusion,
                        unsigned long long* oor) {
@@ -612,7 +559,7 @@ namespace ev {
 // host arrays in, host counters out (added to): copy up, count, read back
 int confusion_on_device(const void* gt, const void* pred, int elem_bytes, uint64_t n, uint64_t valid, uint32_t dim, int mode, int device, uint64_t* confusion,
                         uint64_t* out_of_range) {
-  if (int rc = need_device(device, "sf_eval_confusion")) return rc;
+  if (int rc = open_device(device, SF_ERR_DEVICE, "%s on a device needs an MI355X (device = -1 is the host path)", "sf_eval_confusion")) return rc;
   StreamGuard sg;
   SF_HIP_CHECK(hipStreamCreate(&sg.s));
   const size_t cells = (size_t)dim * dim + 1, bytes = (size_t)n * elem_bytes;
@@ -637,7 +584,7 @@ int confusion_on_device(const void* gt, const void* pred, int elem_bytes, uint64
 
 int confusion_images_on_device(const void* gt, const void* pred, int elem_bytes, uint32_t batch, uint32_t gw, uint32_t gh, uint32_t pw, uint32_t ph, uint32_t dw,
                                uint32_t dh, uint32_t dim, int device, uint64_t* confusion, uint64_t* out_of_range) {
-  if (int rc = need_device(device, "sf_eval_confusion_images")) return rc;
+  if (int rc = open_device(device, SF_ERR_DEVICE, "%s on a device needs an MI355X (device = -1 is the host path)", "sf_eval_confusion_images")) return rc;
   StreamGuard sg;
   SF_HIP_CHECK(hipStreamCreate(&sg.s));
   const size_t cells = (size_t)dim * dim + 1;
@@ -660,7 +607,7 @@ int confusion_images_on_device(const void* gt, const void* pred, int elem_bytes,
 }
 
 int overlaps_on_device(const uint32_t* slot, uint64_t n, uint32_t G, const uint8_t* masks, uint32_t P, uint64_t stride, int device, uint32_t* table) {
-  if (int rc = need_device(device, "sf_eval_instance_overlaps")) return rc;
+  if (int rc = open_device(device, SF_ERR_DEVICE, "%s on a device needs an MI355X (device = -1 is the host path)", "sf_eval_instance_overlaps")) return rc;
   if (P == 0) return SF_OK;
   StreamGuard sg;
   SF_HIP_CHECK(hipStreamCreate(&sg.s));
@@ -682,7 +629,7 @@ int overlaps_on_device(const uint32_t* slot, uint64_t n, uint32_t G, const uint8
 // host images in, the host plan out: copy up, count, compact, read back; nothing is written when an image holds more than `capacity` instances
 int image_plan_on_device(const void* gt, int elem_bytes, uint32_t batch, uint32_t n, const ValidSet& vs, uint32_t capacity, int device, uint32_t* count,
                          int32_t* instance_id, uint32_t* instance_pixels) {
-  if (int rc = need_device(device, "sf_eval_image_plan")) return rc;
+  if (int rc = open_device(device, SF_ERR_DEVICE, "%s on a device needs an MI355X (device = -1 is the host path)", "sf_eval_image_plan")) return rc;
   StreamGuard sg;
   SF_HIP_CHECK(hipStreamCreate(&sg.s));
   const size_t bytes = (size_t)batch * n * elem_bytes, cells = instance_id ? (size_t)batch * capacity : 0;
@@ -720,7 +667,7 @@ int image_plan_on_device(const void* gt, int elem_bytes, uint32_t batch, uint32_
 int overlaps_images_on_device(const void* gt, int elem_bytes, uint32_t batch, uint32_t n, const ValidSet& vs, uint32_t capacity, const uint32_t* count,
                               const int32_t* instance_id, const uint8_t* masks, uint32_t P, uint64_t stride, const uint32_t* mask_image, int device,
                               uint32_t* table) {
-  if (int rc = need_device(device, "sf_eval_overlaps_images")) return rc;
+  if (int rc = open_device(device, SF_ERR_DEVICE, "%s on a device needs an MI355X (device = -1 is the host path)", "sf_eval_overlaps_images")) return rc;
   if (P == 0) return SF_OK;
   StreamGuard sg;
   SF_HIP_CHECK(hipStreamCreate(&sg.s));

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "common.h"
+#include "hip_util.h"
 #include "scanfuse.h"
 
 namespace {
@@ -158,12 +159,9 @@ SF_API int sf_exchange_create(const char* rendezvous_dir, int rank, int ranks, i
       me.rccl_ok = x->rccl.ok() ? 1 : 0;
     }
     {
-      void* probe = nullptr;
+      sf::DevBuf probe;
       hipIpcMemHandle_t h;
-      if (hipMalloc(&probe, PAD) == hipSuccess) {
-        me.ipc_ok = hipIpcGetMemHandle(&h, probe) == hipSuccess ? 1 : 0;
-        (void)hipFree(probe);
-      }
+      if (probe.alloc(PAD) == hipSuccess) me.ipc_ok = hipIpcGetMemHandle(&h, probe.p) == hipSuccess ? 1 : 0;
       (void)hipGetLastError();
     }
     if (!put_file(x->dir + "/dev" + std::to_string(rank), &me, sizeof me)) return fail_with(sf::fail(SF_ERR_IO, "exchange: could not write into %s", x->dir.c_str()));
@@ -229,9 +227,9 @@ SF_API int sf_exchange_boundary(sf_exchange* x, sf_fuser* f, uint64_t* sent, uin
     if (rc != SF_OK) return rc;
     // one device buffer: [coords n x 12 | pad][voxels n x 4096]
     const size_t coord_b = padded((size_t)n * 12), bytes = coord_b + (size_t)n * 4096;
-    uint8_t* mine = nullptr;
-    SFX_HIP(hipMalloc((void**)&mine, bytes ? bytes : PAD));
-    struct Free { void* p; ~Free() { if (p) (void)hipFree(p); } } free_mine{mine};
+    sf::DevBuf own_mine, own_cnt, own_theirs;
+    SFX_HIP(own_mine.alloc(bytes ? bytes : PAD));
+    uint8_t* mine = own_mine.as<uint8_t>();
     if (n) {
       rc = sf_fuser_export_boundary(f, reinterpret_cast<int32_t*>(mine), mine + coord_b, n, &m, 1);
       if (rc != SF_OK) return rc;
@@ -239,9 +237,8 @@ SF_API int sf_exchange_boundary(sf_exchange* x, sf_fuser* f, uint64_t* sent, uin
     }
     if (x->transport == SF_EXCHANGE_RCCL) {
       // counts first (8 bytes each way), then the payloads; a group makes the send and the receive of a rank one operation (no ordering between ranks to get wrong)
-      uint64_t* d_cnt = nullptr;
-      SFX_HIP(hipMalloc((void**)&d_cnt, 2 * PAD));
-      Free free_cnt{d_cnt};
+      SFX_HIP(own_cnt.alloc(2 * PAD));
+      uint64_t* d_cnt = own_cnt.as<uint64_t>();
       SFX_HIP(hipMemcpyAsync(d_cnt, &n, 8, hipMemcpyHostToDevice, x->stream));
       SFX_NCCL(x, x->rccl.GroupStart());
       SFX_NCCL(x, x->rccl.Send(d_cnt, 8, NCCL_UINT8, below, x->comm, x->stream));
@@ -251,9 +248,8 @@ SF_API int sf_exchange_boundary(sf_exchange* x, sf_fuser* f, uint64_t* sent, uin
       SFX_HIP(hipStreamSynchronize(x->stream));
       if (k > (1ull << 26)) return sf::fail(SF_ERR_BOUNDS, "exchange: rank %d announces %llu boundary blocks", above, (unsigned long long)k);
       const size_t kcoord_b = padded((size_t)k * 12), kbytes = kcoord_b + (size_t)k * 4096;
-      uint8_t* theirs = nullptr;
-      SFX_HIP(hipMalloc((void**)&theirs, kbytes ? kbytes : PAD));
-      Free free_theirs{theirs};
+      SFX_HIP(own_theirs.alloc(kbytes ? kbytes : PAD));
+      uint8_t* theirs = own_theirs.as<uint8_t>();
       if (n || k) {
         SFX_NCCL(x, x->rccl.GroupStart());
         if (n) SFX_NCCL(x, x->rccl.Send(mine, bytes, NCCL_UINT8, below, x->comm, x->stream));

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "hip_util.h"
 #include "exp64.h"
 
 namespace {
@@ -239,10 +240,7 @@ SF_API void sf_filter2d_destroy(sf_filter2d* f) {
 
 SF_API int sf_filter2d_create(int depth_width, int depth_height, int color_width, int color_height, int device, sf_filter2d** out) {
   if (!out || depth_width < 2 || depth_height < 2 || color_width < 2 || color_height < 2) return sf::fail(SF_ERR_INVALID_ARG, "invalid image dimensions");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: libscanfuse has no CPU fallback, the annotation filter needs an MI355X");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "libscanfuse has no CPU fallback, the annotation filter needs an MI355X")) return rc;
   sf_filter2d* f = new sf_filter2d();
   f->device = device;
   f->dw = depth_width; f->dh = depth_height; f->cw = color_width; f->ch = color_height;
@@ -389,29 +387,18 @@ __global__ __launch_bounds__(256) void k_f2d_selftest_gauss(float sigma, const f
   if (dx) out_d[i] = gauss_d2(sigma, dx[i], dy[i], s_exp);
 }
 
-// device buffers of one hook call: freed when the call returns, whichever way
-struct StageBufs {
-  void* p[8] = {};
-  int n = 0;
-  ~StageBufs() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
-  template <class T> hipError_t put(T** out, const T* host, size_t count) {   // allocate, and upload `host` when given
-    hipError_t e = hipMalloc((void**)out, std::max(count, (size_t)1) * sizeof(T));
-    if (e != hipSuccess) return e;
-    p[n++] = *out;
-    return host && count ? hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-  }
-};
+// one device buffer of a hook call (freed when the call returns, whichever way): allocate, and upload `host` when given
+template <class T> hipError_t stage_put(sf::DevBuf& buf, T** out, const T* host, size_t count) {
+  const hipError_t e = buf.alloc(count * sizeof(T));
+  *out = buf.as<T>();
+  if (e != hipSuccess) return e;
+  return host && count ? hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+}
 template <class T> hipError_t stage_finish(T* host, const T* dev, size_t count) {   // launch error, then the (synchronising) download
   const hipError_t e = hipGetLastError();
   return e != hipSuccess ? e : hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost);
 }
-int stage_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: libscanfuse has no CPU fallback, the annotation filter needs an MI355X");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
-  return SF_OK;
-}
+int stage_device(int device) { return sf::open_device(device, SF_ERR_INVALID_ARG, "libscanfuse has no CPU fallback, the annotation filter needs an MI355X"); }
 constexpr int F2D_MAX_SIDE = 1 << 14;   // keeps every pixel count of a hook call inside an int
 #define F2D_STAGE_DEVICE(device)                          \
   do {                                                    \
@@ -426,12 +413,12 @@ SF_API int sf_filter2d_stage_prepare(int device, const uint16_t* depth16, int dn
   if (!depth16 || !rgb || !depth_out || !intensity_out || dn < 1 || cn < 1 || dn > F2D_MAX_SIDE * F2D_MAX_SIDE || cn > F2D_MAX_SIDE * F2D_MAX_SIDE)
     return sf::fail(SF_ERR_INVALID_ARG, "invalid argument");
   F2D_STAGE_DEVICE(device);
-  StageBufs b;
+  sf::DevBuf b[4];
   uint16_t* d16; uint8_t* c; float *d, *in;
-  SF_HIP_CHECK(b.put(&d16, depth16, (size_t)dn));
-  SF_HIP_CHECK(b.put(&c, rgb, (size_t)cn * 3));
-  SF_HIP_CHECK(b.put(&d, (const float*)nullptr, (size_t)dn));
-  SF_HIP_CHECK(b.put(&in, (const float*)nullptr, (size_t)cn));
+  SF_HIP_CHECK(stage_put(b[0], &d16, depth16, (size_t)dn));
+  SF_HIP_CHECK(stage_put(b[1], &c, rgb, (size_t)cn * 3));
+  SF_HIP_CHECK(stage_put(b[2], &d, (const float*)nullptr, (size_t)dn));
+  SF_HIP_CHECK(stage_put(b[3], &in, (const float*)nullptr, (size_t)cn));
   launch_prepare(nullptr, d16, d, (size_t)dn, c, in, (size_t)cn);
   SF_HIP_CHECK(stage_finish(depth_out, d, (size_t)dn));
   SF_HIP_CHECK(stage_finish(intensity_out, in, (size_t)cn));
@@ -442,11 +429,11 @@ SF_API int sf_filter2d_stage_bilateral(int device, const float* in, float sigma_
   if (!in || !out || !side_ok(w, h, 1) || !(sigma_d > 0.0f) || !(sigma_r > 0.0f) || !(sigma_d <= 0.5f * F2D_MAX_RADIUS))
     return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (the window radius ceil(2 sigma_d) is at most %d)", F2D_MAX_RADIUS);
   F2D_STAGE_DEVICE(device);
-  StageBufs b;
+  sf::DevBuf b[2];
   float *di, *dout;
   const size_t n = (size_t)w * h;
-  SF_HIP_CHECK(b.put(&di, in, n));
-  SF_HIP_CHECK(b.put(&dout, (const float*)nullptr, n));
+  SF_HIP_CHECK(stage_put(b[0], &di, in, n));
+  SF_HIP_CHECK(stage_put(b[1], &dout, (const float*)nullptr, n));
   launch_bilateral(nullptr, dout, di, sigma_d, sigma_r, w, h);
   SF_HIP_CHECK(stage_finish(out, dout, n));
   return SF_OK;
@@ -455,10 +442,10 @@ SF_API int sf_filter2d_stage_bilateral(int device, const float* in, float sigma_
 SF_API int sf_filter2d_stage_resample_float(int device, const float* in, int iw, int ih, float* out, int ow, int oh) {
   if (!in || !out || !side_ok(iw, ih, 2) || !side_ok(ow, oh, 2)) return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (every side is at least 2)");
   F2D_STAGE_DEVICE(device);
-  StageBufs b;
+  sf::DevBuf b[2];
   float *di, *dout;
-  SF_HIP_CHECK(b.put(&di, in, (size_t)iw * ih));
-  SF_HIP_CHECK(b.put(&dout, out, (size_t)ow * oh));
+  SF_HIP_CHECK(stage_put(b[0], &di, in, (size_t)iw * ih));
+  SF_HIP_CHECK(stage_put(b[1], &dout, out, (size_t)ow * oh));
   launch_resample_float(nullptr, dout, ow, oh, di, iw, ih);
   SF_HIP_CHECK(stage_finish(out, dout, (size_t)ow * oh));
   return SF_OK;
@@ -467,10 +454,10 @@ SF_API int sf_filter2d_stage_resample_float(int device, const float* in, int iw,
 SF_API int sf_filter2d_stage_resample_uchar(int device, const uint8_t* in, int iw, int ih, uint8_t* out, int ow, int oh) {
   if (!in || !out || !side_ok(iw, ih, 2) || !side_ok(ow, oh, 2)) return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (every side is at least 2)");
   F2D_STAGE_DEVICE(device);
-  StageBufs b;
+  sf::DevBuf b[2];
   uint8_t *di, *dout;
-  SF_HIP_CHECK(b.put(&di, in, (size_t)iw * ih));
-  SF_HIP_CHECK(b.put(&dout, out, (size_t)ow * oh));
+  SF_HIP_CHECK(stage_put(b[0], &di, in, (size_t)iw * ih));
+  SF_HIP_CHECK(stage_put(b[1], &dout, out, (size_t)ow * oh));
   launch_resample_uchar(nullptr, dout, ow, oh, di, iw, ih);
   SF_HIP_CHECK(stage_finish(out, dout, (size_t)ow * oh));
   return SF_OK;
@@ -484,16 +471,16 @@ SF_API int sf_filter2d_stage_vote(int device, const uint8_t* instance_in, const 
     return sf::fail(SF_ERR_INVALID_ARG, "invalid argument (the window radius is at most %d)", F2D_MAX_RADIUS);
   F2D_STAGE_DEVICE(device);
   SF_HIP_CHECK(hipFuncSetAttribute((const void*)k_f2d_vote, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F2D_VOTE_LDS_BUDGET));   // as sf_filter2d_create
-  StageBufs b;
+  sf::DevBuf b[6];
   uint8_t *din, *dout, *ti, *tn;
   float *dd, *dint;
   const size_t n = (size_t)w * h;
-  SF_HIP_CHECK(b.put(&din, instance_in, n));
-  SF_HIP_CHECK(b.put(&dd, depth, n));
-  SF_HIP_CHECK(b.put(&dint, intensity, n));
-  SF_HIP_CHECK(b.put(&ti, instance_to_idx, (size_t)256));
-  SF_HIP_CHECK(b.put(&tn, idx_to_instance, (size_t)F2D_LABELS));
-  SF_HIP_CHECK(b.put(&dout, (const uint8_t*)nullptr, n));
+  SF_HIP_CHECK(stage_put(b[0], &din, instance_in, n));
+  SF_HIP_CHECK(stage_put(b[1], &dd, depth, n));
+  SF_HIP_CHECK(stage_put(b[2], &dint, intensity, n));
+  SF_HIP_CHECK(stage_put(b[3], &ti, instance_to_idx, (size_t)256));
+  SF_HIP_CHECK(stage_put(b[4], &tn, idx_to_instance, (size_t)F2D_LABELS));
+  SF_HIP_CHECK(stage_put(b[5], &dout, (const uint8_t*)nullptr, n));
   launch_vote(nullptr, dout, din, dd, dint, ti, tn, radius, w, h, sigma_d, sigma_r, intensity_scale);
   SF_HIP_CHECK(stage_finish(instance_out, dout, n));
   return SF_OK;
@@ -502,11 +489,11 @@ SF_API int sf_filter2d_stage_vote(int device, const uint8_t* instance_in, const 
 SF_API int sf_filter2d_stage_to_label(int device, const uint8_t* instance, const uint16_t instance_to_label[256], int n, uint16_t* label_out) {
   if (!instance || !instance_to_label || !label_out || n < 1 || n > F2D_MAX_SIDE * F2D_MAX_SIDE) return sf::fail(SF_ERR_INVALID_ARG, "invalid argument");
   F2D_STAGE_DEVICE(device);
-  StageBufs b;
+  sf::DevBuf b[3];
   uint8_t* di; uint16_t *lut, *dout;
-  SF_HIP_CHECK(b.put(&di, instance, (size_t)n));
-  SF_HIP_CHECK(b.put(&lut, instance_to_label, (size_t)256));
-  SF_HIP_CHECK(b.put(&dout, (const uint16_t*)nullptr, (size_t)n));
+  SF_HIP_CHECK(stage_put(b[0], &di, instance, (size_t)n));
+  SF_HIP_CHECK(stage_put(b[1], &lut, instance_to_label, (size_t)256));
+  SF_HIP_CHECK(stage_put(b[2], &dout, (const uint16_t*)nullptr, (size_t)n));
   launch_to_label(nullptr, dout, di, lut, (size_t)n);
   SF_HIP_CHECK(stage_finish(label_out, dout, (size_t)n));
   return SF_OK;
@@ -516,11 +503,11 @@ SF_API int sf_filter2d_selftest_gauss(int device, float sigma, const float* dist
   if (!(sigma > 0.0f) || n < 1 || n > (1u << 30) || (!dist && !dx) || (dist && !out_r) || (dx && (!dy || !out_d)) || (!dx && dy))
     return sf::fail(SF_ERR_INVALID_ARG, "invalid argument");
   F2D_STAGE_DEVICE(device);
-  StageBufs b;
+  sf::DevBuf b[5];
   float *dd = nullptr, *dr = nullptr, *dg = nullptr;
   int32_t *x = nullptr, *y = nullptr;
-  if (dist) { SF_HIP_CHECK(b.put(&dd, dist, (size_t)n)); SF_HIP_CHECK(b.put(&dr, (const float*)nullptr, (size_t)n)); }
-  if (dx) { SF_HIP_CHECK(b.put(&x, dx, (size_t)n)); SF_HIP_CHECK(b.put(&y, dy, (size_t)n)); SF_HIP_CHECK(b.put(&dg, (const float*)nullptr, (size_t)n)); }
+  if (dist) { SF_HIP_CHECK(stage_put(b[0], &dd, dist, (size_t)n)); SF_HIP_CHECK(stage_put(b[1], &dr, (const float*)nullptr, (size_t)n)); }
+  if (dx) { SF_HIP_CHECK(stage_put(b[2], &x, dx, (size_t)n)); SF_HIP_CHECK(stage_put(b[3], &y, dy, (size_t)n)); SF_HIP_CHECK(stage_put(b[4], &dg, (const float*)nullptr, (size_t)n)); }
   hipLaunchKernelGGL(k_f2d_selftest_gauss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, sigma, dd, x, y, dr, dg, (unsigned)n);
   if (dist) SF_HIP_CHECK(stage_finish(out_r, dr, (size_t)n));
   if (dx) SF_HIP_CHECK(stage_finish(out_d, dg, (size_t)n));

@@ -247,11 +247,7 @@ SF_API int sf_fuser_create(const sf_params* p, int device, sf_fuser** out) {
     return sf::fail(SF_ERR_INVALID_ARG, "frustum_mode 1 normalises z by the sensor depth range: depth_max must exceed depth_min");
   if ((uint64_t)p->hash_num_buckets * p->hash_bucket_size > 0x7FFFFFFFull || p->num_sdf_blocks > 0x3FFFFFFFu)
     return sf::fail(SF_ERR_INVALID_ARG, "hash table / heap too large for 32-bit slot indices");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return sf::fail(SF_ERR_DEVICE, "no HIP device: libscanfuse has no CPU fallback, the fuser needs an MI355X");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "libscanfuse has no CPU fallback, the fuser needs an MI355X")) return rc;
   // (until round 6 the first fuser of a process started sf_fuse_run's side streams and rings on a background thread here -- 90 MB pinned and
   // 330 MB of device memory also for callers that never run a file.  A caller that will -- bin/depthsensing, bench.py, tools/e2e_bench.py -- asks with
   // sf_fuse_run_prepare(file, params, device) before this call; without it the first sf_fuse_run makes its set itself.)

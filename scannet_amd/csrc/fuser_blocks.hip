@@ -7,6 +7,7 @@
 
 #include "fuser_device.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 
 namespace {
 
@@ -212,16 +213,13 @@ SF_API int sf_fuser_export_blocks(sf_fuser* f, int32_t* coords, void* voxels, ui
   if (!coords || !voxels) return sf::fail(SF_ERR_INVALID_ARG, "coords and voxels must both be given");
   if (capacity < (uint64_t)n) return sf::fail(SF_ERR_BOUNDS, "capacity %llu < %d live blocks", (unsigned long long)capacity, n);
   if (n == 0) return SF_OK;
-  int32_t* d_coords = nullptr;
-  uint4* d_vox = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&d_coords, (size_t)n * 12));
-  if (hipMalloc((void**)&d_vox, (size_t)n * 4096) != hipSuccess) { (void)hipFree(d_coords); return sf::fail(SF_ERR_DEVICE, "hipMalloc export buffer failed"); }
-  hipLaunchKernelGGL(k_gather, dim3(n < 65535 ? n : 65535), dim3(256), 0, f->stream, f->voxels, f->block_keys, f->compact, n, d_coords, d_vox);
-  hipError_t e1 = hipMemcpyAsync(coords, d_coords, (size_t)n * 12, hipMemcpyDeviceToHost, f->stream);
-  hipError_t e2 = hipMemcpyAsync(voxels, d_vox, (size_t)n * 4096, hipMemcpyDeviceToHost, f->stream);
+  sf::DevBuf d_coords, d_vox;
+  SF_HIP_CHECK(d_coords.alloc((size_t)n * 12));
+  SF_HIP_CHECK(d_vox.alloc((size_t)n * 4096));
+  hipLaunchKernelGGL(k_gather, dim3(n < 65535 ? n : 65535), dim3(256), 0, f->stream, f->voxels, f->block_keys, f->compact, n, d_coords.as<int32_t>(), d_vox.as<uint4>());
+  hipError_t e1 = hipMemcpyAsync(coords, d_coords.p, (size_t)n * 12, hipMemcpyDeviceToHost, f->stream);
+  hipError_t e2 = hipMemcpyAsync(voxels, d_vox.p, (size_t)n * 4096, hipMemcpyDeviceToHost, f->stream);
   hipError_t e3 = sf_quiesce(f);
-  (void)hipFree(d_coords);
-  (void)hipFree(d_vox);
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return sf::fail(SF_ERR_DEVICE, "export copy failed");
   return SF_OK;
 }
@@ -270,28 +268,26 @@ SF_API int sf_fuser_export_blocks_where(sf_fuser* f, int axis, int32_t lo, int32
   *n_out = 0;
   if (n_live == 0) return SF_OK;
   SF_HIP_CHECK(hipMemsetAsync(&f->counters[C_GC_FREED], 0, 4, f->stream));  // scratch counter (GC is synchronous, never concurrent)
-  int32_t* d_coords = nullptr;
-  uint4* d_vox = nullptr;
   const bool want = coords != nullptr;
   const int cap = (int)std::min<uint64_t>(capacity, 0x7FFFFFFFull);
-  if (want && !dst_on_device && cap > 0) {
-    SF_HIP_CHECK(hipMalloc((void**)&d_coords, (size_t)cap * 12));
-    if (hipMalloc((void**)&d_vox, (size_t)cap * 4096) != hipSuccess) { (void)hipFree(d_coords); return sf::fail(SF_ERR_DEVICE, "hipMalloc export buffer failed"); }
-  } else if (want) {
-    d_coords = coords;
-    d_vox = (uint4*)voxels;
+  const bool staged = want && !dst_on_device && cap > 0;   // a host destination: gathered into buffers of the call's own, then copied out
+  sf::DevBuf own_coords, own_vox;
+  if (staged) {
+    SF_HIP_CHECK(own_coords.alloc((size_t)cap * 12));
+    SF_HIP_CHECK(own_vox.alloc((size_t)cap * 4096));
   }
+  int32_t* d_coords = staged ? own_coords.as<int32_t>() : coords;   // null when the call only counts
+  uint4* d_vox = staged ? own_vox.as<uint4>() : (uint4*)voxels;
   hipLaunchKernelGGL(k_gather_where, dim3(n_live < 65535 ? n_live : 65535), dim3(256), 0, f->stream, f->voxels, f->block_keys, f->compact, n_live, axis, lo, hi,
                      want ? cap : 0, &f->counters[C_GC_FREED], d_coords, want && cap > 0 ? d_vox : nullptr, f->pk);
   int32_t n = 0;
   hipError_t e = hipMemcpyAsync(&n, &f->counters[C_GC_FREED], 4, hipMemcpyDeviceToHost, f->stream);
   if (e == hipSuccess) e = sf_quiesce(f);
-  if (e == hipSuccess && want && !dst_on_device && cap > 0) {
+  if (e == hipSuccess && staged) {
     const size_t m = (size_t)std::min(n, cap);
     e = hipMemcpy(coords, d_coords, m * 12, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(voxels, d_vox, m * 4096, hipMemcpyDeviceToHost);
   }
-  if (want && !dst_on_device && cap > 0) { (void)hipFree(d_coords); (void)hipFree(d_vox); }
   if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "export failed: %s", hipGetErrorString(e));
   *n_out = (uint64_t)n;
   if (want && (uint64_t)n > capacity) return sf::fail(SF_ERR_BOUNDS, "capacity %llu < %d matching blocks", (unsigned long long)capacity, n);
@@ -316,16 +312,14 @@ static int import_blocks(sf_fuser* f, const int32_t* coords, const void* voxels,
   SF_HIP_CHECK(sf_quiesce(f));
   const int32_t* d_coords = coords;
   const uint4* d_vox = (const uint4*)voxels;
-  int32_t* tmp_c = nullptr;
-  uint4* tmp_v = nullptr;
+  sf::DevBuf tmp_c, tmp_v;
   if (!src_on_device) {
-    SF_HIP_CHECK(hipMalloc((void**)&tmp_c, n * 12));
-    if (hipMalloc((void**)&tmp_v, n * 4096) != hipSuccess) { (void)hipFree(tmp_c); return sf::fail(SF_ERR_DEVICE, "hipMalloc import buffer failed"); }
-    hipError_t e = hipMemcpy(tmp_c, coords, n * 12, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(tmp_v, voxels, n * 4096, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(tmp_c); (void)hipFree(tmp_v); return sf::fail(SF_ERR_DEVICE, "import copy failed: %s", hipGetErrorString(e)); }
-    d_coords = tmp_c;
-    d_vox = tmp_v;
+    SF_HIP_CHECK(tmp_c.alloc(n * 12));
+    SF_HIP_CHECK(tmp_v.alloc(n * 4096));
+    SF_HIP_CHECK(hipMemcpy(tmp_c.p, coords, n * 12, hipMemcpyHostToDevice));
+    SF_HIP_CHECK(hipMemcpy(tmp_v.p, voxels, n * 4096, hipMemcpyHostToDevice));
+    d_coords = tmp_c.as<int32_t>();
+    d_vox = tmp_v.as<uint4>();
   }
   int32_t fail0 = 0, fail1 = 0, took = 0;
   (void)hipMemcpy(&fail0, &f->counters[C_ALLOC_FAIL], 4, hipMemcpyDeviceToHost);
@@ -336,7 +330,6 @@ static int import_blocks(sf_fuser* f, const int32_t* coords, const void* voxels,
   if (e == hipSuccess) e = hipMemcpyAsync(&took, &f->counters[C_IMPORTED], 4, hipMemcpyDeviceToHost, f->stream);
   if (e == hipSuccess) e = sf_quiesce(f);
   if (imported) *imported = (uint64_t)took;
-  if (tmp_c) { (void)hipFree(tmp_c); (void)hipFree(tmp_v); }
   if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "import failed: %s", hipGetErrorString(e));
   if (fail1 != fail0) return sf::fail(SF_ERR_CAPACITY, "%d imported blocks did not fit (heap or hash table exhausted)", fail1 - fail0);
   return SF_OK;

@@ -9,6 +9,7 @@
 
 #include "fuser_device.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 
 namespace {
 
@@ -205,8 +206,9 @@ SF_API int sf_fuser_allocate_box(sf_fuser* f, const int32_t lo_block[3], const i
   if (f->pk.slab_axis >= 0) return sf::fail(SF_ERR_UNSUPPORTED, "sf_fuser_allocate_box: a slab / stripe partition is set on this fuser");
   SF_HIP_CHECK(hipSetDevice(f->device));
   SF_HIP_CHECK(sf_quiesce(f));
-  unsigned long long* d_res = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&d_res, 16));
+  sf::DevBuf res_buf;
+  SF_HIP_CHECK(res_buf.alloc(16));
+  unsigned long long* d_res = res_buf.as<unsigned long long>();
   const int nx = hi_block[0] - lo_block[0] + 1, ny = hi_block[1] - lo_block[1] + 1;
   const uint32_t wgs = (uint32_t)((n + 255) / 256);
   const dim3 grid(wgs < (uint32_t)f->num_cus * 16u ? wgs : (uint32_t)f->num_cus * 16u);
@@ -221,12 +223,10 @@ SF_API int sf_fuser_allocate_box(sf_fuser* f, const int32_t lo_block[3], const i
   if (e == hipSuccess) e = hipMemcpyAsync(&heap_free, &f->counters[C_HEAP_FREE], 4, hipMemcpyDeviceToHost, f->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(&fail0, &f->counters[C_ALLOC_FAIL], 4, hipMemcpyDeviceToHost, f->stream);
   if (e == hipSuccess) e = sf_quiesce(f);
-  if (e != hipSuccess) { (void)hipFree(d_res); return sf::fail(SF_ERR_DEVICE, "sf_fuser_allocate_box: %s", hipGetErrorString(e)); }
-  if (res[0] > (unsigned long long)(heap_free > 0 ? heap_free : 0)) {
-    (void)hipFree(d_res);
+  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_fuser_allocate_box: %s", hipGetErrorString(e));
+  if (res[0] > (unsigned long long)(heap_free > 0 ? heap_free : 0))
     return sf::fail(SF_ERR_CAPACITY, "sf_fuser_allocate_box: the box needs %llu new blocks, the heap has %d free (num_sdf_blocks %u); nothing was changed", res[0],
                     heap_free, f->pk.num_blocks);
-  }
   if (res[0] > 0) {
     hipLaunchKernelGGL(k_alloc_box, grid, dim3(256), 0, f->stream, lo_block[0], lo_block[1], lo_block[2], nx, ny, (uint32_t)n, 1, d_res + 1, f->table, f->heap,
                        f->block_keys, f->block_entry, f->block_flags, f->counters, f->pk);
@@ -236,7 +236,6 @@ SF_API int sf_fuser_allocate_box(sf_fuser* f, const int32_t lo_block[3], const i
   } else {
     fail1 = fail0;
   }
-  (void)hipFree(d_res);
   if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_fuser_allocate_box: %s", hipGetErrorString(e));
   if (fail1 != fail0)
     return sf::fail(SF_ERR_CAPACITY, "sf_fuser_allocate_box: %d blocks of the box found no hash slot within %d probes (hash_num_buckets %u); sf_fuser_reset empties the volume",
@@ -254,15 +253,15 @@ SF_API int sf_fuser_known_bounds(sf_fuser* f, int32_t lo_voxel[3], int32_t hi_vo
   if (rc != SF_OK) return rc;
   if (n == 0) return SF_OK;
   int32_t box[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
-  int32_t* d_box = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&d_box, sizeof(box)));
+  sf::DevBuf box_buf;
+  SF_HIP_CHECK(box_buf.alloc(sizeof(box)));
+  int32_t* d_box = box_buf.as<int32_t>();
   hipError_t e = hipMemcpyAsync(d_box, box, sizeof(box), hipMemcpyHostToDevice, f->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_known_bounds, dim3(n < f->num_cus * 8 ? n : f->num_cus * 8), dim3(256), 0, f->stream, f->voxels, f->block_keys, f->compact, n, d_box);
     e = hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, f->stream);
   }
   if (e == hipSuccess) e = sf_quiesce(f);
-  (void)hipFree(d_box);
   if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_fuser_known_bounds: %s", hipGetErrorString(e));
   uint64_t cnt;
   std::memcpy(&cnt, &box[6], 8);
@@ -299,16 +298,14 @@ SF_API int sf_fuser_export_dense(sf_fuser* f, const int32_t lo_voxel[3], const i
   A.mode = mode;
   A.voxel = f->pk.voxel;
   A.sdf = sdf; A.weight = weight; A.rgb = rgb;
-  void* tmp[3] = {nullptr, nullptr, nullptr};
+  sf::DevBuf tmp[3];   // the staging arrays of a host destination
   hipError_t e = hipSuccess;
   if (!dst_on_device) {
-    if (sdf) { e = hipMalloc(&tmp[0], total * 4); A.sdf = (float*)tmp[0]; }
-    if (e == hipSuccess && weight) { e = hipMalloc(&tmp[1], total); A.weight = (uint8_t*)tmp[1]; }
-    if (e == hipSuccess && rgb) { e = hipMalloc(&tmp[2], total * 3); A.rgb = (uint8_t*)tmp[2]; }
-    if (e != hipSuccess) {
-      for (void* p : tmp) if (p) (void)hipFree(p);
+    if (sdf) { e = tmp[0].alloc(total * 4); A.sdf = tmp[0].as<float>(); }
+    if (e == hipSuccess && weight) { e = tmp[1].alloc(total); A.weight = tmp[1].as<uint8_t>(); }
+    if (e == hipSuccess && rgb) { e = tmp[2].alloc(total * 3); A.rgb = tmp[2].as<uint8_t>(); }
+    if (e != hipSuccess)
       return sf::fail(SF_ERR_DEVICE, "sf_fuser_export_dense: hipMalloc of the staging arrays (%llu voxels) failed: %s", (unsigned long long)total, hipGetErrorString(e));
-    }
   }
   const unsigned long long items = (unsigned long long)((A.nbx + RUN - 1) / RUN) * (unsigned long long)A.nby * (unsigned long long)A.nbz;
   const unsigned long long cap = (unsigned long long)f->num_cus * 16ull;
@@ -321,9 +318,9 @@ SF_API int sf_fuser_export_dense(sf_fuser* f, const int32_t lo_voxel[3], const i
   e = hipGetLastError();
   if (timed) (void)hipEventRecord(ev[1], f->stream);
   if (e == hipSuccess && !dst_on_device) {
-    if (sdf) e = hipMemcpyAsync(sdf, tmp[0], total * 4, hipMemcpyDeviceToHost, f->stream);
-    if (e == hipSuccess && weight) e = hipMemcpyAsync(weight, tmp[1], total, hipMemcpyDeviceToHost, f->stream);
-    if (e == hipSuccess && rgb) e = hipMemcpyAsync(rgb, tmp[2], total * 3, hipMemcpyDeviceToHost, f->stream);
+    if (sdf) e = hipMemcpyAsync(sdf, tmp[0].p, total * 4, hipMemcpyDeviceToHost, f->stream);
+    if (e == hipSuccess && weight) e = hipMemcpyAsync(weight, tmp[1].p, total, hipMemcpyDeviceToHost, f->stream);
+    if (e == hipSuccess && rgb) e = hipMemcpyAsync(rgb, tmp[2].p, total * 3, hipMemcpyDeviceToHost, f->stream);
   }
   const hipError_t e2 = sf_quiesce(f);
   if (timed && e == hipSuccess && e2 == hipSuccess) {
@@ -331,7 +328,6 @@ SF_API int sf_fuser_export_dense(sf_fuser* f, const int32_t lo_voxel[3], const i
     if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_dense_us = ms * 1000.0f;
   }
   for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-  for (void* p : tmp) if (p) (void)hipFree(p);
   if (e != hipSuccess || e2 != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_fuser_export_dense: %s", hipGetErrorString(e != hipSuccess ? e : e2));
   return SF_OK;
 }

@@ -6,6 +6,7 @@
 #include "fuser_device.h"
 #include "fuser_fuse.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 
 namespace {
 
@@ -482,27 +483,20 @@ SF_API int sf_fuser_calib_tile_rmw_ex(sf_fuser* f, int mode, int iters, double* 
   if ((uint32_t)n > (uint32_t)f->p.num_sdf_blocks) return sf::fail(SF_ERR_INVALID_ARG, "sf_fuser_calib_tile_rmw_ex: list length %d out of range", n);
   const int read_only = mode & 1, contiguous = (mode >> 1) & 1, G = 1 << (mode >> 2);
   const int grid = list_grid(f, (n + G - 1) / G);
-  uint32_t* sink = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&sink, 4));
-  hipEvent_t e0, e1;
-  SF_HIP_CHECK(hipEventCreate(&e0));
-  SF_HIP_CHECK(hipEventCreate(&e1));
+  sf::DevBuf sink;
+  SF_HIP_CHECK(sink.alloc(4));
+  sf::EventSpan span;
   const bool nt = sf_big_tile_set((uint32_t)n);   // the cache policy k_integrate_pipe would pick for this tile set
-  double total_ms = 0;
+  double total_us = 0;
   for (int it = 0; it < iters + 1; it++) {  // first launch untimed
-    SF_HIP_CHECK(hipEventRecord(e0, f->stream));
-    if (nt) launch_tile_rmw_g<true>(f, sl, G, grid, read_only, contiguous, sink);
-    else launch_tile_rmw_g<false>(f, sl, G, grid, read_only, contiguous, sink);
-    SF_HIP_CHECK(hipEventRecord(e1, f->stream));
-    SF_HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    SF_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    if (it > 0) total_ms += ms;
+    span.begin(f->stream);
+    if (nt) launch_tile_rmw_g<true>(f, sl, G, grid, read_only, contiguous, sink.as<uint32_t>());
+    else launch_tile_rmw_g<false>(f, sl, G, grid, read_only, contiguous, sink.as<uint32_t>());
+    span.end(f->stream);
+    SF_HIP_CHECK(hipEventSynchronize(span.b));
+    if (it > 0) total_us += span.us();
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(sink);
-  if (avg_us) *avg_us = total_ms * 1e3 / iters;
+  if (avg_us) *avg_us = total_us / iters;
   if (tiles) *tiles = (uint32_t)n;
   return SF_OK;
 }

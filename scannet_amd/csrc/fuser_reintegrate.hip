@@ -17,6 +17,7 @@
 #include "fuser_device.h"
 #include "fuser_fuse.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 
 namespace {
 
@@ -233,20 +234,16 @@ SF_API int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float
   std::vector<uint16_t> hd;
   std::vector<uint8_t> hc;
   std::vector<float> po, pn;
-  void* d_depth = nullptr;
-  void* d_rgb = nullptr;
-  auto release = [&]() { if (d_depth) (void)hipFree(d_depth); if (d_rgb) (void)hipFree(d_rgb); };
+  sf::DevBuf d_depth, d_rgb;   // freed with the call, on every way out (hipFree waits for the passes that still read them)
   SF_HIP_CHECK(hipSetDevice(f->device));
   for (uint64_t step = 0; max_steps == 0 || step < max_steps; step++) {
     uint64_t m = 0;
     rc = sf_reint_plan(integrated_poses, target_poses, n, rp, plan.data(), cap, &m);
-    if (rc != SF_OK) { release(); return rc; }
+    if (rc != SF_OK) return rc;
     if (m == 0) break;
-    if (!d_depth) {
-      if (hipMalloc(&d_depth, dbytes * cap) != hipSuccess || (with_colour && hipMalloc(&d_rgb, cbytes * cap) != hipSuccess)) {
-        release();
-        return sf::fail(SF_ERR_DEVICE, "sf_fuse_update_trajectory: hipMalloc of %llu frames failed", (unsigned long long)cap);
-      }
+    if (!d_depth.p) {
+      SF_HIP_CHECK(d_depth.alloc(dbytes * cap));
+      if (with_colour) SF_HIP_CHECK(d_rgb.alloc(cbytes * cap));
       hd.resize(f->in_px * cap);
       if (with_colour) hc.resize(cbytes * cap);
       po.resize(16 * cap);
@@ -268,21 +265,18 @@ SF_API int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float
     for (int t = 1; t < threads; t++) pool.emplace_back(work);
     work();
     for (auto& t : pool) t.join();
-    if (failed.load() != SF_OK) { release(); return sf::fail(failed.load(), "sf_fuse_update_trajectory: a planned frame could not be decoded"); }
+    if (failed.load() != SF_OK) return sf::fail(failed.load(), "sf_fuse_update_trajectory: a planned frame could not be decoded");
     for (uint64_t k = 0; k < m; k++) {
       std::memcpy(&po[16 * k], integrated_poses + 16 * plan[k], 64);
       std::memcpy(&pn[16 * k], target_poses + 16 * plan[k], 64);
     }
     // the buffers are reused by the next step: the passes of the step before have read them (the blocking copies below order behind nothing of the
     // fuser's own streams)
-    if (step > 0) { rc = sf_fuser_sync(f); if (rc != SF_OK) { release(); return rc; } }
-    if (hipMemcpy(d_depth, hd.data(), dbytes * m, hipMemcpyHostToDevice) != hipSuccess ||
-        (with_colour && hipMemcpy(d_rgb, hc.data(), cbytes * m, hipMemcpyHostToDevice) != hipSuccess)) {
-      release();
-      return sf::fail(SF_ERR_DEVICE, "sf_fuse_update_trajectory: upload failed");
-    }
-    rc = sf_fuser_reintegrate_batch_device(f, d_depth, dbytes, with_colour ? d_rgb : nullptr, cbytes, po.data(), pn.data(), m);
-    if (rc != SF_OK) { (void)sf_fuser_sync(f); release(); return rc; }
+    if (step > 0) { rc = sf_fuser_sync(f); if (rc != SF_OK) return rc; }
+    SF_HIP_CHECK(hipMemcpy(d_depth.p, hd.data(), dbytes * m, hipMemcpyHostToDevice));
+    if (with_colour) SF_HIP_CHECK(hipMemcpy(d_rgb.p, hc.data(), cbytes * m, hipMemcpyHostToDevice));
+    rc = sf_fuser_reintegrate_batch_device(f, d_depth.p, dbytes, with_colour ? d_rgb.p : nullptr, cbytes, po.data(), pn.data(), m);
+    if (rc != SF_OK) { (void)sf_fuser_sync(f); return rc; }
     for (uint64_t k = 0; k < m; k++) {
       const bool lo = pose_lost(&po[16 * k]), ln = pose_lost(&pn[16 * k]);
       if (lo) st.frames_added++;
@@ -294,7 +288,6 @@ SF_API int sf_fuse_update_trajectory(sf_fuser* f, const struct sf_sens* s, float
     st.passes += (uint64_t)sf_fuser_reintegrate_passes(f);
   }
   rc = sf_fuser_sync(f);
-  release();
   st.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (stats) *stats = st;
   return rc;

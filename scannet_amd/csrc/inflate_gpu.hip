@@ -14,6 +14,7 @@
 
 #include "codecs_internal.h"
 #include "common.h"
+#include "hip_util.h"
 #include "inflate_lanes.h"
 
 namespace {
@@ -369,28 +370,25 @@ SF_API int sf_zlib_inflate_gpu_bench(const void* const* srcs, const uint64_t* sr
   SF_HIP_CHECK(hipSetDevice(device));
   InflateBatch b;
   std::memset(&b, 0, sizeof(b));
-  std::vector<void*> owned;
-  auto release = [&]() { for (void* p : owned) (void)hipFree(p); };
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < count && e == hipSuccess; i++) {
+  sf::DevBuf words[IG_BATCH], out[IG_BATCH], plan[IG_BATCH], status;
+  for (int i = 0; i < count; i++) {
     const uint8_t* z = static_cast<const uint8_t*>(srcs[i]);
-    if (!inflate_gpu_takes(z, src_bytes[i])) { release(); return sf::fail(SF_ERR_UNSUPPORTED, "stream %d is not one final fixed-Huffman block", i); }
+    if (!inflate_gpu_takes(z, src_bytes[i])) return sf::fail(SF_ERR_UNSUPPORTED, "stream %d is not one final fixed-Huffman block", i);
     const uint32_t nb = (uint32_t)(src_bytes[i] - 2);
-    void *w = nullptr, *o = nullptr, *pl = nullptr;
-    e = hipMalloc(&w, (size_t)nb + 384);
-    if (e == hipSuccess) { owned.push_back(w); e = hipMemset(w, 0, (size_t)nb + 384); }
-    if (e == hipSuccess) e = hipMemcpy(w, z + 2, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&o, expect_bytes);
-    if (e == hipSuccess) { owned.push_back(o); e = hipMalloc(&pl, 2 * expect_bytes); }
-    if (e == hipSuccess) owned.push_back(pl);
-    b.words[i] = static_cast<const uint32_t*>(w); b.nbytes[i] = nb; b.out[i] = static_cast<uint8_t*>(o); b.plan[i] = static_cast<uint16_t*>(pl); b.tag[i] = i;
+    SF_HIP_CHECK(words[i].alloc((size_t)nb + 384));
+    SF_HIP_CHECK(hipMemset(words[i].p, 0, (size_t)nb + 384));
+    SF_HIP_CHECK(hipMemcpy(words[i].p, z + 2, nb, hipMemcpyHostToDevice));
+    SF_HIP_CHECK(out[i].alloc(expect_bytes));
+    SF_HIP_CHECK(plan[i].alloc(2 * expect_bytes));
+    b.words[i] = words[i].as<const uint32_t>(); b.nbytes[i] = nb; b.out[i] = out[i].as<uint8_t>(); b.plan[i] = plan[i].as<uint16_t>(); b.tag[i] = i;
   }
-  int32_t* d_status = nullptr;
-  if (e == hipSuccess) e = hipMalloc((void**)&d_status, 8 * IG_BATCH);
-  if (e == hipSuccess) { owned.push_back(d_status); e = hipMemset(d_status, 0, 8 * IG_BATCH); }
+  SF_HIP_CHECK(status.alloc(8 * IG_BATCH));
+  SF_HIP_CHECK(hipMemset(status.p, 0, 8 * IG_BATCH));
+  int32_t* d_status = status.as<int32_t>();
   b.expect = (uint32_t)expect_bytes;
   b.status = d_status;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
   for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
   double t_tok = 0, t_cp = 0;
   for (int r = 0; r < repeats + 1 && e == hipSuccess; r++) {   // the first round warms up
@@ -408,7 +406,6 @@ SF_API int sf_zlib_inflate_gpu_bench(const void* const* srcs, const uint64_t* sr
   int32_t st[2 * IG_BATCH] = {0};
   if (e == hipSuccess) e = hipMemcpy(st, d_status, sizeof(st), hipMemcpyDeviceToHost);
   for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-  release();
   if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_zlib_inflate_gpu_bench: %s", hipGetErrorString(e));
   for (int i = 0; i < count; i++) if (st[2 * i] != 0) return sf::fail(SF_ERR_FORMAT, "stream %d: device status %d", i, st[2 * i]);
   *us_tokens = t_tok / repeats;
@@ -424,35 +421,26 @@ SF_API int sf_zlib_inflate_gpu(const void* src_, uint64_t n, uint64_t expect_byt
   if (!src || !dst) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
   if (!inflate_gpu_takes(src, n) || (expect_bytes & 3u) || expect_bytes == 0 || expect_bytes > (1ull << 30))
     return sf::fail(SF_ERR_UNSUPPORTED, "zlib: the device inflates one final fixed-Huffman block to a multiple of 4 bytes; this stream goes to sf_zlib_inflate");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "sf_zlib_inflate_gpu needs one (sf_zlib_inflate is the host path)")) return rc;
   const uint32_t nbytes = (uint32_t)(n - 2);
-  uint32_t* d_words = nullptr;
-  uint8_t* d_out = nullptr;
-  uint16_t* d_plan = nullptr;
-  int32_t* d_status = nullptr;
-  auto release = [&]() { (void)hipFree(d_words); (void)hipFree(d_out); (void)hipFree(d_plan); (void)hipFree(d_status); };
   const size_t wbytes = ((size_t)nbytes + 3) / 4 * 4;
-  hipError_t e = hipMalloc((void**)&d_words, wbytes + 320);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, expect_bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_plan, 2 * expect_bytes);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_status, 8);
-  if (e == hipSuccess) e = hipMemset(d_status, 0, 8);
-  if (e == hipSuccess) e = hipMemset(d_words, 0, wbytes + 320);
-  if (e == hipSuccess) e = hipMemcpy(d_words, src + 2, nbytes, hipMemcpyHostToDevice);
-  int rc = SF_OK;
+  sf::DevBuf words, out, plan, stat;
+  SF_HIP_CHECK(words.alloc(wbytes + 320));
+  SF_HIP_CHECK(out.alloc(expect_bytes));
+  SF_HIP_CHECK(plan.alloc(2 * expect_bytes));
+  SF_HIP_CHECK(stat.alloc(8));
+  SF_HIP_CHECK(hipMemset(stat.p, 0, 8));
+  SF_HIP_CHECK(hipMemset(words.p, 0, wbytes + 320));
+  SF_HIP_CHECK(hipMemcpy(words.p, src + 2, nbytes, hipMemcpyHostToDevice));
+  const uint32_t* w = words.as<uint32_t>();
+  uint8_t* d_out = out.as<uint8_t>();
+  uint16_t* d_plan = plan.as<uint16_t>();
+  const int rc = inflate_gpu_batch(nullptr, 1, &w, &nbytes, &d_out, &d_plan, (uint32_t)expect_bytes, nullptr, stat.as<int32_t>());
+  if (rc != SF_OK) return rc;
   int32_t status[2] = {0, 0};
-  if (e == hipSuccess) {
-    const uint32_t* w = d_words;
-    rc = inflate_gpu_batch(nullptr, 1, &w, &nbytes, &d_out, &d_plan, (uint32_t)expect_bytes, nullptr, d_status);
-    if (rc == SF_OK) e = hipMemcpy(status, d_status, 8, hipMemcpyDeviceToHost);
-    if (rc == SF_OK && e == hipSuccess && status[0] == 0) e = hipMemcpy(dst, d_out, expect_bytes, hipMemcpyDeviceToHost);
-  }
-  release();
-  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_zlib_inflate_gpu: %s", hipGetErrorString(e));
-  if (rc == SF_OK && status[0] != 0)
+  SF_HIP_CHECK(hipMemcpy(status, stat.p, 8, hipMemcpyDeviceToHost));
+  if (status[0] == 0) SF_HIP_CHECK(hipMemcpy(dst, d_out, expect_bytes, hipMemcpyDeviceToHost));
+  if (status[0] != 0)
     return sf::fail(SF_ERR_FORMAT, "zlib: the device reports %s (status %d)",
                     status[0] == IL_ST_SIZE ? "a stream that does not inflate to the expected size" : status[0] == IL_ST_BAD_DISTANCE ? "a match that reaches in front of the output"
                     : status[0] == IL_ST_NO_EOB ? "a block without an end-of-block code" : "an invalid code", status[0]);

@@ -15,6 +15,7 @@
 
 #include "codecs_internal.h"
 #include "common.h"
+#include "hip_util.h"
 #include "jpeg_idct.h"
 
 namespace {
@@ -184,29 +185,22 @@ int jpeg_gpu_planes(hipStream_t stream, int n, const uint8_t* const* d_payload, 
 // for layouts the GPU path leaves to the host decoder (sampling factors above 2).
 SF_API int sf_jpeg_decode_gpu(const uint8_t* data, uint64_t bytes, uint32_t width, uint32_t height, int device, uint8_t* dst_rgb) {
   if (!data || !dst_rgb || width == 0 || height == 0) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: libscanfuse has no CPU fallback for this entry point (sf_jpeg_decode is the host decoder)");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "libscanfuse has no CPU fallback for this entry point (sf_jpeg_decode is the host decoder)")) return rc;
   const uint64_t padded = (uint64_t)((width + 15) & ~15u) * ((height + 15) & ~15u);
   std::vector<uint32_t> host((sizeof(SfJpegLayout) + padded * 3 / 64 * 4 + padded * 3 * 4) / 4 + 64);   // every coefficient of a 4:4:4 frame non-zero
   const int rc = jpeg_decode_coef(data, bytes, width, height, reinterpret_cast<uint8_t*>(host.data()), host.size() * 4);
   if (rc != SF_OK) return rc;
   const SfJpegLayout* L = reinterpret_cast<const SfJpegLayout*>(host.data());
-  uint8_t *d_pay = nullptr, *d_rgb = nullptr, *d_planes = nullptr;
   const size_t pay_b = sf_jpeg_payload_bytes(*L), rgb_b = (size_t)width * height * 3;
-  auto release = [&]() { if (d_pay) (void)hipFree(d_pay); if (d_rgb) (void)hipFree(d_rgb); if (d_planes) (void)hipFree(d_planes); };
-  hipError_t e = hipMalloc((void**)&d_pay, pay_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_rgb, rgb_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_planes, sf_jpeg_plane_bytes(*L));
-  if (e == hipSuccess) e = hipMemcpy(d_pay, host.data(), pay_b, hipMemcpyHostToDevice);
-  int out = SF_OK;
-  if (e == hipSuccess) {
-    const uint8_t* pp = d_pay;
-    out = jpeg_gpu_reconstruct(nullptr, 1, &pp, &d_rgb, &d_planes, L->nblocks, width, height);
-    if (out == SF_OK) e = hipMemcpy(dst_rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost);
-  }
-  release();
-  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_jpeg_decode_gpu: %s", hipGetErrorString(e));
-  return out;
+  sf::DevBuf pay, rgb, planes;
+  SF_HIP_CHECK(pay.alloc(pay_b));
+  SF_HIP_CHECK(rgb.alloc(rgb_b));
+  SF_HIP_CHECK(planes.alloc(sf_jpeg_plane_bytes(*L)));
+  SF_HIP_CHECK(hipMemcpy(pay.p, host.data(), pay_b, hipMemcpyHostToDevice));
+  const uint8_t* d_pay = pay.as<uint8_t>();
+  uint8_t *d_rgb = rgb.as<uint8_t>(), *d_planes = planes.as<uint8_t>();
+  const int out = jpeg_gpu_reconstruct(nullptr, 1, &d_pay, &d_rgb, &d_planes, L->nblocks, width, height);
+  if (out != SF_OK) return out;
+  SF_HIP_CHECK(hipMemcpy(dst_rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost));
+  return SF_OK;
 }

@@ -13,6 +13,7 @@
 
 #include "codecs_internal.h"
 #include "common.h"
+#include "hip_util.h"
 #include "jpeg_huff.h"
 
 namespace {
@@ -227,10 +228,7 @@ int jpeg_gpu_huffman(hipStream_t stream, int n, const uint8_t* const* d_prepared
 // device reports a corrupt stream.
 SF_API int sf_jpeg_decode_gpu_huffman(const uint8_t* data, uint64_t bytes, uint32_t width, uint32_t height, int device, uint8_t* dst_rgb) {
   if (!data || !dst_rgb || width == 0 || height == 0) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "sf_jpeg_decode_gpu_huffman needs one (sf_jpeg_decode is the host decoder)")) return rc;
   const uint64_t padded = (uint64_t)((width + 15) & ~15u) * ((height + 15) & ~15u);
   std::vector<uint32_t> host((sizeof(SfJpegLayout) + sizeof(SfJpegHuffDesc) + bytes + 64) / 4 + 16);
   const int rc = jpeg_prepare_huff(data, bytes, width, height, reinterpret_cast<uint8_t*>(host.data()), host.size() * 4);
@@ -240,30 +238,22 @@ SF_API int sf_jpeg_decode_gpu_huffman(const uint8_t* data, uint64_t bytes, uint3
   const size_t prep_b = sizeof(SfJpegLayout) + sizeof(SfJpegHuffDesc) + 4 * (size_t)D->ecs_words;
   const uint32_t max_entries = (uint32_t)(padded * 3 + 64);   // every coefficient of a 4:4:4 picture non-zero
   const size_t pay_b = sizeof(SfJpegLayout) + 4 * ((size_t)L->nblocks + max_entries), rgb_b = (size_t)width * height * 3;
-  uint8_t *d_prep = nullptr, *d_pay = nullptr, *d_rgb = nullptr, *d_planes = nullptr;
-  int32_t* d_status = nullptr;
-  auto release = [&]() { (void)hipFree(d_prep); (void)hipFree(d_pay); (void)hipFree(d_rgb); (void)hipFree(d_planes); (void)hipFree(d_status); };
-  hipError_t e = hipMalloc((void**)&d_prep, prep_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_pay, pay_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_rgb, rgb_b);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_planes, sf_jpeg_plane_bytes(*L));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_status, 8);
-  if (e == hipSuccess) e = hipMemset(d_status, 0, 8);
-  if (e == hipSuccess) e = hipMemcpy(d_prep, host.data(), prep_b, hipMemcpyHostToDevice);
-  int out = SF_OK;
+  sf::DevBuf prep, pay, rgb, planes, stat;
+  SF_HIP_CHECK(prep.alloc(prep_b));
+  SF_HIP_CHECK(pay.alloc(pay_b));
+  SF_HIP_CHECK(rgb.alloc(rgb_b));
+  SF_HIP_CHECK(planes.alloc(sf_jpeg_plane_bytes(*L)));
+  SF_HIP_CHECK(stat.alloc(8));
+  SF_HIP_CHECK(hipMemset(stat.p, 0, 8));
+  SF_HIP_CHECK(hipMemcpy(prep.p, host.data(), prep_b, hipMemcpyHostToDevice));
+  const uint8_t *d_prep = prep.as<uint8_t>(), *d_coef = pay.as<uint8_t>();
+  uint8_t *d_pay = pay.as<uint8_t>(), *d_rgb = rgb.as<uint8_t>(), *d_planes = planes.as<uint8_t>();
+  int out = jpeg_gpu_huffman(nullptr, 1, &d_prep, &d_pay, &max_entries, nullptr, stat.as<int32_t>());
+  if (out == SF_OK) out = jpeg_gpu_reconstruct(nullptr, 1, &d_coef, &d_rgb, &d_planes, L->nblocks, width, height);
+  if (out != SF_OK) return out;
   int32_t status = 0;
-  if (e == hipSuccess) {
-    const uint8_t* pp = d_prep;
-    out = jpeg_gpu_huffman(nullptr, 1, &pp, &d_pay, &max_entries, nullptr, d_status);
-    if (out == SF_OK) {
-      const uint8_t* pay = d_pay;
-      out = jpeg_gpu_reconstruct(nullptr, 1, &pay, &d_rgb, &d_planes, L->nblocks, width, height);
-    }
-    if (out == SF_OK) e = hipMemcpy(&status, d_status, 4, hipMemcpyDeviceToHost);
-    if (out == SF_OK && e == hipSuccess) e = hipMemcpy(dst_rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost);
-  }
-  release();
-  if (e != hipSuccess) return sf::fail(SF_ERR_DEVICE, "sf_jpeg_decode_gpu_huffman: %s", hipGetErrorString(e));
-  if (out == SF_OK && status != 0) return sf::fail(SF_ERR_FORMAT, "jpeg: the device's entropy decoder reports a corrupt or truncated stream (status %d)", status);
-  return out;
+  SF_HIP_CHECK(hipMemcpy(&status, stat.p, 4, hipMemcpyDeviceToHost));
+  SF_HIP_CHECK(hipMemcpy(dst_rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost));
+  if (status != 0) return sf::fail(SF_ERR_FORMAT, "jpeg: the device's entropy decoder reports a corrupt or truncated stream (status %d)", status);
+  return SF_OK;
 }

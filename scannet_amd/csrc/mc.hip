@@ -29,6 +29,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "fuser_internal.h"
+#include "hip_util.h"
 #include "mc_tables.h"
 #include "mesh.h"
 
@@ -197,13 +198,6 @@ __global__ void k_gather_tris(const uint32_t* __restrict__ tri_src, const uint32
   out_idx[3 * (size_t)i] = soup_vid[3 * (size_t)t]; out_idx[3 * (size_t)i + 1] = soup_vid[3 * (size_t)t + 1]; out_idx[3 * (size_t)i + 2] = soup_vid[3 * (size_t)t + 2];
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <typename T> T* as() { return (T*)p; }
-};
-
 McTables host_tables() {
   McTables t;
   std::memset(&t, 0, sizeof(t));
@@ -220,13 +214,6 @@ McTables host_tables() {
   }
   return t;
 }
-
-#define MC_CHECK(call)                                                                                        \
-  do {                                                                                                        \
-    hipError_t e_ = (call);                                                                                   \
-    if (e_ != hipSuccess) return sf::fail(SF_ERR_DEVICE, "%s failed: %s (mc.hip:%d)", #call, hipGetErrorString(e_), __LINE__); \
-  } while (0)
-
 
 // Device -> host for the mesh arrays (a scan-sized mesh is ~250 MB going into freshly allocated, never touched memory): the runtime's own path for
 // pageable destinations stages through a small pinned buffer on ONE thread -- copy and first-touch page faults serialised, ~6 GB/s.  Here: two
@@ -256,14 +243,14 @@ int download_segments(sf_fuser* f, hipStream_t s, const DlSeg* segs, int nseg) {
     if (b > a) (void)madvise((void*)a, (size_t)(b - a), MADV_HUGEPAGE);   // advisory: a kernel without THP just says no
   }
   for (int q = 0; q < 2; q++) {
-    if (!f->mc_bounce[q]) MC_CHECK(hipHostMalloc(&f->mc_bounce[q], DL_CHUNK, hipHostMallocDefault));
-    if (!f->mc_bounce_ev[q]) MC_CHECK(hipEventCreateWithFlags(&f->mc_bounce_ev[q], hipEventDisableTiming));
+    if (!f->mc_bounce[q]) SF_HIP_CHECK(hipHostMalloc(&f->mc_bounce[q], DL_CHUNK, hipHostMallocDefault));
+    if (!f->mc_bounce_ev[q]) SF_HIP_CHECK(hipEventCreateWithFlags(&f->mc_bounce_ev[q], hipEventDisableTiming));
   }
   struct Pending { uint8_t* dst; size_t n; bool live; } pend[2] = {{nullptr, 0, false}, {nullptr, 0, false}};
   int slot = 0;
   auto drain = [&](int q) -> int {
     if (!pend[q].live) return SF_OK;
-    MC_CHECK(hipEventSynchronize(f->mc_bounce_ev[q]));
+    SF_HIP_CHECK(hipEventSynchronize(f->mc_bounce_ev[q]));
     team_copy(pend[q].dst, (const uint8_t*)f->mc_bounce[q], pend[q].n);
     pend[q].live = false;
     return SF_OK;
@@ -273,8 +260,8 @@ int download_segments(sf_fuser* f, hipStream_t s, const DlSeg* segs, int nseg) {
       const size_t n = std::min(DL_CHUNK, segs[i].bytes - off);
       int rc = drain(slot);   // the bounce buffer is free once its previous chunk has been copied out
       if (rc != SF_OK) return rc;
-      MC_CHECK(hipMemcpyAsync(f->mc_bounce[slot], (const uint8_t*)segs[i].src + off, n, hipMemcpyDeviceToHost, s));
-      MC_CHECK(hipEventRecord(f->mc_bounce_ev[slot], s));
+      SF_HIP_CHECK(hipMemcpyAsync(f->mc_bounce[slot], (const uint8_t*)segs[i].src + off, n, hipMemcpyDeviceToHost, s));
+      SF_HIP_CHECK(hipEventRecord(f->mc_bounce_ev[slot], s));
       pend[slot] = {(uint8_t*)segs[i].dst + off, n, true};
       slot ^= 1;
       rc = drain(slot);       // while that one travels, copy the other out
@@ -311,7 +298,7 @@ SF_API int sf_fuser_mc_timing(const sf_fuser* f, double* out, int n) {
 
 SF_API int sf_fuser_extract_mesh(sf_fuser* f, sf_mesh** out) {
   if (!f || !out) return sf::fail(SF_ERR_INVALID_ARG, "NULL argument");
-  MC_CHECK(hipSetDevice(f->device));
+  SF_HIP_CHECK(hipSetDevice(f->device));
   const double t_begin = wall_ms();
   for (double& v : f->mc_timing) v = 0.0;
   int32_t n_live = 0;
@@ -325,14 +312,14 @@ SF_API int sf_fuser_extract_mesh(sf_fuser* f, sf_mesh** out) {
   const double t_compact = wall_ms();
   const float thresh = f->p.mc_thresh_factor * f->p.voxel_size;
   const McTables ht = host_tables();
-  DevBuf d_tab, d_cnt, d_off, d_tmp, d_bad;
-  MC_CHECK(d_tab.alloc(sizeof(McTables)));
-  MC_CHECK(hipMemcpyAsync(d_tab.p, &ht, sizeof(McTables), hipMemcpyHostToDevice, s));
-  MC_CHECK(d_cnt.alloc((size_t)(n_live + 1) * 4));
-  MC_CHECK(d_off.alloc((size_t)(n_live + 1) * 4));
-  MC_CHECK(hipMemsetAsync(d_cnt.p, 0, (size_t)(n_live + 1) * 4, s));
-  MC_CHECK(d_bad.alloc(8));
-  MC_CHECK(hipMemsetAsync(d_bad.p, 0, 8, s));
+  sf::DevBuf d_tab, d_cnt, d_off, d_tmp, d_bad;
+  SF_HIP_CHECK(d_tab.alloc(sizeof(McTables)));
+  SF_HIP_CHECK(hipMemcpyAsync(d_tab.p, &ht, sizeof(McTables), hipMemcpyHostToDevice, s));
+  SF_HIP_CHECK(d_cnt.alloc((size_t)(n_live + 1) * 4));
+  SF_HIP_CHECK(d_off.alloc((size_t)(n_live + 1) * 4));
+  SF_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, (size_t)(n_live + 1) * 4, s));
+  SF_HIP_CHECK(d_bad.alloc(8));
+  SF_HIP_CHECK(hipMemsetAsync(d_bad.p, 0, 8, s));
   const int grid = n_live < f->num_cus * 8 ? n_live : f->num_cus * 8;
   clk.mark();   // 0
   hipLaunchKernelGGL(k_mc, dim3(grid), dim3(512), 0, s, f->voxels, f->table, f->block_keys, f->compact, n_live, d_tab.as<McTables>(), f->pk,
@@ -340,14 +327,14 @@ SF_API int sf_fuser_extract_mesh(sf_fuser* f, sf_mesh** out) {
                      d_bad.as<unsigned long long>());
   clk.mark();   // 1: count pass done
   size_t tmp_bytes = 0;
-  MC_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), 0u, (size_t)(n_live + 1), rocprim::plus<uint32_t>(), s));
-  MC_CHECK(d_tmp.alloc(tmp_bytes));
-  MC_CHECK(rocprim::exclusive_scan(d_tmp.p, tmp_bytes, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), 0u, (size_t)(n_live + 1), rocprim::plus<uint32_t>(), s));
+  SF_HIP_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), 0u, (size_t)(n_live + 1), rocprim::plus<uint32_t>(), s));
+  SF_HIP_CHECK(d_tmp.alloc(tmp_bytes));
+  SF_HIP_CHECK(rocprim::exclusive_scan(d_tmp.p, tmp_bytes, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), 0u, (size_t)(n_live + 1), rocprim::plus<uint32_t>(), s));
   uint32_t T = 0;
   unsigned long long bad = 0;
-  MC_CHECK(hipMemcpyAsync(&T, d_off.as<uint32_t>() + n_live, 4, hipMemcpyDeviceToHost, s));
-  MC_CHECK(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, s));
-  MC_CHECK(hipStreamSynchronize(s));
+  SF_HIP_CHECK(hipMemcpyAsync(&T, d_off.as<uint32_t>() + n_live, 4, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipMemcpyAsync(&bad, d_bad.p, 8, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipStreamSynchronize(s));
   if (bad) {
     int bx, by, bz;
     unpack_key(bad & ~MC_BAD_TAG, bx, by, bz);
@@ -358,58 +345,58 @@ SF_API int sf_fuser_extract_mesh(sf_fuser* f, sf_mesh** out) {
   if ((uint64_t)T * 3 > 0xFFFFFFF0ull) { return sf::fail(SF_ERR_CAPACITY, "mesh too large: %u triangles", T); }
   const uint32_t NV = 3 * T;
   const double t_counted = wall_ms();
-  DevBuf d_tkey, d_vkey, d_vpos, d_vcol;
-  MC_CHECK(d_tkey.alloc((size_t)T * 8));
-  MC_CHECK(d_vkey.alloc((size_t)NV * 8));
-  MC_CHECK(d_vpos.alloc((size_t)NV * 12));
-  MC_CHECK(d_vcol.alloc((size_t)NV * 4));
+  sf::DevBuf d_tkey, d_vkey, d_vpos, d_vcol;
+  SF_HIP_CHECK(d_tkey.alloc((size_t)T * 8));
+  SF_HIP_CHECK(d_vkey.alloc((size_t)NV * 8));
+  SF_HIP_CHECK(d_vpos.alloc((size_t)NV * 12));
+  SF_HIP_CHECK(d_vcol.alloc((size_t)NV * 4));
   hipLaunchKernelGGL(k_mc, dim3(grid), dim3(512), 0, s, f->voxels, f->table, f->block_keys, f->compact, n_live, d_tab.as<McTables>(), f->pk,
                      thresh, 1, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), d_tkey.as<uint64_t>(), d_vkey.as<uint64_t>(), d_vpos.as<float>(),
                      d_vcol.as<uint32_t>(), (unsigned long long*)nullptr);
   clk.mark();   // 2: emit pass queued behind this
   // ---- weld: sort edge keys, flag heads, scan, scatter
-  DevBuf d_vkey_s, d_src, d_src_s, d_flag, d_excl, d_tmp2;
-  MC_CHECK(d_vkey_s.alloc((size_t)NV * 8));
-  MC_CHECK(d_src.alloc((size_t)NV * 4));
-  MC_CHECK(d_src_s.alloc((size_t)NV * 4));
+  sf::DevBuf d_vkey_s, d_src, d_src_s, d_flag, d_excl, d_tmp2;
+  SF_HIP_CHECK(d_vkey_s.alloc((size_t)NV * 8));
+  SF_HIP_CHECK(d_src.alloc((size_t)NV * 4));
+  SF_HIP_CHECK(d_src_s.alloc((size_t)NV * 4));
   hipLaunchKernelGGL(k_iota, dim3((NV + 255) / 256), dim3(256), 0, s, d_src.as<uint32_t>(), NV);
   size_t sort_bytes = 0;
-  MC_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, d_vkey.as<uint64_t>(), d_vkey_s.as<uint64_t>(), d_src.as<uint32_t>(), d_src_s.as<uint32_t>(), (size_t)NV, 0, 64, s));
-  MC_CHECK(d_tmp2.alloc(sort_bytes));
-  MC_CHECK(rocprim::radix_sort_pairs(d_tmp2.p, sort_bytes, d_vkey.as<uint64_t>(), d_vkey_s.as<uint64_t>(), d_src.as<uint32_t>(), d_src_s.as<uint32_t>(), (size_t)NV, 0, 64, s));
+  SF_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, d_vkey.as<uint64_t>(), d_vkey_s.as<uint64_t>(), d_src.as<uint32_t>(), d_src_s.as<uint32_t>(), (size_t)NV, 0, 64, s));
+  SF_HIP_CHECK(d_tmp2.alloc(sort_bytes));
+  SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp2.p, sort_bytes, d_vkey.as<uint64_t>(), d_vkey_s.as<uint64_t>(), d_src.as<uint32_t>(), d_src_s.as<uint32_t>(), (size_t)NV, 0, 64, s));
   clk.mark();   // 3: vertex sort
-  MC_CHECK(d_flag.alloc((size_t)(NV + 1) * 4));
-  MC_CHECK(d_excl.alloc((size_t)(NV + 1) * 4));
-  MC_CHECK(hipMemsetAsync(d_flag.p, 0, (size_t)(NV + 1) * 4, s));
+  SF_HIP_CHECK(d_flag.alloc((size_t)(NV + 1) * 4));
+  SF_HIP_CHECK(d_excl.alloc((size_t)(NV + 1) * 4));
+  SF_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, (size_t)(NV + 1) * 4, s));
   hipLaunchKernelGGL(k_flag_heads, dim3((NV + 255) / 256), dim3(256), 0, s, d_vkey_s.as<uint64_t>(), d_flag.as<uint32_t>(), NV);
   size_t scan_bytes = 0;
-  DevBuf d_tmp3;
-  MC_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), 0u, (size_t)(NV + 1), rocprim::plus<uint32_t>(), s));
-  MC_CHECK(d_tmp3.alloc(scan_bytes));
-  MC_CHECK(rocprim::exclusive_scan(d_tmp3.p, scan_bytes, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), 0u, (size_t)(NV + 1), rocprim::plus<uint32_t>(), s));
+  sf::DevBuf d_tmp3;
+  SF_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), 0u, (size_t)(NV + 1), rocprim::plus<uint32_t>(), s));
+  SF_HIP_CHECK(d_tmp3.alloc(scan_bytes));
+  SF_HIP_CHECK(rocprim::exclusive_scan(d_tmp3.p, scan_bytes, d_flag.as<uint32_t>(), d_excl.as<uint32_t>(), 0u, (size_t)(NV + 1), rocprim::plus<uint32_t>(), s));
   uint32_t NU = 0;
-  MC_CHECK(hipMemcpyAsync(&NU, d_excl.as<uint32_t>() + NV, 4, hipMemcpyDeviceToHost, s));
-  MC_CHECK(hipStreamSynchronize(s));
-  DevBuf d_vid, d_opos, d_ocol, d_okey;
-  MC_CHECK(d_vid.alloc((size_t)NV * 4));
-  MC_CHECK(d_opos.alloc((size_t)NU * 12));
-  MC_CHECK(d_ocol.alloc((size_t)NU * 4));
-  MC_CHECK(d_okey.alloc((size_t)NU * 8));
+  SF_HIP_CHECK(hipMemcpyAsync(&NU, d_excl.as<uint32_t>() + NV, 4, hipMemcpyDeviceToHost, s));
+  SF_HIP_CHECK(hipStreamSynchronize(s));
+  sf::DevBuf d_vid, d_opos, d_ocol, d_okey;
+  SF_HIP_CHECK(d_vid.alloc((size_t)NV * 4));
+  SF_HIP_CHECK(d_opos.alloc((size_t)NU * 12));
+  SF_HIP_CHECK(d_ocol.alloc((size_t)NU * 4));
+  SF_HIP_CHECK(d_okey.alloc((size_t)NU * 8));
   hipLaunchKernelGGL(k_weld, dim3((NV + 255) / 256), dim3(256), 0, s, d_vkey_s.as<uint64_t>(), d_src_s.as<uint32_t>(), d_flag.as<uint32_t>(),
                      d_excl.as<uint32_t>(), NV, d_vpos.as<float>(), d_vcol.as<uint32_t>(), d_vid.as<uint32_t>(), d_opos.as<float>(),
                      d_ocol.as<uint32_t>(), d_okey.as<uint64_t>());
   clk.mark();   // 4: heads, scan, weld
   // ---- canonical triangle order: sort by (cube key, table order)
-  DevBuf d_tkey_s, d_tsrc, d_tsrc_s, d_tmp4, d_oidx;
-  MC_CHECK(d_tkey_s.alloc((size_t)T * 8));
-  MC_CHECK(d_tsrc.alloc((size_t)T * 4));
-  MC_CHECK(d_tsrc_s.alloc((size_t)T * 4));
+  sf::DevBuf d_tkey_s, d_tsrc, d_tsrc_s, d_tmp4, d_oidx;
+  SF_HIP_CHECK(d_tkey_s.alloc((size_t)T * 8));
+  SF_HIP_CHECK(d_tsrc.alloc((size_t)T * 4));
+  SF_HIP_CHECK(d_tsrc_s.alloc((size_t)T * 4));
   hipLaunchKernelGGL(k_iota, dim3((T + 255) / 256), dim3(256), 0, s, d_tsrc.as<uint32_t>(), T);
   size_t tsort_bytes = 0;
-  MC_CHECK(rocprim::radix_sort_pairs(nullptr, tsort_bytes, d_tkey.as<uint64_t>(), d_tkey_s.as<uint64_t>(), d_tsrc.as<uint32_t>(), d_tsrc_s.as<uint32_t>(), (size_t)T, 0, 64, s));
-  MC_CHECK(d_tmp4.alloc(tsort_bytes));
-  MC_CHECK(rocprim::radix_sort_pairs(d_tmp4.p, tsort_bytes, d_tkey.as<uint64_t>(), d_tkey_s.as<uint64_t>(), d_tsrc.as<uint32_t>(), d_tsrc_s.as<uint32_t>(), (size_t)T, 0, 64, s));
-  MC_CHECK(d_oidx.alloc((size_t)T * 12));
+  SF_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tsort_bytes, d_tkey.as<uint64_t>(), d_tkey_s.as<uint64_t>(), d_tsrc.as<uint32_t>(), d_tsrc_s.as<uint32_t>(), (size_t)T, 0, 64, s));
+  SF_HIP_CHECK(d_tmp4.alloc(tsort_bytes));
+  SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp4.p, tsort_bytes, d_tkey.as<uint64_t>(), d_tkey_s.as<uint64_t>(), d_tsrc.as<uint32_t>(), d_tsrc_s.as<uint32_t>(), (size_t)T, 0, 64, s));
+  SF_HIP_CHECK(d_oidx.alloc((size_t)T * 12));
   hipLaunchKernelGGL(k_gather_tris, dim3((T + 255) / 256), dim3(256), 0, s, d_tsrc_s.as<uint32_t>(), d_vid.as<uint32_t>(), T, d_oidx.as<uint32_t>());
   clk.mark();   // 5: triangle sort + gather
   // ---- download
@@ -426,8 +413,8 @@ SF_API int sf_fuser_extract_mesh(sf_fuser* f, sf_mesh** out) {
     if (rc != SF_OK) return rc;
   }
   clk.mark();   // 6: downloads
-  MC_CHECK(hipStreamSynchronize(s));
-  MC_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipStreamSynchronize(s));
+  SF_HIP_CHECK(hipGetLastError());
   const double t_end = wall_ms();
   // [0] whole call  [1] live-block list  [2] count pass  [3] emit pass  [4] vertex sort  [5] heads + scan + weld  [6] triangle sort + gather
   // [7] downloads (device time)  [8] host: output arrays allocated and zero-filled + waiting for the downloads  [9] live blocks  [10] triangles  [11] vertices

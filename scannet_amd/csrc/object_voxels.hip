@@ -214,38 +214,6 @@ __global__ __launch_bounds__(256) void k_ov_emit(const Kept* __restrict__ kept, 
 // device microseconds of the most recent call's launches: k_ov_key .. k_ov_box, k_ov_raster, k_ov_emit (sf_objvox_kernel_us)
 std::atomic<float> g_group_us{0.0f}, g_raster_us{0.0f}, g_emit_us{0.0f};
 
-struct Span {   // two events on a stream; us() after the stream has been synchronised
-  hipEvent_t a = nullptr, b = nullptr;
-  Span() { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
-  Span(const Span&) = delete;
-  Span& operator=(const Span&) = delete;
-  ~Span() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  void begin(hipStream_t s) { if (a) (void)hipEventRecord(a, s); }
-  void end(hipStream_t s) { if (b) (void)hipEventRecord(b, s); }
-  float us() const {
-    float ms = 0.0f;
-    if (!a || !b || hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0.0f; }
-    return ms * 1000.0f;
-  }
-};
-
-bool on_device(const void* p) {
-  if (!p) return false;
-  hipPointerAttribute_t a;
-  std::memset(&a, 0, sizeof(a));
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice;
-}
-
-// dst may be host or device memory
-hipError_t deliver(void* dst, const void* src, size_t bytes, hipStream_t s) {
-  if (!bytes) return hipSuccess;
-  return hipMemcpyAsync(dst, src, bytes, on_device(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
-}
-
 }  // namespace
 
 namespace sf {
@@ -254,13 +222,7 @@ namespace ov {
 int voxelize_device(const float* xyz, uint64_t nv, const uint32_t* tris, uint64_t nf, const uint32_t* vertex_object, const int32_t* object_class,
                     uint32_t num_objects, const GridRef& grid, uint64_t grid_nodes, const sf_objvox_params& p, int device, uint64_t first, uint64_t max_objects,
                     uint8_t* data, uint8_t* label, int32_t* object_id, float* origin, float* cell, uint64_t* total, const StageOut* stage) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    return sf::fail(SF_ERR_DEVICE, "no HIP device: the object voxeliser on a device needs an MI355X (device = -1 is the host path)");
-  }
-  if (device >= ndev) return sf::fail(SF_ERR_DEVICE, "the object voxeliser: device %d of %d", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = open_device(device, SF_ERR_DEVICE, "the object voxeliser on a device needs an MI355X (device = -1 is the host path)")) return rc;
   *total = 0;
   if (stage && stage->total) *stage->total = 0;
   const uint32_t n_keys = num_objects + 1u;   // indexed by the vertex_object value
@@ -281,7 +243,7 @@ int voxelize_device(const float* xyz, uint64_t nv, const uint32_t* tris, uint64_
   SF_HIP_CHECK(hipMemsetAsync(d_counts.p, 0, (size_t)n_keys * 4, sg.s));
   SF_HIP_CHECK(hipMemsetAsync(d_cursor.p, 0, (size_t)n_keys * 4, sg.s));
   const uint32_t face_blocks = (uint32_t)((nf + 255) / 256);
-  Span t_group, t_fill, t_raster, t_emit;
+  EventSpan t_group, t_fill, t_raster, t_emit;
   t_group.begin(sg.s);
   if (nf) {
     k_ov_key<<<face_blocks, 256, 0, sg.s>>>(d_xyz.as<float>(), d_tris.as<uint32_t>(), d_vo.as<uint32_t>(), (uint32_t)nf, d_fobj.as<uint32_t>(), d_counts.as<uint32_t>());

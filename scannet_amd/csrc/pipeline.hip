@@ -20,6 +20,7 @@
 
 #include "codecs_internal.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 #include "jpeg_huff.h"
 #include "jpeg_idct.h"
 #include "sens.h"
@@ -490,8 +491,8 @@ struct Run {
   bool holding = false;
   RunResources* r = nullptr;     // the set the run works with: res, or own
   ResourceNeed w{};              // ... and what of it the run uses
-  int32_t* d_zstatus = nullptr;   // 2 ints per ring slot and frame, written by the device's inflate only when a frame fails
-  int32_t* d_jstatus = nullptr;   // ... by the device's entropy decoder only when a picture fails
+  sf::DevBuf d_zstatus;   // 2 ints per ring slot and frame, written by the device's inflate only when a frame fails
+  sf::DevBuf d_jstatus;   // ... by the device's entropy decoder only when a picture fails
   int result = SF_OK;
   std::string err;
   uint64_t n_int = 0, n_skip = 0, n_dev_z = 0, n_host_z = 0, n_dev_j = 0, n_host_j = 0;
@@ -530,9 +531,9 @@ struct Run {
     p.h_pool = r->h_pool;
     p.d_pool = r->d_pool;
     const size_t status_b = (size_t)p.NB * p.B * 8;
-    for (int32_t** st : {p.gpu_inflate ? &d_zstatus : nullptr, p.gpu_huffman ? &d_jstatus : nullptr}) {
-      if (st && (e = hipMalloc((void**)st, status_b)) != hipSuccess) return e;
-      if (st && (e = hipMemset(*st, 0, status_b)) != hipSuccess) return e;
+    for (sf::DevBuf* st : {p.gpu_inflate ? &d_zstatus : nullptr, p.gpu_huffman ? &d_jstatus : nullptr}) {
+      if (st && (e = st->alloc(status_b)) != hipSuccess) return e;
+      if (st && (e = hipMemset(st->p, 0, status_b)) != hipSuccess) return e;
     }
     ring = std::vector<BatchSlot>((size_t)p.NB);
     for (BatchSlot& sl : ring)
@@ -543,9 +544,8 @@ struct Run {
     if (!holding) return;
     holding = false;
     ring.clear();
-    if (d_jstatus) (void)hipFree(d_jstatus);
-    if (d_zstatus) (void)hipFree(d_zstatus);
-    d_jstatus = d_zstatus = nullptr;
+    d_jstatus.release();
+    d_zstatus.release();
     if (res) release_resources(res);
     else free_resources(&own);
   }
@@ -672,7 +672,7 @@ struct Run {
       }
       if (nz == 32 || (j == b.cnt && nz > 0)) {   // a launch takes up to 32 frames
         const double tz = tick();
-        const int rcz = inflate_gpu_batch(b.side, nz, zw, zn, zo, zb, (uint32_t)p.depth_b, zt, d_zstatus + 2 * ((size_t)b.sl * p.B + (size_t)slot0));
+        const int rcz = inflate_gpu_batch(b.side, nz, zw, zn, zo, zb, (uint32_t)p.depth_b, zt, d_zstatus.as<int32_t>() + 2 * ((size_t)b.sl * p.B + (size_t)slot0));
         if (p.sw.timing) t_launch_z += now_s() - tz;
         if (rcz != SF_OK) return fail_rc(rcz);
         nz = 0;
@@ -701,7 +701,7 @@ struct Run {
         nh++;
       }
       if (nh == huff_group || (q == j1 && nh > 0)) {
-        const int rch = jpeg_gpu_huffman(stream, nh, seg, out, cap, tag, d_jstatus + 2 * ((size_t)sl * p.B + (size_t)slot0));
+        const int rch = jpeg_gpu_huffman(stream, nh, seg, out, cap, tag, d_jstatus.as<int32_t>() + 2 * ((size_t)sl * p.B + (size_t)slot0));
         if (rch != SF_OK) return fail_rc(rch);
         nh = 0;
       }
@@ -843,8 +843,8 @@ SF_API int sf_fuse_run(sf_fuser* f, const sf_sens* s, uint64_t first, uint64_t l
   for (int q = 0; q < run.w.copy_streams; q++) (void)hipStreamSynchronize(run.r->copy[q]);
   for (int q = 0; q < run.w.side_streams; q++) (void)hipStreamSynchronize(run.r->inflate[q]);
   if (qe == hipSuccess) {
-    run.read_status(run.d_zstatus, "inflate: the device's frame status", "inflate: depth frame ", ": corrupt stream, or it does not inflate to the frame's size");
-    run.read_status(run.d_jstatus, "jpeg: the device's picture status", "jpeg: colour frame ", ": corrupt or truncated entropy-coded segment");
+    run.read_status(run.d_zstatus.as<int32_t>(), "inflate: the device's frame status", "inflate: depth frame ", ": corrupt stream, or it does not inflate to the frame's size");
+    run.read_status(run.d_jstatus.as<int32_t>(), "jpeg: the device's picture status", "jpeg: colour frame ", ": corrupt or truncated entropy-coded segment");
   }
   run.release();
   t_run_counts[0] = run.n_dev_z; t_run_counts[1] = run.n_host_z; t_run_counts[2] = run.n_dev_j; t_run_counts[3] = run.n_host_j;

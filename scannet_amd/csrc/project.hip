@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "common.h"
+#include "hip_util.h"
 
 namespace {
 
@@ -552,10 +553,7 @@ SF_API int sf_projector_create(const sf_project_params* params, int device, sf_p
     return sf::fail(SF_ERR_INVALID_ARG, "invalid image dimensions");
   if (!(params->fx > 0.0f) || !(params->fy > 0.0f) || !(params->depth_min > 0.0f) || !(params->depth_max > params->depth_min))
     return sf::fail(SF_ERR_INVALID_ARG, "invalid camera (fx %g fy %g depth range [%g, %g])", params->fx, params->fy, params->depth_min, params->depth_max);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: libscanfuse has no CPU fallback, the annotation projector needs an MI355X");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "libscanfuse has no CPU fallback, the annotation projector needs an MI355X")) return rc;
   sf_projector* p = new sf_projector();
   p->p = *params;
   p->device = device;

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "fuser_internal.h"
+#include "hip_util.h"
 
 namespace {
 
@@ -322,8 +323,9 @@ SF_API int sf_fuser_raycast(sf_fuser* f, const float pose[16], const sf_raycast_
   SF_HIP_CHECK(hipSetDevice(f->device));
   const size_t npx = (size_t)a.W * a.H;
   const size_t bytes = npx * 4 + (normals_xyz ? npx * 12 : 0) + (rgb ? npx * 3 : 0);
-  uint8_t* buf = nullptr;
-  SF_HIP_CHECK(hipMalloc((void**)&buf, bytes));
+  sf::DevBuf own;
+  SF_HIP_CHECK(own.alloc(bytes));
+  uint8_t* buf = own.as<uint8_t>();
   float* d_depth = (float*)buf;   // always made: the other two follow it
   float* d_nrm = normals_xyz ? (float*)(buf + npx * 4) : nullptr;
   uint8_t* d_rgb = rgb ? buf + npx * 4 + (normals_xyz ? npx * 12 : 0) : nullptr;
@@ -333,7 +335,6 @@ SF_API int sf_fuser_raycast(sf_fuser* f, const float pose[16], const sf_raycast_
   if (out == SF_OK && e == hipSuccess && normals_xyz) e = hipMemcpyAsync(normals_xyz, d_nrm, npx * 12, hipMemcpyDeviceToHost, f->stream);
   if (out == SF_OK && e == hipSuccess && rgb) e = hipMemcpyAsync(rgb, d_rgb, npx * 3, hipMemcpyDeviceToHost, f->stream);
   const hipError_t e2 = hipStreamSynchronize(f->stream);
-  (void)hipFree(buf);
   if (out != SF_OK) return out;
   if (e != hipSuccess || e2 != hipSuccess) return sf::fail(SF_ERR_DEVICE, "ray-cast download failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
   return SF_OK;

@@ -100,17 +100,13 @@ SF_API int sf_renderer_create(const sf_render_params* params, int device, sf_ren
   const int rc = rh::check_params(p, err);
   if (rc != SF_OK) return sf::fail(rc, "%s", err.c_str());
   if (device < -1) return sf::fail(SF_ERR_INVALID_ARG, "sf_renderer_create: device is -1 (the host path) or a HIP device");
+  if (device >= 0)   // before the renderer exists: a refused device leaves nothing to take down on it
+    if (int rc = sf::open_device(device, SF_ERR_DEVICE, "the render on a device needs one (device = -1 is the host path, and it is never taken silently)")) return rc;
   sf_renderer* r = new sf_renderer();
   r->params = p;
   r->device = device;
   if (device >= 0) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-      delete r;
-      return sf::fail(SF_ERR_DEVICE, "no HIP device: the render on a device needs one (device = -1 is the host path, and it is never taken silently)");
-    }
-    hipError_t e = device < ndev ? hipSetDevice(device) : hipErrorInvalidDevice;
-    if (e == hipSuccess) e = hipStreamCreate(&r->stream);
+    hipError_t e = hipStreamCreate(&r->stream);
     if (e == hipSuccess) e = hipEventCreate(&r->ev0);
     if (e == hipSuccess) e = hipEventCreate(&r->ev1);
     if (e != hipSuccess) {

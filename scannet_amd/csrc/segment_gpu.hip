@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "hip_util.h"
 
 namespace {
 
@@ -97,24 +98,14 @@ __global__ __launch_bounds__(256) void k_seg_edge_weights(const float* __restric
   keys[e] = WeightKeyD{w, e};
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
 // keys_out: 3 * nf records {weight, edge number} (host memory), what segment.cpp's own loops produce.  Indices are validated by the caller.
 int segment_weight_keys_gpu(const float* xyz, size_t nv, const uint32_t* tri, size_t nf, int device, void* keys_out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device: sf_segment_mesh_gpu needs one (sf_segment_mesh is the host path)");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "sf_segment_mesh_gpu needs one (sf_segment_mesh is the host path)")) return rc;
   const size_t nc = nf * 3;
   if (nc == 0) return SF_OK;
-  DevBuf d_xyz, d_tri, d_fn, d_vn, d_k0, d_k1, d_c0, d_c1, d_keys, d_tmp;
+  sf::DevBuf d_xyz, d_tri, d_fn, d_vn, d_k0, d_k1, d_c0, d_c1, d_keys, d_tmp;
   SF_HIP_CHECK(d_xyz.alloc(nv * 12)); SF_HIP_CHECK(d_tri.alloc(nc * 4)); SF_HIP_CHECK(d_fn.alloc(nf * 12)); SF_HIP_CHECK(d_vn.alloc(nv * 16));
   SF_HIP_CHECK(d_k0.alloc(nc * 4)); SF_HIP_CHECK(d_k1.alloc(nc * 4)); SF_HIP_CHECK(d_c0.alloc(nc * 4)); SF_HIP_CHECK(d_c1.alloc(nc * 4)); SF_HIP_CHECK(d_keys.alloc(nc * 8));
   hipStream_t s = nullptr;

@@ -52,12 +52,6 @@ constexpr int MAX_RING = 96;   // neighbours of one vertex held in registers / s
 struct Tri { uint32_t a, b, c; };
 
 
-#define DEC_CHECK(call)                                                                                                \
-  do {                                                                                                                 \
-    hipError_t e_ = (call);                                                                                            \
-    if (e_ != hipSuccess) return sf::fail(SF_ERR_DEVICE, "%s failed: %s (simplify_gpu.hip:%d)", #call, hipGetErrorString(e_), __LINE__); \
-  } while (0)
-
 struct Mesh {   // device view
   float* pos;            // 3 per vertex
   uint32_t* tri;         // 3 per face
@@ -359,63 +353,63 @@ struct Decimator {
   int init(uint32_t V_, uint32_t F) {
     V = V_;
     Fc = F;
-    DEC_CHECK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    SF_HIP_CHECK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
     s = sg.s;
     const size_t NC0 = 3 * (size_t)F;
-    DEC_CHECK(d_pos.alloc((size_t)V * 12)); DEC_CHECK(d_tri.alloc(NC0 * 4)); DEC_CHECK(d_alive.alloc(F)); DEC_CHECK(d_vdel.alloc(V));
-    DEC_CHECK(d_Q.alloc((size_t)V * sizeof(Quadric))); DEC_CHECK(d_vbeg.alloc((size_t)V * 4)); DEC_CHECK(d_vcnt.alloc((size_t)V * 4));
-    DEC_CHECK(d_ckey.alloc(NC0 * 4)); DEC_CHECK(d_cval.alloc(NC0 * 4)); DEC_CHECK(d_ckey2.alloc(NC0 * 4)); DEC_CHECK(d_cval2.alloc(NC0 * 4));
-    DEC_CHECK(d_ekey.alloc(NC0 * 8)); DEC_CHECK(d_ekey2.alloc(NC0 * 8)); DEC_CHECK(d_ukey.alloc(NC0 * 8)); DEC_CHECK(d_ucnt.alloc(NC0 * 4)); DEC_CHECK(d_nruns.alloc(8));
-    DEC_CHECK(d_pri.alloc(NC0 * 4)); DEC_CHECK(d_pri2.alloc(NC0 * 4)); DEC_CHECK(d_pri3.alloc(NC0 * 4)); DEC_CHECK(d_x.alloc(NC0 * 12)); DEC_CHECK(d_lock.alloc((size_t)V * 8));
-    DEC_CHECK(d_win.alloc(NC0 * 8)); DEC_CHECK(d_win2.alloc(NC0 * 8)); DEC_CHECK(d_nwin.alloc(16)); DEC_CHECK(d_taken.alloc(V));
+    SF_HIP_CHECK(d_pos.alloc((size_t)V * 12)); SF_HIP_CHECK(d_tri.alloc(NC0 * 4)); SF_HIP_CHECK(d_alive.alloc(F)); SF_HIP_CHECK(d_vdel.alloc(V));
+    SF_HIP_CHECK(d_Q.alloc((size_t)V * sizeof(Quadric))); SF_HIP_CHECK(d_vbeg.alloc((size_t)V * 4)); SF_HIP_CHECK(d_vcnt.alloc((size_t)V * 4));
+    SF_HIP_CHECK(d_ckey.alloc(NC0 * 4)); SF_HIP_CHECK(d_cval.alloc(NC0 * 4)); SF_HIP_CHECK(d_ckey2.alloc(NC0 * 4)); SF_HIP_CHECK(d_cval2.alloc(NC0 * 4));
+    SF_HIP_CHECK(d_ekey.alloc(NC0 * 8)); SF_HIP_CHECK(d_ekey2.alloc(NC0 * 8)); SF_HIP_CHECK(d_ukey.alloc(NC0 * 8)); SF_HIP_CHECK(d_ucnt.alloc(NC0 * 4)); SF_HIP_CHECK(d_nruns.alloc(8));
+    SF_HIP_CHECK(d_pri.alloc(NC0 * 4)); SF_HIP_CHECK(d_pri2.alloc(NC0 * 4)); SF_HIP_CHECK(d_pri3.alloc(NC0 * 4)); SF_HIP_CHECK(d_x.alloc(NC0 * 12)); SF_HIP_CHECK(d_lock.alloc((size_t)V * 8));
+    SF_HIP_CHECK(d_win.alloc(NC0 * 8)); SF_HIP_CHECK(d_win2.alloc(NC0 * 8)); SF_HIP_CHECK(d_nwin.alloc(16)); SF_HIP_CHECK(d_taken.alloc(V));
     // scratch for the rocprim calls: sized once for the largest request
     size_t need = 0;
-    DEC_CHECK(rocprim::radix_sort_pairs(nullptr, need, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC0, 0, 32, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC0, 0, 32, s));
     tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC0, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_keys(nullptr, need, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC0, 0, 64, s));
     tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::run_length_encode(nullptr, need, d_ekey2.as<uint64_t>(), (unsigned int)NC0, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
+    SF_HIP_CHECK(rocprim::run_length_encode(nullptr, need, d_ekey2.as<uint64_t>(), (unsigned int)NC0, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
     tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_pri.as<uint32_t>(), d_pri2.as<uint32_t>(), NC0, 0, 32, s));
+    SF_HIP_CHECK(rocprim::radix_sort_keys(nullptr, need, d_pri.as<uint32_t>(), d_pri2.as<uint32_t>(), NC0, 0, 32, s));
     tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::radix_sort_keys(nullptr, need, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), NC0, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_keys(nullptr, need, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), NC0, 0, 64, s));
     tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(rocprim::select(nullptr, need, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)F, s));
+    SF_HIP_CHECK(rocprim::select(nullptr, need, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)F, s));
     tmp_bytes = std::max(tmp_bytes, need);
-    DEC_CHECK(d_tmp.alloc(tmp_bytes));
+    SF_HIP_CHECK(d_tmp.alloc(tmp_bytes));
     M = Mesh{d_pos.as<float>(), d_tri.as<uint32_t>(), d_alive.as<uint8_t>(), d_vdel.as<uint8_t>(), d_Q.as<Quadric>(), d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>(),
              d_cval2.as<uint32_t>(), V, F};
     return SF_OK;
   }
   int upload(const float* pos, const uint32_t* tri, const uint8_t* alive, const double* Q /* nullable: V x 10 */) {
-    DEC_CHECK(hipMemcpyAsync(d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, s));
-    DEC_CHECK(hipMemcpyAsync(d_tri.p, tri, 3 * (size_t)Fc * 4, hipMemcpyHostToDevice, s));
-    DEC_CHECK(hipMemcpyAsync(d_alive.p, alive, Fc, hipMemcpyHostToDevice, s));
-    DEC_CHECK(hipMemsetAsync(d_vdel.p, 0, V, s));
-    if (Q) DEC_CHECK(hipMemcpyAsync(d_Q.p, Q, (size_t)V * sizeof(Quadric), hipMemcpyHostToDevice, s));
+    SF_HIP_CHECK(hipMemcpyAsync(d_pos.p, pos, (size_t)V * 12, hipMemcpyHostToDevice, s));
+    SF_HIP_CHECK(hipMemcpyAsync(d_tri.p, tri, 3 * (size_t)Fc * 4, hipMemcpyHostToDevice, s));
+    SF_HIP_CHECK(hipMemcpyAsync(d_alive.p, alive, Fc, hipMemcpyHostToDevice, s));
+    SF_HIP_CHECK(hipMemsetAsync(d_vdel.p, 0, V, s));
+    if (Q) SF_HIP_CHECK(hipMemcpyAsync(d_Q.p, Q, (size_t)V * sizeof(Quadric), hipMemcpyHostToDevice, s));
     return SF_OK;
   }
   int download(float* pos, uint32_t* tri, uint8_t* alive, uint8_t* vdel, double* Q /* nullable */) {
-    DEC_CHECK(hipStreamSynchronize(s));
-    DEC_CHECK(hipMemcpyAsync(pos, d_pos.p, (size_t)V * 12, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipMemcpyAsync(tri, d_tri.p, (size_t)Fc * 12, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipMemcpyAsync(alive, d_alive.p, Fc, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipMemcpyAsync(vdel, d_vdel.p, V, hipMemcpyDeviceToHost, s));
-    if (Q) DEC_CHECK(hipMemcpyAsync(Q, d_Q.p, (size_t)V * sizeof(Quadric), hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipStreamSynchronize(s));
+    SF_HIP_CHECK(hipStreamSynchronize(s));
+    SF_HIP_CHECK(hipMemcpyAsync(pos, d_pos.p, (size_t)V * 12, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipMemcpyAsync(tri, d_tri.p, (size_t)Fc * 12, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipMemcpyAsync(alive, d_alive.p, Fc, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipMemcpyAsync(vdel, d_vdel.p, V, hipMemcpyDeviceToHost, s));
+    if (Q) SF_HIP_CHECK(hipMemcpyAsync(Q, d_Q.p, (size_t)V * sizeof(Quadric), hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipStreamSynchronize(s));
     return SF_OK;
   }
   // dead faces out of the device arrays, in order, once a quarter of them has gone
   int squeeze(uint64_t nalive) {
     if (!(nalive * 4 < (uint64_t)Fc * 3)) return SF_OK;
     size_t tb = tmp_bytes;
-    DEC_CHECK(rocprim::select(d_tmp.p, tb, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)Fc, s));
+    SF_HIP_CHECK(rocprim::select(d_tmp.p, tb, d_tri.as<Tri>(), d_alive.as<uint8_t>(), d_ckey.as<Tri>(), d_nruns.as<uint32_t>(), (size_t)Fc, s));
     uint32_t kept = 0;
-    DEC_CHECK(hipMemcpyAsync(&kept, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipStreamSynchronize(s));
+    SF_HIP_CHECK(hipMemcpyAsync(&kept, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipStreamSynchronize(s));
     if (kept != nalive) return sf::fail(SF_ERR_DEVICE, "simplify_gpu: %u faces alive on the device, %llu counted", kept, (unsigned long long)nalive);
-    DEC_CHECK(hipMemcpyAsync(d_tri.p, d_ckey.p, (size_t)kept * 12, hipMemcpyDeviceToDevice, s));
-    DEC_CHECK(hipMemsetAsync(d_alive.p, 1, kept, s));
+    SF_HIP_CHECK(hipMemcpyAsync(d_tri.p, d_ckey.p, (size_t)kept * 12, hipMemcpyDeviceToDevice, s));
+    SF_HIP_CHECK(hipMemsetAsync(d_alive.p, 1, kept, s));
     Fc = kept;
     M.F = Fc;
     return SF_OK;
@@ -426,22 +420,22 @@ struct Decimator {
     const unsigned gF = (Fc + 255) / 256, gC = (unsigned)((NC + 255) / 256), gV = (V + 255) / 256;
     hipLaunchKernelGGL(k_emit, dim3(gF), dim3(256), 0, s, M.tri, M.alive, Fc, d_ckey.as<uint32_t>(), d_cval.as<uint32_t>(), d_ekey.as<uint64_t>());
     size_t tb = tmp_bytes;
-    DEC_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC, 0, 32, s));
-    DEC_CHECK(hipMemsetAsync(d_vbeg.p, 0, (size_t)V * 4, s));
-    DEC_CHECK(hipMemsetAsync(d_vcnt.p, 0, (size_t)V * 4, s));
+    SF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tb, d_ckey.as<uint32_t>(), d_ckey2.as<uint32_t>(), d_cval.as<uint32_t>(), d_cval2.as<uint32_t>(), NC, 0, 32, s));
+    SF_HIP_CHECK(hipMemsetAsync(d_vbeg.p, 0, (size_t)V * 4, s));
+    SF_HIP_CHECK(hipMemsetAsync(d_vcnt.p, 0, (size_t)V * 4, s));
     hipLaunchKernelGGL(k_vertex_ranges, dim3(gC), dim3(256), 0, s, d_ckey2.as<uint32_t>(), (uint32_t)NC, d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>());
     hipLaunchKernelGGL(k_fix_counts, dim3(gV), dim3(256), 0, s, d_vbeg.as<uint32_t>(), d_vcnt.as<uint32_t>(), V);
     tb = tmp_bytes;
-    DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_ekey.as<uint64_t>(), d_ekey2.as<uint64_t>(), NC, 0, 64, s));
     tb = tmp_bytes;
-    DEC_CHECK(rocprim::run_length_encode(d_tmp.p, tb, d_ekey2.as<uint64_t>(), (unsigned int)NC, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
+    SF_HIP_CHECK(rocprim::run_length_encode(d_tmp.p, tb, d_ekey2.as<uint64_t>(), (unsigned int)NC, d_ukey.as<uint64_t>(), d_ucnt.as<uint32_t>(), d_nruns.as<uint32_t>(), s));
     E = 0;
-    DEC_CHECK(hipMemcpyAsync(&E, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipStreamSynchronize(s));
+    SF_HIP_CHECK(hipMemcpyAsync(&E, d_nruns.p, 4, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipStreamSynchronize(s));
     if (E > 0) {   // the run of dead faces' keys (~0) sorts last
       uint64_t lastkey = 0;
-      DEC_CHECK(hipMemcpyAsync(&lastkey, d_ukey.as<uint64_t>() + (E - 1), 8, hipMemcpyDeviceToHost, s));
-      DEC_CHECK(hipStreamSynchronize(s));
+      SF_HIP_CHECK(hipMemcpyAsync(&lastkey, d_ukey.as<uint64_t>() + (E - 1), 8, hipMemcpyDeviceToHost, s));
+      SF_HIP_CHECK(hipStreamSynchronize(s));
       if (lastkey == ~0ull) E--;
     }
     return SF_OK;
@@ -458,20 +452,20 @@ struct Decimator {
   int threshold(uint32_t E, uint64_t needed, int stalled, float& tau) {
     tau = INFINITY;
     if (stalled == 0) {
-      DEC_CHECK(hipMemcpyAsync(d_pri3.p, d_pri.p, (size_t)E * 4, hipMemcpyDeviceToDevice, s));
+      SF_HIP_CHECK(hipMemcpyAsync(d_pri3.p, d_pri.p, (size_t)E * 4, hipMemcpyDeviceToDevice, s));
       size_t tb = tmp_bytes;
-      DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_pri3.as<uint32_t>(), d_pri2.as<uint32_t>(), (size_t)E, 0, 32, s));
+      SF_HIP_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_pri3.as<uint32_t>(), d_pri2.as<uint32_t>(), (size_t)E, 0, 32, s));
       const uint64_t kth = std::min<uint64_t>((uint64_t)E - 1, needed + needed / 2 + 64);
-      DEC_CHECK(hipMemcpyAsync(&tau, d_pri2.as<float>() + kth, 4, hipMemcpyDeviceToHost, s));
-      DEC_CHECK(hipStreamSynchronize(s));
+      SF_HIP_CHECK(hipMemcpyAsync(&tau, d_pri2.as<float>() + kth, 4, hipMemcpyDeviceToHost, s));
+      SF_HIP_CHECK(hipStreamSynchronize(s));
     }
     if (!(tau < 3.0e38f)) tau = 3.0e38f;   // never an edge the link test rejected (infinite priority)
     return SF_OK;
   }
   // 4. one round's winners: winners_begin, PASSES x winners_pass, winners_read
   int winners_begin() {
-    DEC_CHECK(hipMemsetAsync(d_nwin.p, 0, 16, s));
-    DEC_CHECK(hipMemsetAsync(d_taken.p, 0, V, s));
+    SF_HIP_CHECK(hipMemsetAsync(d_nwin.p, 0, 16, s));
+    SF_HIP_CHECK(hipMemsetAsync(d_taken.p, 0, V, s));
     return SF_OK;
   }
   void winners_pass(uint32_t E, float tau, uint32_t round, int pass) {
@@ -483,19 +477,19 @@ struct Decimator {
                        d_lock.as<unsigned long long>(), d_taken.as<uint8_t>(), d_win.as<unsigned long long>(), d_nwin.as<uint32_t>());
   }
   int winners_read(uint32_t cnt[4]) {
-    DEC_CHECK(hipMemcpyAsync(cnt, d_nwin.p, 16, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipStreamSynchronize(s));
+    SF_HIP_CHECK(hipMemcpyAsync(cnt, d_nwin.p, 16, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipStreamSynchronize(s));
     return SF_OK;
   }
   // the last round: the winners in (priority, edge) order in d_win2, and how many of them bring the face count to the target
   int cut(uint32_t nwin, uint32_t E, uint64_t nalive, uint64_t target, uint32_t& take, uint64_t& removed, uint32_t& top) {
     size_t tb = tmp_bytes;
-    DEC_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), (size_t)nwin, 0, 64, s));
+    SF_HIP_CHECK(rocprim::radix_sort_keys(d_tmp.p, tb, d_win.as<uint64_t>(), d_win2.as<uint64_t>(), (size_t)nwin, 0, 64, s));
     win_h.resize(nwin);
-    DEC_CHECK(hipMemcpyAsync(win_h.data(), d_win2.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipMemcpyAsync(win_h.data(), d_win2.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, s));
     ucnt_h.resize(E);
-    DEC_CHECK(hipMemcpyAsync(ucnt_h.data(), d_ucnt.p, (size_t)E * 4, hipMemcpyDeviceToHost, s));
-    DEC_CHECK(hipStreamSynchronize(s));
+    SF_HIP_CHECK(hipMemcpyAsync(ucnt_h.data(), d_ucnt.p, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+    SF_HIP_CHECK(hipStreamSynchronize(s));
     removed = 0;
     take = 0;
     while (take < nwin && nalive - removed > target) {
@@ -509,18 +503,12 @@ struct Decimator {
   int collapse(const unsigned long long* d_take, uint32_t take) {
     if (take == 0) return SF_OK;
     hipLaunchKernelGGL(k_collapse, dim3((take + 255) / 256), dim3(256), 0, s, M, d_ukey.as<uint64_t>(), d_x.as<float>(), d_take, take);
-    DEC_CHECK(hipGetLastError());
+    SF_HIP_CHECK(hipGetLastError());
     return SF_OK;
   }
 };
 
-int stage_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sf::fail(SF_ERR_DEVICE, "no HIP device");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  DEC_CHECK(hipSetDevice(device));
-  return SF_OK;
-}
+int stage_device(int device) { return sf::open_device(device, SF_ERR_INVALID_ARG, "the stages of sf_mesh_simplify_gpu need one"); }
 int stage_mesh(uint32_t V, uint32_t F, const uint32_t* tri) {
   if (V == 0 || F == 0 || F > 0x2FFFFFFFu) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: empty or oversized mesh");
   for (size_t i = 0; i < 3 * (size_t)F; i++)
@@ -549,19 +537,19 @@ SF_API int sf_simplify_stage_edges(int device, uint32_t V, uint32_t F, const flo
   *tau_out = 3.0e38f;
   if (!Q_in) {
     if (E) D.init_quadrics(E, *p);
-    else DEC_CHECK(hipMemsetAsync(D.d_Q.p, 0, (size_t)V * sizeof(Quadric), D.s));
+    else SF_HIP_CHECK(hipMemsetAsync(D.d_Q.p, 0, (size_t)V * sizeof(Quadric), D.s));
   }
   if (E) {
     D.priorities(E, scale, *p);
     if (const int rc = D.threshold(E, needed, stalled, *tau_out)) return rc;
-    DEC_CHECK(hipMemcpyAsync(ukey, D.d_ukey.p, (size_t)E * 8, hipMemcpyDeviceToHost, D.s));
-    DEC_CHECK(hipMemcpyAsync(ucnt, D.d_ucnt.p, (size_t)E * 4, hipMemcpyDeviceToHost, D.s));
-    DEC_CHECK(hipMemcpyAsync(pri, D.d_pri.p, (size_t)E * 4, hipMemcpyDeviceToHost, D.s));
-    DEC_CHECK(hipMemcpyAsync(x, D.d_x.p, (size_t)E * 12, hipMemcpyDeviceToHost, D.s));
+    SF_HIP_CHECK(hipMemcpyAsync(ukey, D.d_ukey.p, (size_t)E * 8, hipMemcpyDeviceToHost, D.s));
+    SF_HIP_CHECK(hipMemcpyAsync(ucnt, D.d_ucnt.p, (size_t)E * 4, hipMemcpyDeviceToHost, D.s));
+    SF_HIP_CHECK(hipMemcpyAsync(pri, D.d_pri.p, (size_t)E * 4, hipMemcpyDeviceToHost, D.s));
+    SF_HIP_CHECK(hipMemcpyAsync(x, D.d_x.p, (size_t)E * 12, hipMemcpyDeviceToHost, D.s));
   }
-  DEC_CHECK(hipMemcpyAsync(Q_out, D.d_Q.p, (size_t)V * sizeof(Quadric), hipMemcpyDeviceToHost, D.s));
-  DEC_CHECK(hipStreamSynchronize(D.s));
-  DEC_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(Q_out, D.d_Q.p, (size_t)V * sizeof(Quadric), hipMemcpyDeviceToHost, D.s));
+  SF_HIP_CHECK(hipStreamSynchronize(D.s));
+  SF_HIP_CHECK(hipGetLastError());
   return SF_OK;
 }
 
@@ -577,7 +565,7 @@ SF_API int sf_simplify_stage_winners(int device, uint32_t V, uint32_t F, const u
   uint32_t E = 0;
   if (const int rc = D.adjacency(E)) return rc;
   if (E != E_in || E == 0) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: %u priorities for %u edges", E_in, E);
-  DEC_CHECK(hipMemcpyAsync(D.d_pri.p, pri, (size_t)E * 4, hipMemcpyHostToDevice, D.s));
+  SF_HIP_CHECK(hipMemcpyAsync(D.d_pri.p, pri, (size_t)E * 4, hipMemcpyHostToDevice, D.s));
   if (const int rc = D.winners_begin()) return rc;
   std::memset(pass_out, 0, E);
   uint32_t cnt[4] = {0, 0, 0, 0}, seen = 0;
@@ -588,8 +576,8 @@ SF_API int sf_simplify_stage_winners(int device, uint32_t V, uint32_t F, const u
     if (cnt[0] > E) return sf::fail(SF_ERR_DEVICE, "simplify stage: %u winners of %u edges", cnt[0], E);
     w.resize(cnt[0] - seen);
     if (cnt[0] > seen) {
-      DEC_CHECK(hipMemcpyAsync(w.data(), D.d_win.as<unsigned long long>() + seen, (size_t)(cnt[0] - seen) * 8, hipMemcpyDeviceToHost, D.s));
-      DEC_CHECK(hipStreamSynchronize(D.s));
+      SF_HIP_CHECK(hipMemcpyAsync(w.data(), D.d_win.as<unsigned long long>() + seen, (size_t)(cnt[0] - seen) * 8, hipMemcpyDeviceToHost, D.s));
+      SF_HIP_CHECK(hipStreamSynchronize(D.s));
     }
     for (unsigned long long k : w) {
       const uint32_t e = (uint32_t)k;
@@ -598,9 +586,9 @@ SF_API int sf_simplify_stage_winners(int device, uint32_t V, uint32_t F, const u
     }
     seen = cnt[0];
   }
-  DEC_CHECK(hipMemcpyAsync(taken_out, D.d_taken.p, V, hipMemcpyDeviceToHost, D.s));
-  DEC_CHECK(hipStreamSynchronize(D.s));
-  DEC_CHECK(hipGetLastError());
+  SF_HIP_CHECK(hipMemcpyAsync(taken_out, D.d_taken.p, V, hipMemcpyDeviceToHost, D.s));
+  SF_HIP_CHECK(hipStreamSynchronize(D.s));
+  SF_HIP_CHECK(hipGetLastError());
   for (int k = 0; k < 3; k++) counters[k] = cnt[k];
   return SF_OK;
 }
@@ -619,10 +607,10 @@ SF_API int sf_simplify_stage_collapse(int device, uint32_t V, uint32_t F, float*
   uint32_t E = 0;
   if (const int rc = D.adjacency(E)) return rc;
   if (E != E_in || E == 0) return sf::fail(SF_ERR_INVALID_ARG, "simplify stage: positions for %u edges, the mesh has %u", E_in, E);
-  DEC_CHECK(hipMemcpyAsync(D.d_x.p, x, (size_t)E * 12, hipMemcpyHostToDevice, D.s));
+  SF_HIP_CHECK(hipMemcpyAsync(D.d_x.p, x, (size_t)E * 12, hipMemcpyHostToDevice, D.s));
   std::vector<unsigned long long> w(n);
   for (uint32_t i = 0; i < n; i++) w[i] = edges[i];
-  if (n) DEC_CHECK(hipMemcpyAsync(D.d_win.p, w.data(), (size_t)n * 8, hipMemcpyHostToDevice, D.s));
+  if (n) SF_HIP_CHECK(hipMemcpyAsync(D.d_win.p, w.data(), (size_t)n * 8, hipMemcpyHostToDevice, D.s));
   if (const int rc = D.collapse(D.d_win.as<unsigned long long>(), n)) return rc;
   return D.download(pos, tri, alive, vdel_out, Q);
 }
@@ -634,11 +622,7 @@ SF_API int sf_mesh_simplify_gpu(const sf_mesh* in, const sf_simplify_params* p, 
                                         "(simplify.mlx ships them all false)");
   if (!(p->target_perc >= 0.0f && p->target_perc <= 1.0f) || !(p->quality_thr >= 0.0f && p->quality_thr <= 1.0f) || !(p->boundary_weight > 0.0f))
     return sf::fail(SF_ERR_INVALID_ARG, "simplify parameters out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return sf::fail(SF_ERR_DEVICE, "no HIP device: sf_mesh_simplify_gpu needs an MI355X (sf_mesh_simplify is the sequential host filter)");
-  if (device < 0 || device >= ndev) return sf::fail(SF_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-  DEC_CHECK(hipSetDevice(device));
+  if (int rc = sf::open_device(device, SF_ERR_INVALID_ARG, "sf_mesh_simplify_gpu needs an MI355X (sf_mesh_simplify is the sequential host filter)")) return rc;
   const uint32_t V = (uint32_t)(in->pos.size() / 3), F = (uint32_t)(in->tri.size() / 3);
   if (in->tri.size() / 3 > 0x2FFFFFFFull) return sf::fail(SF_ERR_CAPACITY, "mesh too large for 32-bit corner ids");
   sf_simplify_stats st;

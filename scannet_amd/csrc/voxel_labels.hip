@@ -208,49 +208,6 @@ __global__ __launch_bounds__(256) void k_vl_sample(const float* __restrict__ val
 // device microseconds of the most recent call's launches: k_vl_count .. k_vl_fill, k_vl_clear + k_vl_nearest, k_vl_sample (sf_voxlabel_kernel_us)
 std::atomic<float> g_bins_us{0.0f}, g_nearest_us{0.0f}, g_sample_us{0.0f};
 
-struct Span {   // two events on a stream; us() after the stream has been synchronised
-  hipEvent_t a = nullptr, b = nullptr;
-  Span() { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
-  Span(const Span&) = delete;
-  Span& operator=(const Span&) = delete;
-  ~Span() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  void begin(hipStream_t s) { if (a) (void)hipEventRecord(a, s); }
-  void end(hipStream_t s) { if (b) (void)hipEventRecord(b, s); }
-  float us() const {
-    float ms = 0.0f;
-    if (!a || !b || hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0.0f; }
-    return ms * 1000.0f;
-  }
-};
-
-bool on_device(const void* p) {
-  if (!p) return false;
-  hipPointerAttribute_t a;
-  std::memset(&a, 0, sizeof(a));
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice;
-}
-
-int open_device(int device, const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    return sf::fail(SF_ERR_DEVICE, "no HIP device: %s on a device needs an MI355X (device = -1 is the host path)", who);
-  }
-  if (device >= ndev) return sf::fail(SF_ERR_DEVICE, "%s: device %d of %d", who, device, ndev);
-  SF_HIP_CHECK(hipSetDevice(device));
-  return SF_OK;
-}
-
-// dst may be host or device memory
-hipError_t deliver(void* dst, const void* src, size_t bytes, hipStream_t s) {
-  if (!bytes) return hipSuccess;
-  return hipMemcpyAsync(dst, src, bytes, on_device(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
-}
-
 }  // namespace
 
 namespace sf {
@@ -258,7 +215,7 @@ namespace vl {
 
 int nearest_device(const sf_grid_header& h, const float* xyz, uint64_t nv, const uint32_t* tris, uint64_t nf, float t, float r2, int device, int32_t* face,
                    float* dist2, const BinsOut* bins) {
-  int rc = open_device(device, "the nearest-face search");
+  int rc = open_device(device, SF_ERR_DEVICE, "%s on a device needs an MI355X (device = -1 is the host path)", "the nearest-face search");
   if (rc != SF_OK) return rc;
   const Geo g = make_geo(h);
   const uint64_t n_nodes = (uint64_t)h.nx * (uint64_t)h.ny * (uint64_t)h.nz;
@@ -283,7 +240,7 @@ int nearest_device(const sf_grid_header& h, const float* xyz, uint64_t nv, const
   SF_HIP_CHECK(hipMemsetAsync(d_counts.p, 0, n_tiles * 4, sg.s));
   SF_HIP_CHECK(hipMemsetAsync(d_cursor.p, 0, n_tiles * 4, sg.s));
   const uint32_t face_blocks = (uint32_t)((nf + 255) / 256);
-  Span t_count, t_fill, t_near;
+  EventSpan t_count, t_fill, t_near;
   t_count.begin(sg.s);
   if (nf) {
     k_vl_count<<<face_blocks, 256, 0, sg.s>>>(d_xyz.as<float>(), d_tris.as<uint32_t>(), (uint32_t)nf, t, g, d_rec.as<FaceRec>(), d_counts.as<uint32_t>());
@@ -343,7 +300,7 @@ int nearest_device(const sf_grid_header& h, const float* xyz, uint64_t nv, const
 
 int sample_device(const sf_grid_header& h, const float* value, const uint8_t* byte_label, int32_t wx, int32_t wy, int32_t wz, int64_t z0, int32_t stride,
                   int device, uint64_t first, uint64_t max_samples, float* data, uint8_t* label, int32_t* xy, uint64_t* total) {
-  int rc = open_device(device, "the column sampler");
+  int rc = open_device(device, SF_ERR_DEVICE, "%s on a device needs an MI355X (device = -1 is the host path)", "the column sampler");
   if (rc != SF_OK) return rc;
   *total = 0;
   const uint64_t n_nodes = (uint64_t)h.nx * (uint64_t)h.ny * (uint64_t)h.nz, n_cols = (uint64_t)h.nx * (uint64_t)h.ny;
@@ -381,7 +338,7 @@ int sample_device(const sf_grid_header& h, const float* value, const uint8_t* by
   if (!data_dev) { SF_HIP_CHECK(d_data.alloc(n * per * 4)); o_data = d_data.as<float>(); }
   if (!label_dev) { SF_HIP_CHECK(d_label.alloc(n * wz)); o_label = d_label.as<uint8_t>(); }
   if (!xy_dev) { SF_HIP_CHECK(d_xy.alloc(n * 8)); o_xy = d_xy.as<int32_t>(); }
-  Span t_sample;
+  EventSpan t_sample;
   t_sample.begin(sg.s);
   k_vl_sample<<<(uint32_t)(n * (uint64_t)wz), 256, 0, sg.s>>>(d_value.as<float>(), d_bl.as<uint8_t>(), h.nx, h.ny, h.nz, d_cols.as<uint32_t>(), first, wx, wy, wz,
                                                              (long long)z0, o_data, o_label, o_xy);

@@ -53,7 +53,10 @@ struct FakeStream {
 };
 
 const char* hipGetErrorString(hipError_t) { return "fake hip error"; }
+hipError_t hipGetLastError() { return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
+hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
+hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) { a->type = hipMemoryTypeHost; a->device = 0; return hipSuccess; }   // "device memory" is host memory
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new FakeStream(); return hipSuccess; }
 hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = new FakeStream(); return hipSuccess; }
@@ -69,6 +72,8 @@ hipError_t hipStreamDestroy(hipStream_t s) {
 }
 hipError_t hipStreamSynchronize(hipStream_t s) { s->drain(); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new FakeEvent(); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.0f; return hipSuccess; }   // events order, they do not time
 hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
   uint64_t gen;

@@ -23,9 +23,14 @@ typedef FakeStream* hipStream_t;
 typedef FakeEvent* hipEvent_t;
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
 constexpr unsigned hipStreamNonBlocking = 1, hipEventDisableTiming = 2, hipHostMallocDefault = 0;
+enum hipMemoryType { hipMemoryTypeHost = 1, hipMemoryTypeDevice = 2 };
+struct hipPointerAttribute_t { hipMemoryType type; int device; };   // what csrc/hip_util.h reads
 
 const char* hipGetErrorString(hipError_t);
+hipError_t hipGetLastError();
 hipError_t hipSetDevice(int);
+hipError_t hipGetDevice(int*);
+hipError_t hipPointerGetAttributes(hipPointerAttribute_t*, const void*);
 hipError_t hipGetDeviceCount(int*);
 hipError_t hipStreamCreateWithFlags(hipStream_t*, unsigned);
 hipError_t hipStreamCreateWithPriority(hipStream_t*, unsigned, int);
@@ -34,6 +39,8 @@ hipError_t hipStreamDestroy(hipStream_t);
 hipError_t hipStreamSynchronize(hipStream_t);
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned);
 hipError_t hipEventCreateWithFlags(hipEvent_t*, unsigned);
+hipError_t hipEventCreate(hipEvent_t*);
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t);
 hipError_t hipEventDestroy(hipEvent_t);
 hipError_t hipEventRecord(hipEvent_t, hipStream_t);
 hipError_t hipEventSynchronize(hipEvent_t);
